@@ -11,7 +11,9 @@ ranks.  The frame is cut into 16-row stripes dealt round-robin to the ranks (str
 ends with one RCCL gather of the float-RGB stripes to rank 0, inside the timed region.  Timing: barrier +
 torch.cuda.synchronize() on both sides of exactly K steps, MAX over ranks.
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: set-up, W warm-up frames, K timed frames, the outputs (--dump-outputs DIR:
+the float32 RGB frame of the last timed step as DIR/frame.npy) and one short JSON line with metric, value, unit, higher_is_better, dtype
+and ms_per_step.  With --full it also measures what follows, and the JSON line carries these extra objects:
   "roofline"      for the dominant kernel (by live HIP-event time) and for every hot kernel: the resource that binds it and the fraction of that
                   resource's peak it reaches -- VALU issue (vector-ALU busy quad-cycles of the committed SQ counter profile / the live kernel
                   time against 1024 SIMDs at 2.4 GHz) or HBM (TCC bytes of the committed profile / the live kernel time against 8 TB/s); every
@@ -54,7 +56,13 @@ def parse_args():
     ap.add_argument("--pool", type=int, default=0, help="path slots of the wavefront pool (0: library default)")
     ap.add_argument("--mode", default="wavefront", choices=["wavefront", "rounds", "megakernel"])
     ap.add_argument("--write-mix", action="store_true", help="record the oracle-counted per-sample mix of this workload in profiles/workload_mix.json")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the roofline (with the executed-work frame), the CPU baseline and BASELINE configs 2 and 4; "
+                                                        "--no-cpu / --no-others / --no-executed leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/frame.npy (float32, [height][width][3])")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def self_launch(args):
@@ -282,7 +290,7 @@ def main():
         stages = {k: float(np.mean([s[k] for s in stage_ms])) for k in stage_ms[0]} if stage_ms else {}
         img = fg.frame.cpu().numpy() if rank == 0 else None
         executed = None
-        if rank == 0 and world == 1 and args.mode == "wavefront" and not args.no_executed:      # what the kernels executed: one more frame, untimed, with their counters on
+        if args.full and rank == 0 and world == 1 and args.mode == "wavefront" and not args.no_executed:      # what the kernels executed: one more frame, untimed, with their counters on
             try:
                 rt.set_counters("stream")
                 rt.run_device(p, fg.local.data_ptr(), f64=False)
@@ -339,6 +347,11 @@ def main():
                        "sharding": f"{STRIPE_H}-row stripes round-robin over {world} GPU(s), RCCL gather to rank 0" if world > 1 else "single GPU",
                        "setup_s_untimed": round(res["setup_s"], 3), "mean_radiance": float(res["img"].mean())},
         }
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "frame.npy"), np.ascontiguousarray(res["img"], dtype=np.float32))
+        out["config"]["library"] = os.path.relpath(gi.LIB_PATH, ROOT)
+    if rank == 0 and args.full:
         key = workload_key(args.scene, w, h, spp, args.photons)
         mix, cpu = stored_mix(key), None
         if world == 1 and not args.no_cpu and args.cpu_rows != 0:
@@ -354,13 +367,12 @@ def main():
                 with open(MIX_FILE, "w") as f:
                     json.dump(allmix, f, indent=1, sort_keys=True)
         out["roofline"] = roofline_of(args.scene, w, h, spp, args.photons, world, args.mode, res["rows"] * w * spp, res["stages"], res["kernel_ms"], mix, res["executed"])
-        out["config"]["library"] = os.path.relpath(gi.LIB_PATH, ROOT)
         if cpu is not None:
             out["cpu_baseline"] = cpu
     del res
 
-    # ---- the closed-box configurations (BASELINE configs 2 and 4), N=1 only, inside the default run's time budget
-    if world == 1 and not args.no_others and args.scene == "caustics":
+    # ---- the closed-box configurations (BASELINE configs 2 and 4), N=1 only, inside the --full run's time budget
+    if args.full and world == 1 and not args.no_others and args.scene == "caustics":
         others = []
         for name, (ow, oh, ospp, oph, osteps, label) in {"cornell": (512, 512, 64, 0, 3, "config 2: scenes/cornell 512x512 64 spp, no photon map"),
                                                             "teapot": (1920, 1080, 256, 200000, 1, "config 4: scenes/cornell + glass teapot 1920x1080 256 spp, 200000 photon indices + gather")}.items():

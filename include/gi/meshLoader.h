@@ -1,5 +1,5 @@
 // include/gi/meshLoader.h -- declarations of the reference's mesh loader (include/meshLoader.h).  The reference's own meshLoader.cpp compiles
-// against these headers unchanged (tests/test_reference_callers.py); include "builtin_loaders.h" instead to get the loader of this package.
+// against these headers unchanged (checked in the build container); include "builtin_loaders.h" instead to get the loader of this package.
 #pragma once
 #include <vector>
 #include "octree.h"

@@ -1,5 +1,8 @@
 """The drop-in boundary checked from the reference's side (build container only: needs /root/reference, which never travels).
 
+Not part of the test suite: it compiles the reference's own sources, which the repository does not hold.  Run it where the reference is, next to
+the fixture generator of this directory:  python -m pytest oracle/ref/check_reference_callers.py
+
 The reference's own, unmodified include/sceneLoader.cpp and include/meshLoader.cpp -- the callers a maintainer keeps -- are compiled from
 where they lie against the headers of include/gi/ (symbolic links in a scratch directory make the compiler resolve their #include "..."
 lines through -I include/gi instead of the reference's own directory; no reference text enters the repository), linked with the C-ABI
@@ -12,9 +15,15 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 REF = "/root/reference"
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include")), reason="no /root/reference here (GPU box): the reference's callers cannot be compiled")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return lambda name: np.load(os.path.join(GOLDEN, name + ".npz"))
 
 
 @pytest.fixture(scope="module")
@@ -25,7 +34,7 @@ def driver(tmp_path_factory):
     exe = d / "driver"
     lib = os.path.join(ROOT, "gi_raytracer_amd")
     subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-DGI_USE_GLM", "-I", str(d), "-I", os.path.join(ROOT, "include", "gi"), "-I", os.path.join(REF, "3rd_party"),
-                    os.path.join(ROOT, "tests", "cpp", "ref_callers_driver.cpp"), str(d / "sceneLoader.cpp"), str(d / "meshLoader.cpp"),
+                    os.path.join(ROOT, "oracle", "ref", "ref_callers_driver.cpp"), str(d / "sceneLoader.cpp"), str(d / "meshLoader.cpp"),
                     "-L" + lib, "-lgi_raytracer_hip", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", str(exe)], check=True)
     return str(exe)
 

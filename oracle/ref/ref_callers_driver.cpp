@@ -1,5 +1,5 @@
-// tests/cpp/ref_callers_driver.cpp -- the reference's main.cpp flow with the REFERENCE'S OWN loaders (its unmodified sceneLoader.cpp and
-// meshLoader.cpp, compiled from where they lie by tests/test_reference_callers.py) on top of the drop-in headers of include/gi/: what a
+// oracle/ref/ref_callers_driver.cpp -- the reference's main.cpp flow with the REFERENCE'S OWN loaders (its unmodified sceneLoader.cpp and
+// meshLoader.cpp, compiled from where they lie by oracle/ref/check_reference_callers.py) on top of the drop-in headers of include/gi/: what a
 // maintainer gets after swapping the headers.  Dumps the flattened tables Octree::rebuild leaves for the GPU, and answers host-side
 // queries (Octree::intersectSorted / intersect over _root, PhotonMap::rebuild / getInRange) for rays / points the test hands in.
 // usage: driver scene.scn io_dir      (io_dir: inputs *.f64 written by the test, outputs written here)

@@ -9,7 +9,7 @@ SCENE=${1:-caustics}; W=${2:-1920}; H=${3:-1080}; SPP=${4:-256}; PH=${5:-200000}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--no-cpu --no-others --no-executed --scene $SCENE --width $W --height $H --spp $SPP --photons $PH"
+ARGS="--full --no-cpu --no-others --no-executed --scene $SCENE --width $W --height $H --spp $SPP --photons $PH"
 python3 bench.py --steps 3 --warmup 1 $ARGS > $OUT/bench.json 2> $OUT/bench.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 bench.py --steps 3 --warmup 1 $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 pass() { name=$1; shift; timeout -k 10 240 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o $name -- python3 bench.py --steps 1 --warmup 0 $ARGS > $OUT/$name.json 2> $OUT/$name.err; echo "$name done: $(tail -c 120 $OUT/$name.err | tr '\n' ' ')"; }
