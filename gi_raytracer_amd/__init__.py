@@ -517,7 +517,8 @@ class RayTracer:
         self._check(self.L.gi_render_device(self.h, C.byref(p), C.c_void_p(out_ptr), 1 if f64 else 0, C.c_void_p(spp_ptr) if spp_ptr else None, None), "render_device")
 
     def set_render_mode(self, mode):
-        """'wavefront' (default) or 'megakernel': two schedules of the same per-path arithmetic."""
+        """'wavefront' (default), 'megakernel' or 'rounds' (the wavefront passes in synchronous rounds, fixed-spp frames too):
+        schedules of the same per-path arithmetic."""
         self._check(self.L.gi_set_render_mode(self.h, {"wavefront": 0, "megakernel": 1, "rounds": 2}[mode]), "set_render_mode")
 
     def set_wide_nodes(self, on):

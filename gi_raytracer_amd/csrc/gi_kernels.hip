@@ -30,6 +30,34 @@ using namespace gi;
 #endif
 
 // ================================================================================================= kernels
+// A pixel of the adaptive loop between launches (streaming and round-based renderers), as PixelState plus n = samples started this round.
+struct PixRec { double color[3], lastCol[3], var; int32_t samps, s, n, pad; };
+__device__ __forceinline__ PixelState pixrec_to_state(const PixRec& r)
+{
+    PixelState ps;
+    ps.color = ld3(r.color); ps.lastCol = ld3(r.lastCol); ps.var = r.var; ps.samps = r.samps; ps.s = r.s;
+    return ps;
+}
+__device__ __forceinline__ void state_to_pixrec(const PixelState& ps, PixRec& r)   // leaves r.n and r.pad as they are
+{
+    r.color[0] = ps.color.x; r.color[1] = ps.color.y; r.color[2] = ps.color.z;
+    r.lastCol[0] = ps.lastCol.x; r.lastCol[1] = ps.lastCol.y; r.lastCol[2] = ps.lastCol.z;
+    r.var = ps.var; r.samps = ps.samps; r.s = ps.s;
+}
+// the pixel's colour so far to out (f32 or f64) and its sample count to out_spp (optional), at (x, local row ly)
+__device__ __forceinline__ void pixel_write(const Frame& F, int x, int ly, const PixelState& ps, void* out, int out_f64, int32_t* out_spp)
+{
+    const size_t o = ((size_t)ly * F.w + x);
+    if (!out_f64) {
+        float* p = (float*)out + o * 3;
+        p[0] = (float)ps.color.x; p[1] = (float)ps.color.y; p[2] = (float)ps.color.z;
+    } else {
+        double* p = (double*)out + o * 3;
+        p[0] = ps.color.x; p[1] = ps.color.y; p[2] = ps.color.z;
+    }
+    if (out_spp) out_spp[o] = ps.s;
+}
+
 template <bool COUNT>
 __global__ __launch_bounds__(GI_BLOCK) void k_render(Scene S, Frame F, void* out, int out_f64, int32_t* out_spp,
                                                      unsigned int* tile_counter, Counters* counters)
@@ -57,15 +85,7 @@ __global__ __launch_bounds__(GI_BLOCK) void k_render(Scene S, Frame F, void* out
                 V3 L = radiance_path(S, ray, idx, F.seed, heap + tid, GI_BLOCK, COUNT ? &cnt : nullptr);
                 pixel_add_sample(ps, F, L);
             }
-            const size_t o = ((size_t)ly * F.w + x);
-            if (out_f64) {
-                double* p = (double*)out + o * 3;
-                p[0] = ps.color.x; p[1] = ps.color.y; p[2] = ps.color.z;
-            } else {
-                float* p = (float*)out + o * 3;
-                p[0] = (float)ps.color.x; p[1] = (float)ps.color.y; p[2] = (float)ps.color.z;
-            }
-            if (out_spp) out_spp[o] = ps.s;
+            pixel_write(F, x, ly, ps, out, out_f64, out_spp);
         }
     }
     if (COUNT) {
@@ -240,14 +260,8 @@ __device__ __forceinline__ void flush_walk_cnt(unsigned long long* dst6, const W
     flush_u64(dst6 + 3, w.cull_tests); flush_u64(dst6 + 4, w.leaves); flush_u64(dst6 + 5, w.tris); flush_u64(dst6 + 6, w.ent_boxes);
 }
 
-// ================================================================================================= wavefront pipeline
-// The frame is rendered in rounds.  In a round every pixel that still wants samples (adaptive loop of RayTracer::run,
-// include/raytracer.h:108-148) starts up to B paths (as many as it is certain to take whatever their variance turns out to
-// be); the paths live as PathRec records in an HBM pool (slot = pixel * B + k) and go through
-//     k_wf_trace  ->  k_wf_shade  ->  k_wf_gather          (one pass per path depth)
-// each kernel working on a compacted queue of slot indices (appended with one atomic per wave from a ballot), so that all
-// 64 lanes of a wave run the same stage; k_wf_accum then folds the finished paths into the per-pixel running mean in sample
-// order.  Per-path arithmetic is the same stage_* code the megakernel runs, so both give the same numbers.
+// ================================================================================================= path pool
+// The streaming passes run the same per-path stage_* code as the megakernel, so both give the same numbers.
 // The streaming pipeline's paths in flight: ONE ARRAY PER GROUP OF FIELDS that a stage reads or writes together, instead of one 224-byte PathRec per
 // path.  A stage wants 40 - 160 bytes of a path; out of records it moved whole DRAM pages for them (exp/aos_bench.hip: the shade stage's
 // read-104-write-172 pattern costs 48 ms per 477 M records as 224-byte structures, 24 ms as field arrays).  pool[slot] gives a PathRef -- the field
@@ -302,7 +316,6 @@ static PathPool make_path_pool(void* base, size_t n)
     P.L = reinterpret_cast<double*>(b);
     return P;
 }
-struct PixRec { double color[3], lastCol[3], var; int32_t samps, s, n, pad; };
 
 __device__ __forceinline__ uint32_t wave_append(unsigned int* counter, bool pred)
 {
@@ -349,118 +362,9 @@ __global__ __launch_bounds__(GI_BLOCK) void k_wf_init(PixRec* pix, uint32_t n_pi
         PixelState ps;
         pixel_begin(ps);
         PixRec r;
-        r.color[0] = ps.color.x; r.color[1] = ps.color.y; r.color[2] = ps.color.z;
-        r.lastCol[0] = 0; r.lastCol[1] = 0; r.lastCol[2] = 0;
-        r.var = 0; r.samps = 0; r.s = 0; r.n = 0; r.pad = 0;
+        state_to_pixrec(ps, r);
+        r.n = 0; r.pad = 0;
         pix[i] = r;
-    }
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_gen(Scene S, Frame F, PixRec* pix, PathRec* pool, uint32_t n_pix, int B)
-{
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += gridDim.x * blockDim.x) {
-        int x, ly;
-        int n = 0;
-        const bool inside = wf_pixel_xy(F, i, x, ly);
-        int s0 = 0;
-        if (inside) {
-            const int s = pix[i].s, samps = pix[i].samps;
-            if (s < F.max_samples && samps < F.min_samples) {
-                // samples this pixel takes for certain: each one adds 1 to samps or subtracts 1 (include/raytracer.h:143-147)
-                n = min(B, min(F.max_samples - s, F.min_samples - samps));
-                s0 = s;
-            }
-            pix[i].n = n;
-        }
-        const int y = inside ? global_row(F, ly) : 0;
-        for (int k = 0; k < B; k++) {
-            PathRec& p = pool[(size_t)i * B + k];
-            if (k < n) {
-                uint32_t idx;
-                Ray ray = primary_ray(S, F, s0 + k, x, y, idx);
-                path_begin(p, ray, idx);
-            } else
-                p.depth = -1;
-        }
-    }
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_trace(Scene S, uint64_t seed, PathRec* pool, const uint32_t* q_in, uint32_t n_in,
-                                                       uint32_t* q_shade, unsigned int* cnt_shade)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_in; i0 += gridDim.x * blockDim.x) {
-        const uint32_t i = i0 + lane;
-        bool hit = false;
-        uint32_t slot = 0;
-        if (i < n_in) {
-            slot = q_in ? q_in[i] : i;
-            PathRec& p = pool[slot];
-            if (p.depth >= 0) hit = stage_trace(S, p, seed, nullptr);
-        }
-        const uint32_t at = wave_append(cnt_shade, hit);
-        if (hit) q_shade[at] = slot;
-    }
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_shade(Scene S, uint64_t seed, PathRec* pool, const uint32_t* q_shade, const unsigned int* cnt_shade,
-                                                       uint32_t* q_next, unsigned int* cnt_next, uint32_t* q_gather, unsigned int* cnt_gather)
-{
-    const uint32_t n_in = *cnt_shade;
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_in; i0 += gridDim.x * blockDim.x) {
-        const uint32_t i = i0 + lane;
-        int fl = 0;
-        uint32_t slot = 0;
-        if (i < n_in) {
-            slot = q_shade[i];
-            fl = stage_shade(S, pool[slot], seed, nullptr);
-        }
-        const uint32_t a = wave_append(cnt_next, (fl & ST_CONTINUE) != 0);
-        if (fl & ST_CONTINUE) q_next[a] = slot;
-        const uint32_t g = wave_append(cnt_gather, (fl & ST_GATHER) != 0);
-        if (fl & ST_GATHER) q_gather[g] = slot;
-    }
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_gather(Scene S, PathRec* pool, const uint32_t* q_gather, const unsigned int* cnt_gather)
-{
-    __shared__ float heap[GI_GATHER_K * GI_BLOCK];
-    const uint32_t n_in = *cnt_gather;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_in; i += gridDim.x * blockDim.x)
-        stage_gather(S, pool[q_gather[i]], heap + threadIdx.x, GI_BLOCK, nullptr);
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_accum(Frame F, PixRec* pix, const PathRec* pool, uint32_t n_pix, int B, void* out, int out_f64,
-                                                       int32_t* out_spp, unsigned int* n_wanting)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n_round = (n_pix + 63u) & ~63u;
-    for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_round; i0 += gridDim.x * blockDim.x) {
-        const uint32_t i = i0 + lane;
-        bool wants = false;
-        int x, ly;
-        if (i < n_pix && wf_pixel_xy(F, i, x, ly)) {
-            PixRec r = pix[i];
-            PixelState ps;
-            ps.color = ld3(r.color); ps.lastCol = ld3(r.lastCol); ps.var = r.var; ps.samps = r.samps; ps.s = r.s;
-            for (int k = 0; k < r.n; k++) pixel_add_sample(ps, F, ld3(pool[(size_t)i * B + k].L));
-            r.color[0] = ps.color.x; r.color[1] = ps.color.y; r.color[2] = ps.color.z;
-            r.lastCol[0] = ps.lastCol.x; r.lastCol[1] = ps.lastCol.y; r.lastCol[2] = ps.lastCol.z;
-            r.var = ps.var; r.samps = ps.samps; r.s = ps.s; r.n = 0;
-            pix[i] = r;
-            wants = pixel_wants_sample(ps, F);
-            const size_t o = ((size_t)ly * F.w + x);
-            if (out_f64) {
-                double* p = (double*)out + o * 3;
-                p[0] = ps.color.x; p[1] = ps.color.y; p[2] = ps.color.z;
-            } else {
-                float* p = (float*)out + o * 3;
-                p[0] = (float)ps.color.x; p[1] = (float)ps.color.y; p[2] = (float)ps.color.z;
-            }
-            if (out_spp) out_spp[o] = ps.s;
-        }
-        (void)wave_append(n_wanting, wants);
     }
 }
 
@@ -518,23 +422,13 @@ __global__ __launch_bounds__(GI_BLOCK) void k_ad_accum(Frame F, PixRec* pix, con
         int x, ly;
         if (i < n_pix && wf_pixel_xy(F, i, x, ly)) {
             PixRec r = pix[i];
-            PixelState ps;
-            ps.color = ld3(r.color); ps.lastCol = ld3(r.lastCol); ps.var = r.var; ps.samps = r.samps; ps.s = r.s;
+            PixelState ps = pixrec_to_state(r);
             for (int k = 0; k < r.n && pixel_wants_sample(ps, F); k++) pixel_add_sample(ps, F, ld3(lbuf + ((size_t)i * B + k) * 3));
-            r.color[0] = ps.color.x; r.color[1] = ps.color.y; r.color[2] = ps.color.z;
-            r.lastCol[0] = ps.lastCol.x; r.lastCol[1] = ps.lastCol.y; r.lastCol[2] = ps.lastCol.z;
-            r.var = ps.var; r.samps = ps.samps; r.s = ps.s; r.n = 0;
+            state_to_pixrec(ps, r);
+            r.n = 0;
             pix[i] = r;
             wants = pixel_wants_sample(ps, F);
-            const size_t o = ((size_t)ly * F.w + x);
-            if (out_f64) {
-                double* p = (double*)out + o * 3;
-                p[0] = ps.color.x; p[1] = ps.color.y; p[2] = ps.color.z;
-            } else {
-                float* p = (float*)out + o * 3;
-                p[0] = (float)ps.color.x; p[1] = (float)ps.color.y; p[2] = (float)ps.color.z;
-            }
-            if (out_spp) out_spp[o] = ps.s;
+            pixel_write(F, x, ly, ps, out, out_f64, out_spp);
         }
         (void)wave_append(n_wanting, wants);
     }
@@ -1639,25 +1533,14 @@ __global__ __launch_bounds__(GI_BLOCK) void k_st_accum(Frame F, PixRec* pix, con
         int x, ly;
         st_pixel_xy(F, i, x, ly);
         PixRec r = pix[i];
-        PixelState ps;
-        ps.color = ld3(r.color); ps.lastCol = ld3(r.lastCol); ps.var = r.var; ps.samps = r.samps; ps.s = r.s;
+        PixelState ps = pixrec_to_state(r);
         for (int k = 0; k < ns; k++) {
             const double* l = lbuf + ((size_t)k * n_pix + i) * 3;
             pixel_add_sample(ps, F, v3(l[0], l[1], l[2]));
         }
-        r.color[0] = ps.color.x; r.color[1] = ps.color.y; r.color[2] = ps.color.z;
-        r.lastCol[0] = ps.lastCol.x; r.lastCol[1] = ps.lastCol.y; r.lastCol[2] = ps.lastCol.z;
-        r.var = ps.var; r.samps = ps.samps; r.s = ps.s;
+        state_to_pixrec(ps, r);
         pix[i] = r;
-        const size_t o = ((size_t)ly * F.w + x);
-        if (out_f64) {
-            double* p = (double*)out + o * 3;
-            p[0] = ps.color.x; p[1] = ps.color.y; p[2] = ps.color.z;
-        } else {
-            float* p = (float*)out + o * 3;
-            p[0] = (float)ps.color.x; p[1] = (float)ps.color.y; p[2] = (float)ps.color.z;
-        }
-        if (out_spp) out_spp[o] = ps.s;
+        pixel_write(F, x, ly, ps, out, out_f64, out_spp);
     }
 }
 
@@ -1804,7 +1687,6 @@ struct StreamGrids { int lds_refused = 0; int init = 0, trace = 0, shade = 0, sh
 struct gi_ctx {
     int device = 0;
     StreamGrids grids;                // launch grids of the streaming kernels on this context's device
-    int wf_grid[6] = {0, 0, 0, 0, 0, 0};
     hipStream_t stream = nullptr;
     std::string err;
     bool have_scene = false;
@@ -1863,17 +1745,15 @@ struct gi_ctx {
     DevBuf<unsigned int> d_tile_counter;
     DevBuf<Counters> d_counters;
     // wavefront pipeline workspaces (grown on demand, kept between frames)
-    DevBuf<PathRec> d_pool;               // paths of the round-based wavefront pipeline (records)
     DevBuf<uint32_t> d_pixtab;               // k_pixel_table of the frame being rendered
     DevBuf<unsigned char> d_spool;        // paths of the streaming pipeline: field arrays (PathPool), GI_POOL_BYTES_PER_SLOT each
     size_t spool_slots = 0;
     DevBuf<PixRec> d_pix;
-    DevBuf<uint32_t> d_q[4];          // trace ping, trace pong, shade, gather
-    DevBuf<unsigned int> d_wfcnt;     // [0] shade, [1] next, [2] gather, [3] pixels still wanting samples
+    DevBuf<unsigned int> d_wfcnt;     // rounds (render_adaptive): [0] paths started by k_ad_gen, [1] pixels still wanting samples
     unsigned int* h_wfcnt = nullptr;  // pinned host mirror of d_wfcnt
     DevBuf<double> d_lbuf;            // streaming variant: per-sample radiance of the current chunk
     DevBuf<unsigned long long> d_slot_sample;
-    DevBuf<uint32_t> d_qs[6];         // streaming queues: new, cont ping, cont pong, shade, gather, free ping/pong share [5] + d_q
+    DevBuf<uint32_t> d_qs[7];         // streaming queues: new, cont ping, cont pong, shade, gather, free ping, free pong
     DevBuf<StreamCtl> d_ctl;
     DevBuf<uint32_t> d_gk[2], d_gv[2];   // gather sort: keys / values, in / out
     DevBuf<uint32_t> d_stage[4];         // staging queues the producers append to, one segment per workgroup (k_st_compact closes the gaps)
@@ -1894,7 +1774,7 @@ struct gi_ctx {
     size_t ev_used = 0;
     bool stage_timing = true;
     float stage_ms[STG_COUNT_MAX] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int render_mode = 0;              // 0 wavefront pipeline, 1 megakernel
+    int render_mode = 0;              // 0 wavefront pipeline, 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
     size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
     uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
     uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
@@ -2203,72 +2083,6 @@ static int render_megakernel(gi_ctx* c, const Frame& F, void* d_out, int out_is_
     return GI_OK;
 }
 
-static int render_wavefront(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    const uint32_t tiles = (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3));
-    const uint32_t n_pix = tiles * 64u;   // padded to whole 8x8 tiles (wf_pixel_xy)
-    int B = (int)std::min<size_t>(32, std::max<size_t>(1, c->pool_slots_max / n_pix));
-    B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
-    const size_t slots = (size_t)n_pix * (size_t)B;
-    if (slots > 0xfffffff0ull) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
-    if (c->d_pool.n < slots) HIP_TRY(c, c->d_pool.alloc(slots));
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
-    for (int k = 0; k < 4; k++) if (c->d_q[k].n < slots) HIP_TRY(c, c->d_q[k].alloc(slots));
-    if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(4));
-    if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 4 * sizeof(unsigned int), hipHostMallocDefault));
-    int &g_init = c->wf_grid[0], &g_gen = c->wf_grid[1], &g_trace = c->wf_grid[2], &g_shade = c->wf_grid[3], &g_gather = c->wf_grid[4], &g_accum = c->wf_grid[5];
-    if (!g_trace) {
-        g_init = grid_for(c, (const void*)k_wf_init); g_gen = grid_for(c, (const void*)k_wf_gen); g_trace = grid_for(c, (const void*)k_wf_trace);
-        g_shade = grid_for(c, (const void*)k_wf_shade); g_gather = grid_for(c, (const void*)k_wf_gather); g_accum = grid_for(c, (const void*)k_wf_accum);
-    }
-    hipStream_t st = c->stream;
-    PathRec* pool = c->d_pool.p;
-    unsigned int* cnt = c->d_wfcnt.p;
-    int launches = 0;
-    HIP_TRY(c, hipEventRecord(c->ev0, st));
-    hipLaunchKernelGGL(k_wf_init, dim3(g_init), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
-    launches++;
-    // 0 samples per pixel still has to write the initial colour: run the accumulate step once in that case
-    bool any = F.max_samples > 0 && F.min_samples > 0;
-    if (!any) {
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_wf_accum, dim3(g_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, pool, n_pix, B, d_out, out_is_f64, d_spp, cnt + 3);
-        launches++;
-    }
-    while (any) {
-        if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
-        hipLaunchKernelGGL(k_wf_gen, dim3(g_gen), dim3(GI_BLOCK), 0, st, c->S, F, c->d_pix.p, pool, n_pix, B);
-        launches++;
-        const uint32_t* q_in = nullptr;
-        uint32_t n_in = (uint32_t)slots;
-        int ping = 0;
-        for (int depth = 0; depth <= GI_MAX_DEPTH && n_in > 0; depth++) {
-            HIP_TRY(c, hipMemsetAsync(cnt, 0, 3 * sizeof(unsigned int), st));
-            uint32_t* q_next = c->d_q[ping].p;
-            hipLaunchKernelGGL(k_wf_trace, dim3(g_trace), dim3(GI_BLOCK), 0, st, c->S, F.seed, pool, q_in, n_in, c->d_q[2].p, cnt + 0);
-            hipLaunchKernelGGL(k_wf_shade, dim3(g_shade), dim3(GI_BLOCK), 0, st, c->S, F.seed, pool, c->d_q[2].p, cnt + 0, q_next, cnt + 1, c->d_q[3].p, cnt + 2);
-            if (c->S.n_pnode > 0) { hipLaunchKernelGGL(k_wf_gather, dim3(g_gather), dim3(GI_BLOCK), 0, st, c->S, pool, c->d_q[3].p, cnt + 2); launches++; }
-            launches += 2;
-            HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt, cnt, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-            HIP_TRY(c, hipStreamSynchronize(st));
-            if (getenv("GI_DEBUG_WF")) fprintf(stderr, "[wf] depth %d in %u shade %u next %u gather %u\n", depth, n_in, c->h_wfcnt[0], c->h_wfcnt[1], c->h_wfcnt[2]);
-            n_in = c->h_wfcnt[1];
-            q_in = q_next;
-            ping ^= 1;
-        }
-        HIP_TRY(c, hipMemsetAsync(cnt + 3, 0, sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_wf_accum, dim3(g_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, pool, n_pix, B, d_out, out_is_f64, d_spp, cnt + 3);
-        launches++;
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 3, cnt + 3, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        any = c->h_wfcnt[3] > 0;
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev1, st));
-    c->last_launches = launches;
-    return GI_OK;
-}
-
 enum { STG_REGEN = 0, STG_TRACE, STG_SHADE, STG_SORT, STG_GATHER, STG_FINISH, STG_ACCUM, STG_OTHER, STG_SHADOW, STG_COUNT };
 static void stage_begin(gi_ctx* c, int stage)
 {
@@ -2316,8 +2130,7 @@ static int stream_alloc(gi_ctx* c, uint32_t P)
 {
     if (c->spool_slots < P) { HIP_TRY(c, c->d_spool.alloc((size_t)P * GI_POOL_BYTES_PER_SLOT)); c->spool_slots = P; }
     if (c->d_slot_sample.n < P) HIP_TRY(c, c->d_slot_sample.alloc(P));
-    for (int k = 0; k < 6; k++) if (c->d_qs[k].n < P) HIP_TRY(c, c->d_qs[k].alloc(P));
-    if (c->d_q[0].n < P) HIP_TRY(c, c->d_q[0].alloc(P));
+    for (int k = 0; k < 7; k++) if (c->d_qs[k].n < P) HIP_TRY(c, c->d_qs[k].alloc(P));
     for (int k = 0; k < 2; k++) { if (c->d_gk[k].n < P) HIP_TRY(c, c->d_gk[k].alloc(P)); if (c->d_gv[k].n < P) HIP_TRY(c, c->d_gv[k].alloc(P)); }
     for (int k = 0; k < 2; k++) if (c->d_ck[k].n < P) HIP_TRY(c, c->d_ck[k].alloc(P));
     const size_t PS = (size_t)P + 4096;   // segments are laid out as if every chunk of a producer's loop were full: up to one chunk of slack
@@ -2363,7 +2176,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
     uint32_t* q_cont[2] = {c->d_qs[1].p, c->d_qs[2].p};
     uint32_t* q_shade = c->d_qs[3].p;
     uint32_t* q_gather = c->d_qs[4].p;
-    uint32_t* q_free[2] = {c->d_qs[5].p, c->d_q[0].p};
+    uint32_t* q_free[2] = {c->d_qs[5].p, c->d_qs[6].p};
     uint32_t n_cont = 0;
     const uint32_t* qf = nullptr;
     int ping = 0;
@@ -2535,7 +2348,7 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t held = c->d_spool.n + c->d_lbuf.n * 8 + (c->d_qs[0].n + c->d_q[0].n) * 4 * 7 + c->d_shq.n * sizeof(ShadowQ);   // ours, re-usable
+            const size_t held = c->d_spool.n + c->d_lbuf.n * 8 + (c->d_qs[0].n + c->d_qs[6].n) * 4 * 7 + c->d_shq.n * sizeof(ShadowQ);   // ours, re-usable
             const size_t per_slot = GI_POOL_BYTES_PER_SLOT + 8 + 13 * 4 + 24 + 40 + (defers_shadows(c) ? sizeof(ShadowQ) * (size_t)c->S.n_light : 0);   // record, sample id, 13 queue / key words, sort scratch, staging queues, shadow queries
             const size_t lbuf = (size_t)n_pix * (size_t)std::min<size_t>((size_t)spp, c->lbuf_bytes_max / ((size_t)n_pix * 24)) * 24;
             const size_t avail = (size_t)((double)(free_b + held) * 0.90);
@@ -2587,9 +2400,10 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
     return GI_OK;
 }
 
-// Adaptive sampling (min_samples != max_samples, include/raytracer.h:108-148): rounds as in render_wavefront -- a pixel starts the
-// samples it is certain to take, the variance rule is applied in sample order -- but the paths of a round run through the streaming
-// passes (sorted queues, octree records in LDS, wave-cooperative gather, staged finisher) instead of one generic kernel per depth.
+// Adaptive sampling (min_samples != max_samples, include/raytracer.h:108-148), and every frame of render mode 2: synchronous rounds --
+// in a round every pixel that still wants samples starts those it is certain to take (k_ad_gen), the paths run through the streaming
+// passes (sorted queues, octree records in LDS, wave-cooperative gather, staged finisher), and k_ad_accum applies the variance rule in
+// sample order.  With min_samples == max_samples this renders the fixed-spp frame of render_streaming, a round of up to B samples at a time.
 static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
     const uint32_t tiles = (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3));
@@ -2602,8 +2416,8 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     if (rc) return rc;
     if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
     if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
-    if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(4));
-    if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 4 * sizeof(unsigned int), hipHostMallocDefault));
+    if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
+    if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 2 * sizeof(unsigned int), hipHostMallocDefault));
     const StreamGrids& G = stream_grids(c);
     hipStream_t st = c->stream;
     unsigned int* cnt = c->d_wfcnt.p;
@@ -2614,13 +2428,13 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     launches++;
     bool any = F.max_samples > 0 && F.min_samples > 0;
     if (!any) {   // 0 samples per pixel still has to write the initial colour
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 3);
+        HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
+        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
         launches++;
     }
     while (any) {
         if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned int), st));
+        HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
         stage_begin(c, STG_REGEN);
         hipLaunchKernelGGL(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, st, c->S, F, c->d_pix.p, make_path_pool(c->d_spool.p, c->spool_slots), c->d_slot_sample.p, n_pix, B, c->d_qs[0].p, cnt + 0);
         stage_end(c);
@@ -2633,12 +2447,12 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
         rc = stream_passes(c, F, 0ull, c->d_lbuf.p, 0u, refill, exhausted, cancel, launches);
         if (rc) return rc;
         stage_begin(c, STG_ACCUM);
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 3);
+        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
         stage_end(c);
         launches++;
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 3, cnt + 3, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 1, cnt + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        any = c->h_wfcnt[3] > 0;
+        any = c->h_wfcnt[1] > 0;
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev1, st));
@@ -2659,12 +2473,11 @@ int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_
     if (F.local_rows == 0) return GI_OK;
     if (c->render_mode == 1 || c->count_enabled) return render_megakernel(c, F, d_out, out_is_f64, d_spp);
     // fixed sample count: streaming pool with path regeneration; adaptive sampling: rounds (sample-order decisions) on the same passes;
-    // mode 2: the plain per-depth rounds, kept as a second schedule of the same arithmetic
+    // mode 2: rounds for every frame, a second schedule of the fixed-spp frames
     if (c->count_stream && !(c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0))
         return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) belong to fixed-sample-count frames of the wavefront pipeline");
     if (c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0) return render_streaming(c, F, d_out, out_is_f64, d_spp, cancel);
-    if (c->render_mode == 0) return render_adaptive(c, F, d_out, out_is_f64, d_spp, cancel);
-    return render_wavefront(c, F, d_out, out_is_f64, d_spp, cancel);
+    return render_adaptive(c, F, d_out, out_is_f64, d_spp, cancel);
 }
 
 int gi_set_wide_nodes(gi_ctx* c, int enable)

@@ -121,7 +121,8 @@ int gi_render_device(gi_ctx*, const gi_render_params*, void* d_out_lin, int out_
 int gi_render_host(gi_ctx*, const gi_render_params*, void* h_out_lin, int out_is_f64, int32_t* h_out_spp, volatile const int* cancel);
 /* Schedules of the same per-path arithmetic: 0 = wavefront pipeline (default: trace / shade / gather kernels over compacted
  * path queues in HBM; fixed-spp frames refill finished slots with new samples, adaptive frames run in synchronous rounds),
- * 1 = megakernel (one lane keeps one pixel, whole path in registers), 2 = wavefront in synchronous rounds always.            */
+ * 1 = megakernel (one lane keeps one pixel, whole path in registers), 2 = synchronous rounds on the streaming passes, fixed
+ * and adaptive frames alike (a second schedule of the fixed-spp frames).                                                     */
 int gi_set_render_mode(gi_ctx*, int mode);
 /* Octree walk: 1 (default) = wide records, the boxes of a node's children tested together from the five planes per axis that
  * Octree::Node::partition builds them from (include/octree.cpp:318-328); 0 = one box test per node record.  Same box
