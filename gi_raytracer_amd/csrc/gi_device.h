@@ -52,6 +52,9 @@ namespace gi {
 #define GI_FEAT_SPHERES 1   // template feature bits: code for entity kinds / media a scene does not contain is not compiled in
 #define GI_FEAT_FOG 2
 #define GI_FEAT_TEX 4       // checkerboard / image textures (include/material.h:32-81): uv carried through the walk, texture alpha in the alpha test
+// The feature level a scene runs (scene_feat, after Scene) is one of four bit sets, not any of the eight: textures -> 7, else fog -> 3,
+// else spheres -> GI_FEAT_SPHERES, else 0.  k_st_trace has no fog level (the medium is marched in the shade stage), so its level
+// (scene_trace_feat) is textures -> 7, else spheres -> GI_FEAT_SPHERES, else 0.
 
 // ------------------------------------------------------------------------------------------------ device tables (HBM layout)
 struct NodeLink { int32_t hit, skip; };
@@ -169,6 +172,9 @@ struct Scene {
     double pjump_cell[3], pjump_inv[3];   // a cell's size per axis and its inverse
     double cut_margin;        // >= 0: a closest-hit walk looks no further than its best hit plus this (trace_wide_step); < 0: it walks on as the reference does
 };
+// the feature levels of the GI_FEAT_* bits
+inline int scene_feat(const Scene& S) { return S.n_tex > 0 ? 7 : (S.n_fog > 0 ? 3 : (S.has_spheres ? GI_FEAT_SPHERES : 0)); }
+inline int scene_trace_feat(const Scene& S) { return S.n_tex > 0 ? 7 : (S.has_spheres ? GI_FEAT_SPHERES : 0); }
 
 #ifndef GI_PJUMP_BITS
 #define GI_PJUMP_BITS 7          // levels of the photon octree the jump table of gather_find_leaf_fast covers: a grid of 128^3 cells, 8 MB (5: 22.3 ms of queue compaction + gather keys on the benchmark, 6: 21.1, 7: 19.9)

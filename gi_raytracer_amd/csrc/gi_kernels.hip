@@ -356,7 +356,8 @@ __device__ __forceinline__ void st_pixel_xy(const Frame& F, uint32_t v, int& x, 
     ly = (int)(r * 8u + t / tw);
 }
 
-__global__ __launch_bounds__(GI_BLOCK) void k_wf_init(PixRec* pix, uint32_t n_pix)
+// every pixel's state before its first sample (render_streaming, render_adaptive)
+__global__ __launch_bounds__(GI_BLOCK) void k_pix_init(PixRec* pix, uint32_t n_pix)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_pix; i += gridDim.x * blockDim.x) {
         PixelState ps;
@@ -1682,7 +1683,7 @@ struct DevBuf {
 }  // namespace
 
 #define STG_COUNT_MAX 10
-struct StreamGrids { int lds_refused = 0; int init = 0, trace = 0, shade = 0, shadow = 0, gather = 0, accum = 0, finish = 0, ad_gen = 0, ad_accum = 0, compact = 0; };
+struct StreamGrids { int lds_refused = 0; int pix = 0, trace = 0, shade = 0, shadow = 0, gather = 0, accum = 0, finish = 0, ad_gen = 0, ad_accum = 0, compact = 0; };
 
 struct gi_ctx {
     int device = 0;
@@ -1738,6 +1739,7 @@ struct gi_ctx {
     DevBuf<PRange> d_pranges;
     DevBuf<int32_t> d_pleaf_rank, d_prank_leaf, d_n_pleaf;
     DevBuf<PDescent> d_pdescent;
+    bool pdescent_ready = false, pjump_ready = false;   // d_pdescent / d_pjump hold the tables of the current photon map (apply_switches)
     bool fast_descent = true;         // GI_FAST_DESCENT=0: every gather query walks the full photon-octree records
     DevBuf<double> d_ph_pos, d_ph_dircol;
     DevBuf<HaltonDim> d_hdims;
@@ -1774,7 +1776,7 @@ struct gi_ctx {
     size_t ev_used = 0;
     bool stage_timing = true;
     float stage_ms[STG_COUNT_MAX] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int render_mode = 0;              // 0 wavefront pipeline, 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
+    int render_mode = 0;              // 0 streaming passes (fixed spp) or rounds (adaptive), 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
     size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
     uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
     uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
@@ -1810,11 +1812,39 @@ int fail(gi_ctx* c, int code, const std::string& msg)
 }  // namespace
 
 __global__ __launch_bounds__(1024) void k_rs_scan(uint32_t* ghist, uint32_t total);   // gi_sort.inc
-// the sort key of the gather queries (k_pleaf_rank), for the photon tables c->S points at
-static int install_pleaf_rank(gi_ctx* c)
+// The Scene fields that follow the context's switches, from the uploaded tables and the switches alone.  Every upload, every change of the
+// photon map and every gi_set_* of a switch ends here, and nothing else assigns these fields.
+static void apply_switches(gi_ctx* c)
 {
     Scene& S = c->S;
-    S.pleaf_rank = nullptr; S.prank_leaf = nullptr; S.n_pleaf = 0; S.pdescent = nullptr; S.pjump = nullptr; S.pcand_off = nullptr; S.pcand = nullptr; S.pcand_dc = nullptr;
+    S.wnodes = (c->wide_enabled && S.n_wnode > 0) ? c->d_wnodes.p : nullptr;                           // gi_set_wide_nodes
+    S.cboxes = (c->cull_enabled && S.wnodes && c->d_cboxes.n > 1) ? c->d_cboxes.p : nullptr;             // gi_set_content_culling
+    // Which of the walks' short cuts are on (all of them leave every result as it is: DESIGN.md section 4): entity boxes; for the closest-hit walk
+    // the boxes cut to the leaves, and no look behind the best hit.  gi_set_entity_boxes(ctx, 0) turns all three off: the walks then ask what the reference asks.
+    S.leaf_boxes = c->entity_boxes ? c->d_leaf_boxes.p : nullptr;
+    S.trace_boxes = !c->entity_boxes ? nullptr : ((c->clip_boxes && c->scene_clipped) ? c->d_trace_boxes.p : c->d_leaf_boxes.p);
+    S.cut_margin = (c->entity_boxes && c->walk_cut) ? c->cut_margin : -1.0;
+    const bool cut_to_leaves = S.trace_boxes == c->d_trace_boxes.p && S.cboxes && c->d_tcboxes.n == c->d_cboxes.n;
+    S.tcboxes = cut_to_leaves ? c->d_tcboxes.p : S.cboxes;
+    S.tcuse = cut_to_leaves ? c->d_tcuse.p : S.cuse;
+    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks)
+    const bool sh = c->lights_clear && S.trace_boxes == c->d_trace_boxes.p;
+    S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
+    S.scboxes = sh ? S.tcboxes : S.cboxes;
+    S.scuse = sh ? S.tcuse : S.cuse;
+    // the photon octree's counterpart of the wide records (gather_find_leaf), and the fast descent of the gather keys over it (build_photon_tables)
+    S.pn_planes = (c->wide_enabled && c->pn_planes_ok) ? 1 : 0;
+    S.pdescent = (S.pn_planes && c->pdescent_ready) ? c->d_pdescent.p : nullptr;
+    S.pjump = (S.pdescent && c->pjump_ready) ? c->d_pjump.p : nullptr;
+}
+
+// The tables derived from the photon map c->S points at: the sort key of the gather queries (k_pleaf_rank), the leaves' candidate lists and, for a
+// map that qualifies whatever the switches are now, the split records of the fast descent and its jump table (apply_switches decides on their use)
+static int build_photon_tables(gi_ctx* c)
+{
+    Scene& S = c->S;
+    S.pleaf_rank = nullptr; S.prank_leaf = nullptr; S.n_pleaf = 0; S.pcand_off = nullptr; S.pcand = nullptr; S.pcand_dc = nullptr;
+    c->pdescent_ready = false; c->pjump_ready = false;
     if (S.n_pnode <= 0) return GI_OK;
     if (c->d_pleaf_rank.n < (size_t)S.n_pnode) { HIP_TRY(c, c->d_pleaf_rank.alloc((size_t)S.n_pnode)); HIP_TRY(c, c->d_prank_leaf.alloc((size_t)S.n_pnode)); }
     if (!c->d_n_pleaf.p) HIP_TRY(c, c->d_n_pleaf.alloc(1));
@@ -1841,7 +1871,7 @@ static int install_pleaf_rank(gi_ctx* c)
         }
     }
     // the split records of the descent and the map's own box (gather_find_leaf_fast); the one-record-per-level layout only (children from the parent's planes)
-    if (c->fast_descent && S.pn_planes) {
+    if (c->fast_descent && c->pn_planes_ok) {
         if (c->d_pdescent.n < (size_t)S.n_pnode) HIP_TRY(c, c->d_pdescent.alloc((size_t)S.n_pnode));
         hipLaunchKernelGGL(k_pdescent, dim3((unsigned)((S.n_pnode + 255) / 256)), dim3(256), 0, c->stream, S.pnodes, S.n_pnode, c->d_pdescent.p);
         HIP_TRY(c, hipGetLastError());
@@ -1849,8 +1879,7 @@ static int install_pleaf_rank(gi_ctx* c)
         HIP_TRY(c, hipMemcpyAsync(&root, S.pnodes, sizeof(PNode), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (int k = 0; k < 3; k++) { S.pmap_bmin[k] = root.bmin[k]; S.pmap_bmax[k] = root.bmax[k]; }
-        S.pdescent = c->d_pdescent.p;
-        S.pjump = nullptr;
+        c->pdescent_ready = true;
         if (c->descent_jump) {
             double ext = 0.0, host[7];
             for (int k = 0; k < 3; k++) { ext = std::max(ext, root.bmax[k] - root.bmin[k]); S.pjump_cell[k] = (root.bmax[k] - root.bmin[k]) / (double)GI_PJUMP_N; S.pjump_inv[k] = (double)GI_PJUMP_N / (root.bmax[k] - root.bmin[k]); }
@@ -1866,15 +1895,86 @@ static int install_pleaf_rank(gi_ctx* c)
                 int bad = 1;
                 HIP_TRY(c, hipMemcpyAsync(&bad, c->d_pjump_aux.p + 6, sizeof bad, hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (!bad) S.pjump = c->d_pjump.p;
+                c->pjump_ready = !bad;
             }
         }
     }
     return GI_OK;
 }
 
+// A photon map now in d_pnodes / d_pranges / d_ph_pos / d_ph_dircol (gi_upload_photons, build_photon_map_on_device): the scene reads it from there
+static int install_photon_map(gi_ctx* c, int32_t n_node, int32_t n_photon, int32_t n_prange, bool planes_ok)
+{
+    Scene& S = c->S;
+    S.pnodes = c->d_pnodes.p; S.pranges = c->d_pranges.p; S.ph_pos = c->d_ph_pos.p; S.ph_dircol = c->d_ph_dircol.p;
+    S.n_pnode = n_node; S.n_photon = n_photon;
+    c->n_prange = n_prange;
+    c->pn_planes_ok = planes_ok;
+    const int rc = build_photon_tables(c);
+    apply_switches(c);
+    return rc;
+}
+
+// no photon map (a fresh PhotonMap): gather queries find nothing
+static void clear_photon_map(gi_ctx* c)
+{
+    Scene& S = c->S;
+    S.pnodes = nullptr; S.ph_pos = nullptr; S.ph_dircol = nullptr; S.n_pnode = 0; S.n_photon = 0; S.n_pleaf = 0;
+    c->pdescent_ready = false; c->pjump_ready = false;
+    apply_switches(c);
+}
+
 #include "gi_sort.inc"
 #include "gi_photon_build.inc"
+
+static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
+static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
+static constexpr size_t kLdsWideBoxes = (size_t)GI_LDS_WIDE_BOXES_BYTES;   // wide records + their content boxes: k_st_trace / k_st_shadow, one 1024-thread workgroup per CU
+
+// The instances of the k_st_* kernels with their dynamic LDS: every instance of a family is named once, in its table; its selector picks the
+// instance a launch runs (FEAT = scene_feat / scene_trace_feat, gi_device.h), and stream_grids walks the same tables.
+template <class Fn> struct StKernel { Fn fn; size_t lds; };
+using TraceK = StKernel<decltype(&k_st_trace<0, 0>)>;
+using ShadeK = StKernel<decltype(&k_st_shade<0, 0, 0>)>;
+using ShadowK = StKernel<decltype(&k_st_shadow<0, 0>)>;
+using FinishK = StKernel<decltype(&k_st_finish<0, 0, 0>)>;
+// k_st_trace<FEAT, WIDE>: FEAT 0, spheres, textures x per-node, wide; then the counting instance
+static constexpr TraceK kTrace[] = {
+    {k_st_trace<0, 0>, kLdsNodes}, {k_st_trace<0, 1>, kLdsWideBoxes}, {k_st_trace<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_st_trace<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
+    {k_st_trace<7, 0>, kLdsNodes}, {k_st_trace<7, 1>, kLdsWideBoxes}, {k_st_trace<0, 1, true>, kLdsWideBoxes}};
+static TraceK st_trace(int feat, bool wide, bool counting) { return counting ? kTrace[6] : kTrace[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
+// k_st_shade<FEAT, WIDE, DEFER>: FEAT 0, spheres, fog, textures x per-node, wide, wide with the shadow walks put off (one light; several lights)
+static constexpr ShadeK kShade[] = {
+    {k_st_shade<0, 0, 0>, kLdsNodes}, {k_st_shade<0, 1, 0>, kLdsNodes}, {k_st_shade<0, 1, 1>, kLdsNodes}, {k_st_shade<0, 1, 2>, kLdsNodes},
+    {k_st_shade<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 1>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 2>, kLdsNodes},
+    {k_st_shade<3, 0, 0>, kLdsNodes}, {k_st_shade<3, 1, 0>, kLdsNodes}, {k_st_shade<3, 1, 1>, kLdsNodes}, {k_st_shade<3, 1, 2>, kLdsNodes},
+    {k_st_shade<7, 0, 0>, kLdsNodes}, {k_st_shade<7, 1, 0>, kLdsNodes}, {k_st_shade<7, 1, 1>, kLdsNodes}, {k_st_shade<7, 1, 2>, kLdsNodes}};
+static int feat_row(int feat) { return feat == 7 ? 3 : (feat == 3 ? 2 : feat); }   // the levels 0, spheres, fog, textures
+static ShadeK st_shade(int feat, bool wide, int defer) { return kShade[feat_row(feat) * 4 + (wide ? 1 + defer : 0)]; }
+// k_st_shadow<FEAT, MULTI>: FEAT 0, spheres, fog, textures x one light, several lights; then the counting instances (one light, several)
+static constexpr ShadowK kShadow[] = {
+    {k_st_shadow<0, 0>, kLdsWideBoxes}, {k_st_shadow<0, 1>, kLdsWideBoxes}, {k_st_shadow<GI_FEAT_SPHERES, 0>, kLdsWideBoxes}, {k_st_shadow<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
+    {k_st_shadow<3, 0>, kLdsWideBoxes}, {k_st_shadow<3, 1>, kLdsWideBoxes}, {k_st_shadow<7, 0>, kLdsWideBoxes}, {k_st_shadow<7, 1>, kLdsWideBoxes},
+    {k_st_shadow<0, 0, true>, kLdsWideBoxes}, {k_st_shadow<0, 1, true>, kLdsWideBoxes}};
+static ShadowK st_shadow(int feat, bool many, bool counting) { return kShadow[(counting ? 4 : feat_row(feat)) * 2 + (many ? 1 : 0)]; }
+// k_st_finish<FEAT, WIDE, MODE>: FEAT 0, spheres, fog, textures x per-node, wide: a path per lane, a path per wave, a path per group of 16 lanes
+static constexpr FinishK kFinish[] = {
+    {k_st_finish<0, 0, 0>, kLdsNodes}, {k_st_finish<0, 1, 0>, kLdsNodes}, {k_st_finish<0, 1, 1>, kLdsFinishCoop}, {k_st_finish<0, 1, 2>, kLdsFinishCoop},
+    {k_st_finish<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_finish<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_finish<GI_FEAT_SPHERES, 1, 1>, kLdsFinishCoop}, {k_st_finish<GI_FEAT_SPHERES, 1, 2>, kLdsFinishCoop},
+    {k_st_finish<3, 0, 0>, kLdsNodes}, {k_st_finish<3, 1, 0>, kLdsNodes}, {k_st_finish<3, 1, 1>, kLdsFinishCoop}, {k_st_finish<3, 1, 2>, kLdsFinishCoop},
+    {k_st_finish<7, 0, 0>, kLdsNodes}, {k_st_finish<7, 1, 0>, kLdsNodes}, {k_st_finish<7, 1, 1>, kLdsFinishCoop}, {k_st_finish<7, 1, 2>, kLdsFinishCoop}};
+static FinishK st_finish(int feat, bool wide, int mode) { return kFinish[feat_row(feat) * 4 + (wide ? 1 + mode : 0)]; }
+// k_st_gather / k_st_gather_wave<COUNT>: no template argument of the scene's, no dynamic LDS
+static auto st_gather(bool counting) { return counting ? k_st_gather<true> : k_st_gather<false>; }
+static auto st_gather_wave(bool counting) { return counting ? k_st_gather_wave<true> : k_st_gather_wave<false>; }
+
+// more than 64 KB of dynamic LDS has to be asked for, per kernel (and per device: the attribute belongs to the loaded code object); a refusal
+// (a part with less LDS than gfx950's 160 KB per CU) would make every later launch of the kernel fail: it is kept to be reported by name
+template <class K, size_t N> static void ask_for_lds(const K (&ks)[N], int& refused)
+{
+    for (const K& k : ks)
+        if (k.lds > 64 * 1024 && hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) != hipSuccess) refused = (int)k.lds;
+}
 
 extern "C" {
 
@@ -1953,24 +2053,6 @@ int gi_set_stream(gi_ctx* c, void* s)
     return GI_OK;
 }
 
-// Which of the walks' short cuts are on (all of them leave every result as it is: DESIGN.md section 4): entity boxes; for the closest-hit walk
-// the boxes cut to the leaves, and no look behind the best hit.  gi_set_entity_boxes(ctx, 0) turns all three off: the walks then ask what the reference asks.
-static void set_walk_shortcuts(gi_ctx* c)
-{
-    Scene& S = c->S;
-    S.leaf_boxes = c->entity_boxes ? c->d_leaf_boxes.p : nullptr;
-    S.trace_boxes = !c->entity_boxes ? nullptr : ((c->clip_boxes && c->scene_clipped) ? c->d_trace_boxes.p : c->d_leaf_boxes.p);
-    S.cut_margin = (c->entity_boxes && c->walk_cut) ? c->cut_margin : -1.0;
-    const bool cut_to_leaves = S.trace_boxes == c->d_trace_boxes.p && S.cboxes && c->d_tcboxes.n == c->d_cboxes.n;
-    S.tcboxes = cut_to_leaves ? c->d_tcboxes.p : S.cboxes;
-    S.tcuse = cut_to_leaves ? c->d_tcuse.p : S.cuse;
-    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks)
-    const bool sh = c->lights_clear && S.trace_boxes == c->d_trace_boxes.p;
-    S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
-    S.scboxes = sh ? S.tcboxes : S.cboxes;
-    S.scuse = sh ? S.tcuse : S.cuse;
-}
-
 int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
 {
     if (!c) return GI_E_INVALID;
@@ -2005,15 +2087,11 @@ int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
     Scene& S = c->S;
     S.tnodes = c->d_tnodes.p; S.leaf_refs = c->d_refs.p; S.leaf_tris = c->d_leaf_tris.p; S.tris = c->d_tris.p; S.shade = c->d_shade.p;
     S.mats = c->d_mats.p; S.lights = c->d_lights.p;
-    set_walk_shortcuts(c);
     S.n_node = H.n_node; S.n_tri = H.n_tri; S.n_light = H.n_light;
     for (int k = 0; k < 3; k++) { S.root_bmin[k] = H.tnodes[0].bmin[k]; S.root_bmax[k] = H.tnodes[0].bmax[k]; }
     S.n_wnode = (int32_t)H.wnodes.size();
-    S.wnodes = (c->wide_enabled && S.n_wnode > 0) ? c->d_wnodes.p : nullptr;
     S.wleaf_id = c->d_wleaf_id.p;
-    S.cboxes = (c->cull_enabled && S.wnodes && !H.cboxes.empty()) ? c->d_cboxes.p : nullptr;
     S.cuse = c->d_cuse.p;
-    set_walk_shortcuts(c);
     S.tri_uv = c->d_tri_uv.p; S.texs = c->d_texs.p; S.tex_pixels = c->d_tex_pixels.p; S.tex_lut = c->d_tex_lut.p; S.n_tex = H.n_tex();
     S.has_spheres = 0;
     S.fogs = c->d_fogs.p; S.fog_grid = c->d_fog_grid.p; S.n_fog = H.n_fog();
@@ -2022,14 +2100,14 @@ int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
     // the photon map stays as it is: the reference keeps a valid map when the scene is edited and rebuilt (include/raytracer.h:56-72);
     // RayTracer::setScene, which allocates a fresh PhotonMap (include/raytracer.h:38), is gi_upload_scene + gi_clear_photons
     c->have_scene = true;
+    apply_switches(c);
     return GI_OK;
 }
 
 int gi_clear_photons(gi_ctx* c)
 {
     if (!c) return GI_E_INVALID;
-    Scene& S = c->S;
-    S.pnodes = nullptr; S.ph_pos = nullptr; S.ph_dircol = nullptr; S.n_pnode = 0; S.n_photon = 0; S.n_pleaf = 0;
+    clear_photon_map(c);
     return GI_OK;
 }
 
@@ -2041,21 +2119,15 @@ int gi_upload_photons(gi_ctx* c, const gi_photon_map_desc* d)
     std::string err;
     if (!layout_photons(d, H, err)) return fail(c, GI_E_INVALID, err);
     HIP_TRY(c, hipSetDevice(c->device));
-    Scene& S = c->S;
     if (H.n_node == 0) {
-        S.pnodes = nullptr; S.ph_pos = nullptr; S.ph_dircol = nullptr; S.n_pnode = 0; S.n_photon = 0; S.n_pleaf = 0;
+        clear_photon_map(c);
         return GI_OK;
     }
     HIP_TRY(c, c->d_pnodes.upload(H.nodes));
     HIP_TRY(c, c->d_pranges.upload(H.ranges));
-    c->n_prange = (int32_t)H.ranges.size();
     HIP_TRY(c, c->d_ph_pos.upload(H.pos));
     HIP_TRY(c, c->d_ph_dircol.upload(H.dircol));
-    S.pnodes = c->d_pnodes.p; S.pranges = c->d_pranges.p; S.ph_pos = c->d_ph_pos.p; S.ph_dircol = c->d_ph_dircol.p;
-    S.n_pnode = H.n_node; S.n_photon = H.n_photon;
-    c->pn_planes_ok = H.planes_ok;
-    S.pn_planes = (c->wide_enabled && c->pn_planes_ok) ? 1 : 0;
-    return install_pleaf_rank(c);
+    return install_photon_map(c, H.n_node, H.n_photon, (int32_t)H.ranges.size(), H.planes_ok);
 }
 
 int gi_local_rows(const gi_render_params* p) { return local_rows(p); }
@@ -2100,26 +2172,15 @@ static void stage_end(gi_ctx* c)
     c->ev_used += 2;
 }
 
-static const size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
-static const size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
-static const size_t kLdsWideBoxes = (size_t)GI_LDS_WIDE_BOXES_BYTES;   // wide records + their content boxes: k_st_trace / k_st_shadow, one 1024-thread workgroup per CU
 static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process may drive several devices (gi_group_*)
 {
     StreamGrids& g = c->grids;
     if (!g.trace) {
-        // more than 64 KB of dynamic LDS has to be asked for, per kernel (and per device: the attribute belongs to the loaded code object)
-        const void* big[] = {(const void*)k_st_trace<0, 1, true>, (const void*)k_st_shadow<0, 0, true>, (const void*)k_st_shadow<0, 1, true>,
-                             (const void*)k_st_trace<0, 1>, (const void*)k_st_trace<GI_FEAT_SPHERES, 1>, (const void*)k_st_trace<7, 1>,
-                             (const void*)k_st_shadow<0, 0>, (const void*)k_st_shadow<GI_FEAT_SPHERES, 0>, (const void*)k_st_shadow<3, 0>, (const void*)k_st_shadow<7, 0>,
-                             (const void*)k_st_shadow<0, 1>, (const void*)k_st_shadow<GI_FEAT_SPHERES, 1>, (const void*)k_st_shadow<3, 1>, (const void*)k_st_shadow<7, 1>};
-        // a refusal here (a part with less LDS than gfx950's 160 KB per CU) would make every later launch of these kernels fail: say so by name
-        for (const void* k : big) if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWideBoxes) != hipSuccess) g.lds_refused = (int)kLdsWideBoxes;
-        const void* coop[] = {(const void*)k_st_finish<0, 1, 1>, (const void*)k_st_finish<0, 1, 2>, (const void*)k_st_finish<GI_FEAT_SPHERES, 1, 1>, (const void*)k_st_finish<GI_FEAT_SPHERES, 1, 2>,
-                              (const void*)k_st_finish<3, 1, 1>, (const void*)k_st_finish<3, 1, 2>, (const void*)k_st_finish<7, 1, 1>, (const void*)k_st_finish<7, 1, 2>};
-        for (const void* k : coop) if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsFinishCoop) != hipSuccess) g.lds_refused = (int)kLdsFinishCoop;
-        g.init = grid_for(c, (const void*)k_wf_init); g.trace = grid_for(c, (const void*)k_st_trace<7, 1>, kLdsWideBoxes, GI_TRACE_BLOCK);
-        g.shade = grid_for(c, (const void*)k_st_shade<7, 1, 0>, kLdsNodes, GI_SHADE_BLOCK); g.shadow = grid_for(c, (const void*)k_st_shadow<7, 1>, kLdsWideBoxes, GI_SHADOW_BLOCK); g.gather = grid_for(c, (const void*)k_st_gather<false>); g.accum = grid_for(c, (const void*)k_st_accum);
-        g.compact = grid_for(c, (const void*)k_st_compact, 0, 256); g.finish = grid_for(c, (const void*)k_st_finish<7, 1, 0>, kLdsNodes, GI_FINISH_BLOCK); g.ad_gen = grid_for(c, (const void*)k_ad_gen); g.ad_accum = grid_for(c, (const void*)k_ad_accum);
+        auto grid_of = [&](const auto& k, int block) { return grid_for(c, (const void*)k.fn, k.lds, block); };
+        ask_for_lds(kTrace, g.lds_refused); ask_for_lds(kShade, g.lds_refused); ask_for_lds(kShadow, g.lds_refused); ask_for_lds(kFinish, g.lds_refused);
+        g.pix = grid_for(c, (const void*)k_pix_init); g.trace = grid_of(st_trace(7, true, false), GI_TRACE_BLOCK);
+        g.shade = grid_of(st_shade(7, true, 0), GI_SHADE_BLOCK); g.shadow = grid_of(st_shadow(7, true, false), GI_SHADOW_BLOCK); g.gather = grid_for(c, (const void*)st_gather(false)); g.accum = grid_for(c, (const void*)k_st_accum);
+        g.compact = grid_for(c, (const void*)k_st_compact, 0, 256); g.finish = grid_of(st_finish(7, true, 0), GI_FINISH_BLOCK); g.ad_gen = grid_for(c, (const void*)k_ad_gen); g.ad_accum = grid_for(c, (const void*)k_ad_accum);
     }
     return g;
 }
@@ -2166,6 +2227,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
     if (G.lds_refused) return fail(c, GI_E_HIP, "render: the device refused " + std::to_string(G.lds_refused) + " bytes of dynamic LDS per workgroup (the traversal kernels are laid out for gfx950's 160 KB per CU)");
     hipStream_t st = c->stream;
     const bool wide = c->S.wnodes != nullptr;
+    const int feat = scene_feat(c->S), trace_feat = scene_trace_feat(c->S);
     // executed-work counters: compiled for the instances the BASELINE scenes run (triangles only, no medium, no texture, shadow walks put off)
     const bool counting = c->count_stream;
     if (counting && !(wide && defers_shadows(c) && !c->S.has_spheres && c->S.n_fog == 0 && c->S.n_tex == 0))
@@ -2193,7 +2255,6 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         uint32_t* qcont_out = q_cont[ping];
         const uint32_t* qcont_in = q_cont[ping ^ 1];
         if (exhausted && n_new == 0 && n_cont <= c->finish_threshold && !counting) {   // (a counted frame runs its stragglers through the counting passes)
-            const bool sphf = c->S.has_spheres != 0, fogf = c->S.n_fog > 0, texf = c->S.n_tex > 0;
             if (c->d_fin_cnt.n < 16) HIP_TRY(c, c->d_fin_cnt.alloc(16));
             HIP_TRY(c, hipMemsetAsync(c->d_fin_cnt.p, 0, 16 * sizeof(unsigned int), st));
             const uint32_t* fq_in = qcont_in;
@@ -2203,14 +2264,13 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
                 const int lanes = c->finish_plan[k].first, vertices = k + 1 == n_stage ? GI_MAX_DEPTH + 1 : c->finish_plan[k].second;
                 const unsigned int* n_in_dev = k == 0 ? nullptr : c->d_fin_cnt.p + (k - 1);
                 stage_begin(c, STG_FINISH);
-                auto fin = [&](auto mode) {
-                    constexpr int M = decltype(mode)::value;
-                    hipLaunchKernelGGL(texf ? (wide ? k_st_finish<7, 1, M> : k_st_finish<7, 0, 0>) : wide ? (fogf ? k_st_finish<3, 1, M> : (sphf ? k_st_finish<GI_FEAT_SPHERES, 1, M> : k_st_finish<0, 1, M>)) : (fogf ? k_st_finish<3, 0, 0> : (sphf ? k_st_finish<GI_FEAT_SPHERES, 0, 0> : k_st_finish<0, 0, 0>)), dim3(G.finish), dim3(GI_FINISH_BLOCK),
-                                       M == 0 ? kLdsNodes : kLdsFinishCoop, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0,
+                auto fin = [&](int mode) {
+                    const FinishK fin_k = st_finish(feat, wide, mode);
+                    hipLaunchKernelGGL(fin_k.fn, dim3(G.finish), dim3(GI_FINISH_BLOCK), fin_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0,
                                        fq_in, n_in_dev, n_cont, lanes, vertices, fq_out, c->d_fin_cnt.p + k, lbuf, (wave_factor << 16) | (c->coop_factor & 0xffffu));
                 };
-                fin(std::integral_constant<int, 0>());
-                if (wide && lanes <= 0) { fin(std::integral_constant<int, 1>()); fin(std::integral_constant<int, 2>()); launches += 2; }
+                fin(0);
+                if (wide && lanes <= 0) { fin(1); fin(2); launches += 2; }
                 stage_end(c);
                 launches++;
                 uint32_t* t = const_cast<uint32_t*>(fq_in); fq_in = fq_out; fq_out = t;   // both are this chunk's continuation queues
@@ -2219,14 +2279,14 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         }
         HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(StreamCtl), st));
         uint32_t* qfree_out = q_free[ping];
-        const bool sph = c->S.has_spheres != 0, fog = c->S.n_fog > 0, tex = c->S.n_tex > 0;
         if (G.trace > GI_MAX_PRODUCER_BLOCKS || G.shade > GI_MAX_PRODUCER_BLOCKS) return fail(c, GI_E_STATE, "render: more producer workgroups than per-workgroup counters");
         unsigned int* bc = c->d_blkcnt.p;
         const size_t bc_bytes = (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE * sizeof(unsigned int);
         // trace: hits -> staging 0, finished paths -> staging 1; compacted into the shade queue and the head of the free list
         HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
         StreamCounters* const sc = counting ? c->d_stream_cnt.p : nullptr;
-        stage_begin(c, STG_TRACE); hipLaunchKernelGGL(counting ? (k_st_trace<0, 1, true>) : tex ? (wide ? k_st_trace<7, 1> : k_st_trace<7, 0>) : wide ? (sph ? k_st_trace<GI_FEAT_SPHERES, 1> : k_st_trace<0, 1>) : (sph ? k_st_trace<GI_FEAT_SPHERES, 0> : k_st_trace<0, 0>), dim3(G.trace), dim3(GI_TRACE_BLOCK), wide ? kLdsWideBoxes : kLdsNodes, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
+        const TraceK trace_k = st_trace(trace_feat, wide, counting);
+        stage_begin(c, STG_TRACE); hipLaunchKernelGGL(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
                            c->d_stage[0].p, c->d_stage[1].p, lbuf, c->refill_min, sc); stage_end(c);
         {
             CompactJob job;
@@ -2258,18 +2318,14 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         // shade: continuing rays (slot + key) -> staging 0 / 1, gather queries (slot + position) -> staging 2 / pos, finished paths -> staging 3
         HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
         const bool many = c->S.n_light > 1;
-        auto shade_kernel = shq ? (many ? (tex ? k_st_shade<7, 1, 2> : fog ? k_st_shade<3, 1, 2> : sph ? k_st_shade<GI_FEAT_SPHERES, 1, 2> : k_st_shade<0, 1, 2>)
-                                        : (tex ? k_st_shade<7, 1, 1> : fog ? k_st_shade<3, 1, 1> : sph ? k_st_shade<GI_FEAT_SPHERES, 1, 1> : k_st_shade<0, 1, 1>))
-                                : tex ? (wide ? k_st_shade<7, 1, 0> : k_st_shade<7, 0, 0>) : wide ? (fog ? k_st_shade<3, 1, 0> : (sph ? k_st_shade<GI_FEAT_SPHERES, 1, 0> : k_st_shade<0, 1, 0>)) : (fog ? k_st_shade<3, 0, 0> : (sph ? k_st_shade<GI_FEAT_SPHERES, 0, 0> : k_st_shade<0, 0, 0>));
-        stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_kernel, dim3(G.shade), dim3(GI_SHADE_BLOCK), kLdsNodes, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, q_shade_use, ctl, bc, c->d_segs.p,
+        const ShadeK shade_k = st_shade(feat, wide, shq ? (many ? 2 : 1) : 0);
+        stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, q_shade_use, ctl, bc, c->d_segs.p,
                            c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, c->d_stage[3].p, lbuf, shq, q_orig);
         stage_end(c);
         if (shq) {   // the walks it put off; before the gather of the same vertices (the order in which a path's radiance is summed)
+            const ShadowK shadow_k = st_shadow(feat, many, counting);
             stage_begin(c, STG_SHADOW);
-            hipLaunchKernelGGL(counting ? (many ? (k_st_shadow<0, 1, true>) : (k_st_shadow<0, 0, true>))
-                               : many ? (tex ? k_st_shadow<7, 1> : fog ? k_st_shadow<3, 1> : sph ? k_st_shadow<GI_FEAT_SPHERES, 1> : k_st_shadow<0, 1>)
-                                      : (tex ? k_st_shadow<7, 0> : fog ? k_st_shadow<3, 0> : sph ? k_st_shadow<GI_FEAT_SPHERES, 0> : k_st_shadow<0, 0>), dim3(G.shadow), dim3(GI_SHADOW_BLOCK), kLdsWideBoxes, st,
-                               c->S, F.seed, pool, shq, ctl, lbuf, c->refill_min, sc);
+            hipLaunchKernelGGL(shadow_k.fn, dim3(G.shadow), dim3(GI_SHADOW_BLOCK), shadow_k.lds, st, c->S, F.seed, pool, shq, ctl, lbuf, c->refill_min, sc);
             stage_end(c);
             launches++;
         }
@@ -2304,9 +2360,9 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
             stage_end(c);
             stage_begin(c, STG_GATHER);
             if (c->S.pcand && n_gather < c->gather_wave_below)      // few queries: a wave each
-                hipLaunchKernelGGL(counting ? (k_st_gather_wave<true>) : (k_st_gather_wave<false>), dim3(std::min<uint32_t>((uint32_t)(5 * c->n_cu), (n_gather + 3u) / 4u)), dim3(GI_GW_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
+                hipLaunchKernelGGL(st_gather_wave(counting), dim3(std::min<uint32_t>((uint32_t)(5 * c->n_cu), (n_gather + 3u) / 4u)), dim3(GI_GW_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
             else
-                hipLaunchKernelGGL(counting ? (k_st_gather<true>) : (k_st_gather<false>), dim3(G.gather), dim3(GI_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
+                hipLaunchKernelGGL(st_gather(counting), dim3(G.gather), dim3(GI_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
             stage_end(c);
             launches += 2;
         }
@@ -2372,9 +2428,9 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
         c->stream_shaded = 0;
     }
     HIP_TRY(c, hipEventRecord(c->ev0, st));
-    hipLaunchKernelGGL(k_wf_init, dim3(G.init), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
+    hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
     if (c->d_pixtab.n < n_pix) HIP_TRY(c, c->d_pixtab.alloc(n_pix));
-    hipLaunchKernelGGL(k_pixel_table, dim3(G.init), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
+    hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
     launches += 2;
     for (int s0 = 0; s0 < spp; s0 += chunk) {
         const int ns = std::min(chunk, spp - s0);
@@ -2424,7 +2480,7 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     int launches = 0;
     c->ev_used = 0; c->ev_stage.clear();
     HIP_TRY(c, hipEventRecord(c->ev0, st));
-    hipLaunchKernelGGL(k_wf_init, dim3(G.init), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
+    hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
     launches++;
     bool any = F.max_samples > 0 && F.min_samples > 0;
     if (!any) {   // 0 samples per pixel still has to write the initial colour
@@ -2484,11 +2540,7 @@ int gi_set_wide_nodes(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
     c->wide_enabled = enable != 0;
-    c->S.wnodes = (c->wide_enabled && c->S.n_wnode > 0) ? c->d_wnodes.p : nullptr;
-    c->S.cboxes = (c->cull_enabled && c->S.wnodes && c->d_cboxes.n > 1) ? c->d_cboxes.p : nullptr;
-    set_walk_shortcuts(c);
-    c->S.pn_planes = (c->wide_enabled && c->pn_planes_ok) ? 1 : 0;   // the photon octree's counterpart (gather_find_leaf)
-    c->S.pdescent = (c->S.pn_planes && c->fast_descent && c->S.n_pnode > 0 && c->d_pdescent.n >= (size_t)c->S.n_pnode) ? c->d_pdescent.p : nullptr;
+    apply_switches(c);
     return (c->S.wnodes ? 1 : 0) | (c->S.pn_planes ? 2 : 0);
 }
 
@@ -2496,8 +2548,7 @@ int gi_set_content_culling(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
     c->cull_enabled = enable != 0;
-    c->S.cboxes = (c->cull_enabled && c->S.wnodes && c->d_cboxes.n > 1) ? c->d_cboxes.p : nullptr;
-    set_walk_shortcuts(c);
+    apply_switches(c);
     return c->S.cboxes ? 1 : 0;
 }
 
@@ -2505,7 +2556,7 @@ int gi_set_entity_boxes(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
     c->entity_boxes = enable != 0;
-    if (c->have_scene) set_walk_shortcuts(c);
+    apply_switches(c);
     return c->S.leaf_boxes ? 1 : 0;
 }
 

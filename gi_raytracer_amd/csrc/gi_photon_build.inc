@@ -139,9 +139,8 @@ struct PBHostNode { double lo[3], hi[3]; int32_t first_child; int32_t seg; };   
 
 int build_photon_map_on_device(gi_ctx* c, const double* d_ph, int32_t n, const double* box6)
 {
-    Scene& S = c->S;
     hipStream_t st = c->stream;
-    S.pnodes = nullptr; S.ph_pos = nullptr; S.ph_dircol = nullptr; S.n_pnode = 0; S.n_photon = 0; S.n_pleaf = 0;
+    clear_photon_map(c);
     if (n <= 0) return GI_OK;
     const int grid = c->n_cu * 4;
     DevBuf<uint32_t> d_order[2], d_keys[2], d_seg_start, d_act, d_counts;
@@ -267,12 +266,7 @@ int build_photon_map_on_device(gi_ctx* c, const double* d_ph, int32_t n, const d
     hipLaunchKernelGGL(k_pb_neighbours, dim3(grid), dim3(256), 0, st, c->d_pnodes.p, d_leaf_rec.p, (uint32_t)leaf_rec.size(), d_leaf_first.p, d_leaf_cnt.p, c->d_pranges.p, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
-    S.pnodes = c->d_pnodes.p; S.pranges = c->d_pranges.p; S.ph_pos = c->d_ph_pos.p; S.ph_dircol = c->d_ph_dircol.p;
-    S.n_pnode = N; S.n_photon = n_final;
-    c->n_prange = std::max(n_rng, 1);
-    c->pn_planes_ok = planes_ok;
-    S.pn_planes = (c->wide_enabled && c->pn_planes_ok) ? 1 : 0;
-    return install_pleaf_rank(c);
+    return install_photon_map(c, N, n_final, std::max(n_rng, 1), planes_ok);
 }
 
 }  // namespace

@@ -161,6 +161,22 @@ def test_wide_and_per_node_frames_are_identical():
     assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
+def test_photon_map_uploaded_with_wide_walk_off_keeps_its_own_descent():
+    """A photon map uploaded while the wide walk is off gets its fast-descent tables all the same: turning the wide walk back on keys the
+    gather queries with that map's records, not with those of the larger map before it.  The frame is the one a fresh context renders."""
+    scene = pc.load_scene("caustics")
+    rt = gi.RayTracer(0).setScene(scene)
+    rt.tracePhotons(20000)
+    assert not rt.set_wide_nodes(False)
+    rt.tracePhotons(3000, seed=7)
+    assert rt.set_wide_nodes(True) and rt.photon_planes
+    a = rt.run(96, 54, min_samples=8, max_samples=8)
+    fresh = gi.RayTracer(0).setScene(scene)
+    fresh.tracePhotons(3000, seed=7)
+    b = fresh.run(96, 54, min_samples=8, max_samples=8)
+    assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
 def test_content_culling_changes_nothing(setup):
     """gi_set_content_culling: the walk with and without the content-box test of the children (gi_device.h: content_cull) -- same hits, same
     visibility, same frame, bit for bit; on every fixture scene, and on the scenes with stochastic alpha, fog and a large tree below."""
