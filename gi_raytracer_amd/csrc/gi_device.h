@@ -1683,6 +1683,93 @@ GI_HD void g_acc(GatherAcc& a, V3 pp, const double* dc)
         else { a.s_eq = a.s_eq + contrib; a.c_eq++; a.r_eq = d2 > a.r_eq ? d2 : a.r_eq; }
     }
 }
+// Pass 1 of the wave-cooperative gather (k_st_gather): tau = the K-th smallest float key, K = min(GI_GATHER_K, ncand), without the heap.
+// A lane keeps its 32 smallest keys sorted in 32 registers and folds the candidates in 32 at a time: sort the 32 new keys, take
+// min(best[i], new[31 - i]) -- the 32 smallest of the 64, as a bitonic sequence -- and merge.  tau is a property of the SET of keys, so
+// any order of groups gives the same number.  The groups are taken from the last candidate back to the first, which puts the one short
+// group (ncand % 32 keys) first: it is sorted on its own by an 8- or 16-key network, its keys become best[0..], the rest stays INFINITY.
+GI_HD void kce(float& a, float& b) { const float lo = fminf(a, b), hi = fmaxf(a, b); a = lo; b = hi; }
+// Batcher's odd-even merge sort of N = 8, 16, 32 keys: 19, 63, 191 compare-exchanges (the bitonic sorter takes 24, 80, 240)
+template <int N>
+GI_HD void ksort(float (&v)[N])
+{
+#pragma unroll
+    for (int p = 1; p < N; p <<= 1)
+#pragma unroll
+        for (int k = p; k >= 1; k >>= 1)
+#pragma unroll
+            for (int j = k % p; j <= N - 1 - k; j += 2 * k)
+#pragma unroll
+                for (int i = 0; i <= (k - 1 < N - 1 - j - k ? k - 1 : N - 1 - j - k); i++)
+                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) kce(v[i + j], v[i + j + k]);
+}
+GI_HD void kmerge32(float (&v)[32])   // bitonic sequence -> ascending
+{
+#pragma unroll
+    for (int j = 16; j > 0; j >>= 1)
+#pragma unroll
+        for (int i = 0; i < 32; i++) {
+            const int l = i ^ j;
+            if (l > i) kce(v[i], v[l]);
+        }
+}
+// the first group: keys [k0, k0 + t) of the current chunk, t <= N, padded with INFINITY to N and sorted into best[0, N)
+template <int N, class Key>
+GI_HD void ksel_first(float (&best)[32], Key key, int k0, int t)
+{
+    float nk[N];
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const int kk = k < t ? k0 + k : k0 + t - 1;   // wave-uniform clamp: no read past the chunk
+        const float v = key(kk);
+        nk[k] = k < t ? v : INFINITY;
+    }
+    ksort<N>(nk);
+#pragma unroll
+    for (int k = 0; k < N; k++) best[k] = nk[k];
+}
+// tau of pass 1.  stage(c0, m) brings candidates [c0, c0 + m) of the leaf in (m <= 64), key(k) is the float key of the k-th of them.
+// Chunks of 64 go from the last to the first, so chunk 0 is the one staged last; within a chunk the groups of 32 go from the last to the first.
+template <class Stage, class Key>
+GI_HD float ksel_tau(int ncand, Stage stage, Key key)
+{
+    float best[32];
+#pragma unroll
+    for (int k = 0; k < 32; k++) best[k] = INFINITY;
+    bool first = true;
+    for (int c0 = (ncand - 1) & ~63; c0 >= 0; c0 -= 64) {
+        const int m = ncand - c0 < 64 ? ncand - c0 : 64;
+        stage(c0, m);
+        for (int k0 = (m - 1) & ~31; k0 >= 0; k0 -= 32) {
+            if (first) {
+                const int t = m - k0;   // 1 .. 32: ncand % 32 keys, or 32
+                if (t <= 8) ksel_first<8>(best, key, k0, t);
+                else if (t <= 16) ksel_first<16>(best, key, k0, t);
+                else ksel_first<32>(best, key, k0, t);
+                first = false;
+                continue;
+            }
+            float nk[32];
+#pragma unroll
+            for (int k = 0; k < 32; k++) nk[k] = key(k0 + k);
+            ksort<32>(nk);
+#pragma unroll
+            for (int k = 0; k < 32; k++) best[k] = fminf(best[k], nk[31 - k]);
+            // after the last group only the largest of the 32 smallest is wanted, which does not need them in order
+            if (c0 != 0 || k0 != 0) kmerge32(best);
+        }
+    }
+    // (what the heap's root holds after pass 1 of gather_in_leaf)
+    float tau = 0.0f;
+    if (ncand < 32) {
+#pragma unroll
+        for (int k = 0; k < 32; k++) tau = best[k] < INFINITY ? fmaxf(tau, best[k]) : tau;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 32; k++) tau = fmaxf(tau, best[k]);   // keys are squared distances: >= 0
+    }
+    return tau;
+}
 // false: float keys tie across rank 32 -- the caller has to resolve the tie group with exact distances (pass 3)
 GI_HD bool g_end(const GatherAcc& a, V3& res)
 {

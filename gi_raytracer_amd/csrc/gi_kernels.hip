@@ -1094,33 +1094,10 @@ __global__ __launch_bounds__(256) void k_st_compact(Scene S, CompactJob job, con
 #ifndef GI_GATHER_WAVES
 #define GI_GATHER_WAVES 4      // waves per SIMD the gather kernel is compiled for (launch bound)
 #endif
-// Pass 1 of the cooperative path keeps a lane's 32 smallest keys sorted in 32 registers and folds the candidates in 32 at a time:
-// sort the 32 new keys (odd-even merge sort network), take min(best[i], new[31 - i]) -- the 32 smallest of the 64, as a bitonic sequence --
-// and merge.  18 branch-free instructions per candidate; the LDS heap costs ~55, because with 64 lanes some lane always has to
-// sift, so the wave pays a full sift for nearly every candidate.  The result (tau = 32nd smallest float key) is the same number.
-__device__ __forceinline__ void kce(float& a, float& b) { const float lo = fminf(a, b), hi = fmaxf(a, b); a = lo; b = hi; }
-__device__ __forceinline__ void ksort32(float (&v)[32])   // Batcher's odd-even merge sort: 191 compare-exchanges (the bitonic sorter takes 240)
-{
-#pragma unroll
-    for (int p = 1; p < 32; p <<= 1)
-#pragma unroll
-        for (int k = p; k >= 1; k >>= 1)
-#pragma unroll
-            for (int j = k % p; j <= 31 - k; j += 2 * k)
-#pragma unroll
-                for (int i = 0; i <= (k - 1 < 31 - j - k ? k - 1 : 31 - j - k); i++)
-                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) kce(v[i + j], v[i + j + k]);
-}
-__device__ __forceinline__ void kmerge32(float (&v)[32])   // bitonic sequence -> ascending
-{
-#pragma unroll
-    for (int j = 16; j > 0; j >>= 1)
-#pragma unroll
-        for (int i = 0; i < 32; i++) {
-            const int l = i ^ j;
-            if (l > i) kce(v[i], v[l]);
-        }
-}
+// Pass 1 of the cooperative path keeps a lane's 32 smallest keys sorted in registers and folds the candidates in 32 at a time
+// (ksel_tau, gi_device.h): 18 branch-free instructions per candidate; the LDS heap costs ~55, because with 64 lanes some lane always has
+// to sift, so the wave pays a full sift for nearly every candidate.  The result (tau = 32nd smallest float key) is the same number.
+static_assert(GI_GCHUNK == 64, "ksel_tau stages the candidates 64 at a time");
 template <bool COUNT>
 __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S, PathPool pool, const uint32_t* keys, const uint32_t* vals, uint32_t n_in,
                                                                          const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
@@ -1168,97 +1145,66 @@ __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S
         GatherAcc a;
         const uint32_t gslot = valid ? vals[i] : 0u;
         g_begin(a, valid ? ld3(pool.hit[gslot].hpos) : v3(0, 0, 0), valid ? ld3(pool.gath[gslot].gdir) : v3(0, 0, 0), heap, 64, ncand);
-        float best[32];
-#pragma unroll
-        for (int k = 0; k < 32; k++) best[k] = INFINITY;
-        for (int pass = 0; pass < 2; pass++) {
-            // the leaf's candidates as one sequence (its ranges back to back, the order gather_in_leaf visits them), 64 per step
-            for (int32_t c0 = 0; c0 < ncand; c0 += GI_GCHUNK) {
-                const int32_t m = min((int32_t)GI_GCHUNK, ncand - c0);
-                __builtin_amdgcn_wave_barrier();
-                if ((int32_t)lane < m) {
-                    const double* pp;
-                    const double* dc;
-                    if (S.pcand) {
-                        const size_t at = (size_t)S.pcand_off[rank0] + (size_t)(c0 + (int32_t)lane);
-                        pp = S.pcand + at * 3; dc = S.pcand_dc + at * 6;
-                    } else {
-                        int32_t off = c0 + (int32_t)lane, r = 0;
-                        while (off >= ranges[r].count) { off -= ranges[r].count; r++; }   // r < n_ranges: off < ncand = sum of the counts
-                        const size_t ph = (size_t)(ranges[r].first + off);
-                        pp = S.ph_pos + ph * 3; dc = S.ph_dircol + ph * 6;
-                    }
-                    cand[lane][0] = pp[0]; cand[lane][1] = pp[1]; cand[lane][2] = pp[2];
-                    if (pass == 1)
-                        for (int k = 0; k < 6; k++) cand[lane][3 + k] = dc[k];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (pass == 0) {
-                    for (int32_t k0 = 0; k0 < m; k0 += 32) {
-                        float nk[32];
-#pragma unroll
-                        for (int k = 0; k < 32; k++) {
-                            const int kk = k0 + k < m ? k0 + k : m - 1;                 // wave-uniform clamp: no out-of-range LDS read
-                            const double* q = cand[kk];
-                            const float key = (float)len2(v3(q[0], q[1], q[2]) - a.pos);   // same expression as g_key
-                            nk[k] = k0 + k < m ? key : INFINITY;
-                        }
-                        ksort32(nk);
-                        // the first 32 keys are the best so far as they are; after the last group only the largest of the 32 smallest is wanted,
-                        // which does not need them in order (wave-uniform conditions: the lanes of the wave scan the same candidates)
-                        const bool first_group = c0 == 0 && k0 == 0, last_group = c0 + (int32_t)GI_GCHUNK >= ncand && k0 + 32 >= m;
-                        if (first_group) {
-#pragma unroll
-                            for (int k = 0; k < 32; k++) best[k] = nk[k];
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 32; k++) best[k] = fminf(best[k], nk[31 - k]);
-                            if (!last_group) kmerge32(best);
-                        }
-                    }
-                } else if (valid) {
-                    // g_acc per candidate, with the rare case set aside: a candidate whose key EQUALS tau (the 32nd smallest itself; one per
-                    // query, more only when float keys tie) is some lane's business for nearly every candidate of the wave, so its branch --
-                    // a sum of its own, a count, a running maximum -- would run for nearly every candidate.  The loop only notes where such
-                    // candidates are; they are added afterwards, in candidate order, by the same g_acc.
-                    int n_eq = 0;
-                    int32_t k_eq = 0;
-                    for (int32_t k = 0; k < m; k++) {
-                        const double* q = cand[k];
-                        const double d2 = len2(v3(q[0], q[1], q[2]) - a.pos);
-                        const float key = (float)d2;
-                        if (key < a.tau) {
-                            const V3 contrib = v3(q[6], q[7], q[8]) * dot(v3(q[3], q[4], q[5]), a.dir);
-                            a.s_lt = a.s_lt + contrib; a.c_lt++;
-                        } else if (key == a.tau) {
-                            if (n_eq == 0) k_eq = k;
-                            n_eq++;
-                        }
-                    }
-                    if (n_eq == 1) {
-                        const double* q = cand[k_eq];
-                        g_acc(a, v3(q[0], q[1], q[2]), q + 3);
-                    } else if (n_eq > 1) {     // float keys tie at tau: walk on from the first of them
-                        for (int32_t k = k_eq; n_eq > 0 && k < m; k++) {
-                            const double* q = cand[k];
-                            if ((float)len2(v3(q[0], q[1], q[2]) - a.pos) == a.tau) { g_acc(a, v3(q[0], q[1], q[2]), q + 3); n_eq--; }
-                        }
-                    }
-                }
-            }
-            if (pass == 0) {
-                // tau = K-th smallest key, K = min(32, ncand) (what the heap's root holds after pass 1 of gather_in_leaf)
-                float tau = 0.0f;
-                if (ncand < 32) {
-#pragma unroll
-                    for (int k = 0; k < 32; k++) tau = best[k] < INFINITY ? fmaxf(tau, best[k]) : tau;
+        // the leaf's candidates as one sequence (its ranges back to back, the order gather_in_leaf visits them), 64 per step: candidates
+        // [c0, c0 + m) into cand[0, m), positions only or (all9) positions, directions and colours
+        auto stage = [&](int32_t c0, int32_t m, bool all9) {
+            __builtin_amdgcn_wave_barrier();
+            if ((int32_t)lane < m) {
+                const double* pp;
+                const double* dc;
+                if (S.pcand) {
+                    const size_t at = (size_t)S.pcand_off[rank0] + (size_t)(c0 + (int32_t)lane);
+                    pp = S.pcand + at * 3; dc = S.pcand_dc + at * 6;
                 } else {
-#pragma unroll
-                    for (int k = 0; k < 32; k++) tau = fmaxf(tau, best[k]);   // keys are squared distances: >= 0
+                    int32_t off = c0 + (int32_t)lane, r = 0;
+                    while (off >= ranges[r].count) { off -= ranges[r].count; r++; }   // r < n_ranges: off < ncand = sum of the counts
+                    const size_t ph = (size_t)(ranges[r].first + off);
+                    pp = S.ph_pos + ph * 3; dc = S.ph_dircol + ph * 6;
                 }
-                a.tau = tau;
+                cand[lane][0] = pp[0]; cand[lane][1] = pp[1]; cand[lane][2] = pp[2];
+                if (all9)
+                    for (int k = 0; k < 6; k++) cand[lane][3 + k] = dc[k];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        };
+        // pass 1 runs the chunks from the last to the first and stages chunk 0 whole, so pass 2 (chunks in candidate order) finds it in LDS
+        a.tau = ksel_tau(ncand, [&](int32_t c0, int32_t m) { stage(c0, m, c0 == 0); }, [&](int32_t k) {
+            const double* q = cand[k];
+            return (float)len2(v3(q[0], q[1], q[2]) - a.pos);   // same expression as g_key
+        });
+        for (int32_t c0 = 0; c0 < ncand; c0 += GI_GCHUNK) {
+            const int32_t m = min((int32_t)GI_GCHUNK, ncand - c0);
+            if (c0 != 0) stage(c0, m, true);
+            if (valid) {
+                // g_acc per candidate, with the rare case set aside: a candidate whose key EQUALS tau (the 32nd smallest itself; one per
+                // query, more only when float keys tie) is some lane's business for nearly every candidate of the wave, so its branch --
+                // a sum of its own, a count, a running maximum -- would run for nearly every candidate.  The loop only notes where such
+                // candidates are; they are added afterwards, in candidate order, by the same g_acc.
+                int n_eq = 0;
+                int32_t k_eq = 0;
+                for (int32_t k = 0; k < m; k++) {
+                    const double* q = cand[k];
+                    const double d2 = len2(v3(q[0], q[1], q[2]) - a.pos);
+                    const float key = (float)d2;
+                    if (key < a.tau) {
+                        const V3 contrib = v3(q[6], q[7], q[8]) * dot(v3(q[3], q[4], q[5]), a.dir);
+                        a.s_lt = a.s_lt + contrib; a.c_lt++;
+                    } else if (key == a.tau) {
+                        if (n_eq == 0) k_eq = k;
+                        n_eq++;
+                    }
+                }
+                if (n_eq == 1) {
+                    const double* q = cand[k_eq];
+                    g_acc(a, v3(q[0], q[1], q[2]), q + 3);
+                } else if (n_eq > 1) {     // float keys tie at tau: walk on from the first of them
+                    for (int32_t k = k_eq; n_eq > 0 && k < m; k++) {
+                        const double* q = cand[k];
+                        if ((float)len2(v3(q[0], q[1], q[2]) - a.pos) == a.tau) { g_acc(a, v3(q[0], q[1], q[2]), q + 3); n_eq--; }
+                    }
+                }
             }
         }
         if (valid) {
