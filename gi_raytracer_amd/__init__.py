@@ -62,7 +62,7 @@ _LIB = None
 ABI_SYMBOLS = [
     "gi_create", "gi_destroy", "gi_last_error", "gi_set_stream", "gi_upload_scene", "gi_upload_photons", "gi_local_rows",
     "gi_render_device", "gi_render_host", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
-    "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
+    "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
     "gih_add_texture", "gih_add_material_tex", "gih_load_png", "gih_free",
@@ -111,6 +111,7 @@ def lib():
     L.gi_debug_leaf_order.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _ip]
     L.gi_debug_sort_pairs.argtypes = [vp, C.c_int32, _up, _up, C.c_int32, C.c_int32, _up, _up]
     L.gi_debug_find_leaves.argtypes = [vp, C.c_int32, _dp, _ip, _ip]
+    L.gi_debug_gather_pass.argtypes = [vp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _up, _up, C.POINTER(C.c_int64)]
     L.gi_kat.argtypes = [vp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp]
     L.gi_clear_photons.argtypes = [vp]
     L.gi_group_clear_photons.argtypes = [vp]
@@ -630,6 +631,18 @@ class RayTracer:
         a = np.zeros(len(p), np.int32); b = np.zeros(len(p), np.int32)
         self._check(self.L.gi_debug_find_leaves(self.h, len(p), _p(p), _p(a, _ip), _p(b, _ip)), "find_leaves")
         return a, b
+
+    GATHER_KERNELS = {"gather": 0, "gather_count": 1, "wave": 2, "wave_count": 3}
+
+    def gather_pass(self, q, kernel, sort=True):
+        """gi_debug_gather_pass: a gather pass of the streaming pipeline (k_st_gather / k_st_gather_wave, "*_count" = the counting instance) on
+        queries q [n][6] = position, direction, in leaf order (sort) or the caller's.  Returns (caustic term [n][3] of query i, the keys and the
+        query order the kernel read, (gather queries, gather candidates) of a counting instance)."""
+        q = _f64(q).reshape(-1, 6)
+        n = len(q)
+        res = np.zeros((n, 3)); keys = np.zeros(n, np.uint32); order = np.zeros(n, np.uint32); cnt = (C.c_int64 * 2)()
+        self._check(self.L.gi_debug_gather_pass(self.h, n, _p(q), self.GATHER_KERNELS[kernel], 1 if sort else 0, _p(res), _p(keys, _up), _p(order, _up), cnt), "gather_pass")
+        return res, keys, order, (int(cnt[0]), int(cnt[1]))
 
     def leaf_order(self, rays, cap=256):
         """Octree::intersectSorted as the device walk produces it: per ray the pre-order indices of the non-empty leaves in visiting order."""

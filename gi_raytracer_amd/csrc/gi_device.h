@@ -1798,30 +1798,34 @@ GI_HD V3 gather_in_leaf(const Scene& S, int32_t node, V3 pos, V3 dir, float* hea
     for_each_candidate(S, ranges, n_ranges, [&](int32_t, V3 pp) { g_key(a, pp); });                                       // pass 1
     for_each_candidate(S, ranges, n_ranges, [&](int32_t idx, V3 pp) { g_acc(a, pp, S.ph_dircol + (size_t)idx * 6); });    // pass 2
     if (g_end(a, res)) return res;
-    // pass 3 (rare): the `need` nearest of the tie group by exact distance, one extraction per scan
+    // pass 3 (rare): the `need` nearest of the tie group by exact distance, one extraction per scan.  The group is taken in the order
+    // (d2, candidate number), so each extraction takes exactly one photon: bit-equal distances (copies of a photon, symmetric layouts)
+    // are resolved in candidate order, and every copy counts
     const int K = ncand < GI_GATHER_K ? ncand : GI_GATHER_K;
     const int need = K - a.c_lt;
     const float tau = a.tau;
     res = a.s_lt;
     double last = -1.0;
+    int32_t last_seq = -1;
     for (int j = 0; j < need; j++) {
         double best = INFINITY;
+        int32_t best_seq = -1, seq = 0;
         V3 bc = v3(0, 0, 0);
         for (int r = 0; r < n_ranges; r++) {
             const PRange rg = ranges[r];
             const double* pp = S.ph_pos + (size_t)rg.first * 3;
-            for (int32_t k = 0; k < rg.count; k++, pp += 3) {
+            for (int32_t k = 0; k < rg.count; k++, pp += 3, seq++) {
                 double d2 = len2(v3(pp[0], pp[1], pp[2]) - pos);
-                if ((float)d2 == tau && d2 > last && d2 < best) {
+                if ((float)d2 == tau && (d2 > last || (d2 == last && seq > last_seq)) && d2 < best) {
                     const double* dc = S.ph_dircol + (size_t)(rg.first + k) * 6;
-                    best = d2;
+                    best = d2; best_seq = seq;
                     bc = v3(dc[3], dc[4], dc[5]) * dot(v3(dc[0], dc[1], dc[2]), dir);
                 }
             }
         }
-        if (best == INFINITY) break;   // exact duplicates exhausted the group
+        if (best == INFINITY) break;   // (not reached: pass 3 runs only when the group holds at least need + 1 photons)
         res = res + bc;
-        last = best;
+        last = best; last_seq = best_seq;
     }
     res = res / (GI_PI * last);
     return res;

@@ -1017,6 +1017,15 @@ __global__ void k_find_leaves(Scene S, int32_t n, const double* pos, int32_t* fa
         full[i] = gather_find_leaf(S, p);
     }
 }
+// The sort key of a gather query (k_st_compact's gather queue, gi_debug_gather_pass): the rank of the photon-map leaf around the position among the
+// leaves with candidates; n_pleaf, the key past the last leaf, when there is nothing to gather (outside the map, a leaf without candidates)
+__device__ __forceinline__ uint32_t gather_key(const Scene& S, V3 pos)
+{
+    int32_t leaf = S.pdescent ? gather_find_leaf_fast(S, pos) : -2;
+    if (leaf == -2) leaf = gather_find_leaf(S, pos);
+    const int32_t rank = leaf < 0 ? -1 : S.pleaf_rank[leaf];
+    return rank < 0 ? (uint32_t)S.n_pleaf : (uint32_t)rank;
+}
 struct CompactStream { const uint32_t* src; uint32_t* dst; int width; };
 struct CompactJob {
     CompactStream st[5];    // streams of queue A (e.g. slot + key), then queue B, queue C: n_streams[q] streams each
@@ -1059,11 +1068,9 @@ __global__ __launch_bounds__(256) void k_st_compact(Scene S, CompactJob job, con
             if (q == job.gather_queue) {
                 const CompactStream& sl = job.st[stream0];
                 const double* pos = reinterpret_cast<const double*>(job.st[stream0 + 1].src) + from * 3;
-                int32_t leaf = S.pdescent ? gather_find_leaf_fast(S, v3(pos[0], pos[1], pos[2])) : -2;
-                if (leaf == -2) leaf = gather_find_leaf(S, v3(pos[0], pos[1], pos[2]));
+                const uint32_t key = gather_key(S, v3(pos[0], pos[1], pos[2]));
                 sl.dst[to] = sl.src[from];
-                const int32_t rank = leaf < 0 ? -1 : S.pleaf_rank[leaf];
-                job.st[stream0 + 1].dst[to] = rank < 0 ? (uint32_t)S.n_pleaf : (uint32_t)rank;   // the key past the last leaf: nothing to gather
+                job.st[stream0 + 1].dst[to] = key;
                 continue;
             }
             for (int k = 0; k < job.n_streams[q]; k++) {
@@ -1333,6 +1340,17 @@ __global__ __launch_bounds__(GI_GW_BLOCK) void k_st_gather_wave(Scene S, PathPoo
         }
     }
     if constexpr (COUNT) { if (lane != 0u) { n_q = 0; n_c = 0; } flush_u64(&sc->gather_queries, n_q); flush_u64(&sc->gather_cand, n_c); }
+}
+// gi_debug_gather_pass: query i in slot i of a pool of n (position, direction, factor 1, sample i) and its key as k_st_compact computes it
+__global__ __launch_bounds__(256) void k_gather_pass_prep(Scene S, PathPool pool, int32_t n, const double* q6, unsigned long long* slot_sample, uint32_t* keys, uint32_t* vals)
+{
+    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const double* q = q6 + (size_t)i * 6;
+    for (int k = 0; k < 3; k++) { pool.hit[i].hpos[k] = q[k]; pool.gath[i].gdir[k] = q[3 + k]; pool.gath[i].gcoef[k] = 1.0; }
+    slot_sample[i] = (unsigned long long)i;
+    keys[i] = gather_key(S, v3(q[0], q[1], q[2]));
+    vals[i] = (uint32_t)i;
 }
 
 // the last stragglers of a chunk (paths bouncing between specular surfaces up to MAX_DEPTH), finished without one nearly
@@ -2130,6 +2148,16 @@ static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process 
     }
     return g;
 }
+// The gather of a pass (stream_passes, gi_debug_gather_pass): n queries in leaf order (keys, vals = their slots), the caustic term added to their
+// radiance in lbuf; a wave per query (k_st_gather_wave) or a lane per query (k_st_gather)
+static void launch_gather(gi_ctx* c, bool wave, bool counting, const PathPool& pool, const uint32_t* keys, const uint32_t* vals, uint32_t n,
+                          const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
+{
+    if (wave)
+        hipLaunchKernelGGL(st_gather_wave(counting), dim3(std::min<uint32_t>((uint32_t)(5 * c->n_cu), (n + 3u) / 4u)), dim3(GI_GW_BLOCK), 0, c->stream, c->S, pool, keys, vals, n, slot_sample, sample0, lbuf, sc);
+    else
+        hipLaunchKernelGGL(st_gather(counting), dim3(stream_grids(c).gather), dim3(GI_BLOCK), 0, c->stream, c->S, pool, keys, vals, n, slot_sample, sample0, lbuf, sc);
+}
 // everything the pass loop needs for P paths in flight (the radiance buffer is the caller's)
 // a few lights, wide records: the shadow walks of the shade stage run in a kernel of their own (ShadowQ)
 static bool defers_shadows(const gi_ctx* c) { return c->defer_shadows && c->S.wnodes != nullptr && c->S.n_light >= 1 && c->S.n_light <= 4; }   // one query per light and shaded hit
@@ -2305,10 +2333,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
             }
             stage_end(c);
             stage_begin(c, STG_GATHER);
-            if (c->S.pcand && n_gather < c->gather_wave_below)      // few queries: a wave each
-                hipLaunchKernelGGL(st_gather_wave(counting), dim3(std::min<uint32_t>((uint32_t)(5 * c->n_cu), (n_gather + 3u) / 4u)), dim3(GI_GW_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
-            else
-                hipLaunchKernelGGL(st_gather(counting), dim3(G.gather), dim3(GI_BLOCK), 0, st, c->S, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);
+            launch_gather(c, c->S.pcand && n_gather < c->gather_wave_below, counting, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);   // few queries: a wave each
             stage_end(c);
             launches += 2;
         }
@@ -2839,6 +2864,55 @@ int gi_debug_find_leaves(gi_ctx* c, int32_t n, const double* pos, int32_t* fast_
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(fast_out, d_a.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(full_out, d_b.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return GI_OK;
+}
+
+int gi_debug_gather_pass(gi_ctx* c, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2)
+{
+    if (!c || n < 0 || kernel < 0 || kernel > 3 || (n && (!q6 || !res3))) return GI_E_INVALID;
+    if (c->S.n_pnode <= 0) return fail(c, GI_E_STATE, "gather_pass: no photon map");
+    const bool wave = (kernel & 2) != 0, counting = (kernel & 1) != 0;
+    if (wave && !c->S.pcand) return fail(c, GI_E_STATE, "gather_pass: k_st_gather_wave needs the written-out candidate lists (off: GI_FLAT_CANDIDATES=0)");
+    if (counters2) counters2[0] = counters2[1] = 0;
+    if (n == 0) return GI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t N = (uint32_t)n;
+    DevBuf<unsigned char> d_pool;
+    DevBuf<unsigned long long> d_ss;
+    DevBuf<double> d_q, d_L;
+    DevBuf<uint32_t> d_k[2], d_v[2], d_t[2], d_hist;
+    DevBuf<StreamCounters> d_sc;
+    HIP_TRY(c, d_q.upload(std::vector<double>(q6, q6 + (size_t)n * 6)));
+    HIP_TRY(c, d_pool.alloc((size_t)N * GI_POOL_BYTES_PER_SLOT));
+    HIP_TRY(c, d_ss.alloc(N)); HIP_TRY(c, d_L.alloc((size_t)N * 3)); HIP_TRY(c, d_sc.alloc(1));
+    for (int k = 0; k < 2; k++) { HIP_TRY(c, d_k[k].alloc(N)); HIP_TRY(c, d_v[k].alloc(N)); HIP_TRY(c, d_t[k].alloc(N)); }
+    HIP_TRY(c, d_hist.alloc((size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS));
+    HIP_TRY(c, hipMemsetAsync(d_pool.p, 0, (size_t)N * GI_POOL_BYTES_PER_SLOT, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_L.p, 0, (size_t)N * 24, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_sc.p, 0, sizeof(StreamCounters), c->stream));
+    const PathPool pool = make_path_pool(d_pool.p, N);
+    hipLaunchKernelGGL(k_gather_pass_prep, GI_GRID(n), 0, c->stream, c->S, pool, n, d_q.p, d_ss.p, d_k[0].p, d_v[0].p);
+    HIP_TRY(c, hipGetLastError());
+    if (sort) {
+        int bits = 1;
+        while ((1u << bits) <= (uint32_t)c->S.n_pleaf) bits++;   // keys 0 .. n_pleaf, as stream_passes sorts them
+        const int rc = rs_sort_pairs(c, d_k[0].p, d_k[1].p, d_v[0].p, d_v[1].p, d_t[0].p, d_t[1].p, N, nullptr, 0, bits, d_hist.p);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(d_k[1].p, d_k[0].p, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_v[1].p, d_v[0].p, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
+    }
+    launch_gather(c, wave, counting, pool, d_k[1].p, d_v[1].p, N, d_ss.p, 0ull, d_L.p, counting ? d_sc.p : nullptr);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(res3, d_L.p, (size_t)N * 24, hipMemcpyDeviceToHost));
+    if (keys_out) HIP_TRY(c, hipMemcpy(keys_out, d_k[1].p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    if (order_out) HIP_TRY(c, hipMemcpy(order_out, d_v[1].p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    if (counters2 && counting) {
+        StreamCounters h;
+        HIP_TRY(c, hipMemcpy(&h, d_sc.p, sizeof h, hipMemcpyDeviceToHost));
+        counters2[0] = (int64_t)h.gather_queries; counters2[1] = (int64_t)h.gather_cand;
+    }
     return GI_OK;
 }
 

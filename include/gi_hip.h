@@ -242,6 +242,13 @@ int gi_debug_sort_pairs(gi_ctx*, int32_t n, const uint32_t* keys, const uint32_t
  * pipeline find it: full_out the one that asks every box on the way (-1: no leaf contains the position), fast_out the one the gather keys of a pass
  * take (split records only, the first five levels through a jump table), -2 where that one declines (a position within 1e-12 of a split plane). */
 int gi_debug_find_leaves(gi_ctx*, int32_t n, const double* pos, int32_t* fast_out, int32_t* full_out);
+/* gi_debug_gather_pass: one gather pass of the streaming pipeline on caller queries q6 [n][6] = position, direction.  Query i takes slot i of a
+ * path pool (gather factor 1, radiance 0) and the sort key k_st_compact gives it; sort = 1 puts the queries in leaf order with the pipeline's
+ * radix sort, sort = 0 keeps the caller's order.  kernel: 0 k_st_gather, 1 its counting instance, 2 k_st_gather_wave, 3 its counting instance,
+ * launched as the pass loop launches them (GI_E_STATE: the wave kernel without written-out candidate lists, GI_FLAT_CANDIDATES=0).
+ * res3 [n][3] = the caustic term of query i (RayTracer::samplePhotons(pos, dir, 32)); keys_out / order_out [n] (optional) = the keys and slots
+ * in the order the kernel read them; counters2 (optional) = gather queries and candidates a counting instance counted (0 otherwise).    */
+int gi_debug_gather_pass(gi_ctx*, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2);
 int gi_kat(gi_ctx*, int32_t what, int32_t n, const double* in, int32_t in_stride, double* out3);
 
 

@@ -299,6 +299,52 @@ def check_gather_float_ties(rt_factory):
     np.testing.assert_allclose(got, ref, rtol=1e-9)
 
 
+def check_gather_exact_duplicates(rt_factory):
+    """Exact copies of photons (same position, direction and colour) inside a float-key tie group that straddles rank 32: every copy is a
+    photon of its own, as in the reference's partial_sort, and the exact pass has to count each.  The layout of check_gather_float_ties with
+    copies of every tie-group photon, of the three nearest ones, and a tie group made only of five copies of one photon (28 nearer ones, 10
+    farther).  Copies are whole photons, so the answer does not depend on which copy is taken."""
+    s = gi.Scene()
+    m = s.add_material(1.0, 1.0, 1.0, (1, 1, 1))
+    s.add_triangles(np.array([[[0, 0, 0], [4, 0, 0], [0, 0, 4]], [[4, 0, 0], [4, 0, 4], [0, 0, 4]], [[0, 4, 0], [4, 4, 0], [0, 4, 4]]], float), mat_idx=[m] * 3)
+    s.add_light((2, 3, 2), (1, 1, 1), .05)
+    s.rebuild()
+    rs = np.random.RandomState(6)
+    q = np.array([1.0, 1.0, 1.0]) * 2.0 ** -3
+
+    def unit(n):
+        u = rs.randn(n, 3)
+        return u / np.linalg.norm(u, axis=1)[:, None]
+
+    def photons(radius):
+        return np.concatenate([q + unit(len(radius)) * radius[:, None], unit(len(radius)), rs.rand(len(radius), 3)], axis=1)
+
+    def d2(ph):
+        d = ph[:, :3] - q
+        return d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+
+    near = photons(2.0 ** -21 * (1 + rs.rand(10) * 0.5))
+    shell = photons(2.0 ** -20 * (1 + rs.permutation(40) * 2.0 ** -30))
+    shell = shell[np.argsort(d2(shell))]                                      # nearest first: the copies fall among the ones pass 3 takes
+    one = photons(np.array([2.0 ** -20]))
+    cases = [np.concatenate([near, shell, shell[:20]]),                       # every photon of the tie group taken twice
+             np.concatenate([near, shell, shell[:3]]),                        # three of them twice
+             np.concatenate([photons(2.0 ** -21 * (1 + rs.rand(28) * 0.5)), np.repeat(one, 5, axis=0), photons(2.0 ** -19 * (1 + rs.rand(10)))])]
+    qq = np.concatenate([np.broadcast_to(q, (4, 3)), unit(4)], axis=1)
+    for ph in cases:
+        key = np.sort(d2(ph).astype(np.float32))
+        assert key[31] == key[32]                                             # float keys tie across rank 32: the exact pass runs
+        rt = rt_factory().setScene(s)
+        s.build_photon_map(ph)
+        rt.upload_photon_map()
+        o = oracle_for(s)
+        o.set_photons(ph).build_photon_map()
+        got, nc = rt.samplePhotons(qq)
+        ref, nco = o.gather(qq)
+        assert (nc == len(ph)).all() and (nco == len(ph)).all()
+        np.testing.assert_allclose(got, ref, rtol=1e-9)
+
+
 def check_stripes(rt, scene, w, h, spp, world, stripe_h):
     """Row-stripe sharding: rendering the stripes of every rank and interleaving them gives the single-GPU frame exactly."""
     full = rt.run(w, h, min_samples=spp, max_samples=spp)

@@ -134,6 +134,10 @@ def test_gather_resolves_float_key_ties_exactly():
     pc.check_gather_float_ties(el.EmulRayTracer)
 
 
+def test_gather_counts_every_copy_of_a_photon():
+    pc.check_gather_exact_duplicates(el.EmulRayTracer)
+
+
 def test_render_with_stochastic_alpha_and_glass_matches_oracle():
     """scenes/spheres/spheres.scn: mirror, glass (refraction + Fresnel lobe choice), glossy Phong lobe, a half-transparent sphere
     (alpha test draws keyed by leaf and entity), non-zero ambient."""

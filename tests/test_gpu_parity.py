@@ -371,6 +371,10 @@ def test_gather_resolves_float_key_ties_exactly():
     pc.check_gather_float_ties(lambda: gi.RayTracer(0))
 
 
+def test_gather_counts_every_copy_of_a_photon():
+    pc.check_gather_exact_duplicates(lambda: gi.RayTracer(0))
+
+
 def test_radiance_entry_matches_oracle(setup):
     name, scene, rt, fx = setup
     o = pc.oracle_for(scene)
