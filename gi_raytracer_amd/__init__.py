@@ -61,7 +61,7 @@ _LIB = None
 # every symbol include/gi_hip.h and csrc/gi_host.h declare (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "gi_create", "gi_destroy", "gi_last_error", "gi_set_stream", "gi_upload_scene", "gi_upload_photons", "gi_local_rows",
-    "gi_render_device", "gi_render_host", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
+    "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
@@ -90,6 +90,9 @@ def lib():
     L.gi_local_rows.argtypes = [C.POINTER(RenderParams)]
     L.gi_render_device.argtypes = [vp, C.POINTER(RenderParams), vp, C.c_int, vp, vp]
     L.gi_render_host.argtypes = [vp, C.POINTER(RenderParams), vp, C.c_int, vp, vp]
+    L.gi_render_features_device.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, vp, C.c_int, vp]
+    L.gi_render_features_host.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, vp, C.c_int, vp]
+    L.gi_last_features_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.gi_set_render_mode.argtypes = [vp, C.c_int]
     L.gi_set_wide_nodes.argtypes = [vp, C.c_int]
     L.gi_set_content_culling.argtypes = [vp, C.c_int]
@@ -325,11 +328,26 @@ class Scene:
 
 
 def save_pfm(path, lin):
-    """Linear radiance [h][w][3] as a little-endian PFM (rows bottom to top)."""
+    """Linear radiance [h][w][3] (`PF`) or a single-channel image [h][w] / [h][w][1] (`Pf`) as a little-endian PFM (rows bottom to top)."""
     a = np.ascontiguousarray(lin, np.float32)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError(f"save_pfm: [h][w][3] or [h][w] expected, got shape {a.shape}")
     with open(path, "wb") as f:
-        f.write(b"PF\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
+        f.write(b"%s\n%d %d\n-1.0\n" % (b"PF" if a.ndim == 3 else b"Pf", a.shape[1], a.shape[0]))
         f.write(a[::-1].astype("<f4").tobytes())
+
+
+def halton_sample_cap(w, h):
+    """Samples per pixel a w x h frame can take before the Halton index leaves 32 bits: index = offset + s * inc with offset < inc = 2^a 3^b,
+    the smallest such powers >= w and >= h (Halton_enum, include/halton_enum.h:69-114)."""
+    pw, ph = 1, 1
+    while pw < w:
+        pw *= 2
+    while ph < h:
+        ph *= 3
+    return (1 << 32) // (pw * ph)
 
 
 def to_rgb8(lin):
@@ -516,6 +534,29 @@ class RayTracer:
     def run_device(self, p, out_ptr, f64=False, spp_ptr=None):
         """Render into device memory (bench / multi-GPU path); out_ptr is a raw device pointer."""
         self._check(self.L.gi_render_device(self.h, C.byref(p), C.c_void_p(out_ptr), 1 if f64 else 0, C.c_void_p(spp_ptr) if spp_ptr else None, None), "render_device")
+
+    def run_features(self, w, h, n, f64=True, want_ids=True, **kw):
+        """First-hit feature buffers of the frame `run` renders (gi_render_features_host; an addition, the reference has no such pass): per pixel the
+        mean over samples 0 .. n-1 of the first hit's diffuse colour, normal, distance and coverage, and the entity / material of sample 0's hit.
+        Returns a dict of views into one array `features` [rows][w][8]: albedo [rows][w][3], normal [rows][w][3], depth [rows][w], coverage [rows][w],
+        and ids [rows][w][2] int32 (None without want_ids).  **kw as for run (stripes, seed); min_samples / max_samples play no part."""
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out = np.zeros((rows, w, 8), np.float64 if f64 else np.float32)
+        ids = np.zeros((rows, w, 2), np.int32) if want_ids else None
+        self._check(self.L.gi_render_features_host(self.h, C.byref(p), int(n), out.ctypes.data_as(C.c_void_p), 1 if f64 else 0,
+                                                   ids.ctypes.data_as(C.c_void_p) if want_ids else None), "render_features_host")
+        return {"features": out, "albedo": out[:, :, 0:3], "normal": out[:, :, 3:6], "depth": out[:, :, 6], "coverage": out[:, :, 7], "ids": ids}
+
+    def run_features_device(self, p, n, out_ptr, f64=False, ids_ptr=None):
+        """The feature pass into device memory; out_ptr ([rows][w][8]) and ids_ptr ([rows][w][2] int32, optional) are raw device pointers."""
+        self._check(self.L.gi_render_features_device(self.h, C.byref(p), int(n), C.c_void_p(out_ptr), 1 if f64 else 0, C.c_void_p(ids_ptr) if ids_ptr else None), "render_features_device")
+
+    def last_features_ms(self):
+        """gi_last_features_ms: device time of the last feature pass (last_render_ms / last_kernel_ms keep the last frame's)."""
+        ms = C.c_float()
+        self._check(self.L.gi_last_features_ms(self.h, C.byref(ms)), "last_features_ms")
+        return ms.value
 
     def set_render_mode(self, mode):
         """'wavefront' (default), 'megakernel' or 'rounds' (the wavefront passes in synchronous rounds, fixed-spp frames too):

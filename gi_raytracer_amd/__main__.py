@@ -1,9 +1,12 @@
 """Headless renderer: what the reference's main.cpp + Viewer do, without Qt.
 
     python -m gi_raytracer_amd scene.scn -o out.ppm [--pfm out.pfm] [--width 1000 --height 1000] [--samples MIN MAX [THRESH]] [--photons N]
+                               [--features PREFIX [--feature-samples N]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
+--features PREFIX (an addition to the reference's program) also writes the first-hit feature buffers of the frame: PREFIX_albedo.pfm,
+PREFIX_normal.pfm (three channels), PREFIX_depth.pfm, PREFIX_coverage.pfm (one channel).
 """
 import argparse
 import sys
@@ -12,7 +15,10 @@ import time
 import gi_raytracer_amd as gi
 
 
-def main(argv=None):
+FEATURE_FILES = ("albedo", "normal", "depth", "coverage")
+
+
+def parser():
     ap = argparse.ArgumentParser(prog="python -m gi_raytracer_amd", description=__doc__.split("\n")[0])
     ap.add_argument("scene")
     ap.add_argument("-o", "--output", default="out.ppm", help="8-bit PPM of the display transform (gamma 2.2, clamp)")
@@ -22,7 +28,21 @@ def main(argv=None):
     ap.add_argument("--samples", type=float, nargs="+", default=None, metavar="N", help="min max [noise threshold]")
     ap.add_argument("--photons", type=int, default=None)
     ap.add_argument("--device", type=int, default=0)
-    a = ap.parse_args(argv)
+    ap.add_argument("--features", default=None, metavar="PREFIX", help="also write the first-hit feature buffers as PREFIX_{albedo,normal,depth,coverage}.pfm")
+    ap.add_argument("--feature-samples", type=int, default=None, metavar="N",
+                    help="samples per pixel of the feature buffers (default: the frame's max samples, cut to what the Halton index of the frame size allows)")
+    return ap
+
+
+def feature_samples(a, max_samples):
+    """n of the feature pass: --feature-samples, else the frame's max_samples cut to the Halton cap of the frame size."""
+    if a.feature_samples is not None:
+        return a.feature_samples
+    return max(1, min(int(max_samples), gi.halton_sample_cap(a.width, a.height)))
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     scene = gi.Scene.load(a.scene).rebuild()
     rt = gi.RayTracer(a.device).setScene(scene)          # raises without a GPU: there is no CPU path
     if a.samples:
@@ -41,9 +61,16 @@ def main(argv=None):
     gi.save_ppm(a.output, lin)
     if a.pfm:
         gi.save_pfm(a.pfm, lin)
+    feat = ""
+    if a.features:
+        nf = feature_samples(a, rt.max_samples)
+        fb = rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
+        for name in FEATURE_FILES:
+            gi.save_pfm(f"{a.features}_{name}.pfm", fb[name])
+        feat = f"; features {nf} spp {rt.last_features_ms():.2f} ms -> {a.features}_*.pfm"
     n = int(spp.sum())
     print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / (a.width * a.height):.1f} spp), {stored} photons stored; "
-          f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}")
+          f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{feat}")
     return 0
 
 

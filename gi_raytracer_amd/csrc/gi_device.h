@@ -2188,6 +2188,36 @@ GI_HD void pixel_add_sample(PixelState& p, const Frame& F, V3 L)
 // local row r of this rank -> frame row (interleaved stripes)
 GI_HD int global_row(const Frame& F, int r) { return ((r / F.stripe_h) * F.stripe_world + F.stripe_rank) * F.stripe_h + r % F.stripe_h; }
 
+// ------------------------------------------------------------------------------------------------ first-hit features (an addition: the reference has no such pass)
+// What RayTracer::radiance holds right after trace() of the primary ray of the sample with Halton index idx (include/raytracer.h:186-210):
+// current->material.diffuse->get(minUV), minNorm as trace returned it (not flipped, not renormalised), glm::length(minHit - ray.origin),
+// the entity and its material.  Same ray, same RNG keys (seed, stream idx, depth 0, P_TRACE_ALPHA) as the beauty pass, so the alpha-test
+// draws -- and with them the first hit -- are the beauty pass's.  Fog is not looked at: the features are those of the first surface.
+struct AovSample { V3 albedo, normal; double depth; int32_t ent, mat; };
+template <int FEAT, class Nodes>
+GI_HD bool aov_sample(const Scene& S, const Nodes& N, const Frame& F, uint64_t seed, uint32_t idx, AovSample& a)
+{
+    const Ray ray = primary_ray_at(S, F, idx);
+    const Rng rng = rng_make(seed, idx);   // depth 0
+    HitRec h;
+    h.tu = 0; h.tv = 0;
+    if (!trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr)) return false;
+    if constexpr (Nodes::kWide) {
+        // as the streaming trace kernel does: hit point and barycentrics again from the entity's record, by the same test with the same
+        // operands, so that the walk has to carry only WHICH entity it hit
+        const TriGeom& tg = S.tris[h.tri];
+        h.mf = ((uint32_t)tg.mat << 3) | tg.flags;
+        ent_hit<FEAT>(tg, h.mf, ray, h.u, h.v, h.pos);
+    }
+    const Mat& m = S.mats[h.mf >> 3];
+    a.albedo = ld3(m.diffuse);
+    if (FEAT & GI_FEAT_TEX) a.albedo = tex_get(S, m.dtex, a.albedo, h.tu, h.tv);
+    a.normal = shading_normal(S, h);
+    a.depth = length(h.pos - ray.o);
+    a.ent = h.tri; a.mat = (int32_t)(h.mf >> 3);
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------------ photon emission (tracePhotons)
 struct PhotonOut { double v[9]; };
 // one (photon index i, light li): up to 500 emission tries; returns true and fills out when a caustic photon is stored

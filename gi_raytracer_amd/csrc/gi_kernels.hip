@@ -1509,6 +1509,49 @@ __global__ __launch_bounds__(GI_BLOCK) void k_st_accum(Frame F, PixRec* pix, con
     }
 }
 
+// First-hit feature buffers (gi_render_features_*; gi_device.h: aov_sample): one lane per pixel of this rank's rows in the 8x8-tile order of
+// st_pixel_xy, so a wave is a tile and all its lanes are on the same sample index s -- rays as coherent as the new paths of k_st_trace, on the same
+// records in LDS and the same wave-uniform leaves.  A lane loops over s (Halton index of sample s = that of sample 0 + s * inc), keeps its eight
+// sums in registers and writes once: no queue, no sort, no per-sample buffer, no atomics, and nothing of the path pool.
+// out [local_rows][w][8] = albedo rgb, normal xyz, depth, coverage: the f64 sums in ascending s, divided once by n.  ids [local_rows][w][2]
+// (optional) = entity and material of sample 0's hit, -1 on a miss.
+#ifndef GI_AOV_BLOCK
+// One workgroup per CU next to the 160 KB of records and boxes, as k_st_trace -- but of 512 lanes: the lane keeps a pixel's eight sums and the
+// frame constants next to the walk, which at the 128 registers of a 1024-lane workgroup spills 408 B per lane (wide triangle instance); at 512
+// it fits in 227 without scratch.  Measured on the benchmark frame (caustics 1920x1080, n = 256): 1024 lanes 76.0 ms, 512 lanes 66.5 ms.
+#define GI_AOV_BLOCK 512
+#endif
+template <int FEAT, int WIDE>
+__global__ __launch_bounds__(GI_AOV_BLOCK) void k_aov(Scene S, Frame F, uint32_t n_pix, int32_t n, void* out, int out_f64, int32_t* ids)
+{
+    const typename LdsSrc<WIDE>::type N = LdsSrc<WIDE>::stage_for_trace(S);   // ends with a barrier
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pix) return;
+    int x, ly;
+    st_pixel_xy(F, p, x, ly);
+    uint32_t idx = halton_index(F.he, 0u, (uint32_t)x, (uint32_t)global_row(F, ly));
+    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int32_t ent0 = -1, mat0 = -1;
+    for (int32_t s = 0; s < n; s++, idx += F.he.inc) {
+        AovSample a;
+        if (!aov_sample<FEAT>(S, N, F, F.seed, idx, a)) continue;
+        sum[0] += a.albedo.x; sum[1] += a.albedo.y; sum[2] += a.albedo.z;
+        sum[3] += a.normal.x; sum[4] += a.normal.y; sum[5] += a.normal.z;
+        sum[6] += a.depth; sum[7] += 1.0;
+        if (s == 0) { ent0 = a.ent; mat0 = a.mat; }
+    }
+    const size_t o = (size_t)ly * F.w + x;
+    const double dn = (double)n;
+    if (out_f64) {
+        double* q = (double*)out + o * 8;
+        for (int k = 0; k < 8; k++) q[k] = sum[k] / dn;
+    } else {
+        float* q = (float*)out + o * 8;
+        for (int k = 0; k < 8; k++) q[k] = (float)(sum[k] / dn);
+    }
+    if (ids) { ids[o * 2] = ent0; ids[o * 2 + 1] = mat0; }
+}
+
 __global__ __launch_bounds__(GI_BLOCK) void k_trace(Scene S, int n, const double* rays, int32_t* hit, int32_t* ent, double* res)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1752,6 +1795,11 @@ struct gi_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0;
     int last_launches = 0;
+    // the feature pass (gi_render_features_*) keeps its own events: it leaves the frame's times (ev0 / ev1, ev_pool) alone
+    hipEvent_t ev_feat0 = nullptr, ev_feat1 = nullptr;
+    float feat_ms = 0;
+    bool feat_pending = false;        // ev_feat0 / ev_feat1 were recorded and not read yet
+    int aov_lds_refused = -1;         // -1: the k_aov instances were not asked for their LDS yet; else as StreamGrids::lds_refused
     bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
     bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
     DevBuf<StreamCounters> d_stream_cnt;
@@ -1928,6 +1976,12 @@ static constexpr FinishK kFinish[] = {
     {k_st_finish<3, 0, 0>, kLdsNodes}, {k_st_finish<3, 1, 0>, kLdsNodes}, {k_st_finish<3, 1, 1>, kLdsFinishCoop}, {k_st_finish<3, 1, 2>, kLdsFinishCoop},
     {k_st_finish<7, 0, 0>, kLdsNodes}, {k_st_finish<7, 1, 0>, kLdsNodes}, {k_st_finish<7, 1, 1>, kLdsFinishCoop}, {k_st_finish<7, 1, 2>, kLdsFinishCoop}};
 static FinishK st_finish(int feat, bool wide, int mode) { return kFinish[feat_row(feat) * 4 + (wide ? 1 + mode : 0)]; }
+// k_aov<FEAT, WIDE> (the feature pass): FEAT 0, spheres, textures x per-node, wide -- the rows of kTrace, with the same LDS
+using AovK = StKernel<decltype(&k_aov<0, 0>)>;
+static constexpr AovK kAov[] = {
+    {k_aov<0, 0>, kLdsNodes}, {k_aov<0, 1>, kLdsWideBoxes}, {k_aov<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_aov<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
+    {k_aov<7, 0>, kLdsNodes}, {k_aov<7, 1>, kLdsWideBoxes}};
+static AovK aov_kernel(int feat, bool wide) { return kAov[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
 // k_st_gather / k_st_gather_wave<COUNT>: no template argument of the scene's, no dynamic LDS
 static auto st_gather(bool counting) { return counting ? k_st_gather<true> : k_st_gather<false>; }
 static auto st_gather_wave(bool counting) { return counting ? k_st_gather_wave<true> : k_st_gather_wave<false>; }
@@ -2005,6 +2059,8 @@ void gi_destroy(gi_ctx* c)
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->ev_feat0) (void)hipEventDestroy(c->ev_feat0);
+    if (c->ev_feat1) (void)hipEventDestroy(c->ev_feat1);
     delete c;
 }
 
@@ -2635,6 +2691,70 @@ int gi_render_host(gi_ctx* c, const gi_render_params* p, void* h_out, int out_is
     (void)hipFree(d_out);
     if (d_spp) (void)hipFree(d_spp);
     return rc;
+}
+
+// ---- first-hit feature buffers (an addition: the reference renders radiance only; the values are those RayTracer::radiance holds after trace()
+// of the primary ray, include/raytracer.h:186-210)
+int gi_render_features_device(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_ids)
+{
+    if (!c || !d_out) return GI_E_INVALID;
+    if (!c->have_scene) return fail(c, GI_E_STATE, "render_features: no scene uploaded");
+    Frame F;
+    std::string ferr;
+    if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
+    if (n_samples < 1) return fail(c, GI_E_INVALID, "render_features: n_samples must be at least 1");
+    // Halton index of sample s = (offset of the pixel < inc) + s * inc, in 32 bits as in the beauty pass
+    if ((unsigned long long)n_samples * F.he.inc > (1ull << 32))
+        return fail(c, GI_E_INVALID, "render_features: n_samples = " + std::to_string(n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
+                                     " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->feat_ms = 0; c->feat_pending = false;
+    if (F.local_rows == 0) return GI_OK;
+    if (c->aov_lds_refused < 0) { c->aov_lds_refused = 0; ask_for_lds(kAov, c->aov_lds_refused); }
+    if (c->aov_lds_refused) return fail(c, GI_E_HIP, "render_features: the device refused " + std::to_string(c->aov_lds_refused) + " bytes of dynamic LDS per workgroup");
+    if (!c->ev_feat0) { HIP_TRY(c, hipEventCreate(&c->ev_feat0)); HIP_TRY(c, hipEventCreate(&c->ev_feat1)); }
+    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
+    const AovK k = aov_kernel(scene_trace_feat(c->S), c->S.wnodes != nullptr);
+    HIP_TRY(c, hipEventRecord(c->ev_feat0, c->stream));
+    hipLaunchKernelGGL(k.fn, dim3((n_pix + GI_AOV_BLOCK - 1) / GI_AOV_BLOCK), dim3(GI_AOV_BLOCK), k.lds, c->stream, c->S, F, n_pix, n_samples, d_out, out_is_f64, d_ids);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_feat1, c->stream));
+    c->feat_pending = true;
+    return GI_OK;
+}
+
+int gi_render_features_host(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_ids)
+{
+    if (!c || !h_out || !p) return GI_E_INVALID;
+    const size_t npix = (size_t)gi_local_rows(p) * (size_t)std::max(p->width, 0);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = std::max<size_t>(npix, 1) * 8 * (out_is_f64 ? 8 : 4);
+    void* d_out = nullptr;
+    int32_t* d_ids = nullptr;
+    HIP_TRY(c, hipMalloc(&d_out, bytes));
+    if (h_ids && hipMalloc((void**)&d_ids, std::max<size_t>(npix, 1) * 8) != hipSuccess) { (void)hipFree(d_out); return fail(c, GI_E_HIP, "hipMalloc ids"); }
+    int rc = gi_render_features_device(c, p, n_samples, d_out, out_is_f64, d_ids);
+    if (rc == GI_OK && npix) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, npix * 8 * (out_is_f64 ? 8 : 4), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && h_ids) e = hipMemcpy(h_ids, d_ids, npix * 8, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("render_features_host: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    if (d_ids) (void)hipFree(d_ids);
+    return rc;
+}
+
+int gi_last_features_ms(gi_ctx* c, float* ms)
+{
+    if (!c || !ms) return GI_E_INVALID;
+    if (c->feat_pending) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_feat1));
+        HIP_TRY(c, hipEventElapsedTime(&c->feat_ms, c->ev_feat0, c->ev_feat1));
+        c->feat_pending = false;
+    }
+    *ms = c->feat_ms;
+    return GI_OK;
 }
 
 // ---- function-level entries: host in, host out

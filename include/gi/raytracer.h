@@ -175,6 +175,35 @@ class RayTracer {
         for (int i = 0; i < n; i++) _st->photon_map->push_back(new Photon(gi::get3(&out[(size_t)i * 9]), gi::get3(&out[(size_t)i * 9 + 3]), gi::get3(&out[(size_t)i * 9 + 6])));
     }
 
+    // ---- ADDITION (the reference has no such member): the first-hit feature buffers of the w x h frame run() renders -- per pixel the mean over
+    // samples 0 .. n-1 of what radiance() holds after trace() of the primary ray (diffuse->get(minUV), minNorm, |minHit - origin|, 1 on a hit), and the
+    // entity / material index of sample 0's hit (-1 on a miss; entity = index into Octree::entities()).  gi_render_features_host on the context of
+    // the per-ray methods (device 0 of a group); false with last_error() set when it cannot run.
+    struct Features {
+        int width = 0, height = 0, samples = 0;
+        std::vector<double> albedo, normal;      // [height][width][3]
+        std::vector<double> depth, coverage;     // [height][width]
+        std::vector<int32_t> entity, material;   // [height][width]
+    };
+    bool renderFeatures(int w, int h, int n, Features& out)
+    {
+        if (!ready()) return false;
+        const gi_render_params rp = params(w, h);
+        const size_t npix = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0);
+        std::vector<double> buf(npix * 8 + 8);
+        std::vector<int32_t> ids(npix * 2 + 2);
+        if (check(gi_render_features_host(_st->ctx, &rp, n, buf.data(), 1, ids.data())) != 0) return false;
+        out.width = w; out.height = h; out.samples = n;
+        out.albedo.resize(npix * 3); out.normal.resize(npix * 3); out.depth.resize(npix); out.coverage.resize(npix);
+        out.entity.resize(npix); out.material.resize(npix);
+        for (size_t i = 0; i < npix; i++) {
+            for (int k = 0; k < 3; k++) { out.albedo[i * 3 + k] = buf[i * 8 + k]; out.normal[i * 3 + k] = buf[i * 8 + 3 + k]; }
+            out.depth[i] = buf[i * 8 + 6]; out.coverage[i] = buf[i * 8 + 7];
+            out.entity[i] = ids[i * 2]; out.material[i] = ids[i * 2 + 1];
+        }
+        return true;
+    }
+
     // ---- single-vertex pieces of radiance(), include/raytracer.h:321-379,481-506,509-529: the kernels' per-lane functions on the host
     uint32_t rng_stream = 0, rng_depth = 0;   // key of the counter RNG for the draws these three make (the reference calls drand())
     int rayType(const Entity* entity, const Ray& ray, gi::dvec3& norm, gi::dvec2& minUV)

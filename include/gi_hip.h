@@ -169,6 +169,22 @@ int gi_set_counters(gi_ctx*, int mode);
 int gi_get_counters(gi_ctx*, int64_t* out8);
 int gi_get_stream_counters(gi_ctx*, int64_t* out19);
 
+/* First-hit feature buffers -- an ADDITION: the reference renders radiance only.  Per sample s = 0 .. n_samples-1 of a pixel the values are what
+ * RayTracer::radiance holds right after trace() of the primary ray (include/raytracer.h:112-129 the ray, 186-210 the hit): albedo =
+ * current->material.diffuse->get(minUV) (include/raytracer.h:200), normal = minNorm as trace returns it (not flipped, not renormalised), depth =
+ * glm::length(minHit - ray.origin) (include/raytracer.h:210), coverage = 1; all 0 on a miss.  The ray and the RNG keys of the alpha test are the
+ * beauty pass's (params->seed, stream = Halton index of the sample, depth 0), so the first hits are the ones gi_render_* shades.  Per pixel: the
+ * f64 sum over s in ascending order, divided once by n_samples.  Fog is ignored, specular chains are not followed (glass and mirrors report their
+ * stored diffuse colour).  n_samples is the caller's and independent of min_samples / max_samples; it must be >= 1 and keep the Halton index
+ * within 32 bits, as the beauty pass does (GI_E_INVALID otherwise).  Stripes as for the frame (gi_local_rows).
+ * out [local_rows][width][8] = albedo rgb, normal xyz, depth, coverage, float (out_is_f64 = 0) or double (1);
+ * ids (optional) [local_rows][width][2] = entity index, material index of sample 0's hit, -1 -1 on a miss.
+ * gi_render_features_device: DEVICE pointers, asynchronous on the context's stream; gi_render_features_host: HOST pointers.
+ * gi_last_features_ms: device time of the last feature pass (HIP events around it); gi_last_render_ms / gi_last_kernel_ms keep the last frame's. */
+int gi_render_features_device(gi_ctx*, const gi_render_params*, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_ids);
+int gi_render_features_host(gi_ctx*, const gi_render_params*, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_ids);
+int gi_last_features_ms(gi_ctx*, float* ms);
+
 /* Function-level entry points (parity tests and the C++ API's public methods).  Host pointers.
  * replaces RayTracer::trace (include/raytracer.h:382-478): rays [n][6] origin + unit dir -> hit, entity, res [n][8]        */
 int gi_trace(gi_ctx*, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res);
