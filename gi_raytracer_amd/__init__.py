@@ -50,6 +50,12 @@ class RenderParams(C.Structure):
                 ("min_samples", C.c_int32), ("max_samples", C.c_int32), ("noise_thresh", C.c_double), ("seed", C.c_uint64)]
 
 
+class DenoiseParams(C.Structure):
+    """gi_denoise_params (include/gi_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_color", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -61,7 +67,8 @@ _LIB = None
 # every symbol include/gi_hip.h and csrc/gi_host.h declare (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "gi_create", "gi_destroy", "gi_last_error", "gi_set_stream", "gi_upload_scene", "gi_upload_photons", "gi_local_rows",
-    "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
+    "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms",
+    "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
@@ -93,6 +100,11 @@ def lib():
     L.gi_render_features_device.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, vp, C.c_int, vp]
     L.gi_render_features_host.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, vp, C.c_int, vp]
     L.gi_last_features_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gi_denoise_default_params.argtypes = [C.POINTER(DenoiseParams)]
+    L.gi_denoise_default_params.restype = None
+    L.gi_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.gi_denoise_host.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.gi_last_denoise_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.gi_set_render_mode.argtypes = [vp, C.c_int]
     L.gi_set_wide_nodes.argtypes = [vp, C.c_int]
     L.gi_set_content_culling.argtypes = [vp, C.c_int]
@@ -556,6 +568,51 @@ class RayTracer:
         """gi_last_features_ms: device time of the last feature pass (last_render_ms / last_kernel_ms keep the last frame's)."""
         ms = C.c_float()
         self._check(self.L.gi_last_features_ms(self.h, C.byref(ms)), "last_features_ms")
+        return ms.value
+
+    def denoise_params(self, w, h, **kw):
+        """gi_denoise_default_params with width, height and any of iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo set."""
+        p = DenoiseParams()
+        self.L.gi_denoise_default_params(C.byref(p))
+        p.width, p.height = int(w), int(h)
+        for k, v in kw.items():
+            if k not in ("iterations", "demodulate", "sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"):
+                raise TypeError(f"denoise: unknown parameter {k!r}")
+            setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+        return p
+
+    def denoise(self, color, features, f64=None, **kw):
+        """The edge-avoiding a-trous denoiser (gi_denoise_host; an addition, the reference has no denoiser) on a whole frame: color [h][w][3] as
+        `run` returns it, features [h][w][8] as `run_features` returns them (its dict is accepted too), each float32 or float64.  Returns
+        [h][w][3], float64 unless f64=False (default: the colour's type).  **kw: iterations (0 .. 8), demodulate, sigma_color, sigma_normal,
+        sigma_depth, sigma_albedo; the formula is stated in include/gi_hip.h.  Needs no scene."""
+        if isinstance(features, dict):
+            features = features["features"]
+        color, features = np.asarray(color), np.asarray(features)
+        color = np.ascontiguousarray(color, np.float32 if color.dtype == np.float32 else np.float64)
+        features = np.ascontiguousarray(features, np.float32 if features.dtype == np.float32 else np.float64)
+        if color.ndim != 3 or color.shape[2] != 3 or features.shape != color.shape[:2] + (8,):
+            raise ValueError(f"denoise: color [h][w][3] and features [h][w][8] expected, got {color.shape} and {features.shape}")
+        if f64 is None:
+            f64 = color.dtype == np.float64
+        h, w = color.shape[:2]
+        p = self.denoise_params(w, h, **kw)
+        out = np.zeros((h, w, 3), np.float64 if f64 else np.float32)
+        self._check(self.L.gi_denoise_host(self.h, C.byref(p), color.ctypes.data_as(C.c_void_p), 1 if color.dtype == np.float64 else 0,
+                                           features.ctypes.data_as(C.c_void_p), 1 if features.dtype == np.float64 else 0,
+                                           out.ctypes.data_as(C.c_void_p), 1 if f64 else 0), "denoise_host")
+        return out
+
+    def denoise_device(self, p, color_ptr, features_ptr, out_ptr, color_f64=False, features_f64=False, out_f64=False):
+        """The denoiser on device memory, asynchronous on the context's stream; p from denoise_params; raw device pointers to [h][w][3],
+        [h][w][8] and [h][w][3]; out_ptr may equal color_ptr."""
+        self._check(self.L.gi_denoise_device(self.h, C.byref(p), C.c_void_p(color_ptr), 1 if color_f64 else 0, C.c_void_p(features_ptr), 1 if features_f64 else 0,
+                                             C.c_void_p(out_ptr), 1 if out_f64 else 0), "denoise_device")
+
+    def last_denoise_ms(self):
+        """gi_last_denoise_ms: device time of the last denoiser pass (the frame's and the feature pass's times keep theirs)."""
+        ms = C.c_float()
+        self._check(self.L.gi_last_denoise_ms(self.h, C.byref(ms)), "last_denoise_ms")
         return ms.value
 
     def set_render_mode(self, mode):

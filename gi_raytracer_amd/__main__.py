@@ -2,11 +2,14 @@
 
     python -m gi_raytracer_amd scene.scn -o out.ppm [--pfm out.pfm] [--width 1000 --height 1000] [--samples MIN MAX [THRESH]] [--photons N]
                                [--features PREFIX [--feature-samples N]]
+                               [--denoise OUT.ppm [--denoise-pfm OUT.pfm] [--denoise-iterations N] [--denoise-sigmas C N Z A]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
 --features PREFIX (an addition to the reference's program) also writes the first-hit feature buffers of the frame: PREFIX_albedo.pfm,
 PREFIX_normal.pfm (three channels), PREFIX_depth.pfm, PREFIX_coverage.pfm (one channel).
+--denoise OUT.ppm (an addition as well) runs the feature pass and the edge-avoiding a-trous denoiser on the frame and writes the result next to
+the frame, which is written as without the flag.
 """
 import argparse
 import sys
@@ -31,7 +34,22 @@ def parser():
     ap.add_argument("--features", default=None, metavar="PREFIX", help="also write the first-hit feature buffers as PREFIX_{albedo,normal,depth,coverage}.pfm")
     ap.add_argument("--feature-samples", type=int, default=None, metavar="N",
                     help="samples per pixel of the feature buffers (default: the frame's max samples, cut to what the Halton index of the frame size allows)")
+    ap.add_argument("--denoise", default=None, metavar="OUT.ppm", help="also write the denoised frame (a-trous filter guided by the feature buffers) as 8-bit PPM")
+    ap.add_argument("--denoise-pfm", default=None, metavar="OUT.pfm", help="with --denoise: the denoised linear radiance as PFM")
+    ap.add_argument("--denoise-iterations", type=int, default=None, metavar="N", help="levels of the filter, 0 .. 8 (default 5)")
+    ap.add_argument("--denoise-sigmas", type=float, nargs=4, default=None, metavar=("C", "N", "Z", "A"),
+                    help="sigmas of colour, normal, depth and albedo (default 1.0 0.5 0.1 0.25; 0 switches a term off)")
     return ap
+
+
+def denoise_kwargs(a):
+    """The keyword arguments of RayTracer.denoise the --denoise-* flags set."""
+    kw = {}
+    if a.denoise_iterations is not None:
+        kw["iterations"] = a.denoise_iterations
+    if a.denoise_sigmas is not None:
+        kw.update(zip(("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"), a.denoise_sigmas))
+    return kw
 
 
 def feature_samples(a, max_samples):
@@ -42,7 +60,10 @@ def feature_samples(a, max_samples):
 
 
 def main(argv=None):
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.denoise is None and (a.denoise_pfm or a.denoise_iterations is not None or a.denoise_sigmas is not None):
+        ap.error("--denoise-pfm, --denoise-iterations and --denoise-sigmas need --denoise OUT.ppm")
     scene = gi.Scene.load(a.scene).rebuild()
     rt = gi.RayTracer(a.device).setScene(scene)          # raises without a GPU: there is no CPU path
     if a.samples:
@@ -68,6 +89,14 @@ def main(argv=None):
         for name in FEATURE_FILES:
             gi.save_pfm(f"{a.features}_{name}.pfm", fb[name])
         feat = f"; features {nf} spp {rt.last_features_ms():.2f} ms -> {a.features}_*.pfm"
+    if a.denoise:
+        nf = feature_samples(a, rt.max_samples)
+        fb = fb if a.features else rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
+        den = rt.denoise(lin, fb["features"], **denoise_kwargs(a))
+        gi.save_ppm(a.denoise, den)
+        if a.denoise_pfm:
+            gi.save_pfm(a.denoise_pfm, den)
+        feat += f"; denoised ({nf} spp features) {rt.last_denoise_ms():.2f} ms -> {a.denoise}"
     n = int(spp.sum())
     print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / (a.width * a.height):.1f} spp), {stored} photons stored; "
           f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{feat}")

@@ -1,0 +1,247 @@
+// gi_denoise.inc -- the edge-avoiding a-trous denoiser (gi_denoise_*; an addition: the reference has no denoiser).  Included by gi_kernels.hip
+// after the context and its helpers.  The formula is stated in include/gi_hip.h; the per-tap function is dn_tap_weight() in gi_device.h.
+//
+// Three kernels, all on the context's stream, no atomics, no host sync between them:
+//   k_dn_pack   widens colour and features to f64, demodulates, and writes the two things a tap reads: the colour [h][w][3] (changes per
+//               level) and the level-invariant guide record [h][w][8] (albedo, normal, depth, coverage: 64 B, one half cache line);
+//   k_dn_level  one level, one lane per pixel, 25 taps from LDS.  A level of step s is a dense 5 x 5 filter on each of the s^2 interleaved
+//               sub-lattices x = ox + s lx, y = oy + s ly, so a workgroup takes a 32 x 16 tile of ONE sub-lattice with a halo of two lattice
+//               cells: 36 x 20 = 720 cells whatever s is.  The cells sit in LDS as 11 planes of doubles (structure of arrays), so the 32 lanes
+//               of a row read 32 consecutive doubles per ds_read_b64: no bank conflicts.  Cells outside the frame get a NaN colour and are
+//               then skipped by the same test that skips non-finite input.  The last level multiplies by the modulation and stores in the
+//               caller's type;
+//   k_dn_copy   iterations = 0: out = colour, converted.
+// Workgroups that share a neighbourhood run next to each other: the sub-lattice index is the fastest part of blockIdx.x, so at large steps the
+// s^2 workgroups that read one region of the frame (each a 1/s^2 sample of its cache lines) are in flight together and the lines come from L2.
+#define GI_DN_TX 32
+#define GI_DN_TY 16
+#define GI_DN_HX (GI_DN_TX + 4)
+#define GI_DN_HY (GI_DN_TY + 4)
+#define GI_DN_CELLS (GI_DN_HX * GI_DN_HY)       // 720
+#define GI_DN_PLANE 724                         // plane stride in doubles: = 4 mod 16, so the loader's 8 components of a cell fall on different banks (2-way at worst)
+#define GI_DN_BLOCK (GI_DN_TX * GI_DN_TY)       // 512
+#define GI_DN_MAX_ITERATIONS 8
+
+struct DnGrid { int32_t w, h, log2s, tiles_x; };
+
+template <class T> __device__ __forceinline__ double dn_widen(const void* p, size_t i) { return (double)((const T*)p)[i]; }
+__device__ __forceinline__ double dn_load(const void* p, int is_f64, size_t i) { return is_f64 ? dn_widen<double>(p, i) : dn_widen<float>(p, i); }
+__device__ __forceinline__ void dn_store(void* p, int is_f64, size_t i, double v)
+{
+    if (is_f64) ((double*)p)[i] = v;
+    else ((float*)p)[i] = (float)v;
+}
+
+// one lane per feature value e = pixel * 8 + k: guides[e] = the value in f64; the lanes of the three albedo channels also write the pixel's
+// demodulated colour channel
+__global__ __launch_bounds__(256) void k_dn_pack(size_t n_pix, const void* color, int color_f64, const void* feat, int feat_f64, int demodulate, double* c, double* guides)
+{
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_pix * 8) return;
+    const double f = dn_load(feat, feat_f64, e);
+    guides[e] = f;
+    const int k = (int)(e & 7);
+    if (k < 3) {
+        const size_t o = (e >> 3) * 3 + k;
+        c[o] = dn_load(color, color_f64, o) / dn_modulation(f, demodulate);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dn_copy(size_t n, const void* color, int color_f64, void* out, int out_f64)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dn_store(out, out_f64, i, dn_load(color, color_f64, i));
+}
+
+__device__ __forceinline__ DnPix dn_cell(const double* lds, int cell)
+{
+    DnPix q;
+    q.c = v3(lds[cell], lds[GI_DN_PLANE + cell], lds[2 * GI_DN_PLANE + cell]);
+    q.a = v3(lds[3 * GI_DN_PLANE + cell], lds[4 * GI_DN_PLANE + cell], lds[5 * GI_DN_PLANE + cell]);
+    q.n = v3(lds[6 * GI_DN_PLANE + cell], lds[7 * GI_DN_PLANE + cell], lds[8 * GI_DN_PLANE + cell]);
+    q.z = lds[9 * GI_DN_PLANE + cell];
+    q.cov = lds[10 * GI_DN_PLANE + cell];
+    return q;
+}
+
+// src, dst: [h][w][3] f64 demodulated colour; guides [h][w][8] f64.  last: dst is not written; out (type out_f64) gets colour * modulation.
+__global__ __launch_bounds__(GI_DN_BLOCK) void k_dn_level(DnGrid G, DnInv inv, const double* __restrict__ src, const double* __restrict__ guides, double* __restrict__ dst,
+                                                          int last, int demodulate, void* out, int out_f64)
+{
+    __shared__ double lds[11 * GI_DN_PLANE];
+    const int s = 1 << G.log2s;
+    const uint32_t sub = blockIdx.x & (uint32_t)(s * s - 1);
+    const uint32_t tile = blockIdx.x >> (2 * G.log2s);
+    const int ox = (int)(sub & (uint32_t)(s - 1)), oy = (int)(sub >> G.log2s);
+    const int lx0 = (int)(tile % (uint32_t)G.tiles_x) * GI_DN_TX - 2, ly0 = (int)(tile / (uint32_t)G.tiles_x) * GI_DN_TY - 2;   // lattice cell of halo cell (0, 0)
+    // colour: 720 cells x 3 doubles
+    for (int idx = threadIdx.x; idx < GI_DN_CELLS * 3; idx += GI_DN_BLOCK) {
+        const int cell = idx / 3, k = idx - cell * 3;
+        const int x = ox + s * (lx0 + cell % GI_DN_HX), y = oy + s * (ly0 + cell / GI_DN_HX);
+        const bool in = x >= 0 && x < G.w && y >= 0 && y < G.h;
+        lds[k * GI_DN_PLANE + cell] = in ? src[((size_t)y * G.w + x) * 3 + k] : __builtin_nan("");
+    }
+    // guides: 720 cells x 4 pairs of doubles (16-byte loads); record = albedo 0..2, normal 3..5, depth 6, coverage 7 -> planes 3 .. 10
+    for (int idx = threadIdx.x; idx < GI_DN_CELLS * 4; idx += GI_DN_BLOCK) {
+        const int cell = idx >> 2, k = (idx & 3) * 2;
+        const int x = ox + s * (lx0 + cell % GI_DN_HX), y = oy + s * (ly0 + cell / GI_DN_HX);
+        double2 v = make_double2(0.0, 0.0);
+        if (x >= 0 && x < G.w && y >= 0 && y < G.h) v = *(const double2*)(guides + ((size_t)y * G.w + x) * 8 + k);
+        lds[(3 + k) * GI_DN_PLANE + cell] = v.x;
+        lds[(4 + k) * GI_DN_PLANE + cell] = v.y;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & (GI_DN_TX - 1), ty = threadIdx.x / GI_DN_TX;
+    const int x = ox + s * (lx0 + 2 + tx), y = oy + s * (ly0 + 2 + ty);
+    if (x >= G.w || y >= G.h) return;
+    const DnPix p = dn_cell(lds, (ty + 2) * GI_DN_HX + tx + 2);
+    const bool p_ok = dn_finite(p.c);
+    const double p_c2 = dn_sq3(p.c);
+    const double h5[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
+    V3 num = v3(0, 0, 0);
+    double den = 0.0;
+#pragma unroll
+    for (int dy = 0; dy < 5; dy++) {
+#pragma unroll
+        for (int dx = 0; dx < 5; dx++) {
+            const DnPix q = dn_cell(lds, (ty + dy) * GI_DN_HX + tx + dx);
+            const bool ok = dn_finite(q.c);        // outside the frame (NaN from the loader) or a non-finite input: skipped
+            const double wq = ok ? dn_tap_weight(p, p_c2, p_ok, q, inv, h5[dy] * h5[dx]) : 0.0;
+            num.x += wq * (ok ? q.c.x : 0.0);
+            num.y += wq * (ok ? q.c.y : 0.0);
+            num.z += wq * (ok ? q.c.z : 0.0);
+            den += wq;
+        }
+    }
+    V3 r = v3(0, 0, 0);
+    if (den > 0.0) r = v3(num.x / den, num.y / den, num.z / den);
+    const size_t o = ((size_t)y * G.w + x) * 3;
+    if (last) {
+        dn_store(out, out_f64, o, r.x * dn_modulation(p.a.x, demodulate));
+        dn_store(out, out_f64, o + 1, r.y * dn_modulation(p.a.y, demodulate));
+        dn_store(out, out_f64, o + 2, r.z * dn_modulation(p.a.z, demodulate));
+    } else {
+        dst[o] = r.x; dst[o + 1] = r.y; dst[o + 2] = r.z;
+    }
+}
+
+namespace {
+
+// false + message when the parameters are not the header's
+bool dn_check(const gi_denoise_params* p, std::string& err)
+{
+    if (!p) { err = "denoise: null parameters"; return false; }
+    if (p->width < 1 || p->height < 1) { err = "denoise: width and height must be at least 1, got " + std::to_string(p->width) + " x " + std::to_string(p->height); return false; }
+    if (p->iterations < 0 || p->iterations > GI_DN_MAX_ITERATIONS) { err = "denoise: iterations must be 0 .. " + std::to_string(GI_DN_MAX_ITERATIONS) + ", got " + std::to_string(p->iterations); return false; }
+    const double sg[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
+    const char* names[4] = {"sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"};
+    for (int k = 0; k < 4; k++)
+        if (!(sg[k] >= 0.0)) { err = std::string("denoise: ") + names[k] + " must be >= 0 (0 switches the term off), got " + std::to_string(sg[k]); return false; }
+    return true;
+}
+
+double dn_inv(double sigma, double scale) { return sigma != 0.0 ? scale / (sigma * sigma) : 0.0; }
+
+}  // namespace
+
+extern "C" {
+
+void gi_denoise_default_params(gi_denoise_params* p)
+{
+    if (!p) return;
+    p->width = 0; p->height = 0;
+    p->iterations = 5; p->demodulate = 1;
+    p->sigma_color = 1.0; p->sigma_normal = 0.5; p->sigma_depth = 0.1; p->sigma_albedo = 0.25;
+}
+
+int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color, int color_is_f64, const void* d_features, int features_is_f64, void* d_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    std::string err;
+    if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
+    if (!d_color || !d_features || !d_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
+    const size_t n_pix = (size_t)p->width * (size_t)p->height;
+    if (n_pix > ((size_t)1 << 28)) return fail(c, GI_E_INVALID, "denoise: frames beyond 2^28 pixels are not supported");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->dn_ms = 0; c->dn_pending = false;
+    if (!c->ev_dn0) { HIP_TRY(c, hipEventCreate(&c->ev_dn0)); HIP_TRY(c, hipEventCreate(&c->ev_dn1)); }
+    const int it = p->iterations;
+    if (it > 0 && c->d_dn_guides.n < n_pix * 8) {
+        // the scratch is the context's: sized on first use and kept; a larger frame replaces it (after the stream has drained: an earlier pass may still read it)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, c->d_dn_guides.alloc(n_pix * 8));
+        HIP_TRY(c, c->d_dn_a.alloc(n_pix * 3));
+        HIP_TRY(c, c->d_dn_b.alloc(n_pix * 3));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_dn0, c->stream));
+    if (it == 0) {
+        if (d_out != d_color || (out_is_f64 != 0) != (color_is_f64 != 0))
+            hipLaunchKernelGGL(k_dn_copy, dim3((unsigned)((n_pix * 3 + 255) / 256)), dim3(256), 0, c->stream, n_pix * 3, d_color, color_is_f64, d_out, out_is_f64);
+    } else {
+        const int demod = p->demodulate != 0;
+        hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((n_pix * 8 + 255) / 256)), dim3(256), 0, c->stream, n_pix, d_color, color_is_f64, d_features, features_is_f64, demod,
+                           c->d_dn_a.p, c->d_dn_guides.p);
+        double* src = c->d_dn_a.p;
+        double* dst = c->d_dn_b.p;
+        for (int i = 0; i < it; i++) {
+            const int s = 1 << i;
+            DnGrid G;
+            G.w = p->width; G.h = p->height; G.log2s = i;
+            const int lw = (p->width + s - 1) / s, lh = (p->height + s - 1) / s;       // the largest sub-lattice (ox = oy = 0)
+            G.tiles_x = (lw + GI_DN_TX - 1) / GI_DN_TX;
+            const int tiles_y = (lh + GI_DN_TY - 1) / GI_DN_TY;
+            DnInv inv;
+            inv.c = dn_inv(p->sigma_color, (double)(1u << (2 * i)));                   // the colour sigma halves per level
+            inv.n = dn_inv(p->sigma_normal, 1.0); inv.z = dn_inv(p->sigma_depth, 1.0); inv.a = dn_inv(p->sigma_albedo, 1.0);
+            const size_t blocks = (size_t)G.tiles_x * tiles_y * s * s;
+            hipLaunchKernelGGL(k_dn_level, dim3((unsigned)blocks), dim3(GI_DN_BLOCK), 0, c->stream, G, inv, src, c->d_dn_guides.p, dst, i == it - 1 ? 1 : 0, demod, d_out, out_is_f64);
+            std::swap(src, dst);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_dn1, c->stream));
+    c->dn_pending = true;
+    return GI_OK;
+}
+
+int gi_denoise_host(gi_ctx* c, const gi_denoise_params* p, const void* h_color, int color_is_f64, const void* h_features, int features_is_f64, void* h_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    std::string err;
+    if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
+    if (!h_color || !h_features || !h_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_pix = (size_t)p->width * (size_t)p->height;
+    const size_t cb = n_pix * 3 * (color_is_f64 ? 8 : 4), fb = n_pix * 8 * (features_is_f64 ? 8 : 4), ob = n_pix * 3 * (out_is_f64 ? 8 : 4);
+    void *d_color = nullptr, *d_feat = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(&d_color, cb);
+    if (e == hipSuccess) e = hipMalloc(&d_feat, fb);
+    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
+    if (e == hipSuccess) e = hipMemcpy(d_color, h_color, cb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_feat, h_features, fb, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? GI_OK : fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
+    if (rc == GI_OK) rc = gi_denoise_device(c, p, d_color, color_is_f64, d_feat, features_is_f64, d_out, out_is_f64);
+    if (rc == GI_OK) {
+        e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, ob, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
+    }
+    if (d_color) (void)hipFree(d_color);
+    if (d_feat) (void)hipFree(d_feat);
+    if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
+int gi_last_denoise_ms(gi_ctx* c, float* ms)
+{
+    if (!c || !ms) return GI_E_INVALID;
+    if (c->dn_pending) {
+        HIP_TRY(c, hipEventSynchronize(c->ev_dn1));
+        HIP_TRY(c, hipEventElapsedTime(&c->dn_ms, c->ev_dn0, c->ev_dn1));
+        c->dn_pending = false;
+    }
+    *ms = c->dn_ms;
+    return GI_OK;
+}
+
+}  // extern "C"

@@ -2218,6 +2218,32 @@ GI_HD bool aov_sample(const Scene& S, const Nodes& N, const Frame& F, uint64_t s
     return true;
 }
 
+// ------------------------------------------------------------------------------------------------ a-trous denoiser (an addition: the reference has no denoiser)
+// One tap of the edge-avoiding a-trous filter (gi_hip.h: gi_denoise_*; Dammertz et al. 2010 with Tukey's biweight as the edge-stopping function).
+// IEEE operations only, in the order the header states, so that with -ffp-contract=off the result equals the tests' numpy statement bit for bit.
+struct DnPix { V3 c, n, a; double z, cov; };     // what a tap reads of a pixel: demodulated colour, normal, albedo, depth, coverage
+struct DnInv { double c, n, z, a; };             // 4^level / sigma_color^2, 1 / sigma_normal^2, 1 / sigma_depth^2, 1 / sigma_albedo^2 (0 = term off)
+#define GI_DN_ALBEDO_FLOOR 1e-3
+#define GI_DN_DC_EPS 1e-12
+GI_HD double dn_sq3(V3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }
+GI_HD bool dn_finite(V3 c) { return fabs(c.x) <= 1.7976931348623157e308 && fabs(c.y) <= 1.7976931348623157e308 && fabs(c.z) <= 1.7976931348623157e308; }
+GI_HD double dn_modulation(double albedo, int demodulate) { return demodulate ? (albedo > GI_DN_ALBEDO_FLOOR ? albedo : GI_DN_ALBEDO_FLOOR) : 1.0; }
+// weight of tap q for the centre p: hh = h[dy] h[dx]; p_c2 = |c_p|^2; p_ok = the centre's colour is finite (else the colour term is 0).
+// The caller skips taps outside the frame and taps whose colour is not finite.
+GI_HD double dn_tap_weight(const DnPix& p, double p_c2, bool p_ok, const DnPix& q, const DnInv& inv, double hh)
+{
+    const double dc = p_ok ? dn_sq3(p.c - q.c) / (p_c2 + (dn_sq3(q.c) + GI_DN_DC_EPS)) : 0.0;
+    const double dn = dn_sq3(p.n - q.n);
+    const double dcov = p.cov - q.cov;
+    const double da = dn_sq3(p.a - q.a) + dcov * dcov;
+    const double zs = p.z + q.z;
+    double dz = 0.0;
+    if (zs > 0.0) { const double r = (p.z - q.z) / zs; dz = r * r; }
+    const double d = ((dc * inv.c + dn * inv.n) + dz * inv.z) + da * inv.a;
+    const double t = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
+    return hh * (t * t);
+}
+
 // ------------------------------------------------------------------------------------------------ photon emission (tracePhotons)
 struct PhotonOut { double v[9]; };
 // one (photon index i, light li): up to 500 emission tries; returns true and fills out when a caustic photon is stored

@@ -1800,6 +1800,12 @@ struct gi_ctx {
     float feat_ms = 0;
     bool feat_pending = false;        // ev_feat0 / ev_feat1 were recorded and not read yet
     int aov_lds_refused = -1;         // -1: the k_aov instances were not asked for their LDS yet; else as StreamGrids::lds_refused
+    // the denoiser (gi_denoise_*, gi_denoise.inc): events of its own again, and its scratch -- the guide records [h][w][8] and two colour
+    // buffers [h][w][3], f64, sized on first use and kept
+    hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
+    float dn_ms = 0;
+    bool dn_pending = false;
+    DevBuf<double> d_dn_guides, d_dn_a, d_dn_b;
     bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
     bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
     DevBuf<StreamCounters> d_stream_cnt;
@@ -1938,6 +1944,7 @@ static void clear_photon_map(gi_ctx* c)
 
 #include "gi_sort.inc"
 #include "gi_photon_build.inc"
+#include "gi_denoise.inc"
 
 static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
 static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
@@ -2061,6 +2068,8 @@ void gi_destroy(gi_ctx* c)
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->ev_feat0) (void)hipEventDestroy(c->ev_feat0);
     if (c->ev_feat1) (void)hipEventDestroy(c->ev_feat1);
+    if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
+    if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
     delete c;
 }
 

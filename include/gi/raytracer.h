@@ -204,6 +204,32 @@ class RayTracer {
         return true;
     }
 
+    // ---- ADDITION (the reference has no denoiser): the edge-avoiding a-trous filter of gi_denoise_host (include/gi_hip.h states the formula) on a
+    // whole frame.  color = [height][width][3] linear radiance of a feat.width x feat.height frame, feat = what renderFeatures filled; out gets
+    // [height][width][3].  dp = nullptr: gi_denoise_default_params; else its width / height are overwritten with feat's.  Needs a device, not a
+    // scene.  false with last_error() set when it cannot run (out is then left alone).
+    bool denoise(const std::vector<double>& color, const Features& feat, std::vector<double>& out, const gi_denoise_params* dp = nullptr)
+    {
+        if (!ensure_context()) return false;
+        gi_denoise_params p;
+        if (dp) p = *dp; else gi_denoise_default_params(&p);
+        p.width = feat.width; p.height = feat.height;
+        const size_t npix = (size_t)(feat.width > 0 ? feat.width : 0) * (size_t)(feat.height > 0 ? feat.height : 0);
+        if (color.size() != npix * 3 || feat.albedo.size() != npix * 3 || feat.normal.size() != npix * 3 || feat.depth.size() != npix || feat.coverage.size() != npix) {
+            _st->err = "denoise: colour and feature buffers do not have the size of a " + std::to_string(feat.width) + " x " + std::to_string(feat.height) + " frame";
+            return false;
+        }
+        std::vector<double> buf(npix * 8 + 8), res(npix * 3 + 3);
+        for (size_t i = 0; i < npix; i++) {
+            for (int k = 0; k < 3; k++) { buf[i * 8 + k] = feat.albedo[i * 3 + k]; buf[i * 8 + 3 + k] = feat.normal[i * 3 + k]; }
+            buf[i * 8 + 6] = feat.depth[i]; buf[i * 8 + 7] = feat.coverage[i];
+        }
+        if (check(gi_denoise_host(_st->ctx, &p, color.data(), 1, buf.data(), 1, res.data(), 1)) != 0) return false;
+        res.resize(npix * 3);
+        out.swap(res);
+        return true;
+    }
+
     // ---- single-vertex pieces of radiance(), include/raytracer.h:321-379,481-506,509-529: the kernels' per-lane functions on the host
     uint32_t rng_stream = 0, rng_depth = 0;   // key of the counter RNG for the draws these three make (the reference calls drand())
     int rayType(const Entity* entity, const Ray& ray, gi::dvec3& norm, gi::dvec2& minUV)

@@ -185,6 +185,44 @@ int gi_render_features_device(gi_ctx*, const gi_render_params*, int32_t n_sample
 int gi_render_features_host(gi_ctx*, const gi_render_params*, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_ids);
 int gi_last_features_ms(gi_ctx*, float* ms);
 
+/* Denoiser -- an ADDITION: the reference has none, so nothing of it is replaced.  A feature-guided, edge-avoiding a-trous wavelet filter
+ * (Dammertz et al. 2010) over a whole frame, guided by the buffers of gi_render_features_*.  No scene is needed: the entries work on any context.
+ * color [height][width][3] linear radiance as gi_render_* writes it; features [height][width][8] = albedo rgb, normal xyz, depth, coverage;
+ * out [height][width][3].  Each of the three is float (flag 0) or double (1): floats are widened on load, the result is rounded once on store.
+ * All arithmetic is f64 with IEEE operations only (+ - * /, compares, selects; no exp / pow / sqrt) in the order written here, so the result
+ * can be restated exactly (the tests' numpy statement is bit-equal); the edge-stopping function is therefore Tukey's biweight, not a Gaussian.
+ *   1. iterations = 0: out = color (converted), nothing else runs.
+ *   2. m = demodulate ? (albedo > 1e-3 ? albedo : 1e-3) : 1 per channel;  c = color / m.
+ *   3. for level i = 0 .. iterations-1, step = 1 << i, h = [1/16, 1/4, 3/8, 1/4, 1/16]: for pixel p the taps q = p + step (dx, dy), dy = -2 .. 2
+ *      outer, dx = -2 .. 2 inner; taps outside the frame are skipped.  With |v|^2 = (x^2 + y^2) + z^2:
+ *        dc = |c_p - c_q|^2 / (|c_p|^2 + (|c_q|^2 + 1e-12))          dn = |n_p - n_q|^2
+ *        da = |a_p - a_q|^2 + (cov_p - cov_q)^2                        dz = r^2, r = (z_p - z_q) / (z_p + z_q) if z_p + z_q > 0, else 0
+ *        d  = ((dc inv_c + dn inv_n) + dz inv_z) + da inv_a,  inv_c = 4^i / sigma_color^2 (the colour sigma halves per level), the others
+ *             1 / sigma^2, computed once on the host in double; a sigma of 0 switches its term off (inv = 0)
+ *        t  = 1 - min(d, 1) (a NaN d counts as 1);   w = (h[dy] h[dx]) (t t);   num += w c_q per channel, den += w, in tap order
+ *      c'_p = num / den.  The centre tap has d = 0 and weight 9/64, so den > 0.
+ *   4. out = c m.
+ *   5. A tap whose (demodulated) colour has a non-finite channel is skipped; a centre pixel with a non-finite channel uses dc = 0 for all
+ *      its taps; if every tap was skipped the pixel becomes 0 0 0.  The output of a level is always finite (finite features given).
+ * Whole frames only: the filter reads neighbours across rows, so callers that render in stripes denoise the gathered frame.
+ * GI_E_INVALID: width or height < 1, iterations outside 0 .. 8, a negative or NaN sigma, a null pointer; the output is not touched.
+ * gi_denoise_default_params: 5 iterations, demodulate 1, sigmas 1.0, 0.5, 0.1, 0.25 (width and height 0: the caller sets them).  A colour sigma of
+ * 2.0 smooths an untextured frame a little more but blurs the lighting of a frame that has little noise to begin with.
+ * gi_denoise_device: DEVICE pointers, asynchronous on the context's stream; out may be the same pointer as color.  The context owns the scratch
+ * (two f64 colour buffers and one f64 guide record per pixel: 112 bytes per pixel), sized on first use and kept.
+ * gi_denoise_host: HOST pointers.  gi_last_denoise_ms: device time of the last pass (HIP events around it); the frame's and the feature
+ * pass's times are left alone. */
+typedef struct gi_denoise_params {
+    int32_t width, height;
+    int32_t iterations;      /* 0 .. 8 levels */
+    int32_t demodulate;      /* 1: filter colour / albedo and multiply back (keeps texture detail) */
+    double sigma_color, sigma_normal, sigma_depth, sigma_albedo;
+} gi_denoise_params;
+void gi_denoise_default_params(gi_denoise_params*);
+int gi_denoise_device(gi_ctx*, const gi_denoise_params*, const void* d_color, int color_is_f64, const void* d_features, int features_is_f64, void* d_out, int out_is_f64);
+int gi_denoise_host(gi_ctx*, const gi_denoise_params*, const void* h_color, int color_is_f64, const void* h_features, int features_is_f64, void* h_out, int out_is_f64);
+int gi_last_denoise_ms(gi_ctx*, float* ms);
+
 /* Function-level entry points (parity tests and the C++ API's public methods).  Host pointers.
  * replaces RayTracer::trace (include/raytracer.h:382-478): rays [n][6] origin + unit dir -> hit, entity, res [n][8]        */
 int gi_trace(gi_ctx*, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res);
