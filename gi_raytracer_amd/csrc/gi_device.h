@@ -1051,6 +1051,29 @@ GI_HD bool trace_wide(const Scene& S, const WN& W, const Ray& ray, const Rng& rn
     while (trace_wide_step<FEAT>(S, W, ray, rng, alpha_purpose, t, best)) { }
     return t.intersected;
 }
+// Does the ray leave the scene without its walk ever standing on a non-empty leaf?  The first turns of trace_wide's own walk -- the same WRay
+// (trace_wide_begin, `plain` for an axis-parallel ray included), the same box tests in the same order (wwalk_begin, wwalk_turn: walk_hits and the
+// content boxes W carries), tc = INFINITY as trace_wide has it until its first hit, and a hit is only ever found from a leaf -- so when the walk
+// ends here without a leaf, trace_wide over the same W meets no leaf either: it tests no entity, draws no alpha number, leaves no uv behind and
+// returns false.  true is therefore a SUFFICIENT condition for a miss; false (a leaf was met, or max_turns turns did not end the walk) says nothing
+// and the ray is traced as usual.  No entity is looked at here.  k_st_shade asks this about the next ray of a vertex: in an open scene most
+// reflected rays are decided within a few records and never become a path record, a queue entry, a sort key or an item of the trace stage.
+template <class WN>
+GI_HD bool ray_leaves_scene(const Scene& S, const WN& W, const Ray& ray, int max_turns)
+{
+    WRay wr = wray_make(ray);
+    wr.plain = !(fabs(ray.inv.x) < INFINITY && fabs(ray.inv.y) < INFINITY && fabs(ray.inv.z) < INFINITY);
+    WWalk k;
+    if (!wwalk_begin(S, W, k, ray, wr, 0.0, INFINITY)) return true;   // misses the scene's box
+    for (int turn = 0; turn < max_turns; turn++) {
+        int32_t lnode = 0, first = 0, cnt = 0;
+        int lslot = 0;
+        const int r = wwalk_turn(W, k, ray, wr, 0.0, INFINITY, lnode, lslot, first, cnt);
+        if (r == WALK_END) return true;
+        if (r == WALK_LEAF) return false;
+    }
+    return false;
+}
 // RayTracer::visible over the wide records, one leaf per call (k_st_shadow hands idle lanes new shadow rays; everybody else loops in visible_wide)
 struct VisWalk {
     WRay wr;

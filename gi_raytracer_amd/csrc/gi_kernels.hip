@@ -696,18 +696,25 @@ __global__ void k_iota(uint32_t* v, uint32_t n) { for (uint32_t i = blockIdx.x *
 template <int FEAT, int WIDE, int DEFER>
 __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_st_shade(Scene S, uint64_t seed, PathPool pool, const unsigned long long* slot_sample, unsigned long long sample0,
                                                        const uint32_t* q_shade, const StreamCtl* ctl, unsigned int* bc, uint32_t* segs, uint32_t* q_cont, uint32_t* k_cont, uint32_t* q_gather, double* g_pos,
-                                                       uint32_t* q_free, double* lbuf, ShadowQ* shq, const uint32_t* q_orig)
+                                                       uint32_t* q_free, double* lbuf, ShadowQ* shq, const uint32_t* q_orig, uint32_t early_turns)
 {
     // the waves of a workgroup take its items 64 at a time from a counter in LDS (in the 128 bytes the wide records leave free) instead of
     // a fixed share each: a wave that drew cheap items takes more of them
-    unsigned int* const s_next = reinterpret_cast<unsigned int*>(gi_dyn_lds + (size_t)GI_LDS_WNODES * sizeof(WNode));
+    unsigned int* const s_next = reinterpret_cast<unsigned int*>(gi_dyn_lds + (DEFER == 1 ? (size_t)GI_LDS_BIG_CNT_OFF : (size_t)GI_LDS_WNODES * sizeof(WNode)));
     if (WIDE != 0 && threadIdx.x == 0) *s_next = 0u;
     typename LdsSrc<WIDE>::type N;
-    if constexpr (DEFER != 0) {   // no walk in this instance: the records stay where they are
+    // early_turns != 0 (stream_passes): the next ray of a vertex is walked for up to that many turns (ray_leaves_scene, gi_device.h); one that leaves
+    // the scene without meeting a leaf ends its path here.  The walk is the trace stage's, over the trace stage's tables: NP is staged as k_st_trace stages N.
+    // One-light instance only (DEFER 1): the several-lights instances have no registers to spare for a walk, and are always handed 0
+    typename LdsSrc<WIDE>::type NP;
+    if constexpr (DEFER != 0) {   // no shadow walk in this instance: the records stay where they are unless the probe wants them
         N.g = S.wnodes; N.cboxes = S.cboxes; N.cuse = S.cuse; N.n_l = 0;
-        __syncthreads();
-    } else
+        if (DEFER == 1 && early_turns != 0u) NP = LdsSrc<WIDE>::stage_for_trace(S);   // ends with a barrier
+        else { NP = N; __syncthreads(); }
+    } else {
         N = LdsSrc<WIDE>::stage(S);   // ends with a barrier
+        NP = N;
+    }
     const uint32_t n_in = ctl->n_shade;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t cs = WIDE != 0 ? (uint32_t)GI_SHADE_CHUNK : blockDim.x;
@@ -754,35 +761,43 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
                 if constexpr (DEFER == 1) fl = stage_shade_nodes<FEAT, typename LdsSrc<WIDE>::type, DEFER>(S, N, p, seed, nullptr, &so, nullptr, &ql);
                 else
                 fl = stage_shade_nodes<FEAT, typename LdsSrc<WIDE>::type, DEFER>(S, N, p, seed, nullptr, &so, nullptr, e);
+                // what does not depend on the probe goes out first (its registers are free for the walk): the shadow query, the gather query, A0
+                if constexpr (DEFER == 1) { ql.idx = (uint32_t)(slot_sample[slot] - sample0); ql.slot = slot; *e = ql; }
+                else
+                for (int li = 0; li < nl; li++) { e[li].idx = (uint32_t)(slot_sample[slot] - sample0); e[li].slot = slot; }
                 if (fl != 0) {
-                    PoolRay r;
-                    for (int k = 0; k < 3; k++) { r.o[k] = p.o[k]; r.d[k] = p.d[k]; }
-                    r.stream = p.stream; r.depth = p.depth; r.pad_[0] = 0u; r.pad_[1] = 0u;
-                    pool.ray[slot] = r;
-                    PoolThru t;
-                    for (int k = 0; k < 3; k++) { t.T[k] = p.T[k]; t.contrib[k] = p.contrib[k]; }
-                    pool.thru[slot] = t;
                     if (fl & ST_GATHER) {
                         PoolGath gq;
                         for (int k = 0; k < 3; k++) { gq.gdir[k] = p.gdir[k]; gq.gcoef[k] = p.gcoef[k]; }
                         pool.gath[slot] = gq;
                     }
                     if (p.L[0] == p.L[0]) { double* Lp = pool.L + (size_t)slot * 3; Lp[0] = p.L[0]; Lp[1] = p.L[1]; Lp[2] = p.L[2]; }   // A0 of an emitting surface waits there for k_st_shadow
+                    // the next ray as the trace stage would read it back; "leaves" = its walk ends without a leaf: the miss adds nothing (no ambient
+                    // light, stream_passes), so the path ends here -- no ray, no throughput, no queue entry, no key
+                    if (DEFER == 1 && early_turns != 0u && (fl & ST_CONTINUE) && ray_leaves_scene(S, NP, make_ray_exact(ld3(p.o), ld3(p.d)), (int)early_turns)) fl &= ~ST_CONTINUE;
+                    if (early_turns == 0u || (fl & ST_CONTINUE)) {
+                        PoolRay r;
+                        for (int k = 0; k < 3; k++) { r.o[k] = p.o[k]; r.d[k] = p.d[k]; }
+                        r.stream = p.stream; r.depth = p.depth; r.pad_[0] = 0u; r.pad_[1] = 0u;
+                        pool.ray[slot] = r;
+                        PoolThru t;
+                        for (int k = 0; k < 3; k++) { t.T[k] = p.T[k]; t.contrib[k] = p.contrib[k]; }
+                        pool.thru[slot] = t;
+                    }
                 }
                 if ((FEAT & GI_FEAT_FOG) && (p.hpos[0] != hp0.x || p.hpos[1] != hp0.y || p.hpos[2] != hp0.z)) {   // the segment ended in the medium: the gather of this vertex uses the scatter point
                     PoolHit& h = pool.hit[slot];
                     h.hpos[0] = p.hpos[0]; h.hpos[1] = p.hpos[1]; h.hpos[2] = p.hpos[2];
                 }
-                if constexpr (DEFER == 1) { ql.idx = (uint32_t)(slot_sample[slot] - sample0); ql.slot = slot; *e = ql; }
-                else
-                for (int li = 0; li < nl; li++) { e[li].idx = (uint32_t)(slot_sample[slot] - sample0); e[li].slot = slot; }
             } else {
                 PathRef pr = pool[slot];
                 fl = stage_shade_nodes<FEAT>(S, N, pr, seed, nullptr, &so, lbuf + (slot_sample[slot] - sample0) * 3);
             }
         }
-        // a path with a pending gather stays alive one more pass even when it may not continue: the trace stage retires it
-        const bool cont = valid && (fl & (ST_CONTINUE | ST_GATHER)) != 0;
+        // a path with a pending gather stays alive one more pass even when it may not continue: the trace stage retires it.  With the probe on it
+        // is released here: the gather adds to lbuf[slot_sample[slot]] and reads the slot's hit and gather fields, and the free list of this pass is
+        // first read by the trace kernel of the next one, which the stream runs after this pass's shadow and gather kernels
+        const bool cont = valid && (fl & (early_turns != 0u ? ST_CONTINUE : (ST_CONTINUE | ST_GATHER))) != 0;
         const uint32_t a = wave_append(c_cont, cont);
         if (cont) { q_cont[seg + a] = slot; k_cont[seg + a] = so.key; }   // the key of the next ray, from the registers that just held it
         const uint32_t g = wave_append(c_gather, (fl & ST_GATHER) != 0);
@@ -1786,6 +1801,8 @@ struct gi_ctx {
     int render_mode = 0;              // 0 streaming passes (fixed spp) or rounds (adaptive), 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
     size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
     uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
+    bool early_miss = true;           // GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (stream_passes)
+    uint32_t early_turns = 4;         // GI_EARLY_MISS_TURNS: turns of the walk that probe may take before it gives the ray to the trace stage
     uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
     uint32_t coop_factor = 4;         // finisher stages with at most 4 x coop_factor x (resident waves) paths run one path per group of 16 lanes (at most 2 x: one per wave)
     // finisher stages {paths per wave (0: spread evenly over the resident waves), max vertices}; the last stage runs to MAX_DEPTH.
@@ -1963,11 +1980,12 @@ static constexpr TraceK kTrace[] = {
     {k_st_trace<7, 0>, kLdsNodes}, {k_st_trace<7, 1>, kLdsWideBoxes}, {k_st_trace<0, 1, true>, kLdsWideBoxes}};
 static TraceK st_trace(int feat, bool wide, bool counting) { return counting ? kTrace[6] : kTrace[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
 // k_st_shade<FEAT, WIDE, DEFER>: FEAT 0, spheres, fog, textures x per-node, wide, wide with the shadow walks put off (one light; several lights)
+// (the one-light form stages the trace stage's records and content boxes for the probe of the next ray: its LDS, one 512-thread workgroup per CU as before)
 static constexpr ShadeK kShade[] = {
-    {k_st_shade<0, 0, 0>, kLdsNodes}, {k_st_shade<0, 1, 0>, kLdsNodes}, {k_st_shade<0, 1, 1>, kLdsNodes}, {k_st_shade<0, 1, 2>, kLdsNodes},
-    {k_st_shade<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 1>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 2>, kLdsNodes},
-    {k_st_shade<3, 0, 0>, kLdsNodes}, {k_st_shade<3, 1, 0>, kLdsNodes}, {k_st_shade<3, 1, 1>, kLdsNodes}, {k_st_shade<3, 1, 2>, kLdsNodes},
-    {k_st_shade<7, 0, 0>, kLdsNodes}, {k_st_shade<7, 1, 0>, kLdsNodes}, {k_st_shade<7, 1, 1>, kLdsNodes}, {k_st_shade<7, 1, 2>, kLdsNodes}};
+    {k_st_shade<0, 0, 0>, kLdsNodes}, {k_st_shade<0, 1, 0>, kLdsNodes}, {k_st_shade<0, 1, 1>, kLdsWideBoxes}, {k_st_shade<0, 1, 2>, kLdsNodes},
+    {k_st_shade<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 1>, kLdsWideBoxes}, {k_st_shade<GI_FEAT_SPHERES, 1, 2>, kLdsNodes},
+    {k_st_shade<3, 0, 0>, kLdsNodes}, {k_st_shade<3, 1, 0>, kLdsNodes}, {k_st_shade<3, 1, 1>, kLdsWideBoxes}, {k_st_shade<3, 1, 2>, kLdsNodes},
+    {k_st_shade<7, 0, 0>, kLdsNodes}, {k_st_shade<7, 1, 0>, kLdsNodes}, {k_st_shade<7, 1, 1>, kLdsWideBoxes}, {k_st_shade<7, 1, 2>, kLdsNodes}};
 static int feat_row(int feat) { return feat == 7 ? 3 : (feat == 3 ? 2 : feat); }   // the levels 0, spheres, fog, textures
 static ShadeK st_shade(int feat, bool wide, int defer) { return kShade[feat_row(feat) * 4 + (wide ? 1 + defer : 0)]; }
 // k_st_shadow<FEAT, MULTI>: FEAT 0, spheres, fog, textures x one light, several lights; then the counting instances (one light, several)
@@ -2028,6 +2046,8 @@ int gi_create(gi_ctx** out, int device_ordinal)
     if (const char* e = getenv("GI_LBUF_MAX_BYTES")) c->lbuf_bytes_max = (size_t)strtoull(e, nullptr, 0);   // per-sample radiance buffer: frames beyond it run in sample chunks
     if (const char* e = getenv("GI_COOP_FACTOR")) c->coop_factor = (uint32_t)strtoul(e, nullptr, 0);
     if (const char* e = getenv("GI_WAVE_FACTOR")) c->wave_factor = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), 0xffffu);
+    if (const char* e = getenv("GI_EARLY_MISS")) c->early_miss = atoi(e) != 0;
+    if (const char* e = getenv("GI_EARLY_MISS_TURNS")) c->early_turns = (uint32_t)std::min(64, std::max(1, atoi(e)));
     if (const char* e = getenv("GI_SORT_CONT")) c->sort_cont = atoi(e) != 0;
     if (const char* e = getenv("GI_DESCENT_JUMP")) c->descent_jump = atoi(e) != 0;
     if (const char* e = getenv("GI_FLAT_CANDIDATES")) c->flat_candidates = atoi(e) != 0;
@@ -2271,6 +2291,12 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
     const bool counting = c->count_stream;
     if (counting && !(wide && defers_shadows(c) && !c->S.has_spheres && c->S.n_fog == 0 && c->S.n_tex == 0))
         return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) cover triangle scenes without spheres, fog or textures, walked over wide records with one to four lights; use mode 1 (reference visits, megakernel) for this scene");
+    // The probe of the next ray in the deferred shade kernel (ray_leaves_scene): a ray that leaves the scene ends its path there.  Only where such a
+    // miss adds nothing and the trace stage's walk culls by content (no ambient light, no medium, content boxes installed, one light: the kernel instance that has the registers for it), and not in a counted
+    // frame (its trace_rays are compared with culling on and off).  With it a path that does not continue is released by the shade stage even
+    // with a gather pending (k_st_shade).
+    const bool no_ambient = c->S.ambient[0] == 0.0 && c->S.ambient[1] == 0.0 && c->S.ambient[2] == 0.0;
+    const uint32_t early_turns = (c->early_miss && wide && defers_shadows(c) && c->S.n_light == 1 && c->S.cboxes != nullptr && c->S.n_fog == 0 && no_ambient && !counting) ? c->early_turns : 0u;
     const PathPool pool = make_path_pool(c->d_spool.p, c->spool_slots);
     StreamCtl* ctl = c->d_ctl.p;
     uint32_t* q_new = c->d_qs[0].p;
@@ -2359,7 +2385,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         const bool many = c->S.n_light > 1;
         const ShadeK shade_k = st_shade(feat, wide, shq ? (many ? 2 : 1) : 0);
         stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, q_shade_use, ctl, bc, c->d_segs.p,
-                           c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, c->d_stage[3].p, lbuf, shq, q_orig);
+                           c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, c->d_stage[3].p, lbuf, shq, q_orig, early_turns);
         stage_end(c);
         if (shq) {   // the walks it put off; before the gather of the same vertices (the order in which a path's radiance is summed)
             const ShadowK shadow_k = st_shadow(feat, many, counting);
