@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms",
     "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
+    "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
+    "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
     "gih_add_texture", "gih_add_material_tex", "gih_load_png", "gih_free",
@@ -133,6 +135,14 @@ def lib():
     L.gi_build_photon_map.argtypes = [vp, C.c_int32, _dp, _dp]
     L.gi_trace_photons.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint64, _dp, C.POINTER(C.c_int64)]
     L.gi_debug_photon_tables.argtypes = [vp, _ip, _ip, _ip, vp, _ip, _dp, _dp]
+    L.gi_progressive_begin.argtypes = [vp, C.POINTER(RenderParams)]
+    L.gi_progressive_step_device.argtypes = [vp, C.c_int32, vp, C.c_int, vp, vp]
+    L.gi_progressive_step_host.argtypes = [vp, C.c_int32, vp, C.c_int, vp, vp]
+    L.gi_progressive_status.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
+    L.gi_progressive_state_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.gi_progressive_save.argtypes = [vp, vp, C.c_int64]
+    L.gi_progressive_restore.argtypes = [vp, vp, C.c_int64]
+    L.gi_progressive_end.argtypes = [vp]
     L.gi_group_create.argtypes = [C.POINTER(vp), C.c_int32, _ip]
     L.gi_group_destroy.argtypes = [vp]
     L.gi_group_size.argtypes = [vp]
@@ -379,6 +389,112 @@ def save_ppm(path, lin):
         f.write(a.tobytes())
 
 
+# The header of a progressive checkpoint (include/gi_hip.h: gi_progressive_save), little-endian, 192 bytes; the 72-byte pixel records follow.
+CHECKPOINT_MAGIC = b"GIPROGR\0"
+CHECKPOINT_VERSION = 1
+CHECKPOINT_HEADER = "<8sII11d7i4xdQiiQIIiiii"
+CHECKPOINT_RECORD_BYTES = 72
+_CHECKPOINT_FIELDS = ("width", "height", "stripe_h", "stripe_rank", "stripe_world", "min_samples", "max_samples", "noise_thresh", "seed",
+                      "schedule", "sample_end", "n_records", "record_bytes", "reserved0", "n_entity", "n_node", "n_photon", "reserved1")
+
+
+def parse_checkpoint_header(blob):
+    """The fields of a checkpoint's header as a dict (no device needed); ValueError when the blob is not a checkpoint of this format."""
+    import struct
+    n = struct.calcsize(CHECKPOINT_HEADER)
+    if len(blob) < n:
+        raise ValueError(f"checkpoint: {len(blob)} bytes, the header alone has {n}")
+    v = struct.unpack(CHECKPOINT_HEADER, bytes(blob[:n]))
+    if v[0] != CHECKPOINT_MAGIC:
+        raise ValueError("checkpoint: bad magic")
+    h = {"magic": v[0], "version": v[1], "header_bytes": v[2], "cam_pos": v[3:6], "cam_up": v[6:9], "cam_forward": v[9:12],
+         "sensor_diag": v[12], "focal_dist": v[13]}
+    h.update(zip(_CHECKPOINT_FIELDS, v[14:]))
+    if h["version"] != CHECKPOINT_VERSION or h["header_bytes"] != n or h["record_bytes"] != CHECKPOINT_RECORD_BYTES:
+        raise ValueError(f"checkpoint: version {h['version']}, header {h['header_bytes']} bytes, records of {h['record_bytes']} bytes: not this format")
+    if len(blob) != n + h["n_records"] * CHECKPOINT_RECORD_BYTES:
+        raise ValueError(f"checkpoint: {len(blob)} bytes, {n + h['n_records'] * CHECKPOINT_RECORD_BYTES} expected (truncated?)")
+    return h
+
+
+class ProgressiveRender:
+    """A progressive render session of a RayTracer (gi_progressive_*, include/gi_hip.h): the frame is refined in steps, and a frame built in steps
+    has the bits of the frame `run` builds in one call.  From RayTracer.progressive(w, h, **kw) or RayTracer.resume(blob); a context manager.
+    A context has one session: opening another, or uploading a scene or photons, ends this one (its next step raises GiError, code -4).
+    An object whose session was replaced by a newer one of the same RayTracer is stale: it raises the same error and its close() does nothing,
+    so closing an old object never ends the newer session."""
+
+    def __init__(self, rt, width, rows):
+        self.rt, self.width, self.rows = rt, width, rows
+        rt._session_serial = self.serial = getattr(rt, "_session_serial", 0) + 1
+
+    def _mine(self):
+        """Raise unless the context's session is still the one this object opened."""
+        if self.rt._session_serial != self.serial:
+            raise GiError(f"progressive: this session was replaced by a newer one of the same RayTracer ({GI_E_STATE})")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _status(self):
+        self._mine()
+        e, n = C.c_int32(), C.c_int64()
+        self.rt._check(self.rt.L.gi_progressive_status(self.rt.h, C.byref(e), C.byref(n)), "progressive_status")
+        return e.value, n.value
+
+    @property
+    def sample_end(self):
+        """E: every pixel has been offered samples [0, E)."""
+        return self._status()[0]
+
+    @property
+    def pixels_wanting(self):
+        """Pixels of this rank that would still take a sample under the session's max_samples."""
+        return self._status()[1]
+
+    @property
+    def done(self):
+        return self.pixels_wanting == 0
+
+    def step(self, n, f64=True, want_spp=False, cancel=None):
+        """Take up to n more samples per pixel and return the frame so far, [rows][w][3] linear (and the samples taken per pixel with want_spp).
+        cancel: an optional ctypes c_int polled during the step; a cancelled step raises GiError (code -5) and the session goes on."""
+        self._mine()
+        out = np.zeros((self.rows, self.width, 3), np.float64 if f64 else np.float32)
+        spp = np.zeros((self.rows, self.width), np.int32) if want_spp else None
+        self.rt._check(self.rt.L.gi_progressive_step_host(self.rt.h, int(n), out.ctypes.data_as(C.c_void_p), 1 if f64 else 0,
+                                                          spp.ctypes.data_as(C.c_void_p) if want_spp else None,
+                                                          C.addressof(cancel) if cancel is not None else None), "progressive_step")
+        return (out, spp) if want_spp else out
+
+    def frame(self, f64=True, want_spp=False):
+        """The frame as it stands (step(0): no path kernel runs)."""
+        return self.step(0, f64=f64, want_spp=want_spp)
+
+    def step_device(self, n, out_ptr, f64=False, spp_ptr=None):
+        """A step into device memory (raw device pointers), asynchronous on the context's stream."""
+        self._mine()
+        self.rt._check(self.rt.L.gi_progressive_step_device(self.rt.h, int(n), C.c_void_p(out_ptr), 1 if f64 else 0, C.c_void_p(spp_ptr) if spp_ptr else None, None), "progressive_step")
+
+    def save(self):
+        """The session as a checkpoint blob (bytes) for RayTracer.resume on a context with the same scene and photons."""
+        self._mine()
+        n = C.c_int64()
+        self.rt._check(self.rt.L.gi_progressive_state_bytes(self.rt.h, C.byref(n)), "progressive_state_bytes")
+        buf = C.create_string_buffer(n.value)
+        self.rt._check(self.rt.L.gi_progressive_save(self.rt.h, buf, n.value), "progressive_save")
+        return buf.raw
+
+    def close(self):
+        """End the session and free its records; nothing when a newer session has replaced this one."""
+        if self.rt._session_serial == self.serial:
+            self.rt.L.gi_progressive_end(self.rt.h)
+
+
 class RayTracerGroup:
     """Several devices driven from one process through the C ABI's gi_group_* entries (include/gi_hip.h): what the C++ RayTracer::run uses when
     more than one GPU is visible.  `devices` may repeat an ordinal (several contexts on one device)."""
@@ -542,6 +658,21 @@ class RayTracer:
         self._check(self.L.gi_render_host(self.h, C.byref(p), out.ctypes.data_as(C.c_void_p), 1 if f64 else 0,
                                           spp.ctypes.data_as(C.c_void_p) if want_spp else None, None), "render_host")
         return (out, spp) if want_spp else out
+
+    def progressive(self, w, h, **kw):
+        """A progressive session of the frame run(w, h, **kw) renders (same keywords): ProgressiveRender.step(n) refines it n samples at a time."""
+        p = self.params(w, h, **kw)
+        self._check(self.L.gi_progressive_begin(self.h, C.byref(p)), "progressive_begin")
+        return ProgressiveRender(self, w, self.local_rows(p))
+
+    def resume(self, blob):
+        """Open a session from ProgressiveRender.save()'s blob.  The caller has set the same scene and traced the same photons (same seed and count)."""
+        blob = bytes(blob)
+        self._check(self.L.gi_progressive_restore(self.h, blob, len(blob)), "progressive_restore")
+        h = parse_checkpoint_header(blob)
+        p = RenderParams()
+        p.width, p.height, p.stripe_h, p.stripe_rank, p.stripe_world = h["width"], h["height"], h["stripe_h"], h["stripe_rank"], h["stripe_world"]
+        return ProgressiveRender(self, h["width"], self.local_rows(p))
 
     def run_device(self, p, out_ptr, f64=False, spp_ptr=None):
         """Render into device memory (bench / multi-GPU path); out_ptr is a raw device pointer."""

@@ -3,6 +3,7 @@
     python -m gi_raytracer_amd scene.scn -o out.ppm [--pfm out.pfm] [--width 1000 --height 1000] [--samples MIN MAX [THRESH]] [--photons N]
                                [--features PREFIX [--feature-samples N]]
                                [--denoise OUT.ppm [--denoise-pfm OUT.pfm] [--denoise-iterations N] [--denoise-sigmas C N Z A]]
+                               [--progressive N [--time-limit SECONDS] [--checkpoint FILE]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -10,8 +11,14 @@ The scene file's own `samples` / `photons` / `camera` lines apply unless overrid
 PREFIX_normal.pfm (three channels), PREFIX_depth.pfm, PREFIX_coverage.pfm (one channel).
 --denoise OUT.ppm (an addition as well) runs the feature pass and the edge-avoiding a-trous denoiser on the frame and writes the result next to
 the frame, which is written as without the flag.
+--progressive N (an addition too) renders the frame in steps of N samples per pixel and rewrites -o (and --pfm) after every step, through a
+temporary file and a rename, so a viewer never reads half a file; the last step leaves the bytes of the run without the flag.  --time-limit
+SECONDS takes no further step once the frame's budget is spent (at least one step is taken); --checkpoint FILE resumes from FILE when it exists
+-- the scene, --photons and the frame size must be those of the run that wrote it; its sample settings apply -- and saves to it after every step.
+--features and --denoise act on the last frame written.
 """
 import argparse
+import os
 import sys
 import time
 
@@ -39,7 +46,78 @@ def parser():
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="N", help="levels of the filter, 0 .. 8 (default 5)")
     ap.add_argument("--denoise-sigmas", type=float, nargs=4, default=None, metavar=("C", "N", "Z", "A"),
                     help="sigmas of colour, normal, depth and albedo (default 1.0 0.5 0.1 0.25; 0 switches a term off)")
+    ap.add_argument("--progressive", type=int, default=None, metavar="N", help="render in steps of N samples per pixel, rewriting the output after every step")
+    ap.add_argument("--time-limit", type=float, default=None, metavar="SECONDS", help="with --progressive: take no further step once this much time went into the frame")
+    ap.add_argument("--checkpoint", default=None, metavar="FILE", help="with --progressive: resume from FILE when it exists, save the session to it after every step")
     return ap
+
+
+def check_args(ap, a):
+    """The rules between the flags; ap.error (exit status 2) on a breach.  Runs before anything touches the device."""
+    if a.denoise is None and (a.denoise_pfm or a.denoise_iterations is not None or a.denoise_sigmas is not None):
+        ap.error("--denoise-pfm, --denoise-iterations and --denoise-sigmas need --denoise OUT.ppm")
+    if a.progressive is None and (a.time_limit is not None or a.checkpoint is not None):
+        ap.error("--time-limit and --checkpoint need --progressive N")
+    if a.progressive is not None and a.progressive < 1:
+        ap.error("--progressive N: N must be at least 1")
+    if a.time_limit is not None and not a.time_limit >= 0:
+        ap.error("--time-limit SECONDS: a number >= 0")
+
+
+def replace_file(path, write):
+    """write(tmp) then rename over path: a reader sees the old file or the new one, never a part of one."""
+    tmp = f"{path}.part"
+    try:
+        write(tmp)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    os.replace(tmp, path)
+
+
+def write_bytes(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def render_progressive(a, rt):
+    """The frame in steps of a.progressive samples; returns (frame, spp, a note for the summary line)."""
+    resumed = a.checkpoint is not None and os.path.exists(a.checkpoint)
+    if resumed:
+        with open(a.checkpoint, "rb") as f:
+            blob = f.read()
+        h = gi.parse_checkpoint_header(blob)
+        if (h["width"], h["height"]) != (a.width, a.height):
+            raise SystemExit(f"{a.checkpoint}: a checkpoint of a {h['width']} x {h['height']} frame, not {a.width} x {a.height}")
+        sess = rt.resume(blob)
+        if (h["min_samples"], h["max_samples"], h["noise_thresh"]) != (rt.min_samples, rt.max_samples, rt.noise_thresh):
+            print(f"{a.checkpoint}: resuming with the checkpoint's sample settings (min {h['min_samples']}, max {h['max_samples']}, noise threshold "
+                  f"{h['noise_thresh']}), not those of this run (min {rt.min_samples}, max {rt.max_samples}, noise threshold {rt.noise_thresh})", file=sys.stderr)
+        rt.min_samples, rt.max_samples, rt.noise_thresh = h["min_samples"], h["max_samples"], h["noise_thresh"]
+    else:
+        sess = rt.progressive(a.width, a.height)
+    t0 = time.time()
+    steps, first = 0, sess.sample_end
+    with sess:
+        while True:
+            lin, spp = sess.step(a.progressive, f64=False, want_spp=True)
+            steps += 1
+            replace_file(a.output, lambda t: gi.save_ppm(t, lin))
+            if a.pfm:
+                replace_file(a.pfm, lambda t: gi.save_pfm(t, lin))
+            if a.checkpoint:
+                blob = sess.save()
+                replace_file(a.checkpoint, lambda t: write_bytes(t, blob))
+            done, end = sess.done, sess.sample_end
+            if done or end >= rt.max_samples:
+                why = "finished"
+                break
+            if a.time_limit is not None and time.time() - t0 >= a.time_limit:
+                why = "time limit reached, frame unfinished"
+                break
+    note = f"; progressive: {steps} step(s) of {a.progressive}, samples {first} .. {end} of {rt.max_samples} offered per pixel ({why})"
+    return lin, spp, note + (f", resumed from {a.checkpoint}" if resumed else "")
 
 
 def denoise_kwargs(a):
@@ -62,8 +140,7 @@ def feature_samples(a, max_samples):
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
-    if a.denoise is None and (a.denoise_pfm or a.denoise_iterations is not None or a.denoise_sigmas is not None):
-        ap.error("--denoise-pfm, --denoise-iterations and --denoise-sigmas need --denoise OUT.ppm")
+    check_args(ap, a)
     scene = gi.Scene.load(a.scene).rebuild()
     rt = gi.RayTracer(a.device).setScene(scene)          # raises without a GPU: there is no CPU path
     if a.samples:
@@ -77,12 +154,16 @@ def main(argv=None):
     if n_photons > 0 and scene.desc().n_light > 0:
         stored = len(rt.tracePhotons(n_photons)[0])
     t1 = time.time()
-    lin, spp = rt.run(a.width, a.height, f64=False, want_spp=True)
-    t2 = time.time()
-    gi.save_ppm(a.output, lin)
-    if a.pfm:
-        gi.save_pfm(a.pfm, lin)
     feat = ""
+    if a.progressive:
+        lin, spp, feat = render_progressive(a, rt)
+        t2 = time.time()
+    else:
+        lin, spp = rt.run(a.width, a.height, f64=False, want_spp=True)
+        t2 = time.time()
+        gi.save_ppm(a.output, lin)
+        if a.pfm:
+            gi.save_pfm(a.pfm, lin)
     if a.features:
         nf = feature_samples(a, rt.max_samples)
         fb = rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)

@@ -1524,6 +1524,38 @@ __global__ __launch_bounds__(GI_BLOCK) void k_st_accum(Frame F, PixRec* pix, con
     }
 }
 
+// Progressive sessions (gi_progressive_*): the frame as the pixel records hold it, nothing folded.  One lane per record, consecutive lanes read
+// consecutive 72-byte records; tiled = 0: the records are in st_pixel_xy order (fixed schedule), 1: in padded 8x8 tiles (rounds, wf_pixel_xy),
+// whose padding records have no pixel.
+__global__ __launch_bounds__(GI_BLOCK) void k_pix_resolve(Frame F, const PixRec* pix, uint32_t n_rec, int tiled, void* out, int out_f64, int32_t* out_spp)
+{
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
+        int x, ly;
+        if (tiled) { if (!wf_pixel_xy(F, i, x, ly)) continue; }
+        else st_pixel_xy(F, i, x, ly);
+        const PixRec r = pix[i];
+        pixel_write(F, x, ly, pixrec_to_state(r), out, out_f64, out_spp);
+    }
+}
+// gi_progressive_status: how many pixels pixel_wants_sample holds for under F (the session's own max_samples); one count per wave, as k_ad_accum
+__global__ __launch_bounds__(GI_BLOCK) void k_pix_wanting(Frame F, const PixRec* pix, uint32_t n_rec, int tiled, unsigned int* n_wanting)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_round = (n_rec + 63u) & ~63u;
+    for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_round; i0 += gridDim.x * blockDim.x) {
+        const uint32_t i = i0 + lane;
+        int x, ly;
+        bool wants = false;
+        if (i < n_rec && (!tiled || wf_pixel_xy(F, i, x, ly))) {
+            const int2 ss = *reinterpret_cast<const int2*>(&pix[i].samps);   // samps and s, adjacent and 8-byte aligned in the 72-byte record
+            PixelState ps;
+            ps.samps = ss.x; ps.s = ss.y;                                      // the two fields the rule reads
+            wants = pixel_wants_sample(ps, F);
+        }
+        (void)wave_append(n_wanting, wants);
+    }
+}
+
 // First-hit feature buffers (gi_render_features_*; gi_device.h: aov_sample): one lane per pixel of this rank's rows in the 8x8-tile order of
 // st_pixel_xy, so a wave is a tile and all its lanes are on the same sample index s -- rays as coherent as the new paths of k_st_trace, on the same
 // records in LDS and the same wave-uniform leaves.  A lane loops over s (Halton index of sample s = that of sample 0 + s * inc), keeps its eight
@@ -1773,7 +1805,17 @@ struct gi_ctx {
     DevBuf<unsigned char> d_spool;        // paths of the streaming pipeline: field arrays (PathPool), GI_POOL_BYTES_PER_SLOT each
     size_t spool_slots = 0;
     DevBuf<PixRec> d_pix;
-    DevBuf<unsigned int> d_wfcnt;     // rounds (render_adaptive): [0] paths started by k_ad_gen, [1] pixels still wanting samples
+    // a progressive session (gi_progressive_*): the pixel records it owns between steps -- everything else a step uses is the shared scratch above and below
+    struct Progressive {
+        bool open = false;
+        gi_render_params rp{};
+        Frame F{};                    // make_frame(rp): max_samples is the session's own
+        int schedule = 0;             // 0: refill pipeline, records in st_pixel_xy order; 1: synchronous rounds, records in padded 8x8 tiles (wf_pixel_xy)
+        int32_t sample_end = 0;       // E: every pixel has been offered samples [0, E)
+        uint32_t n_rec = 0;
+        DevBuf<PixRec> pix;
+    } prog;
+    DevBuf<unsigned int> d_wfcnt;    // rounds (render_adaptive): [0] paths started by k_ad_gen, [1] pixels still wanting samples
     unsigned int* h_wfcnt = nullptr;  // pinned host mirror of d_wfcnt
     DevBuf<double> d_lbuf;            // streaming variant: per-sample radiance of the current chunk
     DevBuf<unsigned long long> d_slot_sample;
@@ -2105,6 +2147,7 @@ int gi_set_stream(gi_ctx* c, void* s)
 int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
 {
     if (!c) return GI_E_INVALID;
+    c->prog.open = false;   // a progressive session belongs to the scene and photon map it began on
     HostScene H;
     std::string err;
     if (!layout_scene(d, H, err)) return fail(c, GI_E_INVALID, err);
@@ -2156,6 +2199,7 @@ int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
 int gi_clear_photons(gi_ctx* c)
 {
     if (!c) return GI_E_INVALID;
+    c->prog.open = false;
     clear_photon_map(c);
     return GI_OK;
 }
@@ -2163,6 +2207,7 @@ int gi_clear_photons(gi_ctx* c)
 int gi_upload_photons(gi_ctx* c, const gi_photon_map_desc* d)
 {
     if (!c || !d) return GI_E_INVALID;
+    c->prog.open = false;
     if (!c->have_scene) return fail(c, GI_E_STATE, "upload_photons: no scene");
     HostPhotons H;
     std::string err;
@@ -2456,10 +2501,15 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
     return GI_OK;
 }
 
-static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
+// Samples [s_begin, s_end) of every pixel of a fixed-spp frame, folded into the records `pix` (st_pixel_xy order) in sample order, one chunk of
+// samples at a time; init: the records are put in their initial state first (a frame from sample 0).  The one-shot frame (render_streaming) is
+// [0, max_samples) on d_pix with init; a step of a progressive session is [E, E') on the session's records.  s_done (optional) follows the
+// samples folded so far, so that a cancelled call tells how far the records got.
+static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, int s_end, bool init, void* d_out, int out_is_f64, int32_t* d_spp,
+                          volatile const int* cancel, int* s_done)
 {
     const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;   // valid pixels only, enumerated in 8x8-tile order (st_pixel_xy)
-    const int spp = F.max_samples;
+    const int spp = s_end - s_begin;
     // Paths in flight: as many as fit -- the whole frame when HBM allows (1080p x 256 spp = 531 M paths = 119 GB of PathRec on a
     // 288 GB part).  More paths per pass = fewer passes and, above all, better-sorted (more coherent) queues.
     size_t slots_budget = c->pool_slots_max;
@@ -2478,7 +2528,6 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
     int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)spp, c->lbuf_bytes_max / ((size_t)n_pix * 24)));
     int rc = stream_alloc(c, P);
     if (rc) return rc;
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
     if (c->d_lbuf.n < (size_t)n_pix * chunk * 3) HIP_TRY(c, c->d_lbuf.alloc((size_t)n_pix * chunk * 3));
     const StreamGrids& G = stream_grids(c);
     hipStream_t st = c->stream;
@@ -2490,12 +2539,12 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
         c->stream_shaded = 0;
     }
     HIP_TRY(c, hipEventRecord(c->ev0, st));
-    hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
+    if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
     if (c->d_pixtab.n < n_pix) HIP_TRY(c, c->d_pixtab.alloc(n_pix));
     hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
-    launches += 2;
-    for (int s0 = 0; s0 < spp; s0 += chunk) {
-        const int ns = std::min(chunk, spp - s0);
+    launches++;
+    for (int s0 = s_begin; s0 < s_end; s0 += chunk) {
+        const int ns = std::min(chunk, s_end - s0);
         const unsigned long long sample0 = (unsigned long long)s0 * n_pix, sample_end = (unsigned long long)(s0 + ns) * n_pix;
         unsigned long long next = sample0;
         bool exhausted = false;
@@ -2509,8 +2558,9 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
         };
         rc = stream_passes(c, F, sample0, c->d_lbuf.p, P, refill, exhausted, cancel, launches);   // pass 0: every slot is free
         if (rc) return rc;
-        stage_begin(c, STG_ACCUM); hipLaunchKernelGGL(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp); stage_end(c);
+        stage_begin(c, STG_ACCUM); hipLaunchKernelGGL(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp); stage_end(c);
         launches++;
+        if (s_done) *s_done = s0 + ns;
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev1, st));
@@ -2518,21 +2568,29 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
     return GI_OK;
 }
 
+static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
+{
+    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
+    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
+    return stream_samples(c, F, c->d_pix.p, 0, F.max_samples, true, d_out, out_is_f64, d_spp, cancel, nullptr);
+}
+
 // Adaptive sampling (min_samples != max_samples, include/raytracer.h:108-148), and every frame of render mode 2: synchronous rounds --
 // in a round every pixel that still wants samples starts those it is certain to take (k_ad_gen), the paths run through the streaming
 // passes (sorted queues, octree records in LDS, wave-cooperative gather, staged finisher), and k_ad_accum applies the variance rule in
 // sample order.  With min_samples == max_samples this renders the fixed-spp frame of render_streaming, a round of up to B samples at a time.
-static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
+// pix: the records the rounds work on (padded 8x8 tiles); init: put them in their initial state first.  The one-shot frame (render_adaptive) is d_pix
+// with init; a step of a progressive session is the session's records with the step's cap E' in F.max_samples -- the same loop, which then stops at E'.
+static uint32_t rounds_records(const Frame& F) { return (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3)) * 64u; }
+static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
-    const uint32_t tiles = (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3));
-    const uint32_t n_pix = tiles * 64u;   // padded to whole 8x8 tiles (wf_pixel_xy)
+    const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (wf_pixel_xy)
     int B = (int)std::min<size_t>(32, std::max<size_t>(1, c->pool_slots_max / n_pix));
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
     const size_t slots = (size_t)n_pix * (size_t)B;
     if (slots > 0xfffffff0ull) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
     int rc = stream_alloc(c, (uint32_t)slots);
     if (rc) return rc;
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
     if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
     if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
     if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 2 * sizeof(unsigned int), hipHostMallocDefault));
@@ -2542,19 +2600,18 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     int launches = 0;
     c->ev_used = 0; c->ev_stage.clear();
     HIP_TRY(c, hipEventRecord(c->ev0, st));
-    hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, c->d_pix.p, n_pix);
-    launches++;
+    if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
     bool any = F.max_samples > 0 && F.min_samples > 0;
     if (!any) {   // 0 samples per pixel still has to write the initial colour
         HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
+        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
         launches++;
     }
     while (any) {
         if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
         HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
         stage_begin(c, STG_REGEN);
-        hipLaunchKernelGGL(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, st, c->S, F, c->d_pix.p, make_path_pool(c->d_spool.p, c->spool_slots), c->d_slot_sample.p, n_pix, B, c->d_qs[0].p, cnt + 0);
+        hipLaunchKernelGGL(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, st, c->S, F, pix, make_path_pool(c->d_spool.p, c->spool_slots), c->d_slot_sample.p, n_pix, B, c->d_qs[0].p, cnt + 0);
         stage_end(c);
         launches++;
         HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt, cnt, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -2565,7 +2622,7 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
         rc = stream_passes(c, F, 0ull, c->d_lbuf.p, 0u, refill, exhausted, cancel, launches);
         if (rc) return rc;
         stage_begin(c, STG_ACCUM);
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, c->d_pix.p, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
+        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
         stage_end(c);
         launches++;
         HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 1, cnt + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -2576,6 +2633,13 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     HIP_TRY(c, hipEventRecord(c->ev1, st));
     c->last_launches = launches;
     return GI_OK;
+}
+
+static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
+{
+    const uint32_t n_pix = rounds_records(F);
+    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
+    return run_rounds(c, F, c->d_pix.p, true, d_out, out_is_f64, d_spp, cancel);
 }
 
 int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
@@ -2726,6 +2790,224 @@ int gi_render_host(gi_ctx* c, const gi_render_params* p, void* h_out, int out_is
     (void)hipFree(d_out);
     if (d_spp) (void)hipFree(d_spp);
     return rc;
+}
+
+// ---- progressive sessions (an addition: the reference renders a frame in one piece).  The session owns its pixel records (c->prog.pix); a step runs
+// the bodies of the one-shot frame on them -- stream_samples over [E, E') for a fixed sample count, run_rounds with the cap E' otherwise -- so a
+// frame built in steps has the bits of the frame built in one call.
+namespace {
+struct ProgBlobHeader {            // little-endian, 192 bytes; the pixel records follow as they lie on the device (include/gi_hip.h)
+    char magic[8];
+    uint32_t version, header_bytes;
+    gi_render_params rp;           // 136 bytes: its fields in declaration order, 4 bytes of padding before noise_thresh
+    int32_t schedule, sample_end;
+    uint64_t n_records;
+    uint32_t record_bytes, reserved0;
+    int32_t n_entity, n_node, n_photon, reserved1;
+};
+static_assert(sizeof(gi_render_params) == 136 && sizeof(ProgBlobHeader) == 192 && sizeof(PixRec) == 72, "checkpoint layout (include/gi_hip.h)");
+const char kProgMagic[8] = {'G', 'I', 'P', 'R', 'O', 'G', 'R', '\0'};
+const uint32_t kProgVersion = 1;
+
+uint32_t prog_records(const Frame& F, int schedule) { return schedule == 0 ? (uint32_t)F.w * (uint32_t)F.local_rows : rounds_records(F); }
+// a session on parameters already validated: the records allocated (not yet filled), E = sample_end
+int prog_open(gi_ctx* c, const gi_render_params& rp, const Frame& F, int schedule, int32_t sample_end)
+{
+    gi_ctx::Progressive& g = c->prog;
+    g.open = false;
+    const uint32_t n_rec = prog_records(F, schedule);
+    if (g.pix.n != n_rec || !g.pix.p) HIP_TRY(c, g.pix.alloc(n_rec));
+    g.rp = rp; g.F = F; g.schedule = schedule; g.sample_end = sample_end; g.n_rec = n_rec;
+    return GI_OK;
+}
+}  // namespace
+
+int gi_progressive_begin(gi_ctx* c, const gi_render_params* p)
+{
+    if (!c) return GI_E_INVALID;
+    c->prog.open = false;
+    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_begin: no scene uploaded");
+    Frame F;
+    std::string ferr;
+    if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
+    if (c->render_mode == 1 || c->count_enabled) return fail(c, GI_E_STATE, "progressive_begin: sessions run on the streaming passes (render mode 0 or 2), not on the megakernel");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int schedule = (c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0) ? 0 : 1;   // as gi_render_device picks
+    int rc = prog_open(c, *p, F, schedule, 0);
+    if (rc) return rc;
+    if (c->prog.n_rec) {
+        hipLaunchKernelGGL(k_pix_init, dim3(stream_grids(c).pix), dim3(GI_BLOCK), 0, c->stream, c->prog.pix.p, c->prog.n_rec);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    c->prog.open = true;
+    return GI_OK;
+}
+
+int gi_progressive_end(gi_ctx* c)
+{
+    if (!c) return GI_E_INVALID;
+    if (c->prog.open || c->prog.pix.p) (void)hipSetDevice(c->device);
+    c->prog.open = false;
+    c->prog.pix.release();
+    return GI_OK;
+}
+
+int gi_progressive_step_device(gi_ctx* c, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
+{
+    if (!c || !d_out || n_samples < 0) return c ? fail(c, GI_E_INVALID, "progressive_step: n_samples < 0 or no output buffer") : GI_E_INVALID;
+    gi_ctx::Progressive& g = c->prog;
+    if (!g.open) return fail(c, GI_E_STATE, "progressive_step: no session open (gi_progressive_begin; scene and photon uploads end a session)");
+    if (cancel && *cancel) return fail(c, GI_E_CANCELLED, "render: cancelled");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->last_ms = 0; c->last_launches = 0;
+    // a rank without rows has no pixel and no output: only E moves (no kernel, no timing beyond the reset above), and d_out is never touched --
+    // which is why gi_progressive_step_host may hand its host pointer through for such a rank
+    if (g.F.local_rows == 0) { g.sample_end = (int32_t)std::min<long long>((long long)g.sample_end + n_samples, g.F.max_samples); return GI_OK; }
+    const int32_t e0 = g.sample_end, e1 = (int32_t)std::min<long long>((long long)e0 + n_samples, g.F.max_samples);
+    if (e1 == e0) {                 // nothing to take: the frame as the records hold it
+        hipStream_t st = c->stream;
+        c->ev_used = 0; c->ev_stage.clear();
+        HIP_TRY(c, hipEventRecord(c->ev0, st));
+        stage_begin(c, STG_ACCUM);
+        hipLaunchKernelGGL(k_pix_resolve, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, st, g.F, g.pix.p, g.n_rec, g.schedule, d_out, out_is_f64, d_spp);
+        stage_end(c);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev1, st));
+        c->last_launches = 1;
+        return GI_OK;
+    }
+    if (g.schedule == 0) {
+        int done = e0;
+        const int rc = stream_samples(c, g.F, g.pix.p, e0, e1, false, d_out, out_is_f64, d_spp, cancel, &done);
+        g.sample_end = done;        // a cancelled step keeps the chunks it folded
+        return rc;
+    }
+    if (c->count_stream) return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) belong to fixed-sample-count frames of the wavefront pipeline");
+    Frame F = g.F;
+    F.max_samples = e1;             // the cap of this step; a pixel the rule has stopped stays stopped
+    const int rc = run_rounds(c, F, g.pix.p, false, d_out, out_is_f64, d_spp, cancel);
+    // cancelled at the top of a round or between the passes of one (whose radiances are dropped: the records change in k_ad_accum alone, and the n that
+    // k_ad_gen left is set again by the next one): every record is at a sample boundary and below the cap; E stays, and the next step offers [.., E')
+    // again to those below it
+    if (rc == GI_OK) g.sample_end = e1;
+    return rc;
+}
+
+int gi_progressive_step_host(gi_ctx* c, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_spp, volatile const int* cancel)
+{
+    if (!c || !h_out || n_samples < 0) return c ? fail(c, GI_E_INVALID, "progressive_step: n_samples < 0 or no output buffer") : GI_E_INVALID;
+    if (!c->prog.open) return fail(c, GI_E_STATE, "progressive_step: no session open (gi_progressive_begin; scene and photon uploads end a session)");
+    const size_t npix = (size_t)c->prog.F.local_rows * (size_t)c->prog.F.w;
+    if (npix == 0) return gi_progressive_step_device(c, n_samples, h_out, out_is_f64, nullptr, cancel);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = npix * 3 * (out_is_f64 ? 8 : 4);
+    void* d_out = nullptr;
+    int32_t* d_spp = nullptr;
+    HIP_TRY(c, hipMalloc(&d_out, bytes));
+    if (h_spp && hipMalloc((void**)&d_spp, npix * 4) != hipSuccess) { (void)hipFree(d_out); return fail(c, GI_E_HIP, "hipMalloc spp"); }
+    int rc = gi_progressive_step_device(c, n_samples, d_out, out_is_f64, d_spp, cancel);
+    if (rc == GI_OK) {
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && h_spp) e = hipMemcpy(h_spp, d_spp, npix * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("progressive_step_host: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    if (d_spp) (void)hipFree(d_spp);
+    return rc;
+}
+
+int gi_progressive_status(gi_ctx* c, int32_t* sample_end, int64_t* pixels_wanting)
+{
+    if (!c) return GI_E_INVALID;
+    gi_ctx::Progressive& g = c->prog;
+    if (!g.open) return fail(c, GI_E_STATE, "progressive_status: no session open");
+    if (sample_end) *sample_end = g.sample_end;
+    if (pixels_wanting) {
+        *pixels_wanting = 0;
+        if (g.n_rec) {
+            HIP_TRY(c, hipSetDevice(c->device));
+            if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
+            HIP_TRY(c, hipMemsetAsync(c->d_wfcnt.p, 0, sizeof(unsigned int), c->stream));
+            hipLaunchKernelGGL(k_pix_wanting, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, c->stream, g.F, g.pix.p, g.n_rec, g.schedule, c->d_wfcnt.p);
+            HIP_TRY(c, hipGetLastError());
+            unsigned int n = 0;
+            HIP_TRY(c, hipMemcpyAsync(&n, c->d_wfcnt.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            *pixels_wanting = (int64_t)n;
+        }
+    }
+    return GI_OK;
+}
+
+int gi_progressive_state_bytes(gi_ctx* c, int64_t* n_bytes)
+{
+    if (!c || !n_bytes) return GI_E_INVALID;
+    if (!c->prog.open) return fail(c, GI_E_STATE, "progressive_state_bytes: no session open");
+    *n_bytes = (int64_t)sizeof(ProgBlobHeader) + (int64_t)c->prog.n_rec * (int64_t)sizeof(PixRec);
+    return GI_OK;
+}
+
+int gi_progressive_save(gi_ctx* c, void* h_blob, int64_t cap_bytes)
+{
+    if (!c || !h_blob) return GI_E_INVALID;
+    gi_ctx::Progressive& g = c->prog;
+    if (!g.open) return fail(c, GI_E_STATE, "progressive_save: no session open");
+    const int64_t need = (int64_t)sizeof(ProgBlobHeader) + (int64_t)g.n_rec * (int64_t)sizeof(PixRec);
+    if (cap_bytes < need) return fail(c, GI_E_INVALID, "progressive_save: the buffer holds " + std::to_string(cap_bytes) + " bytes, the checkpoint needs " + std::to_string(need));
+    ProgBlobHeader h;
+    memset(&h, 0, sizeof h);
+    memcpy(h.magic, kProgMagic, 8);
+    h.version = kProgVersion; h.header_bytes = (uint32_t)sizeof h;
+    memcpy(&h.rp, &g.rp, sizeof h.rp);
+    memset(reinterpret_cast<char*>(&h.rp) + offsetof(gi_render_params, max_samples) + 4, 0, 4);   // the padding before noise_thresh
+    h.schedule = g.schedule; h.sample_end = g.sample_end;
+    h.n_records = g.n_rec; h.record_bytes = (uint32_t)sizeof(PixRec);
+    h.n_entity = c->S.n_tri; h.n_node = c->S.n_node; h.n_photon = c->S.n_photon;
+    memcpy(h_blob, &h, sizeof h);
+    if (g.n_rec) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(static_cast<char*>(h_blob) + sizeof h, g.pix.p, (size_t)g.n_rec * sizeof(PixRec), hipMemcpyDeviceToHost));
+    }
+    return GI_OK;
+}
+
+int gi_progressive_restore(gi_ctx* c, const void* h_blob, int64_t n_bytes)
+{
+    if (!c) return GI_E_INVALID;
+    c->prog.open = false;
+    if (!h_blob || n_bytes < (int64_t)sizeof(ProgBlobHeader)) return fail(c, GI_E_INVALID, "progressive_restore: the blob is shorter than a checkpoint header");
+    ProgBlobHeader h;
+    memcpy(&h, h_blob, sizeof h);
+    if (memcmp(h.magic, kProgMagic, 8) != 0) return fail(c, GI_E_INVALID, "progressive_restore: not a checkpoint (magic)");
+    if (h.version != kProgVersion) return fail(c, GI_E_INVALID, "progressive_restore: checkpoint format version " + std::to_string(h.version) + ", this library reads " + std::to_string(kProgVersion));
+    if (h.header_bytes != sizeof h || h.record_bytes != sizeof(PixRec) || (h.schedule != 0 && h.schedule != 1))
+        return fail(c, GI_E_INVALID, "progressive_restore: header or record size, or schedule, not of this format");
+    Frame F;
+    std::string ferr;
+    if (!make_frame(&h.rp, F, ferr)) return fail(c, GI_E_INVALID, "progressive_restore: " + ferr);
+    if (h.schedule == 0 && !(F.min_samples == F.max_samples && F.max_samples > 0)) return fail(c, GI_E_INVALID, "progressive_restore: the refill schedule needs a fixed sample count");
+    if (h.schedule != 0 && (size_t)(((F.w + 7) >> 3)) * (size_t)((F.local_rows + 7) >> 3) * 64 > 0xfffffff0ull) return fail(c, GI_E_INVALID, "progressive_restore: frame too large");
+    if (h.sample_end < 0 || h.sample_end > F.max_samples) return fail(c, GI_E_INVALID, "progressive_restore: sample counter outside 0 .. max_samples");
+    const uint32_t n_rec = prog_records(F, h.schedule);
+    if (h.n_records != n_rec || n_bytes != (int64_t)sizeof h + (int64_t)n_rec * (int64_t)sizeof(PixRec))
+        return fail(c, GI_E_INVALID, "progressive_restore: " + std::to_string(n_bytes) + " bytes, a checkpoint of this frame has " + std::to_string(sizeof h + (size_t)n_rec * sizeof(PixRec)) + " (truncated?)");
+    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_restore: no scene uploaded");
+    if (c->count_enabled) return fail(c, GI_E_STATE, "progressive_restore: sessions run on the streaming passes, not with the megakernel's work counters (gi_set_counters 1)");
+    if (h.n_entity != c->S.n_tri || h.n_node != c->S.n_node || h.n_photon != c->S.n_photon)
+        return fail(c, GI_E_STATE, "progressive_restore: the checkpoint was taken on another scene or photon map (entities, nodes, photons " + std::to_string(h.n_entity) + ", " + std::to_string(h.n_node) + ", " +
+                                       std::to_string(h.n_photon) + "; uploaded " + std::to_string(c->S.n_tri) + ", " + std::to_string(c->S.n_node) + ", " + std::to_string(c->S.n_photon) + ")");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = prog_open(c, h.rp, F, h.schedule, h.sample_end);
+    if (rc) return rc;
+    if (n_rec) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(c->prog.pix.p, static_cast<const char*>(h_blob) + sizeof h, (size_t)n_rec * sizeof(PixRec), hipMemcpyHostToDevice));
+    }
+    c->prog.open = true;
+    return GI_OK;
 }
 
 // ---- first-hit feature buffers (an addition: the reference renders radiance only; the values are those RayTracer::radiance holds after trace()
@@ -2922,6 +3204,7 @@ int gi_emit_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed, 
 int gi_build_photon_map(gi_ctx* c, int32_t n, const double* photons, const double* box6)
 {
     if (!c || n < 0 || (n && !photons)) return GI_E_INVALID;
+    c->prog.open = false;
     if (!c->have_scene) return fail(c, GI_E_STATE, "build_photon_map: no scene uploaded");
     HIP_TRY(c, hipSetDevice(c->device));
     double box[6];
@@ -2934,6 +3217,7 @@ int gi_build_photon_map(gi_ctx* c, int32_t n, const double* photons, const doubl
 int gi_trace_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed, const double* box6, int64_t* tries_out)
 {
     if (!c || count < 0) return GI_E_INVALID;
+    c->prog.open = false;
     if (!c->have_scene) return fail(c, GI_E_STATE, "trace_photons: no scene uploaded");
     const long long total = (long long)count * c->S.n_light;
     if (tries_out) *tries_out = 0;

@@ -305,6 +305,51 @@ int gi_debug_find_leaves(gi_ctx*, int32_t n, const double* pos, int32_t* fast_ou
 int gi_debug_gather_pass(gi_ctx*, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2);
 int gi_kat(gi_ctx*, int32_t what, int32_t n, const double* in, int32_t in_stride, double* out3);
 
+/* Progressive render sessions -- an ADDITION: the reference renders a frame in one piece (its GUI repaints rows as they finish).  A session keeps
+ * the per-pixel state of RayTracer::run's loop (running mean, last colour, variance, samps, s; include/raytracer.h:102-148) on the device between
+ * calls, in a buffer of its own, and takes further samples when asked.  The contract: A FRAME BUILT IN STEPS HAS THE BITS OF THE FRAME gi_render_*
+ * BUILDS IN ONE CALL with the same parameters, scene, photon map and render mode.  One session per context; a caller with several devices opens
+ * one per context with its stripe fields (the gi_group_* entries have no progressive form).
+ * gi_progressive_begin: validates the parameters as gi_render_* does, picks the schedule gi_render_device would pick (render mode 0 with
+ *   min_samples == max_samples: the refill pipeline; otherwise synchronous rounds), puts every pixel in its initial state and sets the sample
+ *   counter E to 0.  GI_E_STATE without a scene and in render mode 1 (the megakernel keeps a pixel in registers).  A second begin replaces the session.
+ * gi_progressive_step_*: E' = min(E + n_samples, max_samples); every pixel takes samples while s < E' and the reference's rule still wants one
+ *   (fixed sample count: exactly samples [E, E') of every pixel), then E = E'.  out / spp get what gi_render_* writes -- the running mean, linear and
+ *   unclamped, and the samples taken, [local_rows][width] of this rank; DEVICE pointers (asynchronous on the context's stream) or HOST pointers.
+ *   n_samples = 0 runs no path kernel and writes the current state (right after begin: 0.5 everywhere, spp 0, as a 0-sample frame).  GI_E_INVALID:
+ *   n_samples < 0 or a null out; GI_E_STATE: no session.  A step times itself as a frame does: gi_last_render_ms / _stage_ms / _kernel_ms report it.
+ *   cancel is polled where a frame polls it; a cancelled step returns GI_E_CANCELLED, keeps what it folded (E advances by the sample chunks a
+ *   fixed-count step completed, not at all in rounds, where pixels may nevertheless be ahead of E) and leaves the session valid: stepping on ends
+ *   on the same bits.
+ * gi_progressive_status: sample_end = E; pixels_wanting = pixels of this rank that would take another sample under the session's max_samples
+ *   (0: the frame is finished).  Either pointer may be null.
+ * gi_upload_scene, gi_upload_photons, gi_clear_photons, gi_build_photon_map and gi_trace_photons END the session (the next step: GI_E_STATE),
+ *   also when the call itself fails: they end it before they look at their arguments, so a failed upload never leaves a session on a half-set scene.
+ *   Every other entry may be called between steps -- gi_render_* of any size, the feature pass, the denoiser, the function-level and debug
+ *   entries, the result-neutral switches (wide nodes, culling, entity boxes, pool slots): the path pool, the queues and the per-sample buffer
+ *   are shared scratch, only the pixel state is the session's.
+ * gi_progressive_save / _restore: a checkpoint is one little-endian blob of gi_progressive_state_bytes bytes:
+ *     0 char[8] magic "GIPROGR\0"   8 u32 version (1)   12 u32 header bytes (192)
+ *    16 gi_render_params, its fields in declaration order: 11 f64 (cam_pos, cam_up, cam_forward, sensor_diag, focal_dist), 7 i32 (width, height,
+ *       stripe_h, stripe_rank, stripe_world, min_samples, max_samples), 4 bytes 0, f64 noise_thresh, u64 seed
+ *   152 i32 schedule (0 refill pipeline: records in 8x8-tile order without padding; 1 rounds: whole 8x8 tiles, padding records included)
+ *   156 i32 E   160 u64 record count   168 u32 record bytes (72)   172 u32 0
+ *   176 i32 entities, i32 octree nodes, i32 stored photons of the scene it was taken on (a weak fingerprint), i32 0
+ *   192 the records as they lie on the device: f64 colour[3], lastCol[3], var, i32 samps, s, n (scratch of a round), 0
+ *   restore opens a session from a blob, on the blob's schedule.  GI_E_INVALID: bad magic, version, sizes, truncation; GI_E_STATE: no scene, or
+ *   the fingerprint differs.  THE CALLER uploads the same scene and the same photons first (same photon seed and count): the fingerprint only
+ *   catches a different scene, it does not prove an equal one.  restore does not look at the context's render mode (the blob's schedule holds, so
+ *   a checkpoint of either schedule resumes in mode 0, 1 or 2), but like begin it returns GI_E_STATE while the megakernel's work counters are on
+ *   (gi_set_counters 1).  A restore that fails leaves no session open, as a begin that fails does.
+ * gi_progressive_end: closes the session and frees its records (a context's destruction does so too). */
+int gi_progressive_begin(gi_ctx*, const gi_render_params*);
+int gi_progressive_step_device(gi_ctx*, int32_t n_samples, void* d_out_lin, int out_is_f64, int32_t* d_out_spp, volatile const int* cancel);
+int gi_progressive_step_host  (gi_ctx*, int32_t n_samples, void* h_out_lin, int out_is_f64, int32_t* h_out_spp, volatile const int* cancel);
+int gi_progressive_status(gi_ctx*, int32_t* sample_end, int64_t* pixels_wanting);
+int gi_progressive_state_bytes(gi_ctx*, int64_t* n_bytes);
+int gi_progressive_save(gi_ctx*, void* h_blob, int64_t cap_bytes);
+int gi_progressive_restore(gi_ctx*, const void* h_blob, int64_t n_bytes);
+int gi_progressive_end(gi_ctx*);
 
 #ifdef __cplusplus
 }
