@@ -369,6 +369,14 @@ __global__ __launch_bounds__(GI_BLOCK) void k_pix_init(PixRec* pix, uint32_t n_p
     }
 }
 
+// Which sample a slot of the path pool carries.  The table slot_sample[slot] says so in general (slots are handed on from path to path).  When the
+// pool holds every sample of a chunk at once, the trace stage's first pass gives item i slot i and sample sample0 + i and no slot is ever reissued:
+// the table would be the identity plus sample0, so the host passes no table (nullptr, wave-uniform) and nobody writes or reads one (stream_samples).
+__device__ __forceinline__ unsigned long long sample_of(const unsigned long long* slot_sample, unsigned long long sample0, uint32_t slot)
+{
+    return slot_sample ? slot_sample[slot] : sample0 + slot;
+}
+
 // Adaptive rounds on the streaming machinery (render_adaptive): the paths of a round are started here, compacted into q_new, and then
 // go through the k_st_* passes; a finished path leaves its radiance in lbuf[slot] (slot_sample[slot] = slot), which the accumulate
 // step folds into the pixel in sample order.
@@ -566,7 +574,7 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
         const bool gen = i < g.n_gen;
         if (hit) {
             PoolHit p;                                    // put together in registers, stored whole
-            if (gen) { pool_begin(pool, slot, ray, stream); slot_sample[slot] = g.id_base + i; }
+            if (gen) { pool_begin(pool, slot, ray, stream); if (slot_sample) slot_sample[slot] = g.id_base + i; }
             if constexpr (WIDE != 0) {
                 // the walk carries only WHICH entity it hit: hit point and barycentrics are computed again here, by the same test with the same
                 // operands -- ten registers less to hold through the walk (the kernel runs at the 128 its four waves per SIMD leave it)
@@ -591,11 +599,11 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
             const V3 amb = ld3(S.ambient);
             if (depth == 0) {   // generated here, or handed in by the adaptive loop's generator (k_ad_gen)
                 const V3 L = v3(0, 0, 0) + v3(1, 1, 1) * amb;
-                const unsigned long long id = gen ? g.id_base + i : slot_sample[slot];
+                const unsigned long long id = gen ? g.id_base + i : sample_of(slot_sample, sample0, slot);
                 double* o = lbuf + (id - sample0) * 3;
                 o[0] = L.x; o[1] = L.y; o[2] = L.z;
             } else if (amb.x != 0.0 || amb.y != 0.0 || amb.z != 0.0) {
-                double* o = lbuf + (slot_sample[slot] - sample0) * 3;
+                double* o = lbuf + (sample_of(slot_sample, sample0, slot) - sample0) * 3;
                 const V3 L = ld3(o) + ld3(pool.thru[slot].T) * amb;
                 o[0] = L.x; o[1] = L.y; o[2] = L.z;
             }
@@ -762,9 +770,9 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
                 else
                 fl = stage_shade_nodes<FEAT, typename LdsSrc<WIDE>::type, DEFER>(S, N, p, seed, nullptr, &so, nullptr, e);
                 // what does not depend on the probe goes out first (its registers are free for the walk): the shadow query, the gather query, A0
-                if constexpr (DEFER == 1) { ql.idx = (uint32_t)(slot_sample[slot] - sample0); ql.slot = slot; *e = ql; }
+                if constexpr (DEFER == 1) { ql.idx = (uint32_t)(sample_of(slot_sample, sample0, slot) - sample0); ql.slot = slot; *e = ql; }
                 else
-                for (int li = 0; li < nl; li++) { e[li].idx = (uint32_t)(slot_sample[slot] - sample0); e[li].slot = slot; }
+                for (int li = 0; li < nl; li++) { e[li].idx = (uint32_t)(sample_of(slot_sample, sample0, slot) - sample0); e[li].slot = slot; }
                 if (fl != 0) {
                     if (fl & ST_GATHER) {
                         PoolGath gq;
@@ -791,7 +799,7 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
                 }
             } else {
                 PathRef pr = pool[slot];
-                fl = stage_shade_nodes<FEAT>(S, N, pr, seed, nullptr, &so, lbuf + (slot_sample[slot] - sample0) * 3);
+                fl = stage_shade_nodes<FEAT>(S, N, pr, seed, nullptr, &so, lbuf + (sample_of(slot_sample, sample0, slot) - sample0) * 3);
             }
         }
         // a path with a pending gather stays alive one more pass even when it may not continue: the trace stage retires it.  With the probe on it
@@ -1154,7 +1162,7 @@ __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S
             if (has_leaf) {
                 if constexpr (COUNT) n_c += (unsigned long long)S.pnodes[leaf].u.lf.nb_photons;
                 PathRef pr = pool[vals[i]];
-                stage_gather_in_leaf(S, pr, (int32_t)leaf, heap, 64, lbuf + (slot_sample[vals[i]] - sample0) * 3);
+                stage_gather_in_leaf(S, pr, (int32_t)leaf, heap, 64, lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3);
             }
             continue;
         }
@@ -1232,7 +1240,7 @@ __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S
         if (valid) {
             V3 caustic;
             if (!g_end(a, caustic)) caustic = gather_in_leaf(S, (int32_t)leaf0, a.pos, a.dir, heap, 64, nullptr, nullptr);   // float-key tie: exact pass
-            double* Lp = lbuf + (slot_sample[vals[i]] - sample0) * 3;   // the path's radiance lives in the per-sample buffer
+            double* Lp = lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3;   // the path's radiance lives in the per-sample buffer
             V3 L = ld3(Lp) + ld3(pool.gath[gslot].gcoef) * caustic;
             Lp[0] = L.x; Lp[1] = L.y; Lp[2] = L.z;
         }
@@ -1349,7 +1357,7 @@ __global__ __launch_bounds__(GI_GW_BLOCK) void k_st_gather_wave(Scene S, PathPoo
         const V3 caustic = gather_wave(S, leaf, rank, ld3(pool.hit[slot].hpos), ld3(pool.gath[slot].gdir), heaps + wave * GI_GATHER_K, lane, &nc);
         if constexpr (COUNT) n_c += (unsigned long long)nc;
         if (lane == 0u && nc > 0) {
-            double* Lp = lbuf + (slot_sample[slot] - sample0) * 3;   // the path's radiance lives in the per-sample buffer
+            double* Lp = lbuf + (sample_of(slot_sample, sample0, slot) - sample0) * 3;   // the path's radiance lives in the per-sample buffer
             const V3 L = ld3(Lp) + ld3(pool.gath[slot].gcoef) * caustic;
             Lp[0] = L.x; Lp[1] = L.y; Lp[2] = L.z;
         }
@@ -1450,7 +1458,7 @@ __global__ __launch_bounds__(GI_FINISH_BLOCK) void k_st_finish(Scene S, uint64_t
             const bool have = i < n_in;
             const uint32_t slot = have ? q_in[i] : 0u;
             PathRec p;
-            double* const Lb = lbuf + (have ? (slot_sample[slot] - sample0) * 3 : 0ull);   // the path's radiance so far; kept in registers while this stage works on it
+            double* const Lb = lbuf + (have ? (sample_of(slot_sample, sample0, slot) - sample0) * 3 : 0ull);   // the path's radiance so far; kept in registers while this stage works on it
             if (have) { p = pool.load(slot); p.L[0] = Lb[0]; p.L[1] = Lb[1]; p.L[2] = Lb[2]; }
             bool alive = have, running = have;
             for (int b = 0;;) {
@@ -1481,7 +1489,7 @@ __global__ __launch_bounds__(GI_FINISH_BLOCK) void k_st_finish(Scene S, uint64_t
             const bool have = lane < (uint32_t)lanes && i < n_in;
             const uint32_t slot = have ? q_in[i] : 0u;
             PathRec p;
-            double* const Lb = lbuf + (have ? (slot_sample[slot] - sample0) * 3 : 0ull);
+            double* const Lb = lbuf + (have ? (sample_of(slot_sample, sample0, slot) - sample0) * 3 : 0ull);
             if (have) { p = pool.load(slot); p.L[0] = Lb[0]; p.L[1] = Lb[1]; p.L[2] = Lb[2]; }
             bool alive = have, running = have;
             for (int b = 0;;) {
@@ -1843,6 +1851,7 @@ struct gi_ctx {
     int render_mode = 0;              // 0 streaming passes (fixed spp) or rounds (adaptive), 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
     size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
     uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
+    bool sample_identity = true;      // GI_SAMPLE_IDENTITY=0: the stream passes always keep the slot -> sample table, also where it would be the identity (stream_samples)
     bool early_miss = true;           // GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (stream_passes)
     uint32_t early_turns = 4;         // GI_EARLY_MISS_TURNS: turns of the walk that probe may take before it gives the ray to the trace stage
     uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
@@ -2090,6 +2099,7 @@ int gi_create(gi_ctx** out, int device_ordinal)
     if (const char* e = getenv("GI_WAVE_FACTOR")) c->wave_factor = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), 0xffffu);
     if (const char* e = getenv("GI_EARLY_MISS")) c->early_miss = atoi(e) != 0;
     if (const char* e = getenv("GI_EARLY_MISS_TURNS")) c->early_turns = (uint32_t)std::min(64, std::max(1, atoi(e)));
+    if (const char* e = getenv("GI_SAMPLE_IDENTITY")) c->sample_identity = atoi(e) != 0;
     if (const char* e = getenv("GI_SORT_CONT")) c->sort_cont = atoi(e) != 0;
     if (const char* e = getenv("GI_DESCENT_JUMP")) c->descent_jump = atoi(e) != 0;
     if (const char* e = getenv("GI_FLAT_CANDIDATES")) c->flat_candidates = atoi(e) != 0;
@@ -2291,10 +2301,11 @@ static void launch_gather(gi_ctx* c, bool wave, bool counting, const PathPool& p
 // everything the pass loop needs for P paths in flight (the radiance buffer is the caller's)
 // a few lights, wide records: the shadow walks of the shade stage run in a kernel of their own (ShadowQ)
 static bool defers_shadows(const gi_ctx* c) { return c->defer_shadows && c->S.wnodes != nullptr && c->S.n_light >= 1 && c->S.n_light <= 4; }   // one query per light and shaded hit
-static int stream_alloc(gi_ctx* c, uint32_t P)
+// need_table: the caller's passes read slot_sample (sample_of); a chunk whose samples are all in flight at once does without it
+static int stream_alloc(gi_ctx* c, uint32_t P, bool need_table)
 {
     if (c->spool_slots < P) { HIP_TRY(c, c->d_spool.alloc((size_t)P * GI_POOL_BYTES_PER_SLOT)); c->spool_slots = P; }
-    if (c->d_slot_sample.n < P) HIP_TRY(c, c->d_slot_sample.alloc(P));
+    if (need_table && c->d_slot_sample.n < P) HIP_TRY(c, c->d_slot_sample.alloc(P));
     for (int k = 0; k < 7; k++) if (c->d_qs[k].n < P) HIP_TRY(c, c->d_qs[k].alloc(P));
     for (int k = 0; k < 2; k++) { if (c->d_gk[k].n < P) HIP_TRY(c, c->d_gk[k].alloc(P)); if (c->d_gv[k].n < P) HIP_TRY(c, c->d_gv[k].alloc(P)); }
     for (int k = 0; k < 2; k++) if (c->d_ck[k].n < P) HIP_TRY(c, c->d_ck[k].alloc(P));
@@ -2316,8 +2327,9 @@ static int stream_alloc(gi_ctx* c, uint32_t P)
 }
 // The pass loop: trace -> shade -> (keys, sort, gather) -> sort of the continuing rays, until nothing is in flight.  refill(n_free, qf)
 // starts up to n_free new paths in the slots of the free list qf (nullptr: slots 0 .. n_free - 1), writes them to c->d_qs[0] and
-// returns how many; `exhausted` tells that it will start no more.  A finished path leaves its radiance at lbuf[slot_sample[slot] - sample0].
-static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, double* lbuf, uint32_t n_free,
+// returns how many; `exhausted` tells that it will start no more.  A finished path leaves its radiance at lbuf[sample_of(slot) - sample0]:
+// slot_sample is the table the kernels keep that in, or nullptr when the caller knows that slot s carries sample sample0 + s throughout.
+static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, uint32_t n_free,
                          const std::function<uint32_t(uint32_t, const uint32_t*, GenArgs&)>& refill, const bool& exhausted,
                          volatile const int* cancel, int& launches)
 {
@@ -2376,7 +2388,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
                 stage_begin(c, STG_FINISH);
                 auto fin = [&](int mode) {
                     const FinishK fin_k = st_finish(feat, wide, mode);
-                    hipLaunchKernelGGL(fin_k.fn, dim3(G.finish), dim3(GI_FINISH_BLOCK), fin_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0,
+                    hipLaunchKernelGGL(fin_k.fn, dim3(G.finish), dim3(GI_FINISH_BLOCK), fin_k.lds, st, c->S, F.seed, pool, slot_sample, sample0,
                                        fq_in, n_in_dev, n_cont, lanes, vertices, fq_out, c->d_fin_cnt.p + k, lbuf, (wave_factor << 16) | (c->coop_factor & 0xffffu));
                 };
                 fin(0);
@@ -2396,7 +2408,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
         StreamCounters* const sc = counting ? c->d_stream_cnt.p : nullptr;
         const TraceK trace_k = st_trace(trace_feat, wide, counting);
-        stage_begin(c, STG_TRACE); hipLaunchKernelGGL(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
+        stage_begin(c, STG_TRACE); hipLaunchKernelGGL(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
                            c->d_stage[0].p, c->d_stage[1].p, lbuf, c->refill_min, sc); stage_end(c);
         {
             CompactJob job;
@@ -2429,7 +2441,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
         HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
         const bool many = c->S.n_light > 1;
         const ShadeK shade_k = st_shade(feat, wide, shq ? (many ? 2 : 1) : 0);
-        stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, c->d_slot_sample.p, sample0, q_shade_use, ctl, bc, c->d_segs.p,
+        stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, q_shade_use, ctl, bc, c->d_segs.p,
                            c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, c->d_stage[3].p, lbuf, shq, q_orig, early_turns);
         stage_end(c);
         if (shq) {   // the walks it put off; before the gather of the same vertices (the order in which a path's radiance is summed)
@@ -2469,7 +2481,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long sample0, 
             }
             stage_end(c);
             stage_begin(c, STG_GATHER);
-            launch_gather(c, c->S.pcand && n_gather < c->gather_wave_below, counting, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, c->d_slot_sample.p, sample0, lbuf, sc);   // few queries: a wave each
+            launch_gather(c, c->S.pcand && n_gather < c->gather_wave_below, counting, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, slot_sample, sample0, lbuf, sc);   // few queries: a wave each
             stage_end(c);
             launches += 2;
         }
@@ -2526,7 +2538,13 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
     }
     const uint32_t P = (uint32_t)std::max<size_t>(64, std::min<size_t>(std::min<size_t>(slots_budget, 0xfffffff0u), (size_t)n_pix * (size_t)spp));
     int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)spp, c->lbuf_bytes_max / ((size_t)n_pix * 24)));
-    int rc = stream_alloc(c, P);
+    // The sample table.  A chunk of ns samples per pixel whose n_pix * ns samples all fit the pool is started whole by the first pass: refill hands
+    // the trace stage slots 0 .. n_pix * ns - 1 in order (qf == nullptr) with sample ids sample0 + slot, and has nothing left to start in a freed slot
+    // later.  The table would be the identity plus sample0 for the whole chunk, so the kernels are given none (sample_of) -- 8 bytes per sample less
+    // to write in the trace stage and a scattered read less per gather query.  Decided per chunk (fits); the table is allocated when the largest
+    // chunk of this call needs it, and stays in per_slot above either way: a later call may need it.  GI_SAMPLE_IDENTITY=0: always a table.
+    auto fits = [&](int ns) { return c->sample_identity && (size_t)P >= (size_t)n_pix * (size_t)ns; };
+    int rc = stream_alloc(c, P, !fits(chunk));
     if (rc) return rc;
     if (c->d_lbuf.n < (size_t)n_pix * chunk * 3) HIP_TRY(c, c->d_lbuf.alloc((size_t)n_pix * chunk * 3));
     const StreamGrids& G = stream_grids(c);
@@ -2556,7 +2574,8 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
             exhausted = next >= sample_end;
             return 0;                                                                          // nothing prepared: the trace kernel starts them
         };
-        rc = stream_passes(c, F, sample0, c->d_lbuf.p, P, refill, exhausted, cancel, launches);   // pass 0: every slot is free
+        if (getenv("GI_DEBUG_WF")) fprintf(stderr, "[st] chunk of %d samples: pool %u slots, sample table %s\n", ns, P, fits(ns) ? "off" : "on");
+        rc = stream_passes(c, F, fits(ns) ? nullptr : c->d_slot_sample.p, sample0, c->d_lbuf.p, P, refill, exhausted, cancel, launches);   // pass 0: every slot is free
         if (rc) return rc;
         stage_begin(c, STG_ACCUM); hipLaunchKernelGGL(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp); stage_end(c);
         launches++;
@@ -2589,7 +2608,7 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
     const size_t slots = (size_t)n_pix * (size_t)B;
     if (slots > 0xfffffff0ull) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
-    int rc = stream_alloc(c, (uint32_t)slots);
+    int rc = stream_alloc(c, (uint32_t)slots, true);   // k_ad_gen names every path's place in the radiance buffer
     if (rc) return rc;
     if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
     if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
@@ -2619,7 +2638,7 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
         uint32_t pending = c->h_wfcnt[0];          // paths started by this round, already in the new-path queue
         const bool exhausted = true;
         auto refill = [&](uint32_t, const uint32_t*, GenArgs&) -> uint32_t { const uint32_t n = pending; pending = 0; return n; };
-        rc = stream_passes(c, F, 0ull, c->d_lbuf.p, 0u, refill, exhausted, cancel, launches);
+        rc = stream_passes(c, F, c->d_slot_sample.p, 0ull, c->d_lbuf.p, 0u, refill, exhausted, cancel, launches);
         if (rc) return rc;
         stage_begin(c, STG_ACCUM);
         hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
