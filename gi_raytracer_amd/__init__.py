@@ -56,6 +56,12 @@ class DenoiseParams(C.Structure):
                 ("sigma_color", C.c_double), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
+class UpsampleParams(C.Structure):
+    """gi_upsample_params (include/gi_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("low_width", C.c_int32), ("low_height", C.c_int32), ("factor", C.c_int32),
+                ("demodulate", C.c_int32), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -68,7 +74,8 @@ _LIB = None
 ABI_SYMBOLS = [
     "gi_create", "gi_destroy", "gi_last_error", "gi_set_stream", "gi_upload_scene", "gi_upload_photons", "gi_local_rows",
     "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms",
-    "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
+    "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms",
+    "gi_upsample_default_params", "gi_upsample_device", "gi_upsample_host", "gi_last_upsample_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
@@ -107,6 +114,11 @@ def lib():
     L.gi_denoise_device.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.gi_denoise_host.argtypes = [vp, C.POINTER(DenoiseParams), vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.gi_last_denoise_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gi_upsample_default_params.argtypes = [C.POINTER(UpsampleParams)]
+    L.gi_upsample_default_params.restype = None
+    L.gi_upsample_device.argtypes = [vp, C.POINTER(UpsampleParams), vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.gi_upsample_host.argtypes = [vp, C.POINTER(UpsampleParams), vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.gi_last_upsample_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.gi_set_render_mode.argtypes = [vp, C.c_int]
     L.gi_set_wide_nodes.argtypes = [vp, C.c_int]
     L.gi_set_content_culling.argtypes = [vp, C.c_int]
@@ -387,6 +399,39 @@ def save_ppm(path, lin):
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
         f.write(a.tobytes())
+
+
+UPSAMPLE_FACTORS = range(2, 9)
+
+
+def low_frame_size(w, h, factor):
+    """(w / factor, h / factor): the size of the render RayTracer.run_upsampled scales up.  ValueError unless factor is 2 .. 8 and divides both."""
+    w, h, factor = int(w), int(h), int(factor)
+    if factor not in UPSAMPLE_FACTORS:
+        raise ValueError(f"upsample: factor must be {UPSAMPLE_FACTORS[0]} .. {UPSAMPLE_FACTORS[-1]}, got {factor}")
+    if w < 1 or h < 1 or w % factor or h % factor:
+        raise ValueError(f"upsample: factor {factor} does not divide the frame size {w} x {h}")
+    return w // factor, h // factor
+
+
+def upsample_arrays(low_color, low_features, features, factor):
+    """The three inputs of RayTracer.upsample as contiguous float32 / float64 arrays (dicts of run_features are accepted for the features);
+    ValueError unless low_color is [hl][wl][3], low_features [hl][wl][8], features [h][w][8] with wl = ceil(w / factor), hl = ceil(h / factor)."""
+    def arr(a):
+        a = np.asarray(a["features"] if isinstance(a, dict) else a)
+        return np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+    low_color, low_features, features = arr(low_color), arr(low_features), arr(features)
+    factor = int(factor)
+    if factor not in UPSAMPLE_FACTORS:
+        raise ValueError(f"upsample: factor must be {UPSAMPLE_FACTORS[0]} .. {UPSAMPLE_FACTORS[-1]}, got {factor}")
+    if features.ndim != 3 or features.shape[2] != 8 or features.shape[0] < 1 or features.shape[1] < 1:
+        raise ValueError(f"upsample: features [h][w][8] expected, got {features.shape}")
+    h, w = features.shape[:2]
+    hl, wl = -(-h // factor), -(-w // factor)
+    if low_color.shape != (hl, wl, 3) or low_features.shape != (hl, wl, 8):
+        raise ValueError(f"upsample: a {w} x {h} frame at factor {factor} takes low_color [{hl}][{wl}][3] and low_features [{hl}][{wl}][8], "
+                         f"got {low_color.shape} and {low_features.shape}")
+    return low_color, low_features, features
 
 
 # The header of a progressive checkpoint (include/gi_hip.h: gi_progressive_save), little-endian, 192 bytes; the 72-byte pixel records follow.
@@ -745,6 +790,64 @@ class RayTracer:
         ms = C.c_float()
         self._check(self.L.gi_last_denoise_ms(self.h, C.byref(ms)), "last_denoise_ms")
         return ms.value
+
+    def upsample_params(self, w, h, factor, **kw):
+        """gi_upsample_default_params with the full size w x h, the factor, the low size (the ceilings) and any of demodulate, sigma_normal,
+        sigma_depth, sigma_albedo set."""
+        p = UpsampleParams()
+        self.L.gi_upsample_default_params(C.byref(p))
+        p.width, p.height, p.factor = int(w), int(h), int(factor)
+        if p.factor > 0:
+            p.low_width, p.low_height = -(-p.width // p.factor), -(-p.height // p.factor)
+        for k, v in kw.items():
+            if k not in ("demodulate", "sigma_normal", "sigma_depth", "sigma_albedo"):
+                raise TypeError(f"upsample: unknown parameter {k!r}")
+            setattr(p, k, int(v) if k == "demodulate" else float(v))
+        return p
+
+    def upsample(self, low_color, low_features, features, factor, f64=None, **kw):
+        """The guided upsampler (gi_upsample_host; an addition, the reference has none): a full-size frame [h][w][3] from low_color [hl][wl][3] as `run`
+        returns it at the reduced size, low_features [hl][wl][8] and features [h][w][8] as `run_features` returns them at the two sizes (its dicts
+        are accepted too), wl = ceil(w / factor), hl = ceil(h / factor), each float32 or float64.  Returns float64 unless f64=False (default: the
+        colour's type).  **kw: demodulate, sigma_normal, sigma_depth, sigma_albedo; the formula is stated in include/gi_hip.h.  Needs no scene."""
+        low_color, low_features, features = upsample_arrays(low_color, low_features, features, factor)
+        if f64 is None:
+            f64 = low_color.dtype == np.float64
+        h, w = features.shape[:2]
+        p = self.upsample_params(w, h, factor, **kw)
+        out = np.zeros((h, w, 3), np.float64 if f64 else np.float32)
+        self._check(self.L.gi_upsample_host(self.h, C.byref(p), low_color.ctypes.data_as(C.c_void_p), 1 if low_color.dtype == np.float64 else 0,
+                                            low_features.ctypes.data_as(C.c_void_p), 1 if low_features.dtype == np.float64 else 0,
+                                            features.ctypes.data_as(C.c_void_p), 1 if features.dtype == np.float64 else 0,
+                                            out.ctypes.data_as(C.c_void_p), 1 if f64 else 0), "upsample_host")
+        return out
+
+    def upsample_device(self, p, low_color_ptr, low_features_ptr, features_ptr, out_ptr, low_color_f64=False, low_features_f64=False, features_f64=False, out_f64=False):
+        """The upsampler on device memory, asynchronous on the context's stream; p from upsample_params; raw device pointers to [hl][wl][3],
+        [hl][wl][8], [h][w][8] and [h][w][3]; out must not overlap an input."""
+        self._check(self.L.gi_upsample_device(self.h, C.byref(p), C.c_void_p(low_color_ptr), 1 if low_color_f64 else 0, C.c_void_p(low_features_ptr), 1 if low_features_f64 else 0,
+                                              C.c_void_p(features_ptr), 1 if features_f64 else 0, C.c_void_p(out_ptr), 1 if out_f64 else 0), "upsample_device")
+
+    def last_upsample_ms(self):
+        """gi_last_upsample_ms: device time of the last upsampler pass (the frame's, the feature pass's and the denoiser's times keep theirs)."""
+        ms = C.c_float()
+        self._check(self.L.gi_last_upsample_ms(self.h, C.byref(ms)), "last_upsample_ms")
+        return ms.value
+
+    def run_upsampled(self, w, h, factor, feature_samples, denoise=False, f64=True, **kw):
+        """A w x h frame from a (w / factor) x (h / factor) render: `run` at the reduced size with **kw (min_samples, max_samples, noise_thresh,
+        seed; whole frames, so no stripes), `run_features` with feature_samples samples at both sizes, optionally `denoise` (default parameters) on
+        the low frame, then `upsample` (default parameters).  factor must divide w and h (ValueError): only then does the reduced-size frame see
+        the view of the full-size one."""
+        if any(k in kw for k in ("stripe_h", "rank", "world")):
+            raise ValueError("run_upsampled: whole frames only, no stripe keywords")
+        wl, hl = low_frame_size(w, h, factor)
+        low = self.run(wl, hl, f64=f64, **kw)
+        fl = self.run_features(wl, hl, feature_samples, f64=f64, want_ids=False, **kw)
+        ff = self.run_features(w, h, feature_samples, f64=f64, want_ids=False, **kw)
+        if denoise:
+            low = self.denoise(low, fl)
+        return self.upsample(low, fl, ff, factor)
 
     def set_render_mode(self, mode):
         """'wavefront' (default), 'megakernel' or 'rounds' (the wavefront passes in synchronous rounds, fixed-spp frames too):

@@ -4,6 +4,7 @@
                                [--features PREFIX [--feature-samples N]]
                                [--denoise OUT.ppm [--denoise-pfm OUT.pfm] [--denoise-iterations N] [--denoise-sigmas C N Z A]]
                                [--progressive N [--time-limit SECONDS] [--checkpoint FILE]]
+                               [--upsample S [--upsample-pfm LOW.pfm]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -16,6 +17,10 @@ temporary file and a rename, so a viewer never reads half a file; the last step 
 SECONDS takes no further step once the frame's budget is spent (at least one step is taken); --checkpoint FILE resumes from FILE when it exists
 -- the scene, --photons and the frame size must be those of the run that wrote it; its sample settings apply -- and saves to it after every step.
 --features and --denoise act on the last frame written.
+--upsample S (an addition again, S = 2 .. 8 dividing --width and --height) renders the frame at 1/S of the size -- 1/S^2 of the paths -- and scales it
+up with the guided upsampler, led by feature buffers of both sizes; --width and --height stay the size of what is written: -o and --pfm get the
+upsampled frame, --features the full-size buffers, and --denoise the low frame denoised and then upsampled.  --upsample-pfm LOW.pfm also keeps the
+reduced-size render itself.  Not together with --progressive.
 """
 import argparse
 import os
@@ -49,6 +54,8 @@ def parser():
     ap.add_argument("--progressive", type=int, default=None, metavar="N", help="render in steps of N samples per pixel, rewriting the output after every step")
     ap.add_argument("--time-limit", type=float, default=None, metavar="SECONDS", help="with --progressive: take no further step once this much time went into the frame")
     ap.add_argument("--checkpoint", default=None, metavar="FILE", help="with --progressive: resume from FILE when it exists, save the session to it after every step")
+    ap.add_argument("--upsample", type=int, default=None, metavar="S", help="render at 1/S of --width x --height (S = 2 .. 8, dividing both) and scale up with the guided upsampler")
+    ap.add_argument("--upsample-pfm", default=None, metavar="LOW.pfm", help="with --upsample: also write the reduced-size render (linear radiance) as PFM")
     return ap
 
 
@@ -62,6 +69,15 @@ def check_args(ap, a):
         ap.error("--progressive N: N must be at least 1")
     if a.time_limit is not None and not a.time_limit >= 0:
         ap.error("--time-limit SECONDS: a number >= 0")
+    if a.upsample is None and a.upsample_pfm:
+        ap.error("--upsample-pfm needs --upsample S")
+    if a.upsample is not None:
+        if a.progressive is not None:
+            ap.error("--upsample and --progressive do not go together")
+        try:
+            gi.low_frame_size(a.width, a.height, a.upsample)
+        except ValueError as e:
+            ap.error(f"--upsample S: {e}")
 
 
 def replace_file(path, write):
@@ -155,31 +171,44 @@ def main(argv=None):
         stored = len(rt.tracePhotons(n_photons)[0])
     t1 = time.time()
     feat = ""
+    S = a.upsample
     if a.progressive:
         lin, spp, feat = render_progressive(a, rt)
         t2 = time.time()
     else:
-        lin, spp = rt.run(a.width, a.height, f64=False, want_spp=True)
+        rw, rh = gi.low_frame_size(a.width, a.height, S) if S else (a.width, a.height)
+        lin, spp = rt.run(rw, rh, f64=False, want_spp=True)
         t2 = time.time()
+        if S:
+            nf = feature_samples(a, rt.max_samples)
+            low, fl = lin, rt.run_features(rw, rh, nf, f64=False, want_ids=False)
+            fb = rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
+            lin = rt.upsample(low, fl, fb, S)
+            feat = f"; upsampled x{S} from {rw}x{rh} ({nf} spp features) {rt.last_upsample_ms():.2f} ms"
+            if a.upsample_pfm:
+                gi.save_pfm(a.upsample_pfm, low)
         gi.save_ppm(a.output, lin)
         if a.pfm:
             gi.save_pfm(a.pfm, lin)
     if a.features:
         nf = feature_samples(a, rt.max_samples)
-        fb = rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
+        fb = fb if S else rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
         for name in FEATURE_FILES:
             gi.save_pfm(f"{a.features}_{name}.pfm", fb[name])
-        feat = f"; features {nf} spp {rt.last_features_ms():.2f} ms -> {a.features}_*.pfm"
+        feat = (feat if S else "") + f"; features {nf} spp {rt.last_features_ms():.2f} ms -> {a.features}_*.pfm"
     if a.denoise:
         nf = feature_samples(a, rt.max_samples)
-        fb = fb if a.features else rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
-        den = rt.denoise(lin, fb["features"], **denoise_kwargs(a))
+        if S:
+            den = rt.upsample(rt.denoise(low, fl, **denoise_kwargs(a)), fl, fb, S)
+        else:
+            fb = fb if a.features else rt.run_features(a.width, a.height, nf, f64=False, want_ids=False)
+            den = rt.denoise(lin, fb["features"], **denoise_kwargs(a))
         gi.save_ppm(a.denoise, den)
         if a.denoise_pfm:
             gi.save_pfm(a.denoise_pfm, den)
         feat += f"; denoised ({nf} spp features) {rt.last_denoise_ms():.2f} ms -> {a.denoise}"
     n = int(spp.sum())
-    print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / (a.width * a.height):.1f} spp), {stored} photons stored; "
+    print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / spp.size:.1f} spp), {stored} photons stored; "
           f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{feat}")
     return 0
 

@@ -142,6 +142,22 @@ bool dn_check(const gi_denoise_params* p, std::string& err)
 
 double dn_inv(double sigma, double scale) { return sigma != 0.0 ? scale / (sigma * sigma) : 0.0; }
 
+// The context's scratch for a frame of n_pix pixels: the guide records and the two colour buffers, always sized together, on first use and kept; a
+// larger frame replaces them (after the stream has drained: an earlier pass may still read them).  The upsampler packs its low frame here too.
+int dn_reserve(gi_ctx* c, size_t n_pix)
+{
+    if (c->d_dn_guides.n >= n_pix * 8) return GI_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipError_t e = c->d_dn_guides.alloc(n_pix * 8);
+    if (e == hipSuccess) e = c->d_dn_a.alloc(n_pix * 3);
+    if (e == hipSuccess) e = c->d_dn_b.alloc(n_pix * 3);
+    if (e != hipSuccess) {                      // none of the three is kept: the size of the guide records stands for all of them
+        c->d_dn_guides.release(); c->d_dn_a.release(); c->d_dn_b.release();
+        return fail(c, GI_E_HIP, std::string("denoiser scratch: ") + hipGetErrorString(e));
+    }
+    return GI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -166,12 +182,9 @@ int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color
     c->dn_ms = 0; c->dn_pending = false;
     if (!c->ev_dn0) { HIP_TRY(c, hipEventCreate(&c->ev_dn0)); HIP_TRY(c, hipEventCreate(&c->ev_dn1)); }
     const int it = p->iterations;
-    if (it > 0 && c->d_dn_guides.n < n_pix * 8) {
-        // the scratch is the context's: sized on first use and kept; a larger frame replaces it (after the stream has drained: an earlier pass may still read it)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, c->d_dn_guides.alloc(n_pix * 8));
-        HIP_TRY(c, c->d_dn_a.alloc(n_pix * 3));
-        HIP_TRY(c, c->d_dn_b.alloc(n_pix * 3));
+    if (it > 0) {
+        const int rc = dn_reserve(c, n_pix);
+        if (rc != GI_OK) return rc;
     }
     HIP_TRY(c, hipEventRecord(c->ev_dn0, c->stream));
     if (it == 0) {

@@ -2266,6 +2266,20 @@ GI_HD double dn_tap_weight(const DnPix& p, double p_c2, bool p_ok, const DnPix& 
     const double t = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
     return hh * (t * t);
 }
+// The guided upsampler's tap (gi_hip.h: gi_upsample_*): p = the full pixel's guide, q = a low pixel's; the denoiser's dn, dz and da without its
+// colour term, d = (dn inv_n + dz inv_z) + da inv_a (inv.c is not read); hh = ty tx, the tent.
+GI_HD double up_tap_weight(const DnPix& p, const DnPix& q, const DnInv& inv, double hh)
+{
+    const double dn = dn_sq3(p.n - q.n);
+    const double dcov = p.cov - q.cov;
+    const double da = dn_sq3(p.a - q.a) + dcov * dcov;
+    const double zs = p.z + q.z;
+    double dz = 0.0;
+    if (zs > 0.0) { const double r = (p.z - q.z) / zs; dz = r * r; }
+    const double d = (dn * inv.n + dz * inv.z) + da * inv.a;
+    const double e = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
+    return hh * (e * e);
+}
 
 // ------------------------------------------------------------------------------------------------ photon emission (tracePhotons)
 struct PhotonOut { double v[9]; };

@@ -1874,6 +1874,10 @@ struct gi_ctx {
     float dn_ms = 0;
     bool dn_pending = false;
     DevBuf<double> d_dn_guides, d_dn_a, d_dn_b;
+    // the guided upsampler (gi_upsample_*, gi_upsample.inc): events of its own; its low frame is packed into the denoiser's scratch (dn_reserve)
+    hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr;
+    float up_ms = 0;
+    bool up_pending = false;
     bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
     bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
     DevBuf<StreamCounters> d_stream_cnt;
@@ -2013,6 +2017,7 @@ static void clear_photon_map(gi_ctx* c)
 #include "gi_sort.inc"
 #include "gi_photon_build.inc"
 #include "gi_denoise.inc"
+#include "gi_upsample.inc"
 
 static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
 static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
@@ -2142,6 +2147,8 @@ void gi_destroy(gi_ctx* c)
     if (c->ev_feat1) (void)hipEventDestroy(c->ev_feat1);
     if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
     if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
+    if (c->ev_up0) (void)hipEventDestroy(c->ev_up0);
+    if (c->ev_up1) (void)hipEventDestroy(c->ev_up1);
     delete c;
 }
 

@@ -230,6 +230,45 @@ class RayTracer {
         return true;
     }
 
+    // ---- ADDITION (the reference has no upsampler): the guided upsampler of gi_upsample_host (include/gi_hip.h states the formula).  low_color =
+    // [low.height][low.width][3] linear radiance of the reduced-size frame, low and full = what renderFeatures filled at the two sizes, with
+    // low.width = ceil(full.width / factor) and low.height likewise; out gets [full.height][full.width][3].  up = nullptr:
+    // gi_upsample_default_params; else its sizes and factor are overwritten.  Needs a device, not a scene.  false with last_error() set when it
+    // cannot run (out is then left alone).
+    bool upsample(const std::vector<double>& low_color, const Features& low, const Features& full, int factor, std::vector<double>& out, const gi_upsample_params* up = nullptr)
+    {
+        if (!ensure_context()) return false;
+        gi_upsample_params p;
+        if (up) p = *up; else gi_upsample_default_params(&p);
+        p.width = full.width; p.height = full.height; p.low_width = low.width; p.low_height = low.height; p.factor = factor;
+        const size_t nlow = feature_pixels(low), npix = feature_pixels(full);
+        std::vector<double> lbuf, fbuf;
+        if (low_color.size() != nlow * 3 || !pack_features(low, lbuf) || !pack_features(full, fbuf)) {
+            _st->err = "upsample: colour and feature buffers do not have the sizes of a " + std::to_string(low.width) + " x " + std::to_string(low.height) + " and a " +
+                       std::to_string(full.width) + " x " + std::to_string(full.height) + " frame";
+            return false;
+        }
+        std::vector<double> res(npix * 3 + 3);
+        if (check(gi_upsample_host(_st->ctx, &p, low_color.data(), 1, lbuf.data(), 1, fbuf.data(), 1, res.data(), 1)) != 0) return false;
+        res.resize(npix * 3);
+        out.swap(res);
+        return true;
+    }
+    static size_t feature_pixels(const Features& f) { return (size_t)(f.width > 0 ? f.width : 0) * (size_t)(f.height > 0 ? f.height : 0); }
+    // the [height][width][8] records of gi_hip.h from the separate buffers (8 more, so that an empty frame still has an address to refuse);
+    // false when a buffer does not have the frame's size
+    static bool pack_features(const Features& f, std::vector<double>& buf)
+    {
+        const size_t npix = feature_pixels(f);
+        if (f.albedo.size() != npix * 3 || f.normal.size() != npix * 3 || f.depth.size() != npix || f.coverage.size() != npix) return false;
+        buf.assign(npix * 8 + 8, 0.0);
+        for (size_t i = 0; i < npix; i++) {
+            for (int k = 0; k < 3; k++) { buf[i * 8 + k] = f.albedo[i * 3 + k]; buf[i * 8 + 3 + k] = f.normal[i * 3 + k]; }
+            buf[i * 8 + 6] = f.depth[i]; buf[i * 8 + 7] = f.coverage[i];
+        }
+        return true;
+    }
+
     // ---- single-vertex pieces of radiance(), include/raytracer.h:321-379,481-506,509-529: the kernels' per-lane functions on the host
     uint32_t rng_stream = 0, rng_depth = 0;   // key of the counter RNG for the draws these three make (the reference calls drand())
     int rayType(const Entity* entity, const Ray& ray, gi::dvec3& norm, gi::dvec2& minUV)

@@ -223,6 +223,50 @@ int gi_denoise_device(gi_ctx*, const gi_denoise_params*, const void* d_color, in
 int gi_denoise_host(gi_ctx*, const gi_denoise_params*, const void* h_color, int color_is_f64, const void* h_features, int features_is_f64, void* h_out, int out_is_f64);
 int gi_last_denoise_ms(gi_ctx*, float* ms);
 
+/* Guided upsampling -- an ADDITION: a full-size frame from a reduced-size render.  A joint-bilateral upsampler (Kopf et al. 2007) guided by the
+ * buffers of gi_render_features_* at both sizes: the colour is interpolated between low pixels where the full-size normal and depth agree with
+ * theirs, and the full-size albedo multiplied back in restores the texture detail that was never rendered.  gi_layout.h derives the sensor from
+ * the aspect ratio alone, so a (width / factor) x (height / factor) frame with factor | width and factor | height sees the view of the
+ * width x height frame, and low pixel (X, Y) covers the full pixels [factor X, factor X + factor) x [factor Y, factor Y + factor).  No scene is needed.
+ * low_color [low_height][low_width][3] linear radiance; low_features [low_height][low_width][8] and features [height][width][8] = albedo rgb,
+ * normal xyz, depth, coverage; out [height][width][3].  Each of the four is float (flag 0) or double (1): floats are widened on load, the result
+ * is rounded once on store.  All arithmetic is f64 with IEEE operations only, in the order written here (the tests' numpy statement,
+ * tests/upsample_expect.py, is bit-equal).  With S = factor, wl = low_width, hl = low_height, |v|^2 = (x^2 + y^2) + z^2, and the modulation m of
+ * the denoiser (demodulate ? (albedo > 1e-3 ? albedo : 1e-3) : 1 per channel), ml of the low features and mf of the full ones:
+ *   1. c = low_color / ml.
+ *   2. for full pixel (x, y), in integers: Nx = 2 x + 1 - S, X0 = floor(Nx / 2S) (floor division: Nx may be negative); Ny, Y0 likewise.  2S X - Nx is
+ *      twice the distance, in full pixels, between the centre of low pixel X and the centre of x.
+ *   3. the 16 taps (X, Y): Y = Y0-1 .. Y0+2 outer, X = X0-1 .. X0+2 inner; taps outside the low frame are skipped.
+ *   4. the spatial weight is a tent of radius two low pixels: nx = |2S X - Nx|, tx = (double)(4S - nx) / (double)(4S) if nx < 4S, else 0; ty likewise.
+ *   5. between the full pixel's guide p = features[y][x] and the tap's guide q = low_features[Y][X], the denoiser's terms
+ *        dn = |n_p - n_q|^2      da = |a_p - a_q|^2 + (cov_p - cov_q)^2      dz = r^2, r = (z_p - z_q) / (z_p + z_q) if z_p + z_q > 0, else 0
+ *        d  = (dn inv_n + dz inv_z) + da inv_a, inv = 1 / sigma^2 computed once on the host in double; a sigma of 0 switches its term off (inv = 0)
+ *        e  = 1 - min(d, 1) (a NaN d counts as 1).  There is no colour term: the full-size colour is what is being made.
+ *   6. w = (ty tx) (e e); a tap whose c has a non-finite channel is skipped; num += w c per channel, den += w, in tap order.
+ *   7. den > 0: out = (num / den) mf.  Otherwise the nearest low pixel (min(x / S, wl - 1), min(y / S, hl - 1)): out = c mf, or 0 0 0 if that
+ *      pixel has a non-finite channel.  The output is finite for finite features.
+ * GI_E_INVALID: width or height < 1, factor outside 2 .. 8, low_width != ceil(width / factor) or low_height != ceil(height / factor), a negative or
+ * NaN sigma, a null pointer; the output is not touched.
+ * gi_upsample_default_params: demodulate 1, sigmas 0.5, 0.1, 0.0 (sizes and factor 0: the caller sets them).  The albedo term is off by default: a
+ * low-size albedo is the mean of an S x S block of texture, and comparing it with the full-size albedo would reject every tap on a textured surface.
+ * gi_upsample_device: DEVICE pointers, asynchronous on the context's stream; out must not overlap an input.  The low frame is widened and
+ * demodulated into the denoiser's scratch (the context's, sized on first use and kept).  gi_upsample_host: HOST pointers.
+ * gi_last_upsample_ms: device time of the last pass (HIP events around it); the frame's, the feature pass's and the denoiser's times are left
+ * alone, and so is a progressive session. */
+typedef struct gi_upsample_params {
+    int32_t width, height;            /* of the output and of features */
+    int32_t low_width, low_height;    /* of low_color and low_features: ceil(width / factor), ceil(height / factor) */
+    int32_t factor;                   /* 2 .. 8 */
+    int32_t demodulate;               /* 1: interpolate colour / albedo and multiply by the full-size albedo */
+    double sigma_normal, sigma_depth, sigma_albedo;
+} gi_upsample_params;
+void gi_upsample_default_params(gi_upsample_params*);
+int gi_upsample_device(gi_ctx*, const gi_upsample_params*, const void* d_low_color, int low_color_is_f64, const void* d_low_features, int low_features_is_f64,
+                       const void* d_features, int features_is_f64, void* d_out, int out_is_f64);
+int gi_upsample_host(gi_ctx*, const gi_upsample_params*, const void* h_low_color, int low_color_is_f64, const void* h_low_features, int low_features_is_f64,
+                     const void* h_features, int features_is_f64, void* h_out, int out_is_f64);
+int gi_last_upsample_ms(gi_ctx*, float* ms);
+
 /* Function-level entry points (parity tests and the C++ API's public methods).  Host pointers.
  * replaces RayTracer::trace (include/raytracer.h:382-478): rays [n][6] origin + unit dir -> hit, entity, res [n][8]        */
 int gi_trace(gi_ctx*, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res);
@@ -325,7 +369,7 @@ int gi_kat(gi_ctx*, int32_t what, int32_t n, const double* in, int32_t in_stride
  *   (0: the frame is finished).  Either pointer may be null.
  * gi_upload_scene, gi_upload_photons, gi_clear_photons, gi_build_photon_map and gi_trace_photons END the session (the next step: GI_E_STATE),
  *   also when the call itself fails: they end it before they look at their arguments, so a failed upload never leaves a session on a half-set scene.
- *   Every other entry may be called between steps -- gi_render_* of any size, the feature pass, the denoiser, the function-level and debug
+ *   Every other entry may be called between steps -- gi_render_* of any size, the feature pass, the denoiser, the upsampler, the function-level and debug
  *   entries, the result-neutral switches (wide nodes, culling, entity boxes, pool slots): the path pool, the queues and the per-sample buffer
  *   are shared scratch, only the pixel state is the session's.
  * gi_progressive_save / _restore: a checkpoint is one little-endian blob of gi_progressive_state_bytes bytes:
