@@ -173,20 +173,19 @@ void gi_denoise_default_params(gi_denoise_params* p)
 int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color, int color_is_f64, const void* d_features, int features_is_f64, void* d_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
+    c->t_dn.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!d_color || !d_features || !d_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
     const size_t n_pix = (size_t)p->width * (size_t)p->height;
     if (n_pix > ((size_t)1 << 28)) return fail(c, GI_E_INVALID, "denoise: frames beyond 2^28 pixels are not supported");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->dn_ms = 0; c->dn_pending = false;
-    if (!c->ev_dn0) { HIP_TRY(c, hipEventCreate(&c->ev_dn0)); HIP_TRY(c, hipEventCreate(&c->ev_dn1)); }
     const int it = p->iterations;
     if (it > 0) {
         const int rc = dn_reserve(c, n_pix);
         if (rc != GI_OK) return rc;
     }
-    HIP_TRY(c, hipEventRecord(c->ev_dn0, c->stream));
+    HIP_TRY(c, c->t_dn.begin(c->stream));
     if (it == 0) {
         if (d_out != d_color || (out_is_f64 != 0) != (color_is_f64 != 0))
             hipLaunchKernelGGL(k_dn_copy, dim3((unsigned)((n_pix * 3 + 255) / 256)), dim3(256), 0, c->stream, n_pix * 3, d_color, color_is_f64, d_out, out_is_f64);
@@ -212,48 +211,33 @@ int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color
         }
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_dn1, c->stream));
-    c->dn_pending = true;
+    HIP_TRY(c, c->t_dn.end(c->stream));
     return GI_OK;
 }
 
 int gi_denoise_host(gi_ctx* c, const gi_denoise_params* p, const void* h_color, int color_is_f64, const void* h_features, int features_is_f64, void* h_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
+    c->t_dn.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!h_color || !h_features || !h_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n_pix = (size_t)p->width * (size_t)p->height;
     const size_t cb = n_pix * 3 * (color_is_f64 ? 8 : 4), fb = n_pix * 8 * (features_is_f64 ? 8 : 4), ob = n_pix * 3 * (out_is_f64 ? 8 : 4);
-    void *d_color = nullptr, *d_feat = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_color, cb);
-    if (e == hipSuccess) e = hipMalloc(&d_feat, fb);
-    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-    if (e == hipSuccess) e = hipMemcpy(d_color, h_color, cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_feat, h_features, fb, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? GI_OK : fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
-    if (rc == GI_OK) rc = gi_denoise_device(c, p, d_color, color_is_f64, d_feat, features_is_f64, d_out, out_is_f64);
-    if (rc == GI_OK) {
-        e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, ob, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
-    }
-    if (d_color) (void)hipFree(d_color);
-    if (d_feat) (void)hipFree(d_feat);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf<unsigned char> d_color, d_feat, d_out;
+    hipError_t e = d_color.upload((const unsigned char*)h_color, cb);
+    if (e == hipSuccess) e = d_feat.upload((const unsigned char*)h_features, fb);
+    if (e == hipSuccess) e = d_out.alloc(ob);
+    if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
+    const int rc = gi_denoise_device(c, p, d_color.p, color_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
+    return rc != GI_OK ? rc : finish_to_host(c, "denoise_host", {{h_out, d_out.p, ob}}, &c->t_dn);
 }
 
 int gi_last_denoise_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    if (c->dn_pending) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_dn1));
-        HIP_TRY(c, hipEventElapsedTime(&c->dn_ms, c->ev_dn0, c->ev_dn1));
-        c->dn_pending = false;
-    }
-    *ms = c->dn_ms;
+    HIP_TRY(c, c->t_dn.read(ms));
     return GI_OK;
 }
 

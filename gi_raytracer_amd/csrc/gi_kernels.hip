@@ -1714,35 +1714,7 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
 }
 
 // ================================================================================================= host side
-namespace {
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-    hipError_t upload(const std::vector<T>& v)
-    {
-        release();
-        n = v.size();
-        size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-        hipError_t e = hipMalloc((void**)&p, bytes);
-        if (e != hipSuccess) { p = nullptr; return e; }
-        if (n) e = hipMemcpy(p, v.data(), n * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-    hipError_t alloc(size_t count)
-    {
-        release();
-        n = count;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) p = nullptr;
-        return e;
-    }
-};
-
-}  // namespace
+#include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
 #define STG_COUNT_MAX 10
 struct StreamGrids { int lds_refused = 0; int pix = 0, trace = 0, shade = 0, shadow = 0, gather = 0, accum = 0, finish = 0, ad_gen = 0, ad_accum = 0, compact = 0; };
@@ -1763,7 +1735,7 @@ struct gi_ctx {
     DevBuf<int32_t> d_wleaf_id;
     DevBuf<float> d_cboxes;           // content boxes of the wide records' children
     DevBuf<uint32_t> d_cuse;
-    bool cull_enabled = true;         // gi_set_content_culling
+    SceneSwitches sw;                 // gi_set_wide_nodes, gi_set_content_culling, gi_set_entity_boxes, GI_CLIP_BOXES, GI_WALK_CUT (apply_switches)
     bool flat_candidates = true;      // GI_FLAT_CANDIDATES=0: k_st_gather finds a leaf's k-th candidate through its range list, no k_st_gather_wave
     DevBuf<uint32_t> d_pcand_off;
     DevBuf<double> d_pcand, d_pcand_dc;
@@ -1776,7 +1748,6 @@ struct gi_ctx {
     int sort_shade_lo = 5;            // GI_SORT_SHADE_LO: lowest slot bit that sort looks at (32 neighbouring records = 7 KB stay in the trace stage's order)
     int sort_lo_bit = 0;              // GI_SORT_LO_BIT: lowest key bit the sort of the continuing rays looks at (27-bit key: octant, 18 Morton bits, 6 direction bits)
     uint32_t refill_min = 32;         // GI_REFILL_MIN: idle lanes of a wave that make k_st_trace hand out new rays (64: lockstep waves)
-    bool wide_enabled = true;         // gi_set_wide_nodes
     bool pn_planes_ok = false;        // the uploaded photon octree qualifies for the one-record-per-level descent
     int32_t n_prange = 0;             // entries of d_pranges in use
     DevBuf<int32_t> d_refs;
@@ -1788,9 +1759,6 @@ struct gi_ctx {
     bool lights_clear = false;            // of the scene last uploaded: no entity within a light's radius + the shadow bias of it (gi_layout.h)
     double cut_margin = -1;               // of the scene last uploaded
     bool scene_clipped = false;           // its trace boxes differ from the whole ones
-    bool entity_boxes = true;             // GI_ENTITY_BOXES=0: every entity of a leaf is tested, as the reference does
-    bool clip_boxes = true;               // GI_CLIP_BOXES=0: the closest-hit walk uses the entities' whole boxes
-    bool walk_cut = true;                 // GI_WALK_CUT=0: the closest-hit walk goes on behind its best hit, as the reference does
     DevBuf<TriGeom> d_tris;
     DevBuf<TriShade> d_shade;
     DevBuf<Mat> d_mats;
@@ -1860,24 +1828,16 @@ struct gi_ctx {
     // Measured on the default frame (tools/stripe_probe.py): one full-wave stage 60 ms, this plan 51 ms; on 1/8 of the rows 40 -> 30 ms.
     std::vector<std::pair<int, int>> finish_plan = {{0, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 2}, {0, 2}, {0, 4}, {0, 8}, {0, GI_MAX_DEPTH + 1}};
     DevBuf<unsigned int> d_fin_cnt;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float last_ms = 0;
+    EventTimer t_frame;               // around the kernels of the last gi_render_* / gi_progressive_step_* call
     int last_launches = 0;
-    // the feature pass (gi_render_features_*) keeps its own events: it leaves the frame's times (ev0 / ev1, ev_pool) alone
-    hipEvent_t ev_feat0 = nullptr, ev_feat1 = nullptr;
-    float feat_ms = 0;
-    bool feat_pending = false;        // ev_feat0 / ev_feat1 were recorded and not read yet
+    EventTimer t_feat;                // the feature pass (gi_render_features_*) keeps its own: it leaves the frame's times (t_frame, ev_pool) alone
     int aov_lds_refused = -1;         // -1: the k_aov instances were not asked for their LDS yet; else as StreamGrids::lds_refused
-    // the denoiser (gi_denoise_*, gi_denoise.inc): events of its own again, and its scratch -- the guide records [h][w][8] and two colour
+    // the denoiser (gi_denoise_*, gi_denoise.inc): a timer of its own again, and its scratch -- the guide records [h][w][8] and two colour
     // buffers [h][w][3], f64, sized on first use and kept
-    hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;
-    float dn_ms = 0;
-    bool dn_pending = false;
+    EventTimer t_dn;
     DevBuf<double> d_dn_guides, d_dn_a, d_dn_b;
-    // the guided upsampler (gi_upsample_*, gi_upsample.inc): events of its own; its low frame is packed into the denoiser's scratch (dn_reserve)
-    hipEvent_t ev_up0 = nullptr, ev_up1 = nullptr;
-    float up_ms = 0;
-    bool up_pending = false;
+    // the guided upsampler (gi_upsample_*, gi_upsample.inc): a timer of its own; its low frame is packed into the denoiser's scratch (dn_reserve)
+    EventTimer t_up;
     bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
     bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
     DevBuf<StreamCounters> d_stream_cnt;
@@ -1899,33 +1859,84 @@ int fail(gi_ctx* c, int code, const std::string& msg)
         if (e__ != hipSuccess) return fail((c), GI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
     } while (0)
 
+// The photon map's box: the caller's, or the scene's
+void frame_box(const gi_ctx* c, const double* box6, double* out)
+{
+    for (int k = 0; k < 3; k++) { out[k] = box6 ? box6[k] : c->S.root_bmin[k]; out[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
+}
+
+// A frame of npix pixels that `render(d_out, d_spp)` leaves in scratch of this call, copied to the caller's arrays (gi_render_host, gi_progressive_step_host)
+template <class Render>
+int frame_to_host(gi_ctx* c, const char* what, size_t npix, void* h_out, int out_is_f64, int32_t* h_spp, Render render)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = npix * 3 * (out_is_f64 ? 8 : 4);
+    DevBuf<unsigned char> d_out;
+    DevBuf<int32_t> d_spp;
+    HIP_TRY(c, d_out.alloc(bytes));
+    if (h_spp) HIP_TRY(c, d_spp.alloc(npix));
+    const int rc = render((void*)d_out.p, d_spp.p);
+    return rc != GI_OK ? rc : finish_to_host(c, what, {{h_out, d_out.p, bytes}, to_host(h_spp, d_spp, npix)});
+}
+
+// The device side of a function-level entry (gi_entries.inc), after its argument and state checks.  in() uploads a caller's array, out() allocates a
+// result and notes where it goes (h == nullptr: an optional output nobody asked for -- the kernel still writes it), scratch() is memory of this
+// call alone; each takes the element count, once.  run(launch) launches (unless a buffer failed), asks for the launch's status, waits for the
+// stream and copies the results back in the order of the out() calls.  launch returns nothing, or a failure it has recorded with fail().
+struct Entry {
+    gi_ctx* c;
+    const char* what;
+    hipError_t e;
+    DevBuf<unsigned char> buf[16];
+    ToHost outs[6];
+    int n_buf = 0, n_out = 0;
+    Entry(gi_ctx* c_, const char* what_) : c(c_), what(what_), e(hipSetDevice(c_->device)) {}
+    template <class T> T* scratch(size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].alloc(count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> const T* in(const T* h, size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].upload(reinterpret_cast<const unsigned char*>(h), count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<const T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> T* out(T* h, size_t count)
+    {
+        T* d = scratch<T>(count);
+        if (d && n_out == 6) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) outs[n_out++] = ToHost{h, d, count * sizeof(T)};
+        return d;
+    }
+    template <class Launch> int run(Launch launch)
+    {
+        if (e == hipSuccess) {
+            if constexpr (std::is_void<decltype(launch())>::value) launch();
+            else if (const int rc = launch()) return rc;
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return fail(c, GI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return finish_to_host(c, what, outs, (size_t)n_out);
+    }
+};
+
 }  // namespace
 
 __global__ __launch_bounds__(1024) void k_rs_scan(uint32_t* ghist, uint32_t total);   // gi_sort.inc
-// The Scene fields that follow the context's switches, from the uploaded tables and the switches alone.  Every upload, every change of the
-// photon map and every gi_set_* of a switch ends here, and nothing else assigns these fields.
+// The Scene fields that follow the context's switches, from the uploaded tables and the switches alone (gi_layout.h: apply_scene_switches, which
+// the CPU suite's emulator calls too).  Every upload, every change of the photon map and every gi_set_* of a switch ends here, and nothing else
+// assigns these fields.
 static void apply_switches(gi_ctx* c)
 {
-    Scene& S = c->S;
-    S.wnodes = (c->wide_enabled && S.n_wnode > 0) ? c->d_wnodes.p : nullptr;                           // gi_set_wide_nodes
-    S.cboxes = (c->cull_enabled && S.wnodes && c->d_cboxes.n > 1) ? c->d_cboxes.p : nullptr;             // gi_set_content_culling
-    // Which of the walks' short cuts are on (all of them leave every result as it is: DESIGN.md section 4): entity boxes; for the closest-hit walk
-    // the boxes cut to the leaves, and no look behind the best hit.  gi_set_entity_boxes(ctx, 0) turns all three off: the walks then ask what the reference asks.
-    S.leaf_boxes = c->entity_boxes ? c->d_leaf_boxes.p : nullptr;
-    S.trace_boxes = !c->entity_boxes ? nullptr : ((c->clip_boxes && c->scene_clipped) ? c->d_trace_boxes.p : c->d_leaf_boxes.p);
-    S.cut_margin = (c->entity_boxes && c->walk_cut) ? c->cut_margin : -1.0;
-    const bool cut_to_leaves = S.trace_boxes == c->d_trace_boxes.p && S.cboxes && c->d_tcboxes.n == c->d_cboxes.n;
-    S.tcboxes = cut_to_leaves ? c->d_tcboxes.p : S.cboxes;
-    S.tcuse = cut_to_leaves ? c->d_tcuse.p : S.cuse;
-    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks)
-    const bool sh = c->lights_clear && S.trace_boxes == c->d_trace_boxes.p;
-    S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
-    S.scboxes = sh ? S.tcboxes : S.cboxes;
-    S.scuse = sh ? S.tcuse : S.cuse;
-    // the photon octree's counterpart of the wide records (gather_find_leaf), and the fast descent of the gather keys over it (build_photon_tables)
-    S.pn_planes = (c->wide_enabled && c->pn_planes_ok) ? 1 : 0;
-    S.pdescent = (S.pn_planes && c->pdescent_ready) ? c->d_pdescent.p : nullptr;
-    S.pjump = (S.pdescent && c->pjump_ready) ? c->d_pjump.p : nullptr;
+    SceneTables T;
+    T.wnodes = c->d_wnodes.p; T.cboxes = c->d_cboxes.p; T.n_cboxes = c->d_cboxes.n;
+    T.leaf_boxes = c->d_leaf_boxes.p; T.trace_boxes = c->d_trace_boxes.p;
+    T.tcboxes = c->d_tcboxes.p; T.n_tcboxes = c->d_tcboxes.n; T.tcuse = c->d_tcuse.p;
+    T.cut_margin = c->cut_margin; T.clipped = c->scene_clipped; T.lights_clear = c->lights_clear;
+    T.pn_planes_ok = c->pn_planes_ok;
+    T.pdescent = c->pdescent_ready ? c->d_pdescent.p : nullptr;   // (build_photon_tables)
+    T.pjump = c->pjump_ready ? c->d_pjump.p : nullptr;
+    apply_scene_switches(c->S, T, c->sw);
 }
 
 // The tables derived from the photon map c->S points at: the sort key of the gather queries (k_pleaf_rank), the leaves' candidate lists and, for a
@@ -2093,7 +2104,7 @@ int gi_create(gi_ctx** out, int device_ordinal)
     std::vector<uint16_t> table;
     build_halton_tables(dims, table);
     if (c->d_hdims.upload(dims) != hipSuccess || c->d_htable.upload(table) != hipSuccess || c->d_tile_counter.alloc(1) != hipSuccess ||
-        c->d_counters.alloc(1) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
+        c->d_counters.alloc(1) != hipSuccess) {
         delete c;
         return GI_E_HIP;
     }
@@ -2114,9 +2125,9 @@ int gi_create(gi_ctx** out, int device_ordinal)
     if (const char* e = getenv("GI_SORT_LO_BIT")) c->sort_lo_bit = std::min(26, std::max(0, atoi(e)));
     if (const char* e = getenv("GI_DEFER_SHADOWS")) c->defer_shadows = atoi(e) != 0;
     if (const char* e = getenv("GI_FAST_DESCENT")) c->fast_descent = atoi(e) != 0;
-    if (const char* e = getenv("GI_ENTITY_BOXES")) c->entity_boxes = atoi(e) != 0;
-    if (const char* e = getenv("GI_CLIP_BOXES")) c->clip_boxes = atoi(e) != 0;
-    if (const char* e = getenv("GI_WALK_CUT")) c->walk_cut = atoi(e) != 0;
+    if (const char* e = getenv("GI_ENTITY_BOXES")) c->sw.entity_boxes = atoi(e) != 0;
+    if (const char* e = getenv("GI_CLIP_BOXES")) c->sw.clip_boxes = atoi(e) != 0;
+    if (const char* e = getenv("GI_WALK_CUT")) c->sw.walk_cut = atoi(e) != 0;
     if (const char* e = getenv("GI_REFILL_MIN")) c->refill_min = (uint32_t)std::min(64, std::max(1, atoi(e)));
     if (const char* e = getenv("GI_FINISH_THRESHOLD")) c->finish_threshold = (uint32_t)strtoul(e, nullptr, 0);   // tuning knobs
     if (const char* e = getenv("GI_FINISH_PLAN")) {   // "lanes:vertices,lanes:vertices,..."
@@ -2141,14 +2152,7 @@ void gi_destroy(gi_ctx* c)
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_wfcnt) (void)hipHostFree(c->h_wfcnt);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->ev_feat0) (void)hipEventDestroy(c->ev_feat0);
-    if (c->ev_feat1) (void)hipEventDestroy(c->ev_feat1);
-    if (c->ev_dn0) (void)hipEventDestroy(c->ev_dn0);
-    if (c->ev_dn1) (void)hipEventDestroy(c->ev_dn1);
-    if (c->ev_up0) (void)hipEventDestroy(c->ev_up0);
-    if (c->ev_up1) (void)hipEventDestroy(c->ev_up1);
+    for (EventTimer* t : {&c->t_frame, &c->t_feat, &c->t_dn, &c->t_up}) t->destroy();
     delete c;
 }
 
@@ -2255,13 +2259,13 @@ static int render_megakernel(gi_ctx* c, const Frame& F, void* d_out, int out_is_
     HIP_TRY(c, hipMemsetAsync(c->d_tile_counter.p, 0, sizeof(unsigned int), c->stream));
     if (c->count_enabled) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(Counters), c->stream));
     const int grid = c->n_cu * 2;
-    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, c->t_frame.begin(c->stream));
     if (c->count_enabled)
         hipLaunchKernelGGL(k_render<true>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
     else
         hipLaunchKernelGGL(k_render<false>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, c->t_frame.end(c->stream));
     c->last_launches = 1;
     return GI_OK;
 }
@@ -2297,6 +2301,12 @@ static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process 
 }
 // The gather of a pass (stream_passes, gi_debug_gather_pass): n queries in leaf order (keys, vals = their slots), the caustic term added to their
 // radiance in lbuf; a wave per query (k_st_gather_wave) or a lane per query (k_st_gather)
+static int photon_key_bits(const Scene& S)   // of the gather queries' sort key: a leaf's rank, 0 .. n_pleaf
+{
+    int bits = 1;
+    while ((1u << bits) <= (uint32_t)S.n_pleaf) bits++;
+    return bits;
+}
 static void launch_gather(gi_ctx* c, bool wave, bool counting, const PathPool& pool, const uint32_t* keys, const uint32_t* vals, uint32_t n,
                           const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
 {
@@ -2478,8 +2488,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
         const uint32_t n_gather = c->h_ctl->n_gather;
         if (counting) c->stream_shaded += c->h_ctl->n_shade;
         if (c->S.n_pnode > 0 && n_gather > 0) {
-            int bits = 1;
-            while ((1u << bits) <= (uint32_t)c->S.n_pleaf) bits++;   // keys 0 .. n_pleaf
+            const int bits = photon_key_bits(c->S);
             stage_begin(c, STG_SORT);
             {
                 uint32_t* const tk = reinterpret_cast<uint32_t*>(c->d_sort_tmp.p);
@@ -2563,7 +2572,7 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
         HIP_TRY(c, hipMemsetAsync(c->d_stream_cnt.p, 0, sizeof(StreamCounters), st));
         c->stream_shaded = 0;
     }
-    HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, c->t_frame.begin(st));
     if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
     if (c->d_pixtab.n < n_pix) HIP_TRY(c, c->d_pixtab.alloc(n_pix));
     hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
@@ -2589,7 +2598,7 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
         if (s_done) *s_done = s0 + ns;
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev1, st));
+    HIP_TRY(c, c->t_frame.end(st));
     c->last_launches = launches;
     return GI_OK;
 }
@@ -2608,13 +2617,14 @@ static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f
 // pix: the records the rounds work on (padded 8x8 tiles); init: put them in their initial state first.  The one-shot frame (render_adaptive) is d_pix
 // with init; a step of a progressive session is the session's records with the step's cap E' in F.max_samples -- the same loop, which then stops at E'.
 static uint32_t rounds_records(const Frame& F) { return (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3)) * 64u; }
+static bool rounds_fit(const Frame& F) { return (size_t)((F.w + 7) >> 3) * (size_t)((F.local_rows + 7) >> 3) * 64 <= 0xfffffff0ull; }   // the records, and so a round of them, have 32-bit path slots
 static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
+    if (!rounds_fit(F)) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
     const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (wf_pixel_xy)
-    int B = (int)std::min<size_t>(32, std::max<size_t>(1, c->pool_slots_max / n_pix));
+    int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->pool_slots_max, 0xfffffff0ull) / n_pix));
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
     const size_t slots = (size_t)n_pix * (size_t)B;
-    if (slots > 0xfffffff0ull) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
     int rc = stream_alloc(c, (uint32_t)slots, true);   // k_ad_gen names every path's place in the radiance buffer
     if (rc) return rc;
     if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
@@ -2625,7 +2635,7 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
     unsigned int* cnt = c->d_wfcnt.p;
     int launches = 0;
     c->ev_used = 0; c->ev_stage.clear();
-    HIP_TRY(c, hipEventRecord(c->ev0, st));
+    HIP_TRY(c, c->t_frame.begin(st));
     if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
     bool any = F.max_samples > 0 && F.min_samples > 0;
     if (!any) {   // 0 samples per pixel still has to write the initial colour
@@ -2656,7 +2666,7 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
         any = c->h_wfcnt[1] > 0;
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev1, st));
+    HIP_TRY(c, c->t_frame.end(st));
     c->last_launches = launches;
     return GI_OK;
 }
@@ -2668,6 +2678,10 @@ static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f6
     return run_rounds(c, F, c->d_pix.p, true, d_out, out_is_f64, d_spp, cancel);
 }
 
+// fixed sample count: the streaming pool with path regeneration (the refill schedule); adaptive sampling: rounds (sample-order decisions) on the
+// same passes; mode 2: rounds for every frame, a second schedule of the fixed-spp frames
+static bool uses_refill_schedule(const gi_ctx* c, const Frame& F) { return c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0; }
+
 int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
     if (!c || !d_out) return GI_E_INVALID;
@@ -2677,21 +2691,19 @@ int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_
     if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
     if (cancel && *cancel) return fail(c, GI_E_CANCELLED, "render: cancelled");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->last_ms = 0; c->last_launches = 0;
+    c->t_frame.reset(); c->last_launches = 0;
     if (F.local_rows == 0) return GI_OK;
     if (c->render_mode == 1 || c->count_enabled) return render_megakernel(c, F, d_out, out_is_f64, d_spp);
-    // fixed sample count: streaming pool with path regeneration; adaptive sampling: rounds (sample-order decisions) on the same passes;
-    // mode 2: rounds for every frame, a second schedule of the fixed-spp frames
-    if (c->count_stream && !(c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0))
+    if (c->count_stream && !uses_refill_schedule(c, F))
         return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) belong to fixed-sample-count frames of the wavefront pipeline");
-    if (c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0) return render_streaming(c, F, d_out, out_is_f64, d_spp, cancel);
+    if (uses_refill_schedule(c, F)) return render_streaming(c, F, d_out, out_is_f64, d_spp, cancel);
     return render_adaptive(c, F, d_out, out_is_f64, d_spp, cancel);
 }
 
 int gi_set_wide_nodes(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
-    c->wide_enabled = enable != 0;
+    c->sw.wide = enable != 0;
     apply_switches(c);
     return (c->S.wnodes ? 1 : 0) | (c->S.pn_planes ? 2 : 0);
 }
@@ -2699,7 +2711,7 @@ int gi_set_wide_nodes(gi_ctx* c, int enable)
 int gi_set_content_culling(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
-    c->cull_enabled = enable != 0;
+    c->sw.cull = enable != 0;
     apply_switches(c);
     return c->S.cboxes ? 1 : 0;
 }
@@ -2707,7 +2719,7 @@ int gi_set_content_culling(gi_ctx* c, int enable)
 int gi_set_entity_boxes(gi_ctx* c, int enable)
 {
     if (!c) return GI_E_INVALID;
-    c->entity_boxes = enable != 0;
+    c->sw.entity_boxes = enable != 0;
     apply_switches(c);
     return c->S.leaf_boxes ? 1 : 0;
 }
@@ -2729,17 +2741,15 @@ int gi_set_pool_slots(gi_ctx* c, int64_t slots)
 int gi_last_render_ms(gi_ctx* c, float* ms, int32_t* n_launches)
 {
     if (!c) return GI_E_INVALID;
-    if (c->last_launches > 0) {
-        HIP_TRY(c, hipEventSynchronize(c->ev1));
-        HIP_TRY(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    }
+    float frame_ms = 0;
+    HIP_TRY(c, c->t_frame.read(&frame_ms));
     for (int k = 0; k < STG_COUNT_MAX; k++) c->stage_ms[k] = 0;
     for (size_t k = 0; k + 1 < c->ev_used + 1 && k / 2 < c->ev_stage.size() && k + 1 < c->ev_pool.size() && k < c->ev_used; k += 2) {
         float t = 0;
         if (hipEventElapsedTime(&t, c->ev_pool[k], c->ev_pool[k + 1]) == hipSuccess) c->stage_ms[c->ev_stage[k / 2]] += t;
         if (getenv("GI_DEBUG_STAGES")) fprintf(stderr, "[stage] %d %.3f ms\n", c->ev_stage[k / 2], t);
     }
-    if (ms) *ms = c->last_ms;
+    if (ms) *ms = frame_ms;
     if (n_launches) *n_launches = c->last_launches;
     return GI_OK;
 }
@@ -2800,247 +2810,19 @@ int gi_render_host(gi_ctx* c, const gi_render_params* p, void* h_out, int out_is
     if (!c || !h_out || !p) return GI_E_INVALID;
     const size_t npix = (size_t)gi_local_rows(p) * (size_t)std::max(p->width, 0);
     if (npix == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = npix * 3 * (out_is_f64 ? 8 : 4);
-    void* d_out = nullptr;
-    int32_t* d_spp = nullptr;
-    HIP_TRY(c, hipMalloc(&d_out, bytes));
-    if (h_spp && hipMalloc((void**)&d_spp, npix * 4) != hipSuccess) { (void)hipFree(d_out); return fail(c, GI_E_HIP, "hipMalloc spp"); }
-    int rc = gi_render_device(c, p, d_out, out_is_f64, d_spp, cancel);
-    if (rc == GI_OK) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && h_spp) e = hipMemcpy(h_spp, d_spp, npix * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("render_host: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_out);
-    if (d_spp) (void)hipFree(d_spp);
-    return rc;
+    return frame_to_host(c, "render_host", npix, h_out, out_is_f64, h_spp,
+                         [&](void* d_out, int32_t* d_spp) { return gi_render_device(c, p, d_out, out_is_f64, d_spp, cancel); });
 }
 
-// ---- progressive sessions (an addition: the reference renders a frame in one piece).  The session owns its pixel records (c->prog.pix); a step runs
-// the bodies of the one-shot frame on them -- stream_samples over [E, E') for a fixed sample count, run_rounds with the cap E' otherwise -- so a
-// frame built in steps has the bits of the frame built in one call.
-namespace {
-struct ProgBlobHeader {            // little-endian, 192 bytes; the pixel records follow as they lie on the device (include/gi_hip.h)
-    char magic[8];
-    uint32_t version, header_bytes;
-    gi_render_params rp;           // 136 bytes: its fields in declaration order, 4 bytes of padding before noise_thresh
-    int32_t schedule, sample_end;
-    uint64_t n_records;
-    uint32_t record_bytes, reserved0;
-    int32_t n_entity, n_node, n_photon, reserved1;
-};
-static_assert(sizeof(gi_render_params) == 136 && sizeof(ProgBlobHeader) == 192 && sizeof(PixRec) == 72, "checkpoint layout (include/gi_hip.h)");
-const char kProgMagic[8] = {'G', 'I', 'P', 'R', 'O', 'G', 'R', '\0'};
-const uint32_t kProgVersion = 1;
-
-uint32_t prog_records(const Frame& F, int schedule) { return schedule == 0 ? (uint32_t)F.w * (uint32_t)F.local_rows : rounds_records(F); }
-// a session on parameters already validated: the records allocated (not yet filled), E = sample_end
-int prog_open(gi_ctx* c, const gi_render_params& rp, const Frame& F, int schedule, int32_t sample_end)
-{
-    gi_ctx::Progressive& g = c->prog;
-    g.open = false;
-    const uint32_t n_rec = prog_records(F, schedule);
-    if (g.pix.n != n_rec || !g.pix.p) HIP_TRY(c, g.pix.alloc(n_rec));
-    g.rp = rp; g.F = F; g.schedule = schedule; g.sample_end = sample_end; g.n_rec = n_rec;
-    return GI_OK;
-}
-}  // namespace
-
-int gi_progressive_begin(gi_ctx* c, const gi_render_params* p)
-{
-    if (!c) return GI_E_INVALID;
-    c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_begin: no scene uploaded");
-    Frame F;
-    std::string ferr;
-    if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
-    if (c->render_mode == 1 || c->count_enabled) return fail(c, GI_E_STATE, "progressive_begin: sessions run on the streaming passes (render mode 0 or 2), not on the megakernel");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int schedule = (c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0) ? 0 : 1;   // as gi_render_device picks
-    int rc = prog_open(c, *p, F, schedule, 0);
-    if (rc) return rc;
-    if (c->prog.n_rec) {
-        hipLaunchKernelGGL(k_pix_init, dim3(stream_grids(c).pix), dim3(GI_BLOCK), 0, c->stream, c->prog.pix.p, c->prog.n_rec);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    c->prog.open = true;
-    return GI_OK;
-}
-
-int gi_progressive_end(gi_ctx* c)
-{
-    if (!c) return GI_E_INVALID;
-    if (c->prog.open || c->prog.pix.p) (void)hipSetDevice(c->device);
-    c->prog.open = false;
-    c->prog.pix.release();
-    return GI_OK;
-}
-
-int gi_progressive_step_device(gi_ctx* c, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    if (!c || !d_out || n_samples < 0) return c ? fail(c, GI_E_INVALID, "progressive_step: n_samples < 0 or no output buffer") : GI_E_INVALID;
-    gi_ctx::Progressive& g = c->prog;
-    if (!g.open) return fail(c, GI_E_STATE, "progressive_step: no session open (gi_progressive_begin; scene and photon uploads end a session)");
-    if (cancel && *cancel) return fail(c, GI_E_CANCELLED, "render: cancelled");
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->last_ms = 0; c->last_launches = 0;
-    // a rank without rows has no pixel and no output: only E moves (no kernel, no timing beyond the reset above), and d_out is never touched --
-    // which is why gi_progressive_step_host may hand its host pointer through for such a rank
-    if (g.F.local_rows == 0) { g.sample_end = (int32_t)std::min<long long>((long long)g.sample_end + n_samples, g.F.max_samples); return GI_OK; }
-    const int32_t e0 = g.sample_end, e1 = (int32_t)std::min<long long>((long long)e0 + n_samples, g.F.max_samples);
-    if (e1 == e0) {                 // nothing to take: the frame as the records hold it
-        hipStream_t st = c->stream;
-        c->ev_used = 0; c->ev_stage.clear();
-        HIP_TRY(c, hipEventRecord(c->ev0, st));
-        stage_begin(c, STG_ACCUM);
-        hipLaunchKernelGGL(k_pix_resolve, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, st, g.F, g.pix.p, g.n_rec, g.schedule, d_out, out_is_f64, d_spp);
-        stage_end(c);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev1, st));
-        c->last_launches = 1;
-        return GI_OK;
-    }
-    if (g.schedule == 0) {
-        int done = e0;
-        const int rc = stream_samples(c, g.F, g.pix.p, e0, e1, false, d_out, out_is_f64, d_spp, cancel, &done);
-        g.sample_end = done;        // a cancelled step keeps the chunks it folded
-        return rc;
-    }
-    if (c->count_stream) return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) belong to fixed-sample-count frames of the wavefront pipeline");
-    Frame F = g.F;
-    F.max_samples = e1;             // the cap of this step; a pixel the rule has stopped stays stopped
-    const int rc = run_rounds(c, F, g.pix.p, false, d_out, out_is_f64, d_spp, cancel);
-    // cancelled at the top of a round or between the passes of one (whose radiances are dropped: the records change in k_ad_accum alone, and the n that
-    // k_ad_gen left is set again by the next one): every record is at a sample boundary and below the cap; E stays, and the next step offers [.., E')
-    // again to those below it
-    if (rc == GI_OK) g.sample_end = e1;
-    return rc;
-}
-
-int gi_progressive_step_host(gi_ctx* c, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_spp, volatile const int* cancel)
-{
-    if (!c || !h_out || n_samples < 0) return c ? fail(c, GI_E_INVALID, "progressive_step: n_samples < 0 or no output buffer") : GI_E_INVALID;
-    if (!c->prog.open) return fail(c, GI_E_STATE, "progressive_step: no session open (gi_progressive_begin; scene and photon uploads end a session)");
-    const size_t npix = (size_t)c->prog.F.local_rows * (size_t)c->prog.F.w;
-    if (npix == 0) return gi_progressive_step_device(c, n_samples, h_out, out_is_f64, nullptr, cancel);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = npix * 3 * (out_is_f64 ? 8 : 4);
-    void* d_out = nullptr;
-    int32_t* d_spp = nullptr;
-    HIP_TRY(c, hipMalloc(&d_out, bytes));
-    if (h_spp && hipMalloc((void**)&d_spp, npix * 4) != hipSuccess) { (void)hipFree(d_out); return fail(c, GI_E_HIP, "hipMalloc spp"); }
-    int rc = gi_progressive_step_device(c, n_samples, d_out, out_is_f64, d_spp, cancel);
-    if (rc == GI_OK) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && h_spp) e = hipMemcpy(h_spp, d_spp, npix * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("progressive_step_host: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_out);
-    if (d_spp) (void)hipFree(d_spp);
-    return rc;
-}
-
-int gi_progressive_status(gi_ctx* c, int32_t* sample_end, int64_t* pixels_wanting)
-{
-    if (!c) return GI_E_INVALID;
-    gi_ctx::Progressive& g = c->prog;
-    if (!g.open) return fail(c, GI_E_STATE, "progressive_status: no session open");
-    if (sample_end) *sample_end = g.sample_end;
-    if (pixels_wanting) {
-        *pixels_wanting = 0;
-        if (g.n_rec) {
-            HIP_TRY(c, hipSetDevice(c->device));
-            if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
-            HIP_TRY(c, hipMemsetAsync(c->d_wfcnt.p, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(k_pix_wanting, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, c->stream, g.F, g.pix.p, g.n_rec, g.schedule, c->d_wfcnt.p);
-            HIP_TRY(c, hipGetLastError());
-            unsigned int n = 0;
-            HIP_TRY(c, hipMemcpyAsync(&n, c->d_wfcnt.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            *pixels_wanting = (int64_t)n;
-        }
-    }
-    return GI_OK;
-}
-
-int gi_progressive_state_bytes(gi_ctx* c, int64_t* n_bytes)
-{
-    if (!c || !n_bytes) return GI_E_INVALID;
-    if (!c->prog.open) return fail(c, GI_E_STATE, "progressive_state_bytes: no session open");
-    *n_bytes = (int64_t)sizeof(ProgBlobHeader) + (int64_t)c->prog.n_rec * (int64_t)sizeof(PixRec);
-    return GI_OK;
-}
-
-int gi_progressive_save(gi_ctx* c, void* h_blob, int64_t cap_bytes)
-{
-    if (!c || !h_blob) return GI_E_INVALID;
-    gi_ctx::Progressive& g = c->prog;
-    if (!g.open) return fail(c, GI_E_STATE, "progressive_save: no session open");
-    const int64_t need = (int64_t)sizeof(ProgBlobHeader) + (int64_t)g.n_rec * (int64_t)sizeof(PixRec);
-    if (cap_bytes < need) return fail(c, GI_E_INVALID, "progressive_save: the buffer holds " + std::to_string(cap_bytes) + " bytes, the checkpoint needs " + std::to_string(need));
-    ProgBlobHeader h;
-    memset(&h, 0, sizeof h);
-    memcpy(h.magic, kProgMagic, 8);
-    h.version = kProgVersion; h.header_bytes = (uint32_t)sizeof h;
-    memcpy(&h.rp, &g.rp, sizeof h.rp);
-    memset(reinterpret_cast<char*>(&h.rp) + offsetof(gi_render_params, max_samples) + 4, 0, 4);   // the padding before noise_thresh
-    h.schedule = g.schedule; h.sample_end = g.sample_end;
-    h.n_records = g.n_rec; h.record_bytes = (uint32_t)sizeof(PixRec);
-    h.n_entity = c->S.n_tri; h.n_node = c->S.n_node; h.n_photon = c->S.n_photon;
-    memcpy(h_blob, &h, sizeof h);
-    if (g.n_rec) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(static_cast<char*>(h_blob) + sizeof h, g.pix.p, (size_t)g.n_rec * sizeof(PixRec), hipMemcpyDeviceToHost));
-    }
-    return GI_OK;
-}
-
-int gi_progressive_restore(gi_ctx* c, const void* h_blob, int64_t n_bytes)
-{
-    if (!c) return GI_E_INVALID;
-    c->prog.open = false;
-    if (!h_blob || n_bytes < (int64_t)sizeof(ProgBlobHeader)) return fail(c, GI_E_INVALID, "progressive_restore: the blob is shorter than a checkpoint header");
-    ProgBlobHeader h;
-    memcpy(&h, h_blob, sizeof h);
-    if (memcmp(h.magic, kProgMagic, 8) != 0) return fail(c, GI_E_INVALID, "progressive_restore: not a checkpoint (magic)");
-    if (h.version != kProgVersion) return fail(c, GI_E_INVALID, "progressive_restore: checkpoint format version " + std::to_string(h.version) + ", this library reads " + std::to_string(kProgVersion));
-    if (h.header_bytes != sizeof h || h.record_bytes != sizeof(PixRec) || (h.schedule != 0 && h.schedule != 1))
-        return fail(c, GI_E_INVALID, "progressive_restore: header or record size, or schedule, not of this format");
-    Frame F;
-    std::string ferr;
-    if (!make_frame(&h.rp, F, ferr)) return fail(c, GI_E_INVALID, "progressive_restore: " + ferr);
-    if (h.schedule == 0 && !(F.min_samples == F.max_samples && F.max_samples > 0)) return fail(c, GI_E_INVALID, "progressive_restore: the refill schedule needs a fixed sample count");
-    if (h.schedule != 0 && (size_t)(((F.w + 7) >> 3)) * (size_t)((F.local_rows + 7) >> 3) * 64 > 0xfffffff0ull) return fail(c, GI_E_INVALID, "progressive_restore: frame too large");
-    if (h.sample_end < 0 || h.sample_end > F.max_samples) return fail(c, GI_E_INVALID, "progressive_restore: sample counter outside 0 .. max_samples");
-    const uint32_t n_rec = prog_records(F, h.schedule);
-    if (h.n_records != n_rec || n_bytes != (int64_t)sizeof h + (int64_t)n_rec * (int64_t)sizeof(PixRec))
-        return fail(c, GI_E_INVALID, "progressive_restore: " + std::to_string(n_bytes) + " bytes, a checkpoint of this frame has " + std::to_string(sizeof h + (size_t)n_rec * sizeof(PixRec)) + " (truncated?)");
-    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_restore: no scene uploaded");
-    if (c->count_enabled) return fail(c, GI_E_STATE, "progressive_restore: sessions run on the streaming passes, not with the megakernel's work counters (gi_set_counters 1)");
-    if (h.n_entity != c->S.n_tri || h.n_node != c->S.n_node || h.n_photon != c->S.n_photon)
-        return fail(c, GI_E_STATE, "progressive_restore: the checkpoint was taken on another scene or photon map (entities, nodes, photons " + std::to_string(h.n_entity) + ", " + std::to_string(h.n_node) + ", " +
-                                       std::to_string(h.n_photon) + "; uploaded " + std::to_string(c->S.n_tri) + ", " + std::to_string(c->S.n_node) + ", " + std::to_string(c->S.n_photon) + ")");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc = prog_open(c, h.rp, F, h.schedule, h.sample_end);
-    if (rc) return rc;
-    if (n_rec) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(c->prog.pix.p, static_cast<const char*>(h_blob) + sizeof h, (size_t)n_rec * sizeof(PixRec), hipMemcpyHostToDevice));
-    }
-    c->prog.open = true;
-    return GI_OK;
-}
+#include "gi_progressive.inc"
 
 // ---- first-hit feature buffers (an addition: the reference renders radiance only; the values are those RayTracer::radiance holds after trace()
 // of the primary ray, include/raytracer.h:186-210)
 int gi_render_features_device(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_ids)
 {
-    if (!c || !d_out) return GI_E_INVALID;
+    if (!c) return GI_E_INVALID;
+    c->t_feat.reset();
+    if (!d_out) return GI_E_INVALID;
     if (!c->have_scene) return fail(c, GI_E_STATE, "render_features: no scene uploaded");
     Frame F;
     std::string ferr;
@@ -3051,597 +2833,43 @@ int gi_render_features_device(gi_ctx* c, const gi_render_params* p, int32_t n_sa
         return fail(c, GI_E_INVALID, "render_features: n_samples = " + std::to_string(n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
                                      " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->feat_ms = 0; c->feat_pending = false;
     if (F.local_rows == 0) return GI_OK;
     if (c->aov_lds_refused < 0) { c->aov_lds_refused = 0; ask_for_lds(kAov, c->aov_lds_refused); }
     if (c->aov_lds_refused) return fail(c, GI_E_HIP, "render_features: the device refused " + std::to_string(c->aov_lds_refused) + " bytes of dynamic LDS per workgroup");
-    if (!c->ev_feat0) { HIP_TRY(c, hipEventCreate(&c->ev_feat0)); HIP_TRY(c, hipEventCreate(&c->ev_feat1)); }
     const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
     const AovK k = aov_kernel(scene_trace_feat(c->S), c->S.wnodes != nullptr);
-    HIP_TRY(c, hipEventRecord(c->ev_feat0, c->stream));
+    HIP_TRY(c, c->t_feat.begin(c->stream));
     hipLaunchKernelGGL(k.fn, dim3((n_pix + GI_AOV_BLOCK - 1) / GI_AOV_BLOCK), dim3(GI_AOV_BLOCK), k.lds, c->stream, c->S, F, n_pix, n_samples, d_out, out_is_f64, d_ids);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_feat1, c->stream));
-    c->feat_pending = true;
+    HIP_TRY(c, c->t_feat.end(c->stream));
     return GI_OK;
 }
 
 int gi_render_features_host(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_ids)
 {
-    if (!c || !h_out || !p) return GI_E_INVALID;
+    if (!c) return GI_E_INVALID;
+    c->t_feat.reset();
+    if (!h_out || !p) return GI_E_INVALID;
     const size_t npix = (size_t)gi_local_rows(p) * (size_t)std::max(p->width, 0);
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = std::max<size_t>(npix, 1) * 8 * (out_is_f64 ? 8 : 4);
-    void* d_out = nullptr;
-    int32_t* d_ids = nullptr;
-    HIP_TRY(c, hipMalloc(&d_out, bytes));
-    if (h_ids && hipMalloc((void**)&d_ids, std::max<size_t>(npix, 1) * 8) != hipSuccess) { (void)hipFree(d_out); return fail(c, GI_E_HIP, "hipMalloc ids"); }
-    int rc = gi_render_features_device(c, p, n_samples, d_out, out_is_f64, d_ids);
-    if (rc == GI_OK && npix) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, npix * 8 * (out_is_f64 ? 8 : 4), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && h_ids) e = hipMemcpy(h_ids, d_ids, npix * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("render_features_host: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_out);
-    if (d_ids) (void)hipFree(d_ids);
-    return rc;
+    const size_t bytes = npix * 8 * (out_is_f64 ? 8 : 4);
+    DevBuf<unsigned char> d_out;
+    DevBuf<int32_t> d_ids;
+    HIP_TRY(c, d_out.alloc(bytes));
+    if (h_ids) HIP_TRY(c, d_ids.alloc(npix * 2));
+    const int rc = gi_render_features_device(c, p, n_samples, d_out.p, out_is_f64, d_ids.p);
+    return rc != GI_OK ? rc : finish_to_host(c, "render_features_host", {{h_out, d_out.p, bytes}, to_host(h_ids, d_ids, npix * 2)}, &c->t_feat);
 }
 
 int gi_last_features_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    if (c->feat_pending) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_feat1));
-        HIP_TRY(c, hipEventElapsedTime(&c->feat_ms, c->ev_feat0, c->ev_feat1));
-        c->feat_pending = false;
-    }
-    *ms = c->feat_ms;
+    HIP_TRY(c, c->t_feat.read(ms));
     return GI_OK;
 }
 
-// ---- function-level entries: host in, host out
-#define GI_GRID(n) dim3((unsigned)(((n) + GI_BLOCK - 1) / GI_BLOCK)), dim3(GI_BLOCK)
+#include "gi_entries.inc"
 
-int gi_trace(gi_ctx* c, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res)
-{
-    if (!c || n < 0 || (n && (!rays || !hit || !ent || !res))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "trace: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_r, d_o;
-    DevBuf<int32_t> d_h, d_e;
-    HIP_TRY(c, d_r.upload(std::vector<double>(rays, rays + (size_t)n * 6)));
-    HIP_TRY(c, d_o.alloc((size_t)n * 8)); HIP_TRY(c, d_h.alloc(n)); HIP_TRY(c, d_e.alloc(n));
-    hipLaunchKernelGGL(k_trace, GI_GRID(n), 0, c->stream, c->S, n, d_r.p, d_h.p, d_e.p, d_o.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(hit, d_h.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(ent, d_e.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(res, d_o.p, (size_t)n * 64, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_visible(gi_ctx* c, int32_t n, const double* q, int32_t* vis)
-{
-    if (!c || n < 0 || (n && (!q || !vis))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_q;
-    DevBuf<int32_t> d_v;
-    HIP_TRY(c, d_q.upload(std::vector<double>(q, q + (size_t)n * 6)));
-    HIP_TRY(c, d_v.alloc(n));
-    hipLaunchKernelGGL(k_visible, GI_GRID(n), 0, c->stream, c->S, n, d_q.p, d_v.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(vis, d_v.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_visible_rays(gi_ctx* c, int32_t n, const double* rays, const double* mt, int32_t* vis)
-{
-    if (!c || n < 0 || (n && (!rays || !mt || !vis))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_r, d_m;
-    DevBuf<int32_t> d_v;
-    HIP_TRY(c, d_r.upload(std::vector<double>(rays, rays + (size_t)n * 6)));
-    HIP_TRY(c, d_m.upload(std::vector<double>(mt, mt + n)));
-    HIP_TRY(c, d_v.alloc(n));
-    hipLaunchKernelGGL(k_visible_rays, GI_GRID(n), 0, c->stream, c->S, n, d_r.p, d_m.p, d_v.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(vis, d_v.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_gather(gi_ctx* c, int32_t n, const double* q, double* res3, int32_t* n_cand)
-{
-    if (!c || n < 0 || (n && (!q || !res3))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "gather: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_q, d_r;
-    DevBuf<int32_t> d_n;
-    HIP_TRY(c, d_q.upload(std::vector<double>(q, q + (size_t)n * 6)));
-    HIP_TRY(c, d_r.alloc((size_t)n * 3)); HIP_TRY(c, d_n.alloc(n));
-    hipLaunchKernelGGL(k_gather, GI_GRID(n), 0, c->stream, c->S, n, d_q.p, d_r.p, d_n.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(res3, d_r.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-    if (n_cand) HIP_TRY(c, hipMemcpy(n_cand, d_n.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_radiance(gi_ctx* c, int32_t n, const double* rays, const uint32_t* stream, uint64_t seed, double* out3)
-{
-    if (!c || n < 0 || (n && (!rays || !stream || !out3))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "radiance: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_r, d_o;
-    DevBuf<uint32_t> d_s;
-    HIP_TRY(c, d_r.upload(std::vector<double>(rays, rays + (size_t)n * 6)));
-    HIP_TRY(c, d_s.upload(std::vector<uint32_t>(stream, stream + n)));
-    HIP_TRY(c, d_o.alloc((size_t)n * 3));
-    hipLaunchKernelGGL(k_radiance, GI_GRID(n), 0, c->stream, c->S, n, d_r.p, d_s.p, seed, d_o.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out3, d_o.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_emit_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed, double* photons_out, int32_t cap, int64_t* tries_out)
-{
-    if (!c || count < 0 || cap < 0 || (cap && !photons_out)) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "emit_photons: no scene uploaded");
-    const long long total = (long long)count * c->S.n_light;
-    if (tries_out) *tries_out = 0;
-    if (total == 0) return 0;
-    if (total > 0x7fffffffLL) return fail(c, GI_E_INVALID, "emit_photons: count too large");
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<PhotonOut> d_p;
-    DevBuf<int32_t> d_s, d_t;
-    HIP_TRY(c, d_p.alloc((size_t)total)); HIP_TRY(c, d_s.alloc((size_t)total)); HIP_TRY(c, d_t.alloc((size_t)total));
-    hipLaunchKernelGGL(k_emit, GI_GRID(total), 0, c->stream, c->S, count, max_depth, seed, d_p.p, d_s.p, d_t.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<PhotonOut> hp((size_t)total);
-    std::vector<int32_t> hs((size_t)total), ht((size_t)total);
-    HIP_TRY(c, hipMemcpy(hp.data(), d_p.p, (size_t)total * sizeof(PhotonOut), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(hs.data(), d_s.p, (size_t)total * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(ht.data(), d_t.p, (size_t)total * 4, hipMemcpyDeviceToHost));
-    // compaction in (photon index, light) order = the order one reference thread appends them (include/raytracer.h:593-706)
-    int stored = 0;
-    int64_t tries = 0;
-    for (long long j = 0; j < total; j++) {
-        tries += ht[(size_t)j];
-        if (!hs[(size_t)j]) continue;
-        if (stored < cap) memcpy(photons_out + (size_t)stored * 9, hp[(size_t)j].v, 72);
-        stored++;
-    }
-    if (tries_out) *tries_out = tries;
-    if (stored > cap) return fail(c, GI_E_INVALID, "emit_photons: output capacity too small");
-    return stored;
-}
-
-int gi_build_photon_map(gi_ctx* c, int32_t n, const double* photons, const double* box6)
-{
-    if (!c || n < 0 || (n && !photons)) return GI_E_INVALID;
-    c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "build_photon_map: no scene uploaded");
-    HIP_TRY(c, hipSetDevice(c->device));
-    double box[6];
-    for (int k = 0; k < 3; k++) { box[k] = box6 ? box6[k] : c->S.root_bmin[k]; box[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
-    DevBuf<double> d_ph;
-    if (n) HIP_TRY(c, d_ph.upload(std::vector<double>(photons, photons + (size_t)n * 9)));
-    return build_photon_map_on_device(c, d_ph.p, n, box);
-}
-
-int gi_trace_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed, const double* box6, int64_t* tries_out)
-{
-    if (!c || count < 0) return GI_E_INVALID;
-    c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "trace_photons: no scene uploaded");
-    const long long total = (long long)count * c->S.n_light;
-    if (tries_out) *tries_out = 0;
-    if (total > 0x7fffffffLL) return fail(c, GI_E_INVALID, "trace_photons: count too large");
-    HIP_TRY(c, hipSetDevice(c->device));
-    double box[6];
-    for (int k = 0; k < 3; k++) { box[k] = box6 ? box6[k] : c->S.root_bmin[k]; box[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
-    if (total == 0) { const int rc = build_photon_map_on_device(c, nullptr, 0, box); return rc < 0 ? rc : 0; }
-    DevBuf<PhotonOut> d_p;
-    DevBuf<int32_t> d_s, d_t, d_x;
-    HIP_TRY(c, d_p.alloc((size_t)total)); HIP_TRY(c, d_s.alloc((size_t)total)); HIP_TRY(c, d_t.alloc((size_t)total)); HIP_TRY(c, d_x.alloc((size_t)total));
-    hipLaunchKernelGGL(k_emit, GI_GRID(total), 0, c->stream, c->S, count, max_depth, seed, d_p.p, d_s.p, d_t.p);
-    // stored photons in (photon index, light) order = the order one reference thread appends them (include/raytracer.h:593-706)
-    HIP_TRY(c, hipMemcpyAsync(d_x.p, d_s.p, (size_t)total * 4, hipMemcpyDeviceToDevice, c->stream));
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, c->stream, reinterpret_cast<uint32_t*>(d_x.p), (uint32_t)total);   // exclusive prefix sums, in place (gi_sort.inc)
-    int32_t last_x = 0, last_s = 0;
-    HIP_TRY(c, hipMemcpyAsync(&last_x, d_x.p + (total - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(&last_s, d_s.p + (total - 1), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int32_t n = last_x + last_s;
-    if (tries_out) {      // total emission tries (diagnostic): summed on the host from the per-index counts
-        std::vector<int32_t> ht((size_t)total);
-        HIP_TRY(c, hipMemcpy(ht.data(), d_t.p, (size_t)total * 4, hipMemcpyDeviceToHost));
-        int64_t tries = 0;
-        for (int32_t v : ht) tries += v;
-        *tries_out = tries;
-    }
-    DevBuf<double> d_ph;
-    HIP_TRY(c, d_ph.alloc((size_t)std::max(n, 1) * 9));
-    hipLaunchKernelGGL(k_pb_compact_emitted, GI_GRID(total), 0, c->stream, d_p.p, d_s.p, d_x.p, (uint32_t)total, d_ph.p);
-    HIP_TRY(c, hipGetLastError());
-    const int rc = build_photon_map_on_device(c, d_ph.p, n, box);
-    return rc < 0 ? rc : n;
-}
-
-int gi_debug_photon_tables(gi_ctx* c, int32_t* n_node, int32_t* n_range, int32_t* n_photon, void* nodes128, int32_t* ranges2, double* pos3, double* dircol6)
-{
-    if (!c) return GI_E_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const Scene& S = c->S;
-    if (n_node) *n_node = S.n_pnode;
-    if (n_range) *n_range = S.n_pnode > 0 ? c->n_prange : 0;
-    if (n_photon) *n_photon = S.n_photon;
-    if (S.n_pnode <= 0) return GI_OK;
-    if (nodes128) HIP_TRY(c, hipMemcpy(nodes128, S.pnodes, (size_t)S.n_pnode * sizeof(PNode), hipMemcpyDeviceToHost));
-    if (ranges2) HIP_TRY(c, hipMemcpy(ranges2, S.pranges, (size_t)c->n_prange * sizeof(PRange), hipMemcpyDeviceToHost));
-    if (pos3 && S.n_photon) HIP_TRY(c, hipMemcpy(pos3, S.ph_pos, (size_t)S.n_photon * 24, hipMemcpyDeviceToHost));
-    if (dircol6 && S.n_photon) HIP_TRY(c, hipMemcpy(dircol6, S.ph_dircol, (size_t)S.n_photon * 48, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_debug_sort_pairs(gi_ctx* c, int32_t n, const uint32_t* keys, const uint32_t* vals, int32_t begin_bit, int32_t end_bit, uint32_t* keys_out, uint32_t* vals_out)
-{
-    if (!c || n < 0 || begin_bit < 0 || end_bit > 32 || end_bit <= begin_bit || (n && (!keys || !vals || !keys_out || !vals_out))) return GI_E_INVALID;
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<uint32_t> d[6], d_hist;
-    for (int k = 0; k < 6; k++) HIP_TRY(c, d[k].alloc((size_t)n));
-    HIP_TRY(c, d_hist.alloc((size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS));
-    HIP_TRY(c, hipMemcpy(d[0].p, keys, (size_t)n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(d[1].p, vals, (size_t)n * 4, hipMemcpyHostToDevice));
-    int rc = rs_sort_pairs(c, d[0].p, d[2].p, d[1].p, d[3].p, d[4].p, d[5].p, (uint32_t)n, nullptr, begin_bit, end_bit, d_hist.p);
-    if (rc) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(keys_out, d[2].p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(vals_out, d[3].p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_debug_find_leaves(gi_ctx* c, int32_t n, const double* pos, int32_t* fast_out, int32_t* full_out)
-{
-    if (!c || n < 0 || (n && (!pos || !fast_out || !full_out))) return GI_E_INVALID;
-    if (c->S.n_pnode <= 0) return fail(c, GI_E_STATE, "find_leaves: no photon map");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_p;
-    DevBuf<int32_t> d_a, d_b;
-    HIP_TRY(c, d_p.upload(std::vector<double>(pos, pos + (size_t)n * 3)));
-    HIP_TRY(c, d_a.alloc(n)); HIP_TRY(c, d_b.alloc(n));
-    hipLaunchKernelGGL(k_find_leaves, GI_GRID(n), 0, c->stream, c->S, n, d_p.p, d_a.p, d_b.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(fast_out, d_a.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(full_out, d_b.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_debug_gather_pass(gi_ctx* c, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2)
-{
-    if (!c || n < 0 || kernel < 0 || kernel > 3 || (n && (!q6 || !res3))) return GI_E_INVALID;
-    if (c->S.n_pnode <= 0) return fail(c, GI_E_STATE, "gather_pass: no photon map");
-    const bool wave = (kernel & 2) != 0, counting = (kernel & 1) != 0;
-    if (wave && !c->S.pcand) return fail(c, GI_E_STATE, "gather_pass: k_st_gather_wave needs the written-out candidate lists (off: GI_FLAT_CANDIDATES=0)");
-    if (counters2) counters2[0] = counters2[1] = 0;
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t N = (uint32_t)n;
-    DevBuf<unsigned char> d_pool;
-    DevBuf<unsigned long long> d_ss;
-    DevBuf<double> d_q, d_L;
-    DevBuf<uint32_t> d_k[2], d_v[2], d_t[2], d_hist;
-    DevBuf<StreamCounters> d_sc;
-    HIP_TRY(c, d_q.upload(std::vector<double>(q6, q6 + (size_t)n * 6)));
-    HIP_TRY(c, d_pool.alloc((size_t)N * GI_POOL_BYTES_PER_SLOT));
-    HIP_TRY(c, d_ss.alloc(N)); HIP_TRY(c, d_L.alloc((size_t)N * 3)); HIP_TRY(c, d_sc.alloc(1));
-    for (int k = 0; k < 2; k++) { HIP_TRY(c, d_k[k].alloc(N)); HIP_TRY(c, d_v[k].alloc(N)); HIP_TRY(c, d_t[k].alloc(N)); }
-    HIP_TRY(c, d_hist.alloc((size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS));
-    HIP_TRY(c, hipMemsetAsync(d_pool.p, 0, (size_t)N * GI_POOL_BYTES_PER_SLOT, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_L.p, 0, (size_t)N * 24, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_sc.p, 0, sizeof(StreamCounters), c->stream));
-    const PathPool pool = make_path_pool(d_pool.p, N);
-    hipLaunchKernelGGL(k_gather_pass_prep, GI_GRID(n), 0, c->stream, c->S, pool, n, d_q.p, d_ss.p, d_k[0].p, d_v[0].p);
-    HIP_TRY(c, hipGetLastError());
-    if (sort) {
-        int bits = 1;
-        while ((1u << bits) <= (uint32_t)c->S.n_pleaf) bits++;   // keys 0 .. n_pleaf, as stream_passes sorts them
-        const int rc = rs_sort_pairs(c, d_k[0].p, d_k[1].p, d_v[0].p, d_v[1].p, d_t[0].p, d_t[1].p, N, nullptr, 0, bits, d_hist.p);
-        if (rc) return rc;
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(d_k[1].p, d_k[0].p, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_v[1].p, d_v[0].p, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
-    }
-    launch_gather(c, wave, counting, pool, d_k[1].p, d_v[1].p, N, d_ss.p, 0ull, d_L.p, counting ? d_sc.p : nullptr);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(res3, d_L.p, (size_t)N * 24, hipMemcpyDeviceToHost));
-    if (keys_out) HIP_TRY(c, hipMemcpy(keys_out, d_k[1].p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (order_out) HIP_TRY(c, hipMemcpy(order_out, d_v[1].p, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (counters2 && counting) {
-        StreamCounters h;
-        HIP_TRY(c, hipMemcpy(&h, d_sc.p, sizeof h, hipMemcpyDeviceToHost));
-        counters2[0] = (int64_t)h.gather_queries; counters2[1] = (int64_t)h.gather_cand;
-    }
-    return GI_OK;
-}
-
-int gi_debug_leaf_order(gi_ctx* c, int32_t n, const double* rays, int32_t cap, int32_t* leaf_out, int32_t* n_out)
-{
-    if (!c || n < 0 || cap < 1 || (n && (!rays || !leaf_out || !n_out))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "leaf_order: no scene uploaded");
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_r;
-    DevBuf<int32_t> d_l, d_n;
-    HIP_TRY(c, d_r.upload(std::vector<double>(rays, rays + (size_t)n * 6)));
-    HIP_TRY(c, d_l.alloc((size_t)n * cap)); HIP_TRY(c, d_n.alloc(n));
-    HIP_TRY(c, hipMemsetAsync(d_l.p, 0xff, (size_t)n * cap * 4, c->stream));
-    hipLaunchKernelGGL(k_leaf_order, GI_GRID(n), 0, c->stream, c->S, n, d_r.p, cap, d_l.p, d_n.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(leaf_out, d_l.p, (size_t)n * cap * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(n_out, d_n.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_kat(gi_ctx* c, int32_t what, int32_t n, const double* in, int32_t in_stride, double* out3)
-{
-    if (!c || n < 0 || in_stride < 1 || in_stride > 9 || (n && (!in || !out3))) return GI_E_INVALID;
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<double> d_i, d_o;
-    HIP_TRY(c, d_i.upload(std::vector<double>(in, in + (size_t)n * in_stride)));
-    HIP_TRY(c, d_o.alloc((size_t)n * 3));
-    hipLaunchKernelGGL(k_kat, GI_GRID(n), 0, c->stream, what, n, d_i.p, in_stride, d_o.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out3, d_o.p, (size_t)n * 24, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_halton_sample(gi_ctx* c, int32_t n, const uint32_t* dim, const uint32_t* index, float* out)
-{
-    if (!c || n < 0 || (n && (!dim || !index || !out))) return GI_E_INVALID;
-    if (n == 0) return GI_OK;
-    for (int i = 0; i < n; i++) if (dim[i] > 255) return fail(c, GI_E_INVALID, "halton_sample: dimension > 255");
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<uint32_t> d_d, d_i;
-    DevBuf<float> d_o;
-    HIP_TRY(c, d_d.upload(std::vector<uint32_t>(dim, dim + n)));
-    HIP_TRY(c, d_i.upload(std::vector<uint32_t>(index, index + n)));
-    HIP_TRY(c, d_o.alloc(n));
-    hipLaunchKernelGGL(k_halton, GI_GRID(n), 0, c->stream, c->S, n, d_d.p, d_i.p, d_o.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, d_o.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-int gi_halton_index(gi_ctx* c, int32_t width, int32_t height, int32_t n, const uint32_t* sxy, uint32_t* out)
-{
-    if (!c || width <= 0 || height <= 0 || n < 0 || (n && (!sxy || !out))) return GI_E_INVALID;
-    if (n == 0) return GI_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf<uint32_t> d_i, d_o;
-    HIP_TRY(c, d_i.upload(std::vector<uint32_t>(sxy, sxy + (size_t)n * 3)));
-    HIP_TRY(c, d_o.alloc(n));
-    hipLaunchKernelGGL(k_halton_index, GI_GRID(n), 0, c->stream, make_halton_enum((unsigned)width, (unsigned)height), n, d_i.p, d_o.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out, d_o.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return GI_OK;
-}
-
-// ================================================================================================= several GPUs from one process
-// The reference parallelises RayTracer::run over image rows with OpenMP (include/raytracer.h:93).  A group does the same over the GPUs of a
-// node from ONE process (the Qt application): one context and one host thread per device, the frame's stripes dealt round-robin, the scene
-// and photon tables replicated, the finished stripes gathered into one frame -- on device 0 through peer copies over xGMI
-// (gi_group_render_device) or straight into the caller's host frame (gi_group_render_host).
-struct gi_group {
-    std::vector<gi_ctx*> ctx;
-    std::vector<void*> d_part;          // per device: its stripes, compact [local_rows][w][3]
-    std::vector<size_t> part_bytes;
-    std::vector<int32_t*> d_spp;
-    std::vector<size_t> spp_bytes;
-    std::string err;
-};
-}  // extern "C" (C++ helpers below)
-#include <thread>
-namespace {
-int group_fail(gi_group* g, int code, const std::string& m) { if (g) g->err = m; return code; }
-}
-extern "C" {
-
-int gi_device_count(void)
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-
-int gi_group_create(gi_group** out, int32_t n_devices, const int32_t* device_ordinals)
-{
-    if (!out || n_devices < 0) return GI_E_INVALID;
-    *out = nullptr;
-    int visible = 0;
-    if (hipGetDeviceCount(&visible) != hipSuccess || visible <= 0) return GI_E_NO_DEVICE;
-    if (n_devices == 0) n_devices = visible;
-    gi_group* g = new gi_group();
-    for (int i = 0; i < n_devices; i++) {
-        gi_ctx* c = nullptr;
-        const int rc = gi_create(&c, device_ordinals ? device_ordinals[i] : i);
-        if (rc != GI_OK) { for (gi_ctx* k : g->ctx) gi_destroy(k); delete g; return rc; }
-        g->ctx.push_back(c);
-    }
-    g->d_part.assign((size_t)n_devices, nullptr); g->part_bytes.assign((size_t)n_devices, 0);
-    g->d_spp.assign((size_t)n_devices, nullptr); g->spp_bytes.assign((size_t)n_devices, 0);
-    // peer access towards device 0 for the xGMI gather (ignored where it is the same device or already enabled)
-    for (int i = 1; i < n_devices; i++) {
-        if (g->ctx[(size_t)i]->device == g->ctx[0]->device) continue;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, g->ctx[(size_t)i]->device, g->ctx[0]->device) == hipSuccess && can) {
-            (void)hipSetDevice(g->ctx[(size_t)i]->device);
-            (void)hipDeviceEnablePeerAccess(g->ctx[0]->device, 0);
-            (void)hipGetLastError();
-        }
-    }
-    *out = g;
-    return GI_OK;
-}
-
-void gi_group_destroy(gi_group* g)
-{
-    if (!g) return;
-    for (size_t i = 0; i < g->ctx.size(); i++) {
-        (void)hipSetDevice(g->ctx[i]->device);
-        if (g->d_part[i]) (void)hipFree(g->d_part[i]);
-        if (g->d_spp[i]) (void)hipFree(g->d_spp[i]);
-        gi_destroy(g->ctx[i]);
-    }
-    delete g;
-}
-
-int gi_group_size(const gi_group* g) { return g ? (int)g->ctx.size() : 0; }
-gi_ctx* gi_group_ctx(gi_group* g, int32_t i) { return (g && i >= 0 && i < (int)g->ctx.size()) ? g->ctx[(size_t)i] : nullptr; }
-const char* gi_group_last_error(const gi_group* g) { return g ? g->err.c_str() : "null group"; }
-
-int gi_group_upload_scene(gi_group* g, const gi_scene_desc* d)
-{
-    if (!g) return GI_E_INVALID;
-    for (gi_ctx* c : g->ctx) { const int rc = gi_upload_scene(c, d); if (rc) return group_fail(g, rc, gi_last_error(c)); }
-    return GI_OK;
-}
-int gi_group_clear_photons(gi_group* g)
-{
-    if (!g) return GI_E_INVALID;
-    for (gi_ctx* c : g->ctx) gi_clear_photons(c);
-    return GI_OK;
-}
-int gi_group_upload_photons(gi_group* g, const gi_photon_map_desc* d)
-{
-    if (!g) return GI_E_INVALID;
-    for (gi_ctx* c : g->ctx) { const int rc = gi_upload_photons(c, d); if (rc) return group_fail(g, rc, gi_last_error(c)); }
-    return GI_OK;
-}
-
-// Stripes [first_stripe, first_stripe + n_stripes) of the frame (cut into stripes of stripe_h rows), stripe s on device (s - first_stripe) % n.
-// Every device renders on its own host thread; `sink(i, ctx, rp, d_part, d_spp)` then moves device i's stripes where they belong.
-static int group_render(gi_group* g, const gi_render_params* p, int32_t stripe_h, int32_t first_stripe, int32_t n_stripes, int out_is_f64, bool want_spp, volatile const int* cancel,
-                        const std::function<int(int, gi_ctx*, const gi_render_params&, int32_t /*stripe of the call or -1 = all of this device's*/, const void*, const int32_t*)>& sink)
-{
-    if (!g || !p || stripe_h <= 0 || p->width <= 0 || p->height <= 0) return GI_E_INVALID;
-    const int n = (int)g->ctx.size();
-    const int total = (p->height + stripe_h - 1) / stripe_h;
-    if (first_stripe < 0 || n_stripes < 0 || first_stripe + n_stripes > total) return group_fail(g, GI_E_INVALID, "group render: stripe window outside the frame");
-    const bool whole = first_stripe == 0 && n_stripes == total;
-    const size_t px = (size_t)(out_is_f64 ? 8 : 4) * 3;
-    std::vector<int> rcs((size_t)n, GI_OK);
-    std::vector<std::thread> th;
-    for (int i = 0; i < n; i++)
-        th.emplace_back([&, i]() {
-            gi_ctx* c = g->ctx[(size_t)i];
-            if (hipSetDevice(c->device) != hipSuccess) { rcs[(size_t)i] = GI_E_HIP; return; }
-            gi_render_params rp = *p;
-            rp.stripe_h = stripe_h;
-            // whole frame: one call renders all stripes of this device (rank i of n); a window: one call per stripe (rank = the stripe, world = all)
-            std::vector<int32_t> calls;
-            if (whole) { if (i < total) calls.push_back(-1); }
-            else for (int32_t s = first_stripe + i; s < first_stripe + n_stripes; s += n) calls.push_back(s);
-            for (int32_t s : calls) {
-                rp.stripe_rank = s < 0 ? i : s;
-                rp.stripe_world = s < 0 ? n : total;
-                const size_t rows = (size_t)gi_local_rows(&rp);
-                if (rows == 0) continue;
-                const size_t need = rows * (size_t)p->width * px, need_spp = want_spp ? rows * (size_t)p->width * 4 : 0;
-                if (g->part_bytes[(size_t)i] < need) {
-                    if (g->d_part[(size_t)i]) (void)hipFree(g->d_part[(size_t)i]);
-                    g->d_part[(size_t)i] = nullptr; g->part_bytes[(size_t)i] = 0;
-                    if (hipMalloc(&g->d_part[(size_t)i], need) != hipSuccess) { rcs[(size_t)i] = GI_E_HIP; c->err = "group render: hipMalloc of the stripe buffer"; return; }
-                    g->part_bytes[(size_t)i] = need;
-                }
-                if (g->spp_bytes[(size_t)i] < need_spp) {
-                    if (g->d_spp[(size_t)i]) (void)hipFree(g->d_spp[(size_t)i]);
-                    g->d_spp[(size_t)i] = nullptr; g->spp_bytes[(size_t)i] = 0;
-                    if (hipMalloc((void**)&g->d_spp[(size_t)i], need_spp) != hipSuccess) { rcs[(size_t)i] = GI_E_HIP; c->err = "group render: hipMalloc of the sample-count buffer"; return; }
-                    g->spp_bytes[(size_t)i] = need_spp;
-                }
-                int rc = gi_render_device(c, &rp, g->d_part[(size_t)i], out_is_f64, want_spp ? g->d_spp[(size_t)i] : nullptr, cancel);
-                if (rc == GI_OK) rc = sink(i, c, rp, s, g->d_part[(size_t)i], want_spp ? g->d_spp[(size_t)i] : nullptr);
-                if (rc == GI_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = GI_E_HIP;
-                if (rc != GI_OK) { rcs[(size_t)i] = rc; return; }
-            }
-        });
-    for (std::thread& t : th) t.join();
-    for (int i = 0; i < n; i++)
-        if (rcs[(size_t)i] != GI_OK) return group_fail(g, rcs[(size_t)i], std::string("device ") + std::to_string(g->ctx[(size_t)i]->device) + ": " + g->ctx[(size_t)i]->err);
-    return GI_OK;
-}
-
-// rows of the frame held by a call's compact buffer, as (frame row of the block, rows, local row of the block)
-static void stripe_blocks(const gi_render_params& rp, std::vector<std::array<int, 3>>& out)
-{
-    const int total = (rp.height + rp.stripe_h - 1) / rp.stripe_h;
-    int local = 0;
-    for (int k = rp.stripe_rank; k < total; k += rp.stripe_world) {
-        const int rows = std::min(rp.stripe_h, rp.height - k * rp.stripe_h);
-        out.push_back({k * rp.stripe_h, rows, local});
-        local += rows;
-    }
-}
-
-int gi_group_render_host(gi_group* g, const gi_render_params* p, int32_t stripe_h, int32_t first_stripe, int32_t n_stripes, void* h_frame, int out_is_f64, int32_t* h_spp, volatile const int* cancel)
-{
-    if (!h_frame) return GI_E_INVALID;
-    const size_t px = (size_t)(out_is_f64 ? 8 : 4) * 3;
-    return group_render(g, p, stripe_h, first_stripe, n_stripes, out_is_f64, h_spp != nullptr, cancel,
-                        [&](int, gi_ctx* c, const gi_render_params& rp, int32_t, const void* d_part, const int32_t* d_spp) -> int {
-                            std::vector<std::array<int, 3>> blocks;
-                            stripe_blocks(rp, blocks);
-                            if (hipStreamSynchronize(c->stream) != hipSuccess) return GI_E_HIP;
-                            for (const auto& b : blocks) {     // every device writes its own rows of the caller's frame
-                                const size_t w = (size_t)rp.width;
-                                if (hipMemcpy((char*)h_frame + (size_t)b[0] * w * px, (const char*)d_part + (size_t)b[2] * w * px, (size_t)b[1] * w * px, hipMemcpyDeviceToHost) != hipSuccess) return GI_E_HIP;
-                                if (h_spp && hipMemcpy(h_spp + (size_t)b[0] * w, d_spp + (size_t)b[2] * w, (size_t)b[1] * w * 4, hipMemcpyDeviceToHost) != hipSuccess) return GI_E_HIP;
-                            }
-                            return GI_OK;
-                        });
-}
-
-int gi_group_render_device(gi_group* g, const gi_render_params* p, int32_t stripe_h, void* d_frame_on_device0, int out_is_f64, volatile const int* cancel)
-{
-    if (!g || !p || !d_frame_on_device0) return GI_E_INVALID;
-    const size_t px = (size_t)(out_is_f64 ? 8 : 4) * 3;
-    const int dev0 = g->ctx[0]->device;
-    const int total = stripe_h > 0 ? (p->height + stripe_h - 1) / stripe_h : 0;
-    return group_render(g, p, stripe_h, 0, total, out_is_f64, false, cancel,
-                        [&](int, gi_ctx* c, const gi_render_params& rp, int32_t, const void* d_part, const int32_t*) -> int {
-                            std::vector<std::array<int, 3>> blocks;
-                            stripe_blocks(rp, blocks);
-                            for (const auto& b : blocks) {     // the gather: this device's stripes into the frame on device 0, over xGMI when the devices differ
-                                const size_t w = (size_t)rp.width;
-                                void* dst = (char*)d_frame_on_device0 + (size_t)b[0] * w * px;
-                                const void* src = (const char*)d_part + (size_t)b[2] * w * px;
-                                const hipError_t e = c->device == dev0 ? hipMemcpyAsync(dst, src, (size_t)b[1] * w * px, hipMemcpyDeviceToDevice, c->stream)
-                                                                       : hipMemcpyPeerAsync(dst, dev0, src, c->device, (size_t)b[1] * w * px, c->stream);
-                                if (e != hipSuccess) return GI_E_HIP;
-                            }
-                            return GI_OK;
-                        });
-}
+#include "gi_group.inc"
 
 }  // extern "C"

@@ -58,6 +58,52 @@ struct HostPhotons {
     bool planes_ok = true;            // inner records' planes reproduce every child box (gather_find_leaf's one-record-per-level walk)
 };
 
+// The Scene fields that follow the switches.  SceneTables: the tables of the scene and photon map last uploaded, wherever they live (device memory in
+// gi_kernels.hip, the HostScene vectors in tests/host_emul) and what layout_scene / layout_photons said about them; S.n_wnode and S.cuse are set.
+struct SceneTables {
+    const WNode* wnodes = nullptr;
+    const float* cboxes = nullptr;  size_t n_cboxes = 0;
+    const double* leaf_boxes = nullptr;
+    const double* trace_boxes = nullptr;
+    const float* tcboxes = nullptr; size_t n_tcboxes = 0;
+    const uint32_t* tcuse = nullptr;
+    double cut_margin = -1;           // HostScene's
+    bool clipped = false, lights_clear = false;
+    bool pn_planes_ok = false;        // HostPhotons::planes_ok of a map in use
+    const PDescent* pdescent = nullptr;   // the fast descent of the gather keys and its jump table, where they were built for the current map
+    const int32_t* pjump = nullptr;
+};
+struct SceneSwitches {
+    bool wide = true;                 // gi_set_wide_nodes
+    bool cull = true;                 // gi_set_content_culling
+    bool entity_boxes = true;         // gi_set_entity_boxes, GI_ENTITY_BOXES=0: every entity of a leaf is tested, as the reference does
+    bool clip_boxes = true;           // GI_CLIP_BOXES=0: the closest-hit walk uses the entities' whole boxes
+    bool walk_cut = true;             // GI_WALK_CUT=0: the closest-hit walk goes on behind its best hit, as the reference does
+};
+inline void apply_scene_switches(Scene& S, const SceneTables& T, const SceneSwitches& sw)
+{
+    S.wnodes = (sw.wide && S.n_wnode > 0) ? T.wnodes : nullptr;
+    S.cboxes = (sw.cull && S.wnodes && T.n_cboxes > 1) ? T.cboxes : nullptr;
+    // Which of the walks' short cuts are on (all of them leave every result as it is: DESIGN.md section 4): entity boxes; for the closest-hit walk
+    // the boxes cut to the leaves, and no look behind the best hit.  Entity boxes off turns all three off: the walks then ask what the reference asks.
+    const bool clip = sw.entity_boxes && sw.clip_boxes && T.clipped;
+    S.leaf_boxes = sw.entity_boxes ? T.leaf_boxes : nullptr;
+    S.trace_boxes = !sw.entity_boxes ? nullptr : (clip ? T.trace_boxes : T.leaf_boxes);
+    S.cut_margin = (sw.entity_boxes && sw.walk_cut) ? T.cut_margin : -1.0;
+    const bool cut_to_leaves = clip && S.cboxes && T.n_tcboxes == T.n_cboxes;
+    S.tcboxes = cut_to_leaves ? T.tcboxes : S.cboxes;
+    S.tcuse = cut_to_leaves ? T.tcuse : S.cuse;
+    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks)
+    const bool sh = T.lights_clear && clip;
+    S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
+    S.scboxes = sh ? S.tcboxes : S.cboxes;
+    S.scuse = sh ? S.tcuse : S.cuse;
+    // the photon octree's counterpart of the wide records (gather_find_leaf), and the fast descent of the gather keys over it
+    S.pn_planes = (sw.wide && T.pn_planes_ok) ? 1 : 0;
+    S.pdescent = S.pn_planes ? T.pdescent : nullptr;
+    S.pjump = S.pdescent ? T.pjump : nullptr;
+}
+
 // Faure permutations and per-base digit-group tables of Halton_sampler (include/halton_sampler.h:573-603,890-1414).
 inline void build_halton_tables(std::vector<HaltonDim>& dims, std::vector<uint16_t>& table)
 {

@@ -163,17 +163,16 @@ int gi_upsample_device(gi_ctx* c, const gi_upsample_params* p, const void* d_low
                        const void* d_features, int features_is_f64, void* d_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
+    c->t_up.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!d_low_color || !d_low_features || !d_features || !d_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
     const size_t n_pix = (size_t)p->width * (size_t)p->height, n_low = (size_t)p->low_width * (size_t)p->low_height;
     if (n_pix > ((size_t)1 << 28)) return fail(c, GI_E_INVALID, "upsample: frames beyond 2^28 pixels are not supported");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->up_ms = 0; c->up_pending = false;
-    if (!c->ev_up0) { HIP_TRY(c, hipEventCreate(&c->ev_up0)); HIP_TRY(c, hipEventCreate(&c->ev_up1)); }
     const int rc = dn_reserve(c, n_low);
     if (rc != GI_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_up0, c->stream));
+    HIP_TRY(c, c->t_up.begin(c->stream));
     const int demod = p->demodulate != 0;
     hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((n_low * 8 + 255) / 256)), dim3(256), 0, c->stream, n_low, d_low_color, low_color_is_f64, d_low_features, low_features_is_f64, demod,
                        c->d_dn_a.p, c->d_dn_guides.p);
@@ -186,8 +185,7 @@ int gi_upsample_device(gi_ctx* c, const gi_upsample_params* p, const void* d_low
     hipLaunchKernelGGL(k_up_sample, dim3((unsigned)((size_t)G.tiles_x * tiles_y)), dim3(GI_UP_BLOCK), 0, c->stream, G, inv, c->d_dn_a.p, c->d_dn_guides.p, d_features, features_is_f64,
                        demod, d_out, out_is_f64);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_up1, c->stream));
-    c->up_pending = true;
+    HIP_TRY(c, c->t_up.end(c->stream));
     return GI_OK;
 }
 
@@ -195,43 +193,27 @@ int gi_upsample_host(gi_ctx* c, const gi_upsample_params* p, const void* h_low_c
                      const void* h_features, int features_is_f64, void* h_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
+    c->t_up.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!h_low_color || !h_low_features || !h_features || !h_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n_pix = (size_t)p->width * (size_t)p->height, n_low = (size_t)p->low_width * (size_t)p->low_height;
     const size_t cb = n_low * 3 * (low_color_is_f64 ? 8 : 4), lb = n_low * 8 * (low_features_is_f64 ? 8 : 4), fb = n_pix * 8 * (features_is_f64 ? 8 : 4), ob = n_pix * 3 * (out_is_f64 ? 8 : 4);
-    void *d_color = nullptr, *d_low = nullptr, *d_feat = nullptr, *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_color, cb);
-    if (e == hipSuccess) e = hipMalloc(&d_low, lb);
-    if (e == hipSuccess) e = hipMalloc(&d_feat, fb);
-    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-    if (e == hipSuccess) e = hipMemcpy(d_color, h_low_color, cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_low, h_low_features, lb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_feat, h_features, fb, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? GI_OK : fail(c, GI_E_HIP, std::string("upsample_host: ") + hipGetErrorString(e));
-    if (rc == GI_OK) rc = gi_upsample_device(c, p, d_color, low_color_is_f64, d_low, low_features_is_f64, d_feat, features_is_f64, d_out, out_is_f64);
-    if (rc == GI_OK) {
-        e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(h_out, d_out, ob, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(c, GI_E_HIP, std::string("upsample_host: ") + hipGetErrorString(e));
-    }
-    if (d_color) (void)hipFree(d_color);
-    if (d_low) (void)hipFree(d_low);
-    if (d_feat) (void)hipFree(d_feat);
-    if (d_out) (void)hipFree(d_out);
-    return rc;
+    DevBuf<unsigned char> d_color, d_low, d_feat, d_out;
+    hipError_t e = d_color.upload((const unsigned char*)h_low_color, cb);
+    if (e == hipSuccess) e = d_low.upload((const unsigned char*)h_low_features, lb);
+    if (e == hipSuccess) e = d_feat.upload((const unsigned char*)h_features, fb);
+    if (e == hipSuccess) e = d_out.alloc(ob);
+    if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("upsample_host: ") + hipGetErrorString(e));
+    const int rc = gi_upsample_device(c, p, d_color.p, low_color_is_f64, d_low.p, low_features_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
+    return rc != GI_OK ? rc : finish_to_host(c, "upsample_host", {{h_out, d_out.p, ob}}, &c->t_up);
 }
 
 int gi_last_upsample_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    if (c->up_pending) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_up1));
-        HIP_TRY(c, hipEventElapsedTime(&c->up_ms, c->ev_up0, c->ev_up1));
-        c->up_pending = false;
-    }
-    *ms = c->up_ms;
+    HIP_TRY(c, c->t_up.read(ms));
     return GI_OK;
 }
 

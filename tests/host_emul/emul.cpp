@@ -23,31 +23,29 @@ struct Emul {
     {
         S.tnodes = hs.tnodes.data(); S.leaf_refs = hs.refs.data(); S.leaf_tris = hs.leaf_tris.data(); S.tris = hs.tris.data(); S.shade = hs.shade.data();
         S.mats = hs.mats.data(); S.lights = hs.lights.data();
-        auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };   // the product's knobs (gi_kernels.hip: set_walk_shortcuts)
-        S.leaf_boxes = off("GI_ENTITY_BOXES") ? nullptr : hs.leaf_boxes.data();
-        S.trace_boxes = !S.leaf_boxes ? nullptr : ((off("GI_CLIP_BOXES") || !hs.clipped) ? hs.leaf_boxes.data() : hs.trace_boxes.data());
-        S.cut_margin = (S.leaf_boxes && !off("GI_WALK_CUT")) ? hs.cut_margin : -1.0;
         S.n_node = hs.n_node; S.n_tri = hs.n_tri; S.n_light = hs.n_light; S.has_spheres = 1;
         if (!hs.tnodes.empty()) for (int k = 0; k < 3; k++) { S.root_bmin[k] = hs.tnodes[0].bmin[k]; S.root_bmax[k] = hs.tnodes[0].bmax[k]; }
         S.n_wnode = (int32_t)hs.wnodes.size();
-        S.wnodes = (wide && S.n_wnode > 0) ? hs.wnodes.data() : nullptr;
         S.wleaf_id = hs.wleaf_id.data();
-        S.cboxes = (cull && S.wnodes && hs.cboxes.size() > 1) ? hs.cboxes.data() : nullptr;
         S.cuse = hs.cuse.data();
-        const bool cut_to_leaves = S.cboxes && S.trace_boxes == hs.trace_boxes.data() && hs.tcboxes.size() == hs.cboxes.size();   // (gi_kernels.hip: set_walk_shortcuts)
-        S.tcboxes = cut_to_leaves ? hs.tcboxes.data() : S.cboxes;
-        S.tcuse = cut_to_leaves ? hs.tcuse.data() : S.cuse;
-        const bool sh = hs.lights_clear && S.trace_boxes == hs.trace_boxes.data();
-        S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
-        S.scboxes = sh ? S.tcboxes : S.cboxes;
-        S.scuse = sh ? S.tcuse : S.cuse;
         S.tri_uv = hs.tri_uv.data(); S.texs = hs.texs.data(); S.tex_pixels = hs.tex_pixels.data(); S.tex_lut = hs.tex_lut.data(); S.n_tex = hs.n_tex();
         S.fogs = hs.fogs.data(); S.fog_grid = hs.fog_grid.data(); S.n_fog = hs.n_fog();
         for (int k = 0; k < 3; k++) S.ambient[k] = hs.ambient[k];
         S.pnodes = hp.nodes.data(); S.pranges = hp.ranges.data(); S.ph_pos = hp.pos.data(); S.ph_dircol = hp.dircol.data();
         S.n_pnode = hp.n_node; S.n_photon = hp.n_photon;
-        S.pn_planes = (wide && hp.planes_ok) ? 1 : 0;
         S.hdims = hdims.data(); S.htable = htable.data();
+        // what the switches show the walks: the product's rule (gi_layout.h), over the host tables; the product's knobs
+        auto off = [](const char* name) { const char* e = getenv(name); return e && atoi(e) == 0; };
+        SceneTables T;
+        T.wnodes = hs.wnodes.data(); T.cboxes = hs.cboxes.data(); T.n_cboxes = hs.cboxes.size();
+        T.leaf_boxes = hs.leaf_boxes.data(); T.trace_boxes = hs.trace_boxes.data();
+        T.tcboxes = hs.tcboxes.data(); T.n_tcboxes = hs.tcboxes.size(); T.tcuse = hs.tcuse.data();
+        T.cut_margin = hs.cut_margin; T.clipped = hs.clipped; T.lights_clear = hs.lights_clear;
+        T.pn_planes_ok = hp.planes_ok;
+        SceneSwitches sw;
+        sw.wide = wide; sw.cull = cull;
+        sw.entity_boxes = !off("GI_ENTITY_BOXES"); sw.clip_boxes = !off("GI_CLIP_BOXES"); sw.walk_cut = !off("GI_WALK_CUT");
+        apply_scene_switches(S, T, sw);
     }
 };
 
@@ -57,6 +55,19 @@ Emul* emul_create() { Emul* e = new Emul(); build_halton_tables(e->hdims, e->hta
 void emul_destroy(Emul* e) { delete e; }
 int emul_set_wide(Emul* e, int on) { e->wide = on != 0; e->bind(); return (e->S.wnodes != nullptr ? 1 : 0) | (e->S.pn_planes ? 2 : 0); }
 int emul_set_cull(Emul* e, int on) { e->cull = on != 0; e->bind(); return e->S.cboxes != nullptr ? 1 : 0; }
+// which table every Scene field that follows the switches points at (tests/test_scene_views.py): 0 none, 1 wnodes, 2 cboxes, 3 cuse, 4 leaf_boxes,
+// 5 trace_boxes, 6 tcboxes, 7 tcuse, -1 something else; ids10 = wnodes, cboxes, leaf_boxes, trace_boxes, tcboxes, tcuse, shadow_boxes, scboxes, scuse, pn_planes (as it is)
+void emul_scene_views(Emul* e, int32_t* ids10, double* cut_margin)
+{
+    const HostScene& hs = e->hs;
+    const void* tables[7] = {hs.wnodes.data(), hs.cboxes.data(), hs.cuse.data(), hs.leaf_boxes.data(), hs.trace_boxes.data(), hs.tcboxes.data(), hs.tcuse.data()};
+    auto id = [&](const void* p) { if (!p) return 0; for (int k = 0; k < 7; k++) if (p == tables[k]) return k + 1; return -1; };
+    const Scene& S = e->S;
+    const void* views[9] = {S.wnodes, S.cboxes, S.leaf_boxes, S.trace_boxes, S.tcboxes, S.tcuse, S.shadow_boxes, S.scboxes, S.scuse};
+    for (int k = 0; k < 9; k++) ids10[k] = id(views[k]);
+    ids10[9] = S.pn_planes;
+    *cut_margin = S.cut_margin;
+}
 const char* emul_error(Emul* e) { return e->err.c_str(); }
 int emul_upload_scene(Emul* e, const gi_scene_desc* d)
 {
