@@ -951,10 +951,13 @@ GI_HD bool trace_wide_begin(const Scene& S, const WN& W, const Ray& ray, TraceWa
 //  * the reference ends a walk only when the best hit lies inside the leaf it was found from; a hit found from an earlier leaf (a large
 //    entity sticks out of it) lets it walk on to the end of the ray, testing entities that cannot win (it takes a hit only when it is
 //    strictly nearer).  Here nothing that begins more than `cut_margin` behind the best hit is looked at: nodes, leaves, entities.
-//  * trace_boxes: for an opaque entity of a scene without textures, the box of the part of it INSIDE the leaf (widened): a hit outside the
+//  * trace_boxes: for an entity of a scene without textures, the box of the part of it INSIDE the leaf (widened): a hit outside the
 //    leaf is found again from the leaf it lies in, with the same arithmetic, so asking for it here only brings the answer forward.
 // Both widen by 1e-5 of the scene, a hundred times what the float arithmetic of the tree builder can misplace an entity by.  What the second
 // could change is WHICH of two entities at exactly the same distance is met first; such a walk (t.tie) is made again the plain way.
+// Both hold only while no entity of the scene has an alpha test (flag 2 clear): that test draws per (leaf, entity), so an entity that failed from
+// an early leaf is drawn again from every later leaf that refers to it and may win there with a NEARER hit -- behind the cut, or behind the point
+// where a leaf-cut opaque box ends the walk.  layout_scene gives such a scene cut_margin = -1 and trace_boxes == leaf_boxes (gi_layout.h).
 template <class WN>
 GI_HD bool trace_wide_over(const Scene& S, const WN& W, const Ray& ray, TraceWalk& t)   // the walk ended: true when it has to be made again
 {

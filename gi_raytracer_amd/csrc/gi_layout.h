@@ -29,8 +29,8 @@ struct HostScene {
     std::vector<LeafTri> leaf_tris;
     std::vector<double> leaf_boxes;   // [n_refs][6] the entity's own box, widened (gi_device.h: entity_box_missed), parallel to leaf_tris
     std::vector<double> trace_boxes;  // [n_refs][6] for the closest-hit walk: the box of the part of an opaque entity inside its leaf (gi_device.h: trace_wide_step)
-    double cut_margin = -1;           // what the closest-hit walk's short cuts allow for rounding (1e-5 of the scene)
-    bool clipped = false;             // trace_boxes differs from leaf_boxes
+    double cut_margin = -1;           // what the closest-hit walk's short cuts allow for rounding (1e-5 of the scene); -1 where an entity has an alpha test
+    bool clipped = false;             // trace_boxes differs from leaf_boxes (never with textures or an alpha-tested entity in the scene)
     bool lights_clear = false;        // no entity's box within a light's radius + twice the shadow bias (+ 4 margins) of the light: nothing can block a shadow segment in its last stretch
     std::vector<float> tcboxes;       // content boxes made of the trace boxes: what the closest-hit walk culls by (like cboxes; empty when !clipped)
     std::vector<uint32_t> tcuse;
@@ -451,14 +451,20 @@ inline bool layout_scene(const gi_scene_desc* d, HostScene& H, std::string& err)
         // The closest-hit walk's boxes: the part of the entity inside the leaf that refers to it.  The tree builder decides in float arithmetic which
         // leaves an entity overlaps (relative error 1e-7 of the coordinates), so the leaf is taken 1e-5 of the scene larger before the entity
         // is cut to it, and the box of what is left is widened by as much again: a hit point within rounding of a leaf is never refused there.
-        // Entities with an alpha test keep their whole box (the test draws per leaf: include/raytracer.h:455), and so does everything in a
-        // scene with textures (a hit leaves its uv behind for the next entity's alpha look-up).
+        // Both short cuts of the closest-hit walk (this one and `cut_margin`: no look behind the best hit) take for granted that an entity asked from a
+        // later leaf cannot yield a strictly nearer hit.  An entity with an alpha test (flag 2 clear) breaks that: the test draws per (leaf, entity)
+        // (include/raytracer.h:455), so one that failed its draw from an early leaf is drawn again from every later leaf that refers to it and may win
+        // there, nearer than the best hit so far -- and the reference walks on to the end of the ray unless the best hit lies inside the leaf it was found
+        // from.  Cutting only the OPAQUE entities of such a scene is wrong too: it moves the point where the walk ends in front of that later draw.
+        // So a scene with any alpha-tested entity gets neither: cut_margin = -1, whole boxes, no tcboxes.  Everything in a scene with textures keeps
+        // its whole box as well (a hit leaves its uv behind for the next entity's alpha look-up).
         const double wide = 1e-5 * std::max(std::max(extent, reach), 1e-3);
-        H.cut_margin = wide;
+        const bool alpha_tested = [&] { for (const TriGeom& g : H.tris) if (!(g.flags & 2u)) return true; return false; }();
+        H.cut_margin = alpha_tested ? -1.0 : wide;
         H.trace_boxes = H.leaf_boxes;
         H.clipped = false;
         const bool textured = [&] { for (int t = 0; t < d->n_tex; t++) if (d->tex_kind[t] != 0) return true; return false; }();
-        for (int n = 0; n < d->n_node && !textured; n++) {
+        for (int n = 0; n < d->n_node && !textured && !alpha_tested; n++) {
             bool inner = false;
             for (int k = 0; k < 8; k++) if (d->node_child[(size_t)n * 8 + k] >= 0) inner = true;
             if (inner) continue;
@@ -466,7 +472,6 @@ inline bool layout_scene(const gi_scene_desc* d, HostScene& H, std::string& err)
             for (int ax = 0; ax < 3; ax++) { lo[ax] = d->node_bbox[(size_t)n * 6 + ax] - wide; hi[ax] = d->node_bbox[(size_t)n * 6 + 3 + ax] + wide; }
             for (int r = d->node_ent_off[n]; r < d->node_ent_off[n + 1]; r++) {
                 const int e = H.refs[(size_t)r];
-                if (!(H.tris[(size_t)e].flags & 2u)) continue;
                 const double* P = d->tri_pos + (size_t)e * 9;
                 double* b = &H.trace_boxes[(size_t)r * 6];
                 H.clipped = true;

@@ -1,7 +1,8 @@
 """GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (gi_device.h: ray_leaves_scene), and
 with it releases the slot of a path that does not continue even while its gather is pending.  A schedule, not arithmetic: frames with the knob at 0
 and at 1 are the same bit for bit.  Open and closed triangle scenes (caustics; cornell, teapot), a textured scene, and three scenes where part or
-all of the frame takes the path the knob does not touch: spheres, the medium (the probe is off with fog) and two lights.  Each as a streaming
+all of the frame takes the path the knob does not touch: spheres, the medium (the probe is off with fog) and two lights; and large alpha-tested
+triangles over an open floor (pc.large_alpha_scene: a path ends or goes on with the draw of a later leaf).  Each as a streaming
 frame with every path in flight at once, with a pool so small that slots are handed on from pass to pass (what releasing a slot with its gather
 pending has to survive), and in render mode 2 (rounds)."""
 import numpy as np
@@ -35,9 +36,9 @@ def _frames(scene, monkeypatch, knob):
     return out
 
 
-@pytest.mark.parametrize("name", ["caustics", "cornell", "teapot", "textures", "spheres", "fog", "two_lights"])
+@pytest.mark.parametrize("name", ["caustics", "cornell", "teapot", "textures", "spheres", "fog", "two_lights", "large_alpha"])
 def test_early_miss_changes_nothing(name, monkeypatch):
-    scene = pc.two_light_scene(False) if name == "two_lights" else pc.load_scene(name)
+    scene = pc.named_scene(name)
     off = _frames(scene, monkeypatch, "0")
     on = _frames(scene, monkeypatch, "1")
     for what in off:

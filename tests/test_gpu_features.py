@@ -7,7 +7,7 @@ What is exact and what has an allowance:
    (tests/parity_checks.py: check_kats) was on offer: measured on the MI355X they came out bit-equal on every pixel of all fourteen cases, so
    that is what is asserted;
  * single-sample spot checks elsewhere (large frames, gi_trace comparison) keep the 4 ulp allowance for the depth.
-Fractional-alpha hits (scenes `spheres`, `textures`) are covered by construction -- aov_sample calls the beauty pass's trace with the beauty pass's
+Fractional-alpha hits (scenes `spheres`, `textures`, `large_alpha`) are covered by construction -- aov_sample calls the beauty pass's trace with the beauty pass's
 keys -- plus determinism, dependence on the seed and agreement with gi_trace where the draw cannot matter; the oracle offers no way to replay the draw
 of a frame's sample without changing it."""
 import ctypes as C
@@ -33,7 +33,7 @@ def setups():
 
     def get(name):
         if name not in cache:
-            scene = pc.load_scene(name)
+            scene = pc.named_scene(name)
             cache[name] = (scene, gi.RayTracer(0).setScene(scene), pc.oracle_for(scene), scene.tables())
         return cache[name]
 
@@ -65,7 +65,12 @@ def test_features_match_the_oracle_on_every_pixel(setups, name, n):
     assert (f[got["coverage"] == 0] == 0).all()
 
 
-@pytest.mark.parametrize("name", ["spheres", "textures"])
+# whether the hit FLAG of some primary ray depends on the alpha draw (worked out with the oracle alone, fe.hit_depends_on_draw): in large_alpha the
+# half-transparent triangles stand against the empty background above the floor's far edge
+FLAG_DEPENDS_ON_DRAW = {"spheres": False, "textures": True, "large_alpha": True}
+
+
+@pytest.mark.parametrize("name", ["spheres", "textures", "large_alpha"])
 def test_fractional_alpha_uses_the_frame_keys(setups, name):
     scene, rt, o, t = setups(name)
     n = 6
@@ -78,7 +83,7 @@ def test_fractional_alpha_uses_the_frame_keys(setups, name):
     # the translucent sphere has other geometry behind it for every ray of this camera, so the draw decides which entity is hit and never whether
     # one is (measured with the oracle: 0 of 6912 rays per sample change their flag, ~95 their entity) -- there the coverage must NOT move.
     vary = any(fe.hit_depends_on_draw(o, fe.sample_rays(o, W, H, s)[0]) for s in range(n))
-    assert vary == (name == "textures")
+    assert vary == FLAG_DEPENDS_ON_DRAW[name]
     assert bool((a["coverage"] != c["coverage"]).any()) == vary
     # where the draw cannot matter -- sample 0 lands on an opacity-1, IOR-1 entity and gi_trace (seed 0, stream = ray number) lands on the same --
     # the features of that sample are that entity's
@@ -208,7 +213,8 @@ def test_the_frame_is_left_alone(setups):
 
 
 def test_per_node_walk_gives_the_same_buffers(setups):
-    for name in ("caustics", "spheres_opaque", "textures_opaque"):
+    # (large_alpha: k_aov's first hits come from the beauty pass's trace, which in a scene with large alpha-tested entities must not cut its walk short)
+    for name in ("caustics", "spheres_opaque", "textures_opaque", "large_alpha", "large_alpha_tex"):
         scene, rt, o, t = setups(name)
         wide = rt.run_features(W, H, 2)
         try:

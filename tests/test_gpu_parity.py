@@ -81,6 +81,30 @@ def test_hits_at_equal_distance_go_to_the_entity_met_first():
     assert rmse < 5e-3, rmse        # the same picture up to those few pixels
 
 
+ALPHA_CASES = [(0.5, False), (0.5, True), (0.05, False), (0.95, False)]      # opacity, textured; at 0.05 / 0.95 almost every draw fails / passes
+
+
+@pytest.mark.parametrize("opacity,textured", ALPHA_CASES)
+def test_large_alpha_entities_walks_match_per_node_walk_and_oracle(opacity, textured):
+    """pc.large_alpha_scene: large alpha-tested triangles that reach through many leaves.  Such an entity is drawn again from every later leaf that
+    refers to it and may win there with a nearer hit, so the closest-hit walk's short cuts are off in such a scene (gi_layout.h): gi_trace with
+    wide records and per node and the oracle agree on every one of 20 000 rays, hit points bit for bit, and gi_visible on the segments to the light."""
+    scene = pc.alpha_case(opacity, textured)
+    rt = gi.RayTracer(0).setScene(scene)
+    assert pc.check_alpha_walks(rt, scene, rt.set_wide_nodes) == (0, 0)
+
+
+@pytest.mark.parametrize("mode", ["wavefront", "rounds", "megakernel"])
+@pytest.mark.parametrize("opacity,textured", ALPHA_CASES)
+def test_large_alpha_entities_frames_match_oracle(opacity, textured, mode):
+    """Frames of the same scenes against the oracle, 48 x 32 at 4 spp, in every render mode: without a photon map inside 1e-9 (a wrong first hit
+    moved the frame of the CPU build by 5e-4), with one inside pc.ALPHA_PHOTON_FRAME_TOL."""
+    scene = pc.alpha_case(opacity, textured)
+    rt = gi.RayTracer(0).setScene(scene)
+    rt.set_render_mode(mode)
+    pc.check_alpha_frames(rt, scene)
+
+
 # Refractive / textured scenes.  The CPU build of the same device code matches the oracle to 1e-17 on all of them (test_device_logic_cpu.py); on
 # the GPU the libm is OCML, which differs from glibc in the last bit of some sin / cos / acos / asin / atan2 / pow results (shares measured by
 # tools/libm_probe.py, DESIGN.md "Numerics").  A specular chain through a refracting object amplifies such a bit until, for a few paths per
@@ -183,19 +207,22 @@ def test_content_culling_changes_nothing(setup):
     assert pc.check_content_culling(setup[2], setup[1]) or setup[0] == "textures_opaque"
 
 
-@pytest.mark.parametrize("name", ["spheres", "fog", "textures", "teapot"])
+@pytest.mark.parametrize("name", ["spheres", "fog", "textures", "teapot", "large_alpha", "large_alpha_tex"])
 def test_content_culling_changes_nothing_more_scenes(name):
-    scene = pc.load_scene(name)
+    scene = pc.named_scene(name)
     pc.check_content_culling(gi.RayTracer(0).setScene(scene), scene)
 
 
-@pytest.mark.parametrize("name", ["caustics", "cornell", "spheres", "fog", "textures", "teapot", "two_lights", "two_lights_glass"])
+@pytest.mark.parametrize("name", ["caustics", "cornell", "spheres", "fog", "textures", "teapot", "two_lights", "two_lights_glass", "large_alpha", "large_alpha_tex"])
 def test_schedule_knobs_change_nothing(name, monkeypatch):
     """Where a shadow segment is walked (inside k_st_shade, or put off to k_st_shadow) and how many idle lanes make a wave of k_st_trace /
     k_st_shadow take new rays (GI_REFILL_MIN; 64 = lockstep waves) are schedules, not arithmetic: the frame is the same bit for bit.  The
     textured scene has emitting and non-emitting texels on one material (both forms of the put-off query), fog adds the medium's march
-    to the put-off segment.  GI_COOP_FACTOR moves the finisher between one path per lane, per group of 16 lanes and per wave."""
-    scene = pc.two_light_scene(name.endswith("glass")) if name.startswith("two_lights") else pc.load_scene(name)   # two lights: one put-off query per light
+    to the put-off segment.  GI_COOP_FACTOR moves the finisher between one path per lane, per group of 16 lanes and per wave.  The scenes with
+    large alpha-tested entities (pc.large_alpha_scene, 96 x 64 at 4 spp) are where the cooperative and finisher walks' own copy of "no look behind the
+    best hit" (gi_device.h: trace_wide_coop) and GI_WALK_CUT / GI_CLIP_BOXES would show: there the scene turns the short cuts off."""
+    scene = pc.named_scene(name)                 # two lights: one put-off query per light
+    w, h, spp = (96, 64, 4) if name.startswith("large_alpha") else (160, 90, 12)
     frames = []
     for env in ({}, {"GI_DEFER_SHADOWS": "0"}, {"GI_REFILL_MIN": "64"}, {"GI_REFILL_MIN": "5"}, {"GI_COOP_FACTOR": "0"}, {"GI_COOP_FACTOR": "64"}, {"GI_WAVE_FACTOR": "1"}, {"GI_WAVE_FACTOR": "200"}, {"GI_FINISH_THRESHOLD": "1000"}, {"GI_ENTITY_BOXES": "0"}, {"GI_CLIP_BOXES": "0"}, {"GI_WALK_CUT": "0"}, {"GI_SORT_CONT": "0"}, {"GI_SORT_SHADE": "0"}, {"GI_SORT_SHADE_LO": "0"}, {"GI_FAST_DESCENT": "0"}, {"GI_DESCENT_JUMP": "0"}, {"GI_FLAT_CANDIDATES": "0"}, {"GI_GATHER_WAVE_BELOW": "0"}, {"GI_GATHER_WAVE_BELOW": "4000000000"}):
         for k in ("GI_DEFER_SHADOWS", "GI_REFILL_MIN", "GI_COOP_FACTOR", "GI_WAVE_FACTOR", "GI_FINISH_THRESHOLD", "GI_ENTITY_BOXES", "GI_CLIP_BOXES", "GI_WALK_CUT", "GI_SORT_CONT", "GI_SORT_SHADE", "GI_SORT_SHADE_LO", "GI_FAST_DESCENT", "GI_DESCENT_JUMP", "GI_FLAT_CANDIDATES", "GI_GATHER_WAVE_BELOW"):
@@ -205,7 +232,7 @@ def test_schedule_knobs_change_nothing(name, monkeypatch):
         rt = gi.RayTracer(0).setScene(scene)     # the knobs are read when the context is created
         if scene.desc().n_light > 0:
             rt.tracePhotons(4000)
-        frames.append(rt.run(160, 90, min_samples=12, max_samples=12, seed=11))
+        frames.append(rt.run(w, h, min_samples=spp, max_samples=spp, seed=11))
     for f in frames[1:]:
         assert np.array_equal(frames[0].view(np.uint64), f.view(np.uint64))
 

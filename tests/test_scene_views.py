@@ -22,7 +22,7 @@ def scene_views(name, environ=os.environ):
     """{"wide cull entity_boxes clip_boxes walk_cut" as 0/1: {field: table name or None, pn_planes: 0/1, cut_margin: float}} for all 32 settings"""
     E = emul_lib.lib()
     E.emul_scene_views.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    rt = emul_lib.EmulRayTracer().setScene(pc.load_scene(name))
+    rt = emul_lib.EmulRayTracer().setScene(pc.named_scene(name) if isinstance(name, str) else name)
     out = {}
     for bits in itertools.product((0, 1), repeat=len(SWITCHES)):
         on = dict(zip(SWITCHES, bits))
@@ -40,7 +40,12 @@ def scene_views(name, environ=os.environ):
     return out
 
 
-@pytest.mark.parametrize("name", ["test_scene", "caustics"])
+# the last three are BASELINE configs 3, 2 and 4: their tables are the benchmark's.  test_scene has 500 entities of opacity 0 and IOR 1 (an alpha test
+# that never passes): since the short cuts of the closest-hit walk depend on the scene it walks on behind its best hit, over whole boxes.
+GOLDEN_SCENES = ("test_scene", "caustics", "cornell", "teapot")
+
+
+@pytest.mark.parametrize("name", GOLDEN_SCENES)
 def test_scene_views_follow_the_switches(name, monkeypatch):
     for var in ENV.values():
         monkeypatch.setenv(var, "1")           # restored afterwards; scene_views sets them per setting
@@ -53,5 +58,45 @@ def test_scene_views_follow_the_switches(name, monkeypatch):
             assert got[setting][field] == want[setting][field], (name, dict(zip(SWITCHES, setting.split())), field)
 
 
+def _env_on(monkeypatch):
+    for var in ENV.values():
+        monkeypatch.setenv(var, "1")
+
+
+ALL_ON = "1 1 1 1 1"
+
+
+@pytest.mark.parametrize("name", ["cornell", "caustics", "teapot", "coplanar", "large_opaque"])
+def test_scenes_without_an_alpha_test_keep_the_short_cuts(name, monkeypatch):
+    """No entity with an alpha test (glass has IOR != 1: no test either): under the default switches the closest-hit walk looks no further than its
+    best hit and walks the boxes cut to the leaves, with the content boxes made of them.  large_opaque is large_alpha_scene at opacity 1: the very
+    geometry that loses the short cuts once its large triangles are half transparent."""
+    _env_on(monkeypatch)
+    scene = pc.coplanar_scene() if name == "coplanar" else (pc.large_alpha_scene(opacity=1.0) if name == "large_opaque" else pc.load_scene(name))
+    assert not pc.alpha_entities(scene).any()
+    row = scene_views(scene)[ALL_ON]
+    assert row["cut_margin"] >= 0 and row["trace_boxes"] == "trace_boxes" and row["tcboxes"] == "tcboxes" and row["tcuse"] == "tcuse"
+    assert row["leaf_boxes"] == "leaf_boxes" and row["shadow_boxes"] == "trace_boxes" and row["scboxes"] == "tcboxes"
+
+
+@pytest.mark.parametrize("name", ["large_alpha", "large_alpha_tex", "spheres", "textures"])
+def test_scenes_with_an_alpha_test_lose_the_short_cuts_under_every_setting(name, monkeypatch):
+    """One entity with an alpha test (opacity < 1 at IOR 1, or an image with an alpha channel) and the closest-hit walk of the whole scene goes on
+    behind its best hit (cut_margin -1) over whole entity boxes and the content boxes made of those -- and the shadow walk with it -- whatever the
+    five switches say."""
+    _env_on(monkeypatch)
+    scene = pc.named_scene(name)
+    assert pc.alpha_entities(scene).any()
+    views = scene_views(scene)
+    assert len(views) == 32
+    for setting, row in views.items():
+        on = dict(zip(SWITCHES, map(int, setting.split())))
+        assert row["cut_margin"] == -1.0, (name, on)
+        assert row["trace_boxes"] == row["leaf_boxes"] == row["shadow_boxes"] == ("leaf_boxes" if on["entity_boxes"] else None), (name, on, row)
+        assert row["tcboxes"] == row["cboxes"] == row["scboxes"] and row["tcuse"] == row["scuse"] == "cuse", (name, on, row)
+    if name.startswith("large_alpha"):      # (the two scene files are too small for wide records)
+        assert views[ALL_ON]["cboxes"] == "cboxes" and views[ALL_ON]["wnodes"] == "wnodes"
+
+
 if __name__ == "__main__":   # records the table: python tests/test_scene_views.py > tests/golden/scene_views.json
-    print(json.dumps({n: scene_views(n) for n in ("test_scene", "caustics")}, indent=0, sort_keys=True))
+    print(json.dumps({n: scene_views(n) for n in GOLDEN_SCENES}, indent=0, sort_keys=True))
