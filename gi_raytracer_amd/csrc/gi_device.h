@@ -135,7 +135,7 @@ struct Scene {
     const int32_t* leaf_refs;
     const LeafTri* leaf_tris; // [n_refs], parallel to leaf_refs
     const double* leaf_boxes; // [n_refs][6] every reference's own box (min xyz, max xyz, widened): a ray that misses it cannot hit the entity; null = not used
-    const double* trace_boxes;// [n_refs][6] the same for the closest-hit walk: where the rules of trace_wide_step allow it, the part of the entity inside its leaf; null with leaf_boxes
+    const double* trace_boxes;// [n_refs][6] the same for the closest-hit walk: where the rules of trace_wide_over allow it, the part of the entity inside its leaf; null with leaf_boxes
     const TriGeom* tris;
     const TriShade* shade;
     const TriUV* tri_uv;      // [n_tri], only when n_tex > 0
@@ -170,7 +170,7 @@ struct Scene {
     double pmap_bmin[3], pmap_bmax[3];   // box of the photon map's root (gather_find_leaf_fast)
     const int32_t* pjump;     // [N][N][N] (y, z, x; N = GI_PJUMP_N) the node the descent of a position in that cell of the map's box has reached after GI_PJUMP_BITS levels (or its leaf); null = not used
     double pjump_cell[3], pjump_inv[3];   // a cell's size per axis and its inverse
-    double cut_margin;        // >= 0: a closest-hit walk looks no further than its best hit plus this (trace_wide_step); < 0: it walks on as the reference does
+    double cut_margin;        // >= 0: a closest-hit walk looks no further than its best hit plus this (trace_wide_step, cut_behind_hit); < 0: it walks on as the reference does
 };
 // the feature levels of the GI_FEAT_* bits
 inline int scene_feat(const Scene& S) { return S.n_tex > 0 ? 7 : (S.n_fog > 0 ? 3 : (S.has_spheres ? GI_FEAT_SPHERES : 0)); }
@@ -607,6 +607,45 @@ GI_HD bool ent_hit(const Tri& g, uint32_t flags, const Ray& ray, double& u, doub
     u = 0; v = 0;   // the reference derives texture coordinates here (asin / atan2); constant textures never read them
     return true;
 }
+// Does the ray hit this leaf reference, and does the hit count?  Entity::intersect, then the alpha test of RayTracer::trace / visible
+// (include/raytracer.h:290-305,446-472) for an entity whose material has one (flag 2 clear): the hit counts when a number drawn per
+// (purpose, leaf, entity) falls below the material's alpha, or the material refracts.  The draw is per (leaf, entity): an entity that failed
+// from one leaf is drawn again from every later leaf that refers to it -- what the closest-hit short cuts have to respect (trace_wide_over).
+// leaf_id: where the leaf's canonical id stands (read only when a number is drawn).  uv, under GI_FEAT_TEX, is the walk's texture-coordinate policy:
+//  * closest-hit walk: the pair the walk carries across entities -- the reference's `uv` variable of trace(), written by every successful
+//    intersect of a smooth triangle or sphere and left as it was by a flat one (ent_uv), so the alpha look-up of a flat entity reads what the
+//    entity before it left behind;
+//  * any-hit walk: null -- a fresh (0, 0) pair, computed only when an alpha test needs it.
+// Called by the one-ray-per-group walks (trace_wide_coop, visible_wide_coop).  The per-lane walks (trace_wide_step, visible_leaf_blocks, trace_nodes,
+// visible_nodes) still spell the same rule out themselves: moving them here cost four kernels scratch, so they wait for a form that does not.
+template <int FEAT, class Tri>
+GI_HD bool ent_accepts(const Scene& S, const Tri& g, const Ray& ray, const Rng& rng, uint32_t purpose, const int32_t* leaf_id, double* uv, double& u, double& v, V3& hp)
+{
+    if (!ent_hit<FEAT>(g, g.matflags, ray, u, v, hp)) return false;
+    if ((FEAT & GI_FEAT_TEX) && uv) ent_uv(S, g, g.matflags, g.tri, u, v, hp, uv[0], uv[1]);
+    if (!(g.matflags & 2u)) {
+        const Mat& m = S.mats[g.matflags >> 3];
+        double alpha = m.opacity * 1.0;
+        if (FEAT & GI_FEAT_TEX) {
+            double fresh[2] = {0, 0};
+            double* const c = uv ? uv : fresh;
+            if (!uv) ent_uv(S, g, g.matflags, g.tri, u, v, hp, c[0], c[1]);
+            alpha = mat_alpha(S, m, c[0], c[1]);
+        }
+        if (!(rng_draw(rng, purpose, (uint32_t)*leaf_id, (uint32_t)g.tri) < alpha || m.ior != 1)) return false;
+    }
+    return true;
+}
+// the any-hit walk's question (RayTracer::visible): an accepted hit strictly between the origin and the light, 0 < |hit - o|^2 < mt
+template <int FEAT, class Tri>
+GI_HD bool ent_blocks(const Scene& S, const Tri& g, const Ray& ray, double mt, const Rng& rng, uint32_t light_index, const int32_t* leaf_id)
+{
+    double u, v;
+    V3 hp;
+    if (!ent_accepts<FEAT>(S, g, ray, rng, P_SHADOW_ALPHA | (light_index << 8), leaf_id, nullptr, u, v, hp)) return false;
+    const double ts = len2(hp - ray.o);
+    return (ts < mt) && (ts > 0);
+}
 
 // Where node records come from: plain global memory here; gi_kernels.hip adds a source that serves the first nodes from LDS.
 struct NodeView { double bmin[3], bmax[3]; int32_t first_ref, n_ref, hit, skip; };
@@ -932,19 +971,21 @@ struct TraceWalk {
     WRay wr;
     WWalk k;
     bool intersected;
-    bool tie;          // two entities at the very same distance were met (trace_wide_step)
+    bool tie;          // two entities at the very same distance were met (trace_wide_step, trace_wide_over)
     double best_d2;
-    double cu, cv;   // the reference's `glm::dvec2 uv` of trace(): written by every successful intersect of a smooth triangle or sphere
+    double uv[2];    // the reference's `glm::dvec2 uv` of trace(), carried across entities (ent_accepts)
 };
+// a ray that runs exactly along an axis plane may lie IN the face two leaves share and touch both all the way: leaves then do not follow
+// each other along it, which the short cuts of the closest-hit walk (trace_wide_over) take for granted -- such a ray walks the plain way.
+// trace_wide_begin and the probe ray_leaves_scene ask this one function: the probe is only sound while the two walks agree
+GI_HD bool ray_walks_plain(const Ray& ray) { return !(fabs(ray.inv.x) < INFINITY && fabs(ray.inv.y) < INFINITY && fabs(ray.inv.z) < INFINITY); }
 template <int FEAT, class WN>
 GI_HD bool trace_wide_begin(const Scene& S, const WN& W, const Ray& ray, TraceWalk& t)   // false: the ray misses the scene's box
 {
     t.wr = wray_make(ray);
-    // a ray that runs exactly along an axis plane may lie IN the face two leaves share and touch both all the way: leaves then do not follow
-    // each other along it, which the short cuts of trace_wide_step take for granted -- such a ray walks the plain way
     t.intersected = false; t.tie = false;
-    t.wr.plain = !(fabs(ray.inv.x) < INFINITY && fabs(ray.inv.y) < INFINITY && fabs(ray.inv.z) < INFINITY);
-    t.best_d2 = 0; t.cu = 0; t.cv = 0;
+    t.wr.plain = ray_walks_plain(ray);
+    t.best_d2 = 0; t.uv[0] = 0; t.uv[1] = 0;
     return wwalk_begin(S, W, t.k, ray, t.wr, 0.0, INFINITY);
 }
 // Two short cuts of the closest-hit walk, both leaving the hit RayTracer::trace returns (include/raytracer.h:446-472) as it is:
@@ -964,9 +1005,11 @@ GI_HD bool trace_wide_over(const Scene& S, const WN& W, const Ray& ray, TraceWal
     if (!t.tie || t.wr.plain || S.trace_boxes == S.leaf_boxes) return false;   // (whole boxes: the entities were met in the reference's order anyway)
     t.wr.tc = INFINITY;
     t.intersected = false; t.tie = false; t.wr.plain = true;
-    t.best_d2 = 0; t.cu = 0; t.cv = 0;
+    t.best_d2 = 0; t.uv[0] = 0; t.uv[1] = 0;
     return wwalk_begin(S, W, t.k, ray, t.wr, 0.0, INFINITY);
 }
+// nothing that begins behind the best hit (at squared distance d2) can be nearer: the first short cut above
+GI_HD void cut_behind_hit(const Scene& S, WRay& wr, double d2) { if (S.cut_margin >= 0 && !wr.plain) wr.tc = sqrt(d2) + S.cut_margin; }
 template <int FEAT, class WN>
 GI_HD bool trace_wide_step(const Scene& S, const WN& W, const Ray& ray, const Rng& rng, uint32_t alpha_purpose, TraceWalk& t, HitRec& best)   // false: the walk is over
 {
@@ -977,7 +1020,7 @@ GI_HD bool trace_wide_step(const Scene& S, const WN& W, const Ray& ray, const Rn
     GI_DIV(W, 2);
     W.tick_leaf();
     // an entity beyond the best hit cannot replace it (strict <): without textures its test changes nothing; with them a successful intersect
-    // leaves its uv behind for the alpha look-up of the next flat entity (t.cu / t.cv), so every entity of a visited leaf is still asked
+    // leaves its uv behind for the alpha look-up of the next flat entity (t.uv), so every entity of a visited leaf is still asked
 #define GI_TCE ((FEAT & GI_FEAT_TEX) ? INFINITY : t.wr.tc)
     auto test = [&](const LeafTri& g) {
         const int32_t ti = g.tri;
@@ -985,17 +1028,17 @@ GI_HD bool trace_wide_step(const Scene& S, const WN& W, const Ray& ray, const Rn
         V3 hp;
         W.tick_tri();
         if (!ent_hit<FEAT>(g, g.matflags, ray, u, v, hp)) return;
-        if (FEAT & GI_FEAT_TEX) ent_uv(S, g, g.matflags, ti, u, v, hp, t.cu, t.cv);
+        if (FEAT & GI_FEAT_TEX) ent_uv(S, g, g.matflags, ti, u, v, hp, t.uv[0], t.uv[1]);
         if (!(g.matflags & 2u)) {
             const Mat& m = S.mats[g.matflags >> 3];
-            const double alpha = (FEAT & GI_FEAT_TEX) ? mat_alpha(S, m, t.cu, t.cv) : m.opacity * 1.0;
+            const double alpha = (FEAT & GI_FEAT_TEX) ? mat_alpha(S, m, t.uv[0], t.uv[1]) : m.opacity * 1.0;
             if (!(rng_draw(rng, alpha_purpose, (uint32_t)S.wleaf_id[lnode * 8 + lslot], (uint32_t)ti) < alpha || m.ior != 1)) return;
         }
         double d2 = len2(hp - ray.o);
         if (t.intersected && d2 == t.best_d2 && ti != best.tri) t.tie = true;
         if (!t.intersected || d2 < t.best_d2) {
             best.pos = hp; best.u = u; best.v = v; best.tri = ti; best.mf = g.matflags;
-            if (FEAT & GI_FEAT_TEX) { best.tu = t.cu; best.tv = t.cv; }
+            if (FEAT & GI_FEAT_TEX) { best.tu = t.uv[0]; best.tv = t.uv[1]; }
             t.best_d2 = d2;
             t.intersected = true;
             if (S.cut_margin >= 0 && !t.wr.plain) t.wr.tc = sqrt(d2) + S.cut_margin;   // nothing that begins behind this can be nearer
@@ -1065,7 +1108,7 @@ template <class WN>
 GI_HD bool ray_leaves_scene(const Scene& S, const WN& W, const Ray& ray, int max_turns)
 {
     WRay wr = wray_make(ray);
-    wr.plain = !(fabs(ray.inv.x) < INFINITY && fabs(ray.inv.y) < INFINITY && fabs(ray.inv.z) < INFINITY);
+    wr.plain = ray_walks_plain(ray);
     WWalk k;
     if (!wwalk_begin(S, W, k, ray, wr, 0.0, INFINITY)) return true;   // misses the scene's box
     for (int turn = 0; turn < max_turns; turn++) {
@@ -1083,12 +1126,14 @@ struct VisWalk {
     WWalk k;
     double tmax;
 };
+// the any-hit walk's cut for a segment of squared length mt: a blocker lies before the light, 0 < |hit - o|^2 < mt
+GI_HD double shadow_cut(double mt) { return sqrt(mt) * (1.0 + 1e-9); }
 template <int FEAT, class WN>
 GI_HD bool visible_wide_begin(const Scene& S, const WN& W, const Ray& ray, double mt, VisWalk& v)   // false: the segment misses the scene's box
 {
     v.wr = wray_make(ray);
     v.tmax = sqrt(mt) - GI_SHADOW_BIAS;
-    v.wr.tc = sqrt(mt) * (1.0 + 1e-9);   // a blocker lies before the light: 0 < |hit - o|^2 < mt
+    v.wr.tc = shadow_cut(mt);
     return wwalk_begin(S, W, v.k, ray, v.wr, 0.0, v.tmax);
 }
 enum { VIS_DONE = 0, VIS_MORE = 1, VIS_BLOCKED = 2 };
@@ -1117,7 +1162,7 @@ GI_HD bool visible_leaf_blocks(const Scene& S, const WN& W, const Ray& ray, doub
     int32_t first_u, cnt_u;
     if (leaf_is_wave_uniform(first, cnt, first_u, cnt_u)) {
         bool hit = false;
-        const double tc = sqrt(mt) * (1.0 + 1e-9);
+        const double tc = shadow_cut(mt);
         if (boxes) W.tick_ebox((uint32_t)cnt_u);
         for (int32_t j = 0; j < cnt_u; j++) {     // wave-uniform trip count: the record address stays scalar
             bool touch = !hit;
@@ -1135,7 +1180,7 @@ GI_HD bool visible_leaf_blocks(const Scene& S, const WN& W, const Ray& ray, doub
     }
 #endif
     if (boxes && cnt <= 32) {
-        uint32_t m = entity_survivors(boxes, first, cnt, ray, sqrt(mt) * (1.0 + 1e-9));   // a blocker lies before the light: 0 < |hit - o|^2 < mt
+        uint32_t m = entity_survivors(boxes, first, cnt, ray, shadow_cut(mt));
         W.tick_ebox((uint32_t)cnt);
         while (m) {
             const int j = __builtin_ctz(m);
@@ -1159,7 +1204,7 @@ GI_HD int visible_wide_step(const Scene& S, const WN& W, const Ray& ray, double 
     if (!wwalk_next_leaf(W, v.k, ray, v.wr, 0.0, v.tmax, lnode, lslot, first, cnt)) return VIS_DONE;
     return visible_leaf_blocks<FEAT>(S, W, ray, mt, rng, light_index, lnode, lslot, first, cnt, S.leaf_boxes) ? VIS_BLOCKED : VIS_MORE;
 }
-// what visible() asks of the medium once nothing solid blocks the segment: include/raytracer.h:308-316
+// what visible() asks of the medium once nothing solid blocks the segment: include/raytracer.h:308-316 (the reference bounds this march by the SQUARED length)
 template <int FEAT>
 GI_HD bool visible_through_fog(const Scene& S, const Ray& ray, double mt, const Rng& rng, uint32_t light_index)
 {
@@ -1230,11 +1275,7 @@ __device__ __forceinline__ bool trace_wide_coop(const Scene& S, const WN& W, con
             if (j < cnt) {
                 const LeafTri g = S.leaf_tris[first + j];
                 ti = g.tri; mf = g.matflags;
-                ok = ent_hit<FEAT>(g, mf, ray, u, v, hp);
-                if (ok && !(mf & 2u)) {
-                    const Mat& m = S.mats[mf >> 3];
-                    ok = rng_draw(rng, alpha_purpose, (uint32_t)S.wleaf_id[lnode * 8 + lslot], (uint32_t)ti) < m.opacity * 1.0 || m.ior != 1;
-                }
+                ok = ent_accepts<FEAT>(S, g, ray, rng, alpha_purpose, S.wleaf_id + lnode * 8 + lslot, nullptr, u, v, hp);
                 if (ok) d2 = len2(hp - ray.o);
             }
             double pm = ok ? d2 : INFINITY;   // inclusive prefix minimum over the group's lanes
@@ -1255,8 +1296,7 @@ __device__ __forceinline__ bool trace_wide_coop(const Scene& S, const WN& W, con
                 best.tri = __shfl(ti, last); best.mf = (uint32_t)__shfl((int)mf, last);
                 best_d2 = __shfl(d2, last);
                 intersected = true;
-                if (S.cut_margin >= 0) wr.tc = sqrt(best_d2) + S.cut_margin;   // no look behind the best hit (trace_wide_step): the reference walks on to the end of the ray
-                                                                              // when the hit was found from an earlier leaf -- a lone path inside a glass body does that at every bounce
+                cut_behind_hit(S, wr, best_d2);   // (wr.plain stays false here: wray_make, and this walk has no re-walk) the reference walks on to the end of the ray when the hit was found from an earlier leaf -- a lone path inside a glass body does that at every bounce
             }
         }
         if (term) break;
@@ -1273,7 +1313,7 @@ __device__ __forceinline__ bool visible_wide_coop(const Scene& S, const WN& W, c
     const int gl = (int)(threadIdx.x & (unsigned)(G - 1));
     WRay wr = wray_make(ray);
     const double tmax = sqrt(mt) - GI_SHADOW_BIAS;
-    wr.tc = sqrt(mt) * (1.0 + 1e-9);
+    wr.tc = shadow_cut(mt);
     WWalk k;
     if (wwalk_begin(S, W, k, ray, wr, 0.0, tmax)) {
         for (;;) {
@@ -1282,18 +1322,7 @@ __device__ __forceinline__ bool visible_wide_coop(const Scene& S, const WN& W, c
             if (!wwalk_next_leaf(W, k, ray, wr, 0.0, tmax, lnode, lslot, first, cnt)) break;
             for (int32_t base = 0; base < cnt; base += G) {
                 const int32_t j = base + gl;
-                bool blocks = false;
-                if (j < cnt) {
-                    const LeafTri g = S.leaf_tris[first + j];
-                    double u, v;
-                    V3 hp;
-                    bool ok = ent_hit<FEAT>(g, g.matflags, ray, u, v, hp);
-                    if (ok && !(g.matflags & 2u)) {
-                        const Mat& m = S.mats[g.matflags >> 3];
-                        ok = rng_draw(rng, P_SHADOW_ALPHA | (light_index << 8), (uint32_t)S.wleaf_id[lnode * 8 + lslot], (uint32_t)g.tri) < m.opacity * 1.0 || m.ior != 1;
-                    }
-                    if (ok) { const double ts = len2(hp - ray.o); blocks = (ts < mt) && (ts > 0); }
-                }
+                const bool blocks = j < cnt && ent_blocks<FEAT>(S, S.leaf_tris[first + j], ray, mt, rng, light_index, S.wleaf_id + lnode * 8 + lslot);
                 if (group_ballot<G>(blocks) != 0ull) return false;
             }
         }

@@ -28,7 +28,7 @@ struct HostScene {
     std::vector<int32_t> refs;
     std::vector<LeafTri> leaf_tris;
     std::vector<double> leaf_boxes;   // [n_refs][6] the entity's own box, widened (gi_device.h: entity_box_missed), parallel to leaf_tris
-    std::vector<double> trace_boxes;  // [n_refs][6] for the closest-hit walk: the box of the part of an opaque entity inside its leaf (gi_device.h: trace_wide_step)
+    std::vector<double> trace_boxes;  // [n_refs][6] for the closest-hit walk: the box of the part of an opaque entity inside its leaf (gi_device.h: trace_wide_over)
     double cut_margin = -1;           // what the closest-hit walk's short cuts allow for rounding (1e-5 of the scene); -1 where an entity has an alpha test
     bool clipped = false;             // trace_boxes differs from leaf_boxes (never with textures or an alpha-tested entity in the scene)
     bool lights_clear = false;        // no entity's box within a light's radius + twice the shadow bias (+ 4 margins) of the light: nothing can block a shadow segment in its last stretch
@@ -93,7 +93,7 @@ inline void apply_scene_switches(Scene& S, const SceneTables& T, const SceneSwit
     const bool cut_to_leaves = clip && S.cboxes && T.n_tcboxes == T.n_cboxes;
     S.tcboxes = cut_to_leaves ? T.tcboxes : S.cboxes;
     S.tcuse = cut_to_leaves ? T.tcuse : S.cuse;
-    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks)
+    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks, shadow_cut)
     const bool sh = T.lights_clear && clip;
     S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
     S.scboxes = sh ? S.tcboxes : S.cboxes;
