@@ -628,8 +628,10 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
                 if (pend) retire(item, slot, ray, stream, depth, hit, h);
                 const uint32_t at = wave_append(c_shade, hit);
                 if (hit) q_shade[seg + at] = slot;
-                const uint32_t af = wave_append(c_free, fin);
-                if (fin) q_free[seg + af] = slot;
+                if (q_free) {        // (a kernel argument: null when nothing will read this pass's free list, stream_passes)
+                    const uint32_t af = wave_append(c_free, fin);
+                    if (fin) q_free[seg + af] = slot;
+                }
                 pend = false;
                 if (more) {
                     const unsigned long long want = ~busy;
@@ -683,8 +685,10 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
             }
             const uint32_t at = wave_append(c_shade, hit);
             if (hit) q_shade[seg + at] = slot;
-            const uint32_t af = wave_append(c_free, fin);
-            if (fin) q_free[seg + af] = slot;
+            if (q_free) {
+                const uint32_t af = wave_append(c_free, fin);
+                if (fin) q_free[seg + af] = slot;
+            }
         }
     }
 #ifdef GI_EXP_DIV
@@ -815,7 +819,7 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
             q_gather[seg + g] = slot;
             g_pos[(size_t)(seg + g) * 3] = so.gpos.x; g_pos[(size_t)(seg + g) * 3 + 1] = so.gpos.y; g_pos[(size_t)(seg + g) * 3 + 2] = so.gpos.z;
         }
-        st_release(slot, q_free + seg, c_free, valid && !cont);
+        if (q_free) st_release(slot, q_free + seg, c_free, valid && !cont);   // null: nothing will read this pass's free list (stream_passes)
     }
 #ifdef GI_EXP_DIV
     if constexpr (WIDE != 0) div_flush(N, 1);
@@ -1084,10 +1088,21 @@ __global__ __launch_bounds__(256) void k_st_compact(Scene S, CompactJob job, con
         __syncthreads();
         const uint32_t total = prefix[n_blocks];
         const uint32_t base = (job.total_field[q] == 3 && job.free_base_from_trace) ? ctl->n_free_trace : 0u;
-        for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-            uint32_t lo = 0, hi = n_blocks;                          // largest r with prefix[r] <= t
-            while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (prefix[mid] <= t) lo = mid; else hi = mid; }
-            const size_t from = (size_t)segs[lo] + (t - prefix[lo]), to = (size_t)base + t;
+        // Every workgroup copies one contiguous run of output positions, a multiple of the workgroup's size long; a thread's positions are 256 apart.
+        // Its producer segment lo (largest r with prefix[r] <= t) is searched for once; from one position to the next it stays, or moves on by the
+        // one comparison below -- and only a thread that steps over the end of a segment searches again, in what lies ahead.
+        const unsigned long long run = (((unsigned long long)total + gridDim.x - 1u) / gridDim.x + 255ull) & ~255ull;   // (64 bits: total may be close to 2^32)
+        const uint32_t t_begin = (uint32_t)(blockIdx.x * run < total ? blockIdx.x * run : total);
+        const uint32_t t_end = (uint32_t)(t_begin + run < total ? t_begin + run : total);
+        uint32_t lo = 0, seg_end = 0, seg_off = 0;                  // prefix[lo + 1]; segs[lo] - prefix[lo] (mod 2^32): from = t + seg_off
+        for (uint32_t t = t_begin + threadIdx.x; t < t_end; t += blockDim.x) {
+            if (t >= seg_end) {
+                uint32_t hi = n_blocks;
+                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (prefix[mid] <= t) lo = mid; else hi = mid; }
+                seg_end = prefix[lo + 1];
+                seg_off = segs[lo] - prefix[lo];
+            }
+            const size_t from = (size_t)(uint32_t)(t + seg_off), to = (size_t)base + t;
             if (q == job.gather_queue) {
                 const CompactStream& sl = job.st[stream0];
                 const double* pos = reinterpret_cast<const double*>(job.st[stream0 + 1].src) + from * 3;
@@ -1820,6 +1835,7 @@ struct gi_ctx {
     size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
     uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
     bool sample_identity = true;      // GI_SAMPLE_IDENTITY=0: the stream passes always keep the slot -> sample table, also where it would be the identity (stream_samples)
+    bool keep_free_list = false;      // GI_KEEP_FREE_LIST=1: the stream passes write the free list in every pass, also where nothing will read it (stream_passes)
     bool early_miss = true;           // GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (stream_passes)
     uint32_t early_turns = 4;         // GI_EARLY_MISS_TURNS: turns of the walk that probe may take before it gives the ray to the trace stage
     uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
@@ -2116,6 +2132,7 @@ int gi_create(gi_ctx** out, int device_ordinal)
     if (const char* e = getenv("GI_EARLY_MISS")) c->early_miss = atoi(e) != 0;
     if (const char* e = getenv("GI_EARLY_MISS_TURNS")) c->early_turns = (uint32_t)std::min(64, std::max(1, atoi(e)));
     if (const char* e = getenv("GI_SAMPLE_IDENTITY")) c->sample_identity = atoi(e) != 0;
+    if (const char* e = getenv("GI_KEEP_FREE_LIST")) c->keep_free_list = atoi(e) != 0;
     if (const char* e = getenv("GI_SORT_CONT")) c->sort_cont = atoi(e) != 0;
     if (const char* e = getenv("GI_DESCENT_JUMP")) c->descent_jump = atoi(e) != 0;
     if (const char* e = getenv("GI_FLAT_CANDIDATES")) c->flat_candidates = atoi(e) != 0;
@@ -2417,7 +2434,13 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
             break;
         }
         HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(StreamCtl), st));
-        uint32_t* qfree_out = q_free[ping];
+        // The free list of this pass has one reader, the refill of the next.  Once refill has started its last sample (`exhausted`, set by the call
+        // above: this pass still reads the previous list, nobody reads the one it would write; rounds never hand a freed slot out again) the kernels
+        // get no free queue and skip its appends, the compaction leaves the queue out, and n_free stays 0.  GI_KEEP_FREE_LIST=1: written always.
+        const bool want_free = c->keep_free_list || !exhausted;
+        uint32_t* qfree_out = want_free ? q_free[ping] : nullptr;
+        uint32_t* const stage_free_trace = want_free ? c->d_stage[1].p : nullptr;
+        uint32_t* const stage_free_shade = want_free ? c->d_stage[3].p : nullptr;
         if (G.trace > GI_MAX_PRODUCER_BLOCKS || G.shade > GI_MAX_PRODUCER_BLOCKS) return fail(c, GI_E_STATE, "render: more producer workgroups than per-workgroup counters");
         unsigned int* bc = c->d_blkcnt.p;
         const size_t bc_bytes = (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE * sizeof(unsigned int);
@@ -2426,12 +2449,12 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
         StreamCounters* const sc = counting ? c->d_stream_cnt.p : nullptr;
         const TraceK trace_k = st_trace(trace_feat, wide, counting);
         stage_begin(c, STG_TRACE); hipLaunchKernelGGL(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
-                           c->d_stage[0].p, c->d_stage[1].p, lbuf, c->refill_min, sc); stage_end(c);
+                           c->d_stage[0].p, stage_free_trace, lbuf, c->refill_min, sc); stage_end(c);
         {
             CompactJob job;
             memset(&job, 0, sizeof job);
             job.st[0] = {c->d_stage[0].p, q_shade, 1}; job.n_streams[0] = 1; job.kind[0] = QC_SHADE; job.total_field[0] = 0;
-            job.st[1] = {c->d_stage[1].p, qfree_out, 1}; job.n_streams[1] = 1; job.kind[1] = QC_FREE; job.total_field[1] = 4;
+            job.st[1] = {c->d_stage[1].p, qfree_out, 1}; job.n_streams[1] = 1; job.kind[1] = want_free ? QC_FREE : -1; job.total_field[1] = 4;
             job.kind[2] = -1; job.gather_queue = -1;
             stage_begin(c, STG_OTHER); hipLaunchKernelGGL(k_st_compact, dim3(G.compact), dim3(256), 0, st, c->S, job, bc, c->d_segs.p, (uint32_t)G.trace, ctl); stage_end(c);
         }
@@ -2459,7 +2482,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
         const bool many = c->S.n_light > 1;
         const ShadeK shade_k = st_shade(feat, wide, shq ? (many ? 2 : 1) : 0);
         stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, q_shade_use, ctl, bc, c->d_segs.p,
-                           c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, c->d_stage[3].p, lbuf, shq, q_orig, early_turns);
+                           c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, stage_free_shade, lbuf, shq, q_orig, early_turns);
         stage_end(c);
         if (shq) {   // the walks it put off; before the gather of the same vertices (the order in which a path's radiance is summed)
             const ShadowK shadow_k = st_shadow(feat, many, counting);
@@ -2479,7 +2502,7 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
             job.n_streams[1] = 2; job.kind[1] = QC_GATHER; job.total_field[1] = 2; job.gather_queue = c->S.n_pnode > 0 ? 1 : -1;
             if (c->S.n_pnode <= 0) job.kind[1] = -1;                                                            // no photon map: no gather queries
             job.st[4] = {c->d_stage[3].p, qfree_out, 1};
-            job.n_streams[2] = 1; job.kind[2] = QC_FREE; job.total_field[2] = 3; job.free_base_from_trace = 1;
+            job.n_streams[2] = 1; job.kind[2] = want_free ? QC_FREE : -1; job.total_field[2] = 3; job.free_base_from_trace = 1;
             stage_begin(c, STG_OTHER); hipLaunchKernelGGL(k_st_compact, dim3(G.compact), dim3(256), 0, st, c->S, job, bc, c->d_segs.p, (uint32_t)G.shade, ctl); stage_end(c);
         }
         launches += 4;
