@@ -62,6 +62,11 @@ class UpsampleParams(C.Structure):
                 ("demodulate", C.c_int32), ("sigma_normal", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
+class OcclusionParams(C.Structure):
+    """gi_occlusion_params (include/gi_hip.h)."""
+    _fields_ = [("n_samples", C.c_int32), ("n_dirs", C.c_int32), ("radius", C.c_double)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -75,7 +80,8 @@ ABI_SYMBOLS = [
     "gi_create", "gi_destroy", "gi_last_error", "gi_set_stream", "gi_upload_scene", "gi_upload_photons", "gi_local_rows",
     "gi_render_device", "gi_render_host", "gi_render_features_device", "gi_render_features_host", "gi_last_features_ms",
     "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms",
-    "gi_upsample_default_params", "gi_upsample_device", "gi_upsample_host", "gi_last_upsample_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
+    "gi_upsample_default_params", "gi_upsample_device", "gi_upsample_host", "gi_last_upsample_ms",
+    "gi_occlusion_default_params", "gi_render_occlusion_device", "gi_render_occlusion_host", "gi_last_occlusion_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
@@ -119,6 +125,11 @@ def lib():
     L.gi_upsample_device.argtypes = [vp, C.POINTER(UpsampleParams), vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.gi_upsample_host.argtypes = [vp, C.POINTER(UpsampleParams), vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.gi_last_upsample_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gi_occlusion_default_params.argtypes = [C.POINTER(OcclusionParams)]
+    L.gi_occlusion_default_params.restype = None
+    L.gi_render_occlusion_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(OcclusionParams), vp, C.c_int]
+    L.gi_render_occlusion_host.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(OcclusionParams), vp, C.c_int]
+    L.gi_last_occlusion_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.gi_set_render_mode.argtypes = [vp, C.c_int]
     L.gi_set_wide_nodes.argtypes = [vp, C.c_int]
     L.gi_set_content_culling.argtypes = [vp, C.c_int]
@@ -432,6 +443,45 @@ def upsample_arrays(low_color, low_features, features, factor):
         raise ValueError(f"upsample: a {w} x {h} frame at factor {factor} takes low_color [{hl}][{wl}][3] and low_features [{hl}][{wl}][8], "
                          f"got {low_color.shape} and {low_features.shape}")
     return low_color, low_features, features
+
+
+OCCLUSION_MAX_DIRS = 64
+
+
+def occlusion_params(n=None, dirs=None, radius=None, width=None, height=None):
+    """gi_occlusion_default_params (16 samples, 16 directions, radius 0 = a tenth of the scene box's diagonal) with any of n, dirs, radius set.
+    No device needed.  ValueError for what the library would refuse: n < 1 (or, when the frame size is given, beyond halton_sample_cap(width,
+    height)), dirs outside 1 .. 64, a negative, NaN or infinite radius."""
+    p = OcclusionParams()
+    lib().gi_occlusion_default_params(C.byref(p))
+    if n is not None:
+        p.n_samples = _whole("n", n)
+    if dirs is not None:
+        p.n_dirs = _whole("dirs", dirs)
+    if radius is not None:
+        radius = float(radius)
+        if not (0.0 <= radius < float("inf")):
+            raise ValueError(f"occlusion: radius must be finite and >= 0 (0: a tenth of the scene box's diagonal), got {radius}")
+        p.radius = radius
+    if p.n_samples < 1:
+        raise ValueError(f"occlusion: n must be at least 1, got {p.n_samples}")
+    if width is not None and height is not None and p.n_samples > halton_sample_cap(width, height):
+        raise ValueError(f"occlusion: n = {p.n_samples} takes the Halton index of a {width} x {height} frame beyond 32 bits "
+                         f"(at most {halton_sample_cap(width, height)})")
+    if not 1 <= p.n_dirs <= OCCLUSION_MAX_DIRS:
+        raise ValueError(f"occlusion: dirs must be 1 .. {OCCLUSION_MAX_DIRS}, got {p.n_dirs}")
+    return p
+
+
+def _whole(name, v):
+    """An integer argument of occlusion_params: ValueError for anything that is not a whole number an int32 holds."""
+    try:
+        i = int(v)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"occlusion: {name} must be a whole number, got {v!r}") from None
+    if i != v or not -2 ** 31 <= i < 2 ** 31:
+        raise ValueError(f"occlusion: {name} must be a whole number, got {v!r}")
+    return i
 
 
 # The header of a progressive checkpoint (include/gi_hip.h: gi_progressive_save), little-endian, 192 bytes; the 72-byte pixel records follow.
@@ -832,6 +882,34 @@ class RayTracer:
         """gi_last_upsample_ms: device time of the last upsampler pass (the frame's, the feature pass's and the denoiser's times keep theirs)."""
         ms = C.c_float()
         self._check(self.L.gi_last_upsample_ms(self.h, C.byref(ms)), "last_upsample_ms")
+        return ms.value
+
+    def occlusion_params(self, **kw):
+        """The module's occlusion_params: n, dirs, radius (and width, height for the Halton cap) -> gi_occlusion_params; ValueError for bad values."""
+        return occlusion_params(**kw)
+
+    def run_occlusion(self, w, h, n=16, dirs=16, radius=0.0, f64=True, **kw):
+        """Ambient occlusion and bent normals of the frame `run` renders (gi_render_occlusion_host; an addition, the reference has no such pass): per
+        pixel the mean over samples 0 .. n-1 of the share of `dirs` cosine-distributed segments of length `radius` above the first hit that meet
+        nothing, and of the mean direction of those.  radius=0: a tenth of the scene box's diagonal.  Returns a dict of views into one array
+        `occlusion` [rows][w][4]: open [rows][w], bent [rows][w][3].  **kw as for run (stripes, seed).  ValueError for a bad n, dirs or radius,
+        before the library is called; the definition is stated in include/gi_hip.h."""
+        op = occlusion_params(n=n, dirs=dirs, radius=radius, width=w, height=h)
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out = np.zeros((rows, w, 4), np.float64 if f64 else np.float32)
+        self._check(self.L.gi_render_occlusion_host(self.h, C.byref(p), C.byref(op), out.ctypes.data_as(C.c_void_p), 1 if f64 else 0), "render_occlusion_host")
+        return {"occlusion": out, "open": out[:, :, 0], "bent": out[:, :, 1:4]}
+
+    def run_occlusion_device(self, p, op, out_ptr, f64=False):
+        """The occlusion pass into device memory, asynchronous on the context's stream; p from params, op from occlusion_params; out_ptr
+        ([rows][w][4]) is a raw device pointer."""
+        self._check(self.L.gi_render_occlusion_device(self.h, C.byref(p), C.byref(op), C.c_void_p(out_ptr), 1 if f64 else 0), "render_occlusion_device")
+
+    def last_occlusion_ms(self):
+        """gi_last_occlusion_ms: device time of the last occlusion pass (the frame's and the other passes' times keep theirs)."""
+        ms = C.c_float()
+        self._check(self.L.gi_last_occlusion_ms(self.h, C.byref(ms)), "last_occlusion_ms")
         return ms.value
 
     def run_upsampled(self, w, h, factor, feature_samples, denoise=False, f64=True, **kw):

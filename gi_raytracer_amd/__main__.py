@@ -5,6 +5,7 @@
                                [--denoise OUT.ppm [--denoise-pfm OUT.pfm] [--denoise-iterations N] [--denoise-sigmas C N Z A]]
                                [--progressive N [--time-limit SECONDS] [--checkpoint FILE]]
                                [--upsample S [--upsample-pfm LOW.pfm]]
+                               [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -21,6 +22,9 @@ SECONDS takes no further step once the frame's budget is spent (at least one ste
 up with the guided upsampler, led by feature buffers of both sizes; --width and --height stay the size of what is written: -o and --pfm get the
 upsampled frame, --features the full-size buffers, and --denoise the low frame denoised and then upsampled.  --upsample-pfm LOW.pfm also keeps the
 reduced-size render itself.  Not together with --progressive.
+--occlusion PREFIX (one more addition) also writes the ambient occlusion of the frame, at --width x --height: PREFIX.open.pfm (one channel, 1 = nothing
+within the radius) and PREFIX.bent.pfm (three channels, the mean free direction).  --occlusion-samples N samples per pixel and --occlusion-dirs K
+segments per sample (default 16 and 16), --occlusion-radius R their length (default 0: a tenth of the scene box's diagonal).
 """
 import argparse
 import os
@@ -56,6 +60,10 @@ def parser():
     ap.add_argument("--checkpoint", default=None, metavar="FILE", help="with --progressive: resume from FILE when it exists, save the session to it after every step")
     ap.add_argument("--upsample", type=int, default=None, metavar="S", help="render at 1/S of --width x --height (S = 2 .. 8, dividing both) and scale up with the guided upsampler")
     ap.add_argument("--upsample-pfm", default=None, metavar="LOW.pfm", help="with --upsample: also write the reduced-size render (linear radiance) as PFM")
+    ap.add_argument("--occlusion", default=None, metavar="PREFIX", help="also write ambient occlusion and bent normals as PREFIX.open.pfm and PREFIX.bent.pfm")
+    ap.add_argument("--occlusion-samples", type=int, default=None, metavar="N", help="with --occlusion: samples per pixel (default 16)")
+    ap.add_argument("--occlusion-dirs", type=int, default=None, metavar="K", help="with --occlusion: segments per sample, 1 .. 64 (default 16)")
+    ap.add_argument("--occlusion-radius", type=float, default=None, metavar="R", help="with --occlusion: length of a segment (default 0: a tenth of the scene box's diagonal)")
     return ap
 
 
@@ -71,6 +79,13 @@ def check_args(ap, a):
         ap.error("--time-limit SECONDS: a number >= 0")
     if a.upsample is None and a.upsample_pfm:
         ap.error("--upsample-pfm needs --upsample S")
+    if a.occlusion is None and (a.occlusion_samples is not None or a.occlusion_dirs is not None or a.occlusion_radius is not None):
+        ap.error("--occlusion-samples, --occlusion-dirs and --occlusion-radius need --occlusion PREFIX")
+    if a.occlusion is not None:
+        try:
+            gi.occlusion_params(**occlusion_kwargs(a), width=a.width, height=a.height)
+        except ValueError as e:
+            ap.error(f"--occlusion: {e}")
     if a.upsample is not None:
         if a.progressive is not None:
             ap.error("--upsample and --progressive do not go together")
@@ -146,6 +161,12 @@ def denoise_kwargs(a):
     return kw
 
 
+def occlusion_kwargs(a):
+    """The keyword arguments of RayTracer.run_occlusion the --occlusion-* flags set."""
+    kw = {"n": a.occlusion_samples, "dirs": a.occlusion_dirs, "radius": a.occlusion_radius}
+    return {k: v for k, v in kw.items() if v is not None}
+
+
 def feature_samples(a, max_samples):
     """n of the feature pass: --feature-samples, else the frame's max_samples cut to the Halton cap of the frame size."""
     if a.feature_samples is not None:
@@ -207,6 +228,11 @@ def main(argv=None):
         if a.denoise_pfm:
             gi.save_pfm(a.denoise_pfm, den)
         feat += f"; denoised ({nf} spp features) {rt.last_denoise_ms():.2f} ms -> {a.denoise}"
+    if a.occlusion:
+        ao = rt.run_occlusion(a.width, a.height, f64=False, **occlusion_kwargs(a))
+        gi.save_pfm(f"{a.occlusion}.open.pfm", ao["open"])
+        gi.save_pfm(f"{a.occlusion}.bent.pfm", ao["bent"])
+        feat += f"; occlusion {rt.last_occlusion_ms():.2f} ms -> {a.occlusion}.open.pfm, {a.occlusion}.bent.pfm"
     n = int(spp.sum())
     print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / spp.size:.1f} spp), {stored} photons stored; "
           f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{feat}")

@@ -1854,6 +1854,9 @@ struct gi_ctx {
     DevBuf<double> d_dn_guides, d_dn_a, d_dn_b;
     // the guided upsampler (gi_upsample_*, gi_upsample.inc): a timer of its own; its low frame is packed into the denoiser's scratch (dn_reserve)
     EventTimer t_up;
+    // the occlusion pass (gi_render_occlusion_*, gi_occlusion.inc): a timer of its own, and the answer of its kernels' LDS request (as aov_lds_refused)
+    EventTimer t_ao;
+    int ao_lds_refused = -1;
     bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
     bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
     DevBuf<StreamCounters> d_stream_cnt;
@@ -2045,6 +2048,7 @@ static void clear_photon_map(gi_ctx* c)
 #include "gi_photon_build.inc"
 #include "gi_denoise.inc"
 #include "gi_upsample.inc"
+#include "gi_occlusion.inc"
 
 static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
 static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
@@ -2169,7 +2173,7 @@ void gi_destroy(gi_ctx* c)
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->h_wfcnt) (void)hipHostFree(c->h_wfcnt);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    for (EventTimer* t : {&c->t_frame, &c->t_feat, &c->t_dn, &c->t_up}) t->destroy();
+    for (EventTimer* t : {&c->t_frame, &c->t_feat, &c->t_dn, &c->t_up, &c->t_ao}) t->destroy();
     delete c;
 }
 

@@ -204,6 +204,33 @@ class RayTracer {
         return true;
     }
 
+    // ---- ADDITION (the reference has no such member): ambient occlusion and bent normals of the w x h frame run() renders (include/gi_hip.h states
+    // the definition): per pixel the share of the segments above the first hit that meet nothing within the radius, and their mean direction.
+    // op = nullptr: gi_occlusion_default_params (16 samples, 16 directions, a tenth of the scene box's diagonal).  gi_render_occlusion_host on the
+    // context of the per-ray methods; false with last_error() set when it cannot run (out is then left alone).
+    struct Occlusion {
+        int width = 0, height = 0, samples = 0, dirs = 0;
+        std::vector<double> open;                // [height][width]
+        std::vector<double> bent;                // [height][width][3]
+    };
+    bool renderOcclusion(int w, int h, Occlusion& out, const gi_occlusion_params* op = nullptr)
+    {
+        if (!ready()) return false;
+        const gi_render_params rp = params(w, h);
+        gi_occlusion_params p;
+        if (op) p = *op; else gi_occlusion_default_params(&p);
+        const size_t npix = (size_t)(w > 0 ? w : 0) * (size_t)(h > 0 ? h : 0);
+        std::vector<double> buf(npix * 4 + 4);
+        if (check(gi_render_occlusion_host(_st->ctx, &rp, &p, buf.data(), 1)) != 0) return false;
+        out.width = w; out.height = h; out.samples = p.n_samples; out.dirs = p.n_dirs;
+        out.open.resize(npix); out.bent.resize(npix * 3);
+        for (size_t i = 0; i < npix; i++) {
+            out.open[i] = buf[i * 4];
+            for (int k = 0; k < 3; k++) out.bent[i * 3 + k] = buf[i * 4 + 1 + k];
+        }
+        return true;
+    }
+
     // ---- ADDITION (the reference has no denoiser): the edge-avoiding a-trous filter of gi_denoise_host (include/gi_hip.h states the formula) on a
     // whole frame.  color = [height][width][3] linear radiance of a feat.width x feat.height frame, feat = what renderFeatures filled; out gets
     // [height][width][3].  dp = nullptr: gi_denoise_default_params; else its width / height are overwritten with feat's.  Needs a device, not a

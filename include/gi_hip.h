@@ -267,6 +267,40 @@ int gi_upsample_host(gi_ctx*, const gi_upsample_params*, const void* h_low_color
                      const void* h_features, int features_is_f64, void* h_out, int out_is_f64);
 int gi_last_upsample_ms(gi_ctx*, float* ms);
 
+/* Ambient occlusion and bent normals -- an ADDITION: the reference renders radiance only.  A buffer beside the first-hit features: how much of the
+ * hemisphere above the first surface is free of geometry within `radius`, and the mean free direction.  Per pixel and per sample
+ * s = 0 .. n_samples-1:
+ *   1. the primary ray and its first hit are those of gi_render_features_* and of the beauty pass: Halton index idx of sample s, RNG stream
+ *      (params->seed, idx), depth 0, the alpha test of RayTracer::trace (include/raytracer.h:382-478).
+ *   2. a miss: the sample's openness is 1, its bent vector 0 0 0.
+ *   3. a hit at P with shading normal N (minNorm of trace, include/raytracer.h:461): n = N * (1 / sqrt(dot(N, N))), Nf = -n if dot(n, ray.dir) > 0
+ *      else n (the side the ray came from), O = P + 0.0001 Nf (SHADOW_BIAS, the offset of the reference's shadow rays, include/raytracer.h:241).
+ *   4. for j = 0 .. n_dirs-1: u = (float) draw(purpose 32, a = j), v = (float) draw(purpose 33, a = j) of that stream (DESIGN.md "RNG contract";
+ *      gi_kat 8), d_j = hemisphereSample_cos(Nf, u, v, 1) (include/util.cpp:35-58), T_j = O + radius d_j.
+ *   5. segment j is open when RayTracer::visible (include/raytracer.h:280-319) finds no occluder between O and T_j: the ray (O, d_j), maxt = the
+ *      squared length of T_j - O as gi_visible forms it (x x + y y + z z), so gi_visible on the rows (O, T_j) states it.  The alpha test of a
+ *      translucent occluder draws with the light index 65536 + j, which no light has.  The medium is not asked: fog does not occlude.
+ *   6. open_s = (open segments) / n_dirs;  bent_s = (sum of d_j over the open j, ascending) / n_dirs per component.
+ * Per pixel: the f64 sums of open_s and bent_s over s in ascending order, divided once by n_samples.  bent is not renormalised: its length is a
+ * cosine-weighted openness, its direction the mean free direction.  The result does not depend on stripes, the octree walk in use or the launch.
+ * out [local_rows][width][4] = openness, bent x y z, float (out_is_f64 = 0) or double (1), rounded once on store.  Stripes as for the frame.
+ * radius = 0 stands for a tenth of the diagonal of the scene's root box: 0.1 sqrt((dx dx + dy dy) + dz dz).
+ * GI_E_INVALID: n_samples < 1 or taking the Halton index beyond 32 bits (as the feature pass), n_dirs outside 1 .. 64, a negative, NaN or infinite
+ * radius, a null pointer; GI_E_STATE: no scene.  The output is not touched then.
+ * gi_occlusion_default_params: 16 samples, 16 directions, radius 0.
+ * gi_render_occlusion_device: DEVICE pointer, asynchronous on the context's stream; gi_render_occlusion_host: HOST pointer.
+ * gi_last_occlusion_ms: device time of the last pass (HIP events around it); the frame's, the feature pass's, the denoiser's and the upsampler's
+ * times are left alone, and so is a progressive session. */
+typedef struct gi_occlusion_params {
+    int32_t n_samples;       /* >= 1 */
+    int32_t n_dirs;          /* 1 .. 64 segments per sample */
+    double radius;           /* length of a segment; 0 = a tenth of the scene box's diagonal */
+} gi_occlusion_params;
+void gi_occlusion_default_params(gi_occlusion_params*);
+int gi_render_occlusion_device(gi_ctx*, const gi_render_params*, const gi_occlusion_params*, void* d_out, int out_is_f64);
+int gi_render_occlusion_host(gi_ctx*, const gi_render_params*, const gi_occlusion_params*, void* h_out, int out_is_f64);
+int gi_last_occlusion_ms(gi_ctx*, float* ms);
+
 /* Function-level entry points (parity tests and the C++ API's public methods).  Host pointers.
  * replaces RayTracer::trace (include/raytracer.h:382-478): rays [n][6] origin + unit dir -> hit, entity, res [n][8]        */
 int gi_trace(gi_ctx*, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res);
