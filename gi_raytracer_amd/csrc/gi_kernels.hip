@@ -13,7 +13,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -275,6 +274,7 @@ struct PathRef {
     double (&T)[3]; double (&contrib)[3]; double (&gdir)[3]; double (&gcoef)[3]; double (&hpos)[3]; double& hu; double& hv; double (&L)[3];
 };
 #define GI_POOL_BYTES_PER_SLOT (sizeof(PoolRay) + sizeof(PoolHit) + sizeof(PoolThru) + sizeof(PoolGath) + 24)
+static_assert(GI_POOL_BYTES_PER_SLOT == kPoolRecordBytes, "the pool budget (gi_layout.h: plan_pool) counts this record");
 struct PathPool {
     PoolRay* ray; PoolHit* hit; PoolThru* thru; PoolGath* gath; double* L;
     __device__ __forceinline__ PathRef operator[](size_t s) const
@@ -1731,8 +1731,7 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
 // ================================================================================================= host side
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
-#define STG_COUNT_MAX 10
-struct StreamGrids { int lds_refused = 0; int pix = 0, trace = 0, shade = 0, shadow = 0, gather = 0, accum = 0, finish = 0, ad_gen = 0, ad_accum = 0, compact = 0; };
+#include "gi_stream.inc"   // StreamGrids, StreamWork, STG_*: what the context holds of the scheduler
 
 struct gi_ctx {
     int device = 0;
@@ -1810,17 +1809,12 @@ struct gi_ctx {
     unsigned int* h_wfcnt = nullptr;  // pinned host mirror of d_wfcnt
     DevBuf<double> d_lbuf;            // streaming variant: per-sample radiance of the current chunk
     DevBuf<unsigned long long> d_slot_sample;
-    DevBuf<uint32_t> d_qs[7];         // streaming queues: new, cont ping, cont pong, shade, gather, free ping, free pong
+    StreamWork work;                     // queues, keys and scratch of the stream passes (gi_stream.inc)
     DevBuf<StreamCtl> d_ctl;
-    DevBuf<uint32_t> d_gk[2], d_gv[2];   // gather sort: keys / values, in / out
-    DevBuf<uint32_t> d_stage[4];         // staging queues the producers append to, one segment per workgroup (k_st_compact closes the gaps)
-    DevBuf<double> d_stage_pos;
     DevBuf<ShadowQ> d_shq;               // shadow queries the shade stage put off (one light, wide records): entry i belongs to item i of the shade queue
     bool defer_shadows = true;           // GI_DEFER_SHADOWS=0: the shade kernel walks its shadow segments itself
     DevBuf<unsigned int> d_blkcnt;       // per-workgroup append counters [QC_KINDS][GI_MAX_PRODUCER_BLOCKS], 128 bytes apart
     DevBuf<uint32_t> d_segs;             // segment start of every producer workgroup
-    DevBuf<uint32_t> d_ck[2], d_cv;      // continuing-ray sort: keys in / out, unsorted slots
-    DevBuf<unsigned char> d_sort_tmp;
     DevBuf<uint32_t> d_rs_hist;          // gi_sort.inc: [digit][workgroup] counters of a radix pass
     bool rs_attr_set = false;
     StreamCtl* h_ctl = nullptr;
@@ -2268,446 +2262,7 @@ int gi_upload_photons(gi_ctx* c, const gi_photon_map_desc* d)
 
 int gi_local_rows(const gi_render_params* p) { return local_rows(p); }
 
-static int grid_for(gi_ctx* c, const void* kernel, size_t dyn_lds = 0, int block = GI_BLOCK)
-{
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, dyn_lds) != hipSuccess || per_cu <= 0) per_cu = 1;
-    return c->n_cu * per_cu;
-}
-
-static int render_megakernel(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp)
-{
-    HIP_TRY(c, hipMemsetAsync(c->d_tile_counter.p, 0, sizeof(unsigned int), c->stream));
-    if (c->count_enabled) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(Counters), c->stream));
-    const int grid = c->n_cu * 2;
-    HIP_TRY(c, c->t_frame.begin(c->stream));
-    if (c->count_enabled)
-        hipLaunchKernelGGL(k_render<true>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
-    else
-        hipLaunchKernelGGL(k_render<false>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_frame.end(c->stream));
-    c->last_launches = 1;
-    return GI_OK;
-}
-
-enum { STG_REGEN = 0, STG_TRACE, STG_SHADE, STG_SORT, STG_GATHER, STG_FINISH, STG_ACCUM, STG_OTHER, STG_SHADOW, STG_COUNT };
-static void stage_begin(gi_ctx* c, int stage)
-{
-    if (!c->stage_timing) return;
-    if (c->ev_used + 2 > c->ev_pool.size()) {
-        for (int k = 0; k < 2; k++) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; c->ev_pool.push_back(e); }
-    }
-    c->ev_stage.push_back(stage);
-    (void)hipEventRecord(c->ev_pool[c->ev_used], c->stream);
-}
-static void stage_end(gi_ctx* c)
-{
-    if (!c->stage_timing || c->ev_used + 2 > c->ev_pool.size()) return;
-    (void)hipEventRecord(c->ev_pool[c->ev_used + 1], c->stream);
-    c->ev_used += 2;
-}
-
-static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process may drive several devices (gi_group_*)
-{
-    StreamGrids& g = c->grids;
-    if (!g.trace) {
-        auto grid_of = [&](const auto& k, int block) { return grid_for(c, (const void*)k.fn, k.lds, block); };
-        ask_for_lds(kTrace, g.lds_refused); ask_for_lds(kShade, g.lds_refused); ask_for_lds(kShadow, g.lds_refused); ask_for_lds(kFinish, g.lds_refused);
-        g.pix = grid_for(c, (const void*)k_pix_init); g.trace = grid_of(st_trace(7, true, false), GI_TRACE_BLOCK);
-        g.shade = grid_of(st_shade(7, true, 0), GI_SHADE_BLOCK); g.shadow = grid_of(st_shadow(7, true, false), GI_SHADOW_BLOCK); g.gather = grid_for(c, (const void*)st_gather(false)); g.accum = grid_for(c, (const void*)k_st_accum);
-        g.compact = grid_for(c, (const void*)k_st_compact, 0, 256); g.finish = grid_of(st_finish(7, true, 0), GI_FINISH_BLOCK); g.ad_gen = grid_for(c, (const void*)k_ad_gen); g.ad_accum = grid_for(c, (const void*)k_ad_accum);
-    }
-    return g;
-}
-// The gather of a pass (stream_passes, gi_debug_gather_pass): n queries in leaf order (keys, vals = their slots), the caustic term added to their
-// radiance in lbuf; a wave per query (k_st_gather_wave) or a lane per query (k_st_gather)
-static int photon_key_bits(const Scene& S)   // of the gather queries' sort key: a leaf's rank, 0 .. n_pleaf
-{
-    int bits = 1;
-    while ((1u << bits) <= (uint32_t)S.n_pleaf) bits++;
-    return bits;
-}
-static void launch_gather(gi_ctx* c, bool wave, bool counting, const PathPool& pool, const uint32_t* keys, const uint32_t* vals, uint32_t n,
-                          const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
-{
-    if (wave)
-        hipLaunchKernelGGL(st_gather_wave(counting), dim3(std::min<uint32_t>((uint32_t)(5 * c->n_cu), (n + 3u) / 4u)), dim3(GI_GW_BLOCK), 0, c->stream, c->S, pool, keys, vals, n, slot_sample, sample0, lbuf, sc);
-    else
-        hipLaunchKernelGGL(st_gather(counting), dim3(stream_grids(c).gather), dim3(GI_BLOCK), 0, c->stream, c->S, pool, keys, vals, n, slot_sample, sample0, lbuf, sc);
-}
-// everything the pass loop needs for P paths in flight (the radiance buffer is the caller's)
-// a few lights, wide records: the shadow walks of the shade stage run in a kernel of their own (ShadowQ)
-static bool defers_shadows(const gi_ctx* c) { return c->defer_shadows && c->S.wnodes != nullptr && c->S.n_light >= 1 && c->S.n_light <= 4; }   // one query per light and shaded hit
-// need_table: the caller's passes read slot_sample (sample_of); a chunk whose samples are all in flight at once does without it
-static int stream_alloc(gi_ctx* c, uint32_t P, bool need_table)
-{
-    if (c->spool_slots < P) { HIP_TRY(c, c->d_spool.alloc((size_t)P * GI_POOL_BYTES_PER_SLOT)); c->spool_slots = P; }
-    if (need_table && c->d_slot_sample.n < P) HIP_TRY(c, c->d_slot_sample.alloc(P));
-    for (int k = 0; k < 7; k++) if (c->d_qs[k].n < P) HIP_TRY(c, c->d_qs[k].alloc(P));
-    for (int k = 0; k < 2; k++) { if (c->d_gk[k].n < P) HIP_TRY(c, c->d_gk[k].alloc(P)); if (c->d_gv[k].n < P) HIP_TRY(c, c->d_gv[k].alloc(P)); }
-    for (int k = 0; k < 2; k++) if (c->d_ck[k].n < P) HIP_TRY(c, c->d_ck[k].alloc(P));
-    const size_t PS = (size_t)P + 4096;   // segments are laid out as if every chunk of a producer's loop were full: up to one chunk of slack
-    for (int k = 0; k < 4; k++) if (c->d_stage[k].n < PS) HIP_TRY(c, c->d_stage[k].alloc(PS));
-    if (c->d_stage_pos.n < PS * 3) HIP_TRY(c, c->d_stage_pos.alloc(PS * 3));
-    if (defers_shadows(c) && c->d_shq.n < (size_t)P * (size_t)c->S.n_light) HIP_TRY(c, c->d_shq.alloc((size_t)P * (size_t)c->S.n_light));
-    if (!c->d_blkcnt.p) HIP_TRY(c, c->d_blkcnt.alloc((size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE));
-    if (!c->d_segs.p) HIP_TRY(c, c->d_segs.alloc(GI_MAX_PRODUCER_BLOCKS));
-    if (c->d_cv.n < P) HIP_TRY(c, c->d_cv.alloc(P));
-    {
-        const size_t need = (size_t)P * 8;   // gi_sort.inc ping-pongs through one more copy of keys and values
-        if (c->d_sort_tmp.n < need) HIP_TRY(c, c->d_sort_tmp.alloc(need));
-        if (!c->d_rs_hist.p) HIP_TRY(c, c->d_rs_hist.alloc((size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS));
-    }
-    if (!c->d_ctl.p) HIP_TRY(c, c->d_ctl.alloc(1));
-    if (!c->h_ctl) HIP_TRY(c, hipHostMalloc((void**)&c->h_ctl, sizeof(StreamCtl), hipHostMallocDefault));
-    return GI_OK;
-}
-// The pass loop: trace -> shade -> (keys, sort, gather) -> sort of the continuing rays, until nothing is in flight.  refill(n_free, qf)
-// starts up to n_free new paths in the slots of the free list qf (nullptr: slots 0 .. n_free - 1), writes them to c->d_qs[0] and
-// returns how many; `exhausted` tells that it will start no more.  A finished path leaves its radiance at lbuf[sample_of(slot) - sample0]:
-// slot_sample is the table the kernels keep that in, or nullptr when the caller knows that slot s carries sample sample0 + s throughout.
-static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, uint32_t n_free,
-                         const std::function<uint32_t(uint32_t, const uint32_t*, GenArgs&)>& refill, const bool& exhausted,
-                         volatile const int* cancel, int& launches)
-{
-    // the finisher's one-path-per-wave form: up to 2 paths per resident wave (more of them side by side are faster in groups of 16: benchmark frame's
-    // finisher 19.6 ms against 27.3 with 32 per wave; closed box 4.4 against 7.0) -- except for a small frame that gathers photons, such as a rank's share
-    // of the benchmark frame on 8 GPUs (66 M samples): its tail is a larger part of it and holds fewer paths, and a lone path's gather is the wave
-    // routine's: up to 32 (a 1/8 share 60.6 ms against 64.0; tools/fin_share.sh)
-    const bool small_frame = (unsigned long long)F.w * (unsigned long long)F.local_rows * (unsigned long long)std::max(F.max_samples, 1) < 200000000ull;
-    const uint32_t wave_factor = c->wave_factor ? c->wave_factor : ((small_frame && c->S.pcand) ? 32u : 2u);
-    const StreamGrids& G = stream_grids(c);
-    if (G.lds_refused) return fail(c, GI_E_HIP, "render: the device refused " + std::to_string(G.lds_refused) + " bytes of dynamic LDS per workgroup (the traversal kernels are laid out for gfx950's 160 KB per CU)");
-    hipStream_t st = c->stream;
-    const bool wide = c->S.wnodes != nullptr;
-    const int feat = scene_feat(c->S), trace_feat = scene_trace_feat(c->S);
-    // executed-work counters: compiled for the instances the BASELINE scenes run (triangles only, no medium, no texture, shadow walks put off)
-    const bool counting = c->count_stream;
-    if (counting && !(wide && defers_shadows(c) && !c->S.has_spheres && c->S.n_fog == 0 && c->S.n_tex == 0))
-        return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) cover triangle scenes without spheres, fog or textures, walked over wide records with one to four lights; use mode 1 (reference visits, megakernel) for this scene");
-    // The probe of the next ray in the deferred shade kernel (ray_leaves_scene): a ray that leaves the scene ends its path there.  Only where such a
-    // miss adds nothing and the trace stage's walk culls by content (no ambient light, no medium, content boxes installed, one light: the kernel instance that has the registers for it), and not in a counted
-    // frame (its trace_rays are compared with culling on and off).  With it a path that does not continue is released by the shade stage even
-    // with a gather pending (k_st_shade).
-    const bool no_ambient = c->S.ambient[0] == 0.0 && c->S.ambient[1] == 0.0 && c->S.ambient[2] == 0.0;
-    const uint32_t early_turns = (c->early_miss && wide && defers_shadows(c) && c->S.n_light == 1 && c->S.cboxes != nullptr && c->S.n_fog == 0 && no_ambient && !counting) ? c->early_turns : 0u;
-    const PathPool pool = make_path_pool(c->d_spool.p, c->spool_slots);
-    StreamCtl* ctl = c->d_ctl.p;
-    uint32_t* q_new = c->d_qs[0].p;
-    uint32_t* q_cont[2] = {c->d_qs[1].p, c->d_qs[2].p};
-    uint32_t* q_shade = c->d_qs[3].p;
-    uint32_t* q_gather = c->d_qs[4].p;
-    uint32_t* q_free[2] = {c->d_qs[5].p, c->d_qs[6].p};
-    uint32_t n_cont = 0;
-    const uint32_t* qf = nullptr;
-    int ping = 0;
-    for (;;) {
-        if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
-        // new paths of this pass: either samples the trace kernel starts itself (gen, streaming frames) or paths a caller prepared in
-        // the new-path queue (adaptive rounds) -- refill() says which by filling gen.n_gen or returning a count
-        GenArgs gen;
-        memset(&gen, 0, sizeof gen);
-        gen.F = F;
-        const uint32_t n_prepared = refill(n_free, qf, gen);
-        const uint32_t n_new = n_prepared + gen.n_gen;
-        if (n_new + n_cont == 0) break;
-        uint32_t* qcont_out = q_cont[ping];
-        const uint32_t* qcont_in = q_cont[ping ^ 1];
-        if (exhausted && n_new == 0 && n_cont <= c->finish_threshold && !counting) {   // (a counted frame runs its stragglers through the counting passes)
-            if (c->d_fin_cnt.n < 16) HIP_TRY(c, c->d_fin_cnt.alloc(16));
-            HIP_TRY(c, hipMemsetAsync(c->d_fin_cnt.p, 0, 16 * sizeof(unsigned int), st));
-            const uint32_t* fq_in = qcont_in;
-            uint32_t* fq_out = qcont_out;
-            const size_t n_stage = std::min<size_t>(c->finish_plan.size(), 15);
-            for (size_t k = 0; k < n_stage; k++) {
-                const int lanes = c->finish_plan[k].first, vertices = k + 1 == n_stage ? GI_MAX_DEPTH + 1 : c->finish_plan[k].second;
-                const unsigned int* n_in_dev = k == 0 ? nullptr : c->d_fin_cnt.p + (k - 1);
-                stage_begin(c, STG_FINISH);
-                auto fin = [&](int mode) {
-                    const FinishK fin_k = st_finish(feat, wide, mode);
-                    hipLaunchKernelGGL(fin_k.fn, dim3(G.finish), dim3(GI_FINISH_BLOCK), fin_k.lds, st, c->S, F.seed, pool, slot_sample, sample0,
-                                       fq_in, n_in_dev, n_cont, lanes, vertices, fq_out, c->d_fin_cnt.p + k, lbuf, (wave_factor << 16) | (c->coop_factor & 0xffffu));
-                };
-                fin(0);
-                if (wide && lanes <= 0) { fin(1); fin(2); launches += 2; }
-                stage_end(c);
-                launches++;
-                uint32_t* t = const_cast<uint32_t*>(fq_in); fq_in = fq_out; fq_out = t;   // both are this chunk's continuation queues
-            }
-            break;
-        }
-        HIP_TRY(c, hipMemsetAsync(ctl, 0, sizeof(StreamCtl), st));
-        // The free list of this pass has one reader, the refill of the next.  Once refill has started its last sample (`exhausted`, set by the call
-        // above: this pass still reads the previous list, nobody reads the one it would write; rounds never hand a freed slot out again) the kernels
-        // get no free queue and skip its appends, the compaction leaves the queue out, and n_free stays 0.  GI_KEEP_FREE_LIST=1: written always.
-        const bool want_free = c->keep_free_list || !exhausted;
-        uint32_t* qfree_out = want_free ? q_free[ping] : nullptr;
-        uint32_t* const stage_free_trace = want_free ? c->d_stage[1].p : nullptr;
-        uint32_t* const stage_free_shade = want_free ? c->d_stage[3].p : nullptr;
-        if (G.trace > GI_MAX_PRODUCER_BLOCKS || G.shade > GI_MAX_PRODUCER_BLOCKS) return fail(c, GI_E_STATE, "render: more producer workgroups than per-workgroup counters");
-        unsigned int* bc = c->d_blkcnt.p;
-        const size_t bc_bytes = (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE * sizeof(unsigned int);
-        // trace: hits -> staging 0, finished paths -> staging 1; compacted into the shade queue and the head of the free list
-        HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
-        StreamCounters* const sc = counting ? c->d_stream_cnt.p : nullptr;
-        const TraceK trace_k = st_trace(trace_feat, wide, counting);
-        stage_begin(c, STG_TRACE); hipLaunchKernelGGL(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, gen, q_new, n_prepared, qcont_in, n_cont, bc, c->d_segs.p,
-                           c->d_stage[0].p, stage_free_trace, lbuf, c->refill_min, sc); stage_end(c);
-        {
-            CompactJob job;
-            memset(&job, 0, sizeof job);
-            job.st[0] = {c->d_stage[0].p, q_shade, 1}; job.n_streams[0] = 1; job.kind[0] = QC_SHADE; job.total_field[0] = 0;
-            job.st[1] = {c->d_stage[1].p, qfree_out, 1}; job.n_streams[1] = 1; job.kind[1] = want_free ? QC_FREE : -1; job.total_field[1] = 4;
-            job.kind[2] = -1; job.gather_queue = -1;
-            stage_begin(c, STG_OTHER); hipLaunchKernelGGL(k_st_compact, dim3(G.compact), dim3(256), 0, st, c->S, job, bc, c->d_segs.p, (uint32_t)G.trace, ctl); stage_end(c);
-        }
-        // A pass of continuing rays leaves the trace stage in the rays' coherence order, which scatters the shade stage's reads and writes of
-        // the path records over the whole pool.  The shade queue is put into slot order for it (a radix sort of slot / place pairs); the shadow
-        // queries still land at the place the trace stage gave the item, so the shadow walks keep that (coherent) order.
-        const uint32_t* q_shade_use = q_shade;
-        const uint32_t* q_orig = nullptr;
-        if (c->sort_shade && n_cont > 0) {
-            int sbits = 1;
-            while ((1ull << sbits) < (unsigned long long)c->spool_slots) sbits++;
-            uint32_t* const tk = reinterpret_cast<uint32_t*>(c->d_sort_tmp.p);
-            const uint32_t bound = n_new + n_cont;      // every item of the trace stage may have hit something
-            stage_begin(c, STG_SORT);
-            hipLaunchKernelGGL(k_iota, dim3(std::min<uint32_t>((bound + 1023u) / 1024u, 4096u)), dim3(1024), 0, st, c->d_gv[0].p, bound);
-            const int rc = rs_sort_pairs(c, q_shade, c->d_gk[1].p, c->d_gv[0].p, c->d_gv[1].p, tk, tk + bound, bound, reinterpret_cast<const uint32_t*>(&ctl->n_shade), std::min(c->sort_shade_lo, sbits - 1), sbits, c->d_rs_hist.p);
-            if (rc) return rc;
-            stage_end(c);
-            q_shade_use = c->d_gk[1].p;
-            q_orig = c->d_gv[1].p;
-        }
-        ShadowQ* const shq = defers_shadows(c) ? c->d_shq.p : nullptr;
-        // shade: continuing rays (slot + key) -> staging 0 / 1, gather queries (slot + position) -> staging 2 / pos, finished paths -> staging 3
-        HIP_TRY(c, hipMemsetAsync(bc, 0, bc_bytes, st));
-        const bool many = c->S.n_light > 1;
-        const ShadeK shade_k = st_shade(feat, wide, shq ? (many ? 2 : 1) : 0);
-        stage_begin(c, STG_SHADE); hipLaunchKernelGGL(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, st, c->S, F.seed, pool, slot_sample, sample0, q_shade_use, ctl, bc, c->d_segs.p,
-                           c->d_stage[0].p, c->d_stage[1].p, c->d_stage[2].p, c->d_stage_pos.p, stage_free_shade, lbuf, shq, q_orig, early_turns);
-        stage_end(c);
-        if (shq) {   // the walks it put off; before the gather of the same vertices (the order in which a path's radiance is summed)
-            const ShadowK shadow_k = st_shadow(feat, many, counting);
-            stage_begin(c, STG_SHADOW);
-            hipLaunchKernelGGL(shadow_k.fn, dim3(G.shadow), dim3(GI_SHADOW_BLOCK), shadow_k.lds, st, c->S, F.seed, pool, shq, ctl, lbuf, c->refill_min, sc);
-            stage_end(c);
-            launches++;
-        }
-        {
-            CompactJob job;
-            memset(&job, 0, sizeof job);
-            // streams in queue order: [0] continuing slot, [1] its coherence key, [2] gather slot, [3] gather position (3 doubles = 6 words), [4] freed slot
-            job.st[0] = {c->d_stage[0].p, c->d_cv.p, 1}; job.st[1] = {c->d_stage[1].p, c->d_ck[0].p, 1};
-            job.n_streams[0] = 2; job.kind[0] = QC_CONT; job.total_field[0] = 1;
-            job.st[2] = {c->d_stage[2].p, c->d_gv[0].p, 1};                                                     // gather: slot -> values of the sort by leaf
-            job.st[3] = {reinterpret_cast<const uint32_t*>(c->d_stage_pos.p), c->d_gk[0].p, 6};                 //         position -> key (leaf)
-            job.n_streams[1] = 2; job.kind[1] = QC_GATHER; job.total_field[1] = 2; job.gather_queue = c->S.n_pnode > 0 ? 1 : -1;
-            if (c->S.n_pnode <= 0) job.kind[1] = -1;                                                            // no photon map: no gather queries
-            job.st[4] = {c->d_stage[3].p, qfree_out, 1};
-            job.n_streams[2] = 1; job.kind[2] = want_free ? QC_FREE : -1; job.total_field[2] = 3; job.free_base_from_trace = 1;
-            stage_begin(c, STG_OTHER); hipLaunchKernelGGL(k_st_compact, dim3(G.compact), dim3(256), 0, st, c->S, job, bc, c->d_segs.p, (uint32_t)G.shade, ctl); stage_end(c);
-        }
-        launches += 4;
-        HIP_TRY(c, hipMemcpyAsync(c->h_ctl, ctl, sizeof(StreamCtl), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        const uint32_t n_gather = c->h_ctl->n_gather;
-        if (counting) c->stream_shaded += c->h_ctl->n_shade;
-        if (c->S.n_pnode > 0 && n_gather > 0) {
-            const int bits = photon_key_bits(c->S);
-            stage_begin(c, STG_SORT);
-            {
-                uint32_t* const tk = reinterpret_cast<uint32_t*>(c->d_sort_tmp.p);
-                const int rc = rs_sort_pairs(c, c->d_gk[0].p, c->d_gk[1].p, c->d_gv[0].p, c->d_gv[1].p, tk, tk + n_gather, n_gather, nullptr, 0, bits, c->d_rs_hist.p);
-                if (rc) return rc;
-            }
-            stage_end(c);
-            stage_begin(c, STG_GATHER);
-            launch_gather(c, c->S.pcand && n_gather < c->gather_wave_below, counting, pool, c->d_gk[1].p, c->d_gv[1].p, n_gather, slot_sample, sample0, lbuf, sc);   // few queries: a wave each
-            stage_end(c);
-            launches += 2;
-        }
-        n_cont = c->h_ctl->n_cont;
-        n_free = c->h_ctl->n_free;
-        if (n_cont > 0) {   // continuing rays in coherence order for the next trace pass
-            stage_begin(c, STG_SORT);
-            if (c->sort_cont) {
-                uint32_t* const tk = reinterpret_cast<uint32_t*>(c->d_sort_tmp.p);
-                const int rc = rs_sort_pairs(c, c->d_ck[0].p, c->d_ck[1].p, c->d_cv.p, qcont_out, tk, tk + n_cont, n_cont, nullptr, c->sort_lo_bit, 27, c->d_rs_hist.p);
-                if (rc) return rc;
-            }
-            else HIP_TRY(c, hipMemcpyAsync(qcont_out, c->d_cv.p, (size_t)n_cont * 4, hipMemcpyDeviceToDevice, st));   // GI_SORT_CONT=0: queue order (tuning aid)
-            stage_end(c);
-            launches++;
-        }
-        qf = qfree_out;
-        ping ^= 1;
-        if (getenv("GI_DEBUG_WF")) {
-            fprintf(stderr, "[st] new %u cont %u free %u gather %u\n", n_new, n_cont, n_free, n_gather);
-            if (counting) {   // what this pass executed (tuning aid): cumulative counters, printed per pass
-                StreamCounters h;
-                if (hipMemcpy(&h, c->d_stream_cnt.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
-                    fprintf(stderr, "[cnt] trace rays %llu walks %llu records %llu boxes %llu cboxes %llu leaves %llu eboxes %llu tris %llu | shadow rays %llu records %llu boxes %llu cboxes %llu leaves %llu eboxes %llu tris %llu | gather q %llu cand %llu\n",
-                            h.trace_rays, h.trace[0], h.trace[1], h.trace[2], h.trace[3], h.trace[4], h.trace[6], h.trace[5], h.shadow_rays, h.shadow[1], h.shadow[2], h.shadow[3], h.shadow[4], h.shadow[6], h.shadow[5], h.gather_queries, h.gather_cand);
-            }
-        }
-    }
-    return GI_OK;
-}
-
-// Samples [s_begin, s_end) of every pixel of a fixed-spp frame, folded into the records `pix` (st_pixel_xy order) in sample order, one chunk of
-// samples at a time; init: the records are put in their initial state first (a frame from sample 0).  The one-shot frame (render_streaming) is
-// [0, max_samples) on d_pix with init; a step of a progressive session is [E, E') on the session's records.  s_done (optional) follows the
-// samples folded so far, so that a cancelled call tells how far the records got.
-static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, int s_end, bool init, void* d_out, int out_is_f64, int32_t* d_spp,
-                          volatile const int* cancel, int* s_done)
-{
-    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;   // valid pixels only, enumerated in 8x8-tile order (st_pixel_xy)
-    const int spp = s_end - s_begin;
-    // Paths in flight: as many as fit -- the whole frame when HBM allows (1080p x 256 spp = 531 M paths = 119 GB of PathRec on a
-    // 288 GB part).  More paths per pass = fewer passes and, above all, better-sorted (more coherent) queues.
-    size_t slots_budget = c->pool_slots_max;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t held = c->d_spool.n + c->d_lbuf.n * 8 + (c->d_qs[0].n + c->d_qs[6].n) * 4 * 7 + c->d_shq.n * sizeof(ShadowQ);   // ours, re-usable
-            const size_t per_slot = GI_POOL_BYTES_PER_SLOT + 8 + 13 * 4 + 24 + 40 + (defers_shadows(c) ? sizeof(ShadowQ) * (size_t)c->S.n_light : 0);   // record, sample id, 13 queue / key words, sort scratch, staging queues, shadow queries
-            const size_t lbuf = (size_t)n_pix * (size_t)std::min<size_t>((size_t)spp, c->lbuf_bytes_max / ((size_t)n_pix * 24)) * 24;
-            const size_t avail = (size_t)((double)(free_b + held) * 0.90);
-            if (avail > lbuf) slots_budget = std::min(slots_budget, (avail - lbuf) / per_slot);
-            else slots_budget = std::min<size_t>(slots_budget, 1u << 20);
-        }
-    }
-    const uint32_t P = (uint32_t)std::max<size_t>(64, std::min<size_t>(std::min<size_t>(slots_budget, 0xfffffff0u), (size_t)n_pix * (size_t)spp));
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)spp, c->lbuf_bytes_max / ((size_t)n_pix * 24)));
-    // The sample table.  A chunk of ns samples per pixel whose n_pix * ns samples all fit the pool is started whole by the first pass: refill hands
-    // the trace stage slots 0 .. n_pix * ns - 1 in order (qf == nullptr) with sample ids sample0 + slot, and has nothing left to start in a freed slot
-    // later.  The table would be the identity plus sample0 for the whole chunk, so the kernels are given none (sample_of) -- 8 bytes per sample less
-    // to write in the trace stage and a scattered read less per gather query.  Decided per chunk (fits); the table is allocated when the largest
-    // chunk of this call needs it, and stays in per_slot above either way: a later call may need it.  GI_SAMPLE_IDENTITY=0: always a table.
-    auto fits = [&](int ns) { return c->sample_identity && (size_t)P >= (size_t)n_pix * (size_t)ns; };
-    int rc = stream_alloc(c, P, !fits(chunk));
-    if (rc) return rc;
-    if (c->d_lbuf.n < (size_t)n_pix * chunk * 3) HIP_TRY(c, c->d_lbuf.alloc((size_t)n_pix * chunk * 3));
-    const StreamGrids& G = stream_grids(c);
-    hipStream_t st = c->stream;
-    int launches = 0;
-    c->ev_used = 0; c->ev_stage.clear();
-    if (c->count_stream) {
-        if (!c->d_stream_cnt.p) HIP_TRY(c, c->d_stream_cnt.alloc(1));
-        HIP_TRY(c, hipMemsetAsync(c->d_stream_cnt.p, 0, sizeof(StreamCounters), st));
-        c->stream_shaded = 0;
-    }
-    HIP_TRY(c, c->t_frame.begin(st));
-    if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
-    if (c->d_pixtab.n < n_pix) HIP_TRY(c, c->d_pixtab.alloc(n_pix));
-    hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
-    launches++;
-    for (int s0 = s_begin; s0 < s_end; s0 += chunk) {
-        const int ns = std::min(chunk, s_end - s0);
-        const unsigned long long sample0 = (unsigned long long)s0 * n_pix, sample_end = (unsigned long long)(s0 + ns) * n_pix;
-        unsigned long long next = sample0;
-        bool exhausted = false;
-        auto refill = [&](uint32_t n_free, const uint32_t* qf, GenArgs& gen) -> uint32_t {   // path regeneration: free slots take the next samples
-            const uint32_t n_new = (uint32_t)std::min<unsigned long long>(n_free, sample_end - next);
-            gen.q_free = qf; gen.n_gen = n_new; gen.n_pix = n_pix; gen.id_base = next; gen.sample_begin = sample0; gen.s_begin = s0;
-            gen.pixtab = c->d_pixtab.p; gen.inv_n_pix = 1.0 / (double)n_pix;
-            next += n_new;
-            exhausted = next >= sample_end;
-            return 0;                                                                          // nothing prepared: the trace kernel starts them
-        };
-        if (getenv("GI_DEBUG_WF")) fprintf(stderr, "[st] chunk of %d samples: pool %u slots, sample table %s\n", ns, P, fits(ns) ? "off" : "on");
-        rc = stream_passes(c, F, fits(ns) ? nullptr : c->d_slot_sample.p, sample0, c->d_lbuf.p, P, refill, exhausted, cancel, launches);   // pass 0: every slot is free
-        if (rc) return rc;
-        stage_begin(c, STG_ACCUM); hipLaunchKernelGGL(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp); stage_end(c);
-        launches++;
-        if (s_done) *s_done = s0 + ns;
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_frame.end(st));
-    c->last_launches = launches;
-    return GI_OK;
-}
-
-static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
-    return stream_samples(c, F, c->d_pix.p, 0, F.max_samples, true, d_out, out_is_f64, d_spp, cancel, nullptr);
-}
-
-// Adaptive sampling (min_samples != max_samples, include/raytracer.h:108-148), and every frame of render mode 2: synchronous rounds --
-// in a round every pixel that still wants samples starts those it is certain to take (k_ad_gen), the paths run through the streaming
-// passes (sorted queues, octree records in LDS, wave-cooperative gather, staged finisher), and k_ad_accum applies the variance rule in
-// sample order.  With min_samples == max_samples this renders the fixed-spp frame of render_streaming, a round of up to B samples at a time.
-// pix: the records the rounds work on (padded 8x8 tiles); init: put them in their initial state first.  The one-shot frame (render_adaptive) is d_pix
-// with init; a step of a progressive session is the session's records with the step's cap E' in F.max_samples -- the same loop, which then stops at E'.
-static uint32_t rounds_records(const Frame& F) { return (uint32_t)(((F.w + 7) >> 3) * ((F.local_rows + 7) >> 3)) * 64u; }
-static bool rounds_fit(const Frame& F) { return (size_t)((F.w + 7) >> 3) * (size_t)((F.local_rows + 7) >> 3) * 64 <= 0xfffffff0ull; }   // the records, and so a round of them, have 32-bit path slots
-static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    if (!rounds_fit(F)) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
-    const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (wf_pixel_xy)
-    int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->pool_slots_max, 0xfffffff0ull) / n_pix));
-    B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
-    const size_t slots = (size_t)n_pix * (size_t)B;
-    int rc = stream_alloc(c, (uint32_t)slots, true);   // k_ad_gen names every path's place in the radiance buffer
-    if (rc) return rc;
-    if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
-    if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
-    if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 2 * sizeof(unsigned int), hipHostMallocDefault));
-    const StreamGrids& G = stream_grids(c);
-    hipStream_t st = c->stream;
-    unsigned int* cnt = c->d_wfcnt.p;
-    int launches = 0;
-    c->ev_used = 0; c->ev_stage.clear();
-    HIP_TRY(c, c->t_frame.begin(st));
-    if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
-    bool any = F.max_samples > 0 && F.min_samples > 0;
-    if (!any) {   // 0 samples per pixel still has to write the initial colour
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
-        launches++;
-    }
-    while (any) {
-        if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
-        stage_begin(c, STG_REGEN);
-        hipLaunchKernelGGL(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, st, c->S, F, pix, make_path_pool(c->d_spool.p, c->spool_slots), c->d_slot_sample.p, n_pix, B, c->d_qs[0].p, cnt + 0);
-        stage_end(c);
-        launches++;
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt, cnt, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        uint32_t pending = c->h_wfcnt[0];          // paths started by this round, already in the new-path queue
-        const bool exhausted = true;
-        auto refill = [&](uint32_t, const uint32_t*, GenArgs&) -> uint32_t { const uint32_t n = pending; pending = 0; return n; };
-        rc = stream_passes(c, F, c->d_slot_sample.p, 0ull, c->d_lbuf.p, 0u, refill, exhausted, cancel, launches);
-        if (rc) return rc;
-        stage_begin(c, STG_ACCUM);
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
-        stage_end(c);
-        launches++;
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 1, cnt + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        any = c->h_wfcnt[1] > 0;
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_frame.end(st));
-    c->last_launches = launches;
-    return GI_OK;
-}
-
-static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    const uint32_t n_pix = rounds_records(F);
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
-    return run_rounds(c, F, c->d_pix.p, true, d_out, out_is_f64, d_spp, cancel);
-}
-
-// fixed sample count: the streaming pool with path regeneration (the refill schedule); adaptive sampling: rounds (sample-order decisions) on the
-// same passes; mode 2: rounds for every frame, a second schedule of the fixed-spp frames
-static bool uses_refill_schedule(const gi_ctx* c, const Frame& F) { return c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0; }
+#include "gi_stream.inc"   // the scheduler: stream_samples, run_rounds, stream_passes and what the render entries below choose between
 
 int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
@@ -2771,10 +2326,11 @@ int gi_last_render_ms(gi_ctx* c, float* ms, int32_t* n_launches)
     float frame_ms = 0;
     HIP_TRY(c, c->t_frame.read(&frame_ms));
     for (int k = 0; k < STG_COUNT_MAX; k++) c->stage_ms[k] = 0;
+    const bool debug_stages = getenv("GI_DEBUG_STAGES") != nullptr;   // read at every call
     for (size_t k = 0; k + 1 < c->ev_used + 1 && k / 2 < c->ev_stage.size() && k + 1 < c->ev_pool.size() && k < c->ev_used; k += 2) {
         float t = 0;
         if (hipEventElapsedTime(&t, c->ev_pool[k], c->ev_pool[k + 1]) == hipSuccess) c->stage_ms[c->ev_stage[k / 2]] += t;
-        if (getenv("GI_DEBUG_STAGES")) fprintf(stderr, "[stage] %d %.3f ms\n", c->ev_stage[k / 2], t);
+        if (debug_stages) fprintf(stderr, "[stage] %d %.3f ms\n", c->ev_stage[k / 2], t);
     }
     if (ms) *ms = frame_ms;
     if (n_launches) *n_launches = c->last_launches;

@@ -745,4 +745,36 @@ inline bool make_frame(const gi_render_params* p, Frame& F, std::string& err)
     return true;
 }
 
+// ---- the pool budget of a fixed-spp call (gi_stream.inc: stream_samples): how many paths are in flight, P, and how many samples per pixel
+// the radiance buffer takes at a time, chunk.  As many paths as fit -- the whole frame when HBM allows (1080p x 256 spp = 531 M paths = 123 GB
+// of path records on a 288 GB part): more paths per pass are fewer passes and, above all, better-sorted (more coherent) queues.
+// What a slot is budgeted, in bytes: the terms beside the record are kBudgetWorkBytes, which gi_stream.inc asserts to cover what its workspace
+// table (kStreamWork) really allocates per slot.  The figure is somewhat larger than that table's (124 against 112 bytes), and P of
+// the benchmark frame, which is bound by HBM, follows from it: changing a term changes that frame's speed.
+constexpr size_t kPoolRecordBytes = 232;         // the field arrays of PathPool (gi_kernels.hip: GI_POOL_BYTES_PER_SLOT, asserted there)
+constexpr size_t kBudgetSampleIdBytes = 8;       // the slot -> sample table
+constexpr size_t kBudgetQueueBytes = 13 * 4;     // 13 queue / key words
+constexpr size_t kBudgetSortBytes = 24;          // sort scratch
+constexpr size_t kBudgetStagingBytes = 40;       // staging queues
+constexpr size_t kBudgetWorkBytes = kBudgetSampleIdBytes + kBudgetQueueBytes + kBudgetSortBytes + kBudgetStagingBytes;
+static_assert(kBudgetWorkBytes == 124, "the pool of the benchmark frame is sized with this figure");
+struct PoolPlan { uint32_t P; int chunk; };
+// free_b: free device memory, when mem_known (the query succeeded); held_b: what the context already holds of its workspaces and would re-use;
+// n_deferred_lights: shadow queries (ShadowQ) per slot, 0 where the shade stage walks its shadow segments itself.  No HIP call: the CPU suite runs it.
+inline PoolPlan plan_pool(bool mem_known, size_t free_b, size_t held_b, uint32_t n_pix, int spp, size_t pool_slots_max, size_t lbuf_bytes_max, int n_deferred_lights)
+{
+    size_t slots_budget = pool_slots_max;
+    if (mem_known) {
+        const size_t per_slot = kPoolRecordBytes + kBudgetWorkBytes + sizeof(ShadowQ) * (size_t)n_deferred_lights;
+        const size_t lbuf = (size_t)n_pix * (size_t)std::min<size_t>((size_t)spp, lbuf_bytes_max / ((size_t)n_pix * 24)) * 24;
+        const size_t avail = (size_t)((double)(free_b + held_b) * 0.90);
+        if (avail > lbuf) slots_budget = std::min(slots_budget, (avail - lbuf) / per_slot);
+        else slots_budget = std::min<size_t>(slots_budget, 1u << 20);
+    }
+    PoolPlan plan;
+    plan.P = (uint32_t)std::max<size_t>(64, std::min<size_t>(std::min<size_t>(slots_budget, 0xfffffff0u), (size_t)n_pix * (size_t)spp));
+    plan.chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)spp, lbuf_bytes_max / ((size_t)n_pix * 24)));
+    return plan;
+}
+
 }  // namespace gi

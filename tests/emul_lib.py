@@ -43,6 +43,8 @@ def lib():
         L.emul_set_cull.argtypes = [vp, C.c_int]
         L.emul_leaf_order.argtypes = [vp, C.c_int, _dp, C.c_int, _ip, _ip]
         L.emul_kat.argtypes = [C.c_int, C.c_int, _dp, C.c_int, _dp]
+        L.emul_pool_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
+        L.emul_pool_plan.restype = None
         _LIB = L
     return _LIB
 

@@ -259,4 +259,10 @@ double emul_rng(uint64_t seed, uint32_t stream, uint32_t depth, uint32_t purpose
     r.depth = depth;
     return rng_draw(r, purpose, a, b);
 }
+// the pool budget of a fixed-spp call (gi_layout.h: plan_pool), as stream_samples calls it; out2 = {P, chunk}
+void emul_pool_plan(int mem_known, uint64_t free_b, uint64_t held_b, uint32_t n_pix, int spp, uint64_t pool_slots_max, uint64_t lbuf_bytes_max, int n_deferred_lights, int64_t* out2)
+{
+    const PoolPlan plan = plan_pool(mem_known != 0, (size_t)free_b, (size_t)held_b, n_pix, spp, (size_t)pool_slots_max, (size_t)lbuf_bytes_max, n_deferred_lights);
+    out2[0] = (int64_t)plan.P; out2[1] = (int64_t)plan.chunk;
+}
 }
