@@ -146,13 +146,13 @@ double dn_inv(double sigma, double scale) { return sigma != 0.0 ? scale / (sigma
 // larger frame replaces them (after the stream has drained: an earlier pass may still read them).  The upsampler packs its low frame here too.
 int dn_reserve(gi_ctx* c, size_t n_pix)
 {
-    if (c->d_dn_guides.n >= n_pix * 8) return GI_OK;
+    if (c->dn.d_guides.n >= n_pix * 8) return GI_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipError_t e = c->d_dn_guides.alloc(n_pix * 8);
-    if (e == hipSuccess) e = c->d_dn_a.alloc(n_pix * 3);
-    if (e == hipSuccess) e = c->d_dn_b.alloc(n_pix * 3);
+    hipError_t e = c->dn.d_guides.alloc(n_pix * 8);
+    if (e == hipSuccess) e = c->dn.d_a.alloc(n_pix * 3);
+    if (e == hipSuccess) e = c->dn.d_b.alloc(n_pix * 3);
     if (e != hipSuccess) {                      // none of the three is kept: the size of the guide records stands for all of them
-        c->d_dn_guides.release(); c->d_dn_a.release(); c->d_dn_b.release();
+        c->dn.d_guides.release(); c->dn.d_a.release(); c->dn.d_b.release();
         return fail(c, GI_E_HIP, std::string("denoiser scratch: ") + hipGetErrorString(e));
     }
     return GI_OK;
@@ -173,7 +173,7 @@ void gi_denoise_default_params(gi_denoise_params* p)
 int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color, int color_is_f64, const void* d_features, int features_is_f64, void* d_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_dn.reset();
+    c->dn.timer.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!d_color || !d_features || !d_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
@@ -185,16 +185,16 @@ int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color
         const int rc = dn_reserve(c, n_pix);
         if (rc != GI_OK) return rc;
     }
-    HIP_TRY(c, c->t_dn.begin(c->stream));
+    HIP_TRY(c, c->dn.timer.begin(c->stream));
     if (it == 0) {
         if (d_out != d_color || (out_is_f64 != 0) != (color_is_f64 != 0))
             hipLaunchKernelGGL(k_dn_copy, dim3((unsigned)((n_pix * 3 + 255) / 256)), dim3(256), 0, c->stream, n_pix * 3, d_color, color_is_f64, d_out, out_is_f64);
     } else {
         const int demod = p->demodulate != 0;
         hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((n_pix * 8 + 255) / 256)), dim3(256), 0, c->stream, n_pix, d_color, color_is_f64, d_features, features_is_f64, demod,
-                           c->d_dn_a.p, c->d_dn_guides.p);
-        double* src = c->d_dn_a.p;
-        double* dst = c->d_dn_b.p;
+                           c->dn.d_a.p, c->dn.d_guides.p);
+        double* src = c->dn.d_a.p;
+        double* dst = c->dn.d_b.p;
         for (int i = 0; i < it; i++) {
             const int s = 1 << i;
             DnGrid G;
@@ -206,19 +206,19 @@ int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color
             inv.c = dn_inv(p->sigma_color, (double)(1u << (2 * i)));                   // the colour sigma halves per level
             inv.n = dn_inv(p->sigma_normal, 1.0); inv.z = dn_inv(p->sigma_depth, 1.0); inv.a = dn_inv(p->sigma_albedo, 1.0);
             const size_t blocks = (size_t)G.tiles_x * tiles_y * s * s;
-            hipLaunchKernelGGL(k_dn_level, dim3((unsigned)blocks), dim3(GI_DN_BLOCK), 0, c->stream, G, inv, src, c->d_dn_guides.p, dst, i == it - 1 ? 1 : 0, demod, d_out, out_is_f64);
+            hipLaunchKernelGGL(k_dn_level, dim3((unsigned)blocks), dim3(GI_DN_BLOCK), 0, c->stream, G, inv, src, c->dn.d_guides.p, dst, i == it - 1 ? 1 : 0, demod, d_out, out_is_f64);
             std::swap(src, dst);
         }
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_dn.end(c->stream));
+    HIP_TRY(c, c->dn.timer.end(c->stream));
     return GI_OK;
 }
 
 int gi_denoise_host(gi_ctx* c, const gi_denoise_params* p, const void* h_color, int color_is_f64, const void* h_features, int features_is_f64, void* h_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_dn.reset();
+    c->dn.timer.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!h_color || !h_features || !h_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
@@ -231,13 +231,13 @@ int gi_denoise_host(gi_ctx* c, const gi_denoise_params* p, const void* h_color, 
     if (e == hipSuccess) e = d_out.alloc(ob);
     if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
     const int rc = gi_denoise_device(c, p, d_color.p, color_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
-    return rc != GI_OK ? rc : finish_to_host(c, "denoise_host", {{h_out, d_out.p, ob}}, &c->t_dn);
+    return rc != GI_OK ? rc : finish_to_host(c, "denoise_host", {{h_out, d_out.p, ob}}, &c->dn.timer);
 }
 
 int gi_last_denoise_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->t_dn.read(ms));
+    HIP_TRY(c, c->dn.timer.read(ms));
     return GI_OK;
 }
 

@@ -1,12 +1,65 @@
 // gi_entries.inc -- the function-level and debug entries of the C ABI: host arrays in, one kernel (or one pass), host arrays out.  Included by
-// gi_kernels.hip inside its extern "C" block, after the frame entries.  Each reads: argument and state checks, buffers (Entry, gi_kernels.hip:
+// gi_kernels.hip behind the passes.  Each reads: argument and state checks, buffers (Entry, below:
 // element counts once per buffer), the launch, and Entry::run copies the outputs back in the order they were named.
+namespace {
+
+// The photon map's box: the caller's, or the scene's
+void frame_box(const gi_ctx* c, const double* box6, double* out)
+{
+    for (int k = 0; k < 3; k++) { out[k] = box6 ? box6[k] : c->S.root_bmin[k]; out[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
+}
+
+// The device side of a function-level entry, after its argument and state checks.  in() uploads a caller's array, out() allocates a
+// result and notes where it goes (h == nullptr: an optional output nobody asked for -- the kernel still writes it), scratch() is memory of this
+// call alone; each takes the element count, once.  run(launch) launches (unless a buffer failed), asks for the launch's status, waits for the
+// stream and copies the results back in the order of the out() calls.  launch returns nothing, or a failure it has recorded with fail().
+struct Entry {
+    gi_ctx* c;
+    const char* what;
+    hipError_t e;
+    DevBuf<unsigned char> buf[16];
+    ToHost outs[6];
+    int n_buf = 0, n_out = 0;
+    Entry(gi_ctx* c_, const char* what_) : c(c_), what(what_), e(hipSetDevice(c_->device)) {}
+    template <class T> T* scratch(size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].alloc(count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> const T* in(const T* h, size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].upload(reinterpret_cast<const unsigned char*>(h), count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<const T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> T* out(T* h, size_t count)
+    {
+        T* d = scratch<T>(count);
+        if (d && n_out == 6) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) outs[n_out++] = ToHost{h, d, count * sizeof(T)};
+        return d;
+    }
+    template <class Launch> int run(Launch launch)
+    {
+        if (e == hipSuccess) {
+            if constexpr (std::is_void<decltype(launch())>::value) launch();
+            else if (const int rc = launch()) return rc;
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return fail(c, GI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return finish_to_host(c, what, outs, (size_t)n_out);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
 #define GI_GRID(n) dim3((unsigned)(((n) + GI_BLOCK - 1) / GI_BLOCK)), dim3(GI_BLOCK)
 
 int gi_trace(gi_ctx* c, int32_t n, const double* rays, int32_t* hit, int32_t* ent, double* res)
 {
     if (!c || n < 0 || (n && (!rays || !hit || !ent || !res))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "trace: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "trace: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "trace");
@@ -20,7 +73,7 @@ int gi_trace(gi_ctx* c, int32_t n, const double* rays, int32_t* hit, int32_t* en
 int gi_visible(gi_ctx* c, int32_t n, const double* q, int32_t* vis)
 {
     if (!c || n < 0 || (n && (!q || !vis))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "visible");
@@ -32,7 +85,7 @@ int gi_visible(gi_ctx* c, int32_t n, const double* q, int32_t* vis)
 int gi_visible_rays(gi_ctx* c, int32_t n, const double* rays, const double* mt, int32_t* vis)
 {
     if (!c || n < 0 || (n && (!rays || !mt || !vis))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "visible: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "visible_rays");
@@ -45,7 +98,7 @@ int gi_visible_rays(gi_ctx* c, int32_t n, const double* rays, const double* mt, 
 int gi_gather(gi_ctx* c, int32_t n, const double* q, double* res3, int32_t* n_cand)
 {
     if (!c || n < 0 || (n && (!q || !res3))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "gather: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "gather: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "gather");
@@ -58,7 +111,7 @@ int gi_gather(gi_ctx* c, int32_t n, const double* q, double* res3, int32_t* n_ca
 int gi_radiance(gi_ctx* c, int32_t n, const double* rays, const uint32_t* stream, uint64_t seed, double* out3)
 {
     if (!c || n < 0 || (n && (!rays || !stream || !out3))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "radiance: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "radiance: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "radiance");
@@ -71,7 +124,7 @@ int gi_radiance(gi_ctx* c, int32_t n, const double* rays, const uint32_t* stream
 int gi_emit_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed, double* photons_out, int32_t cap, int64_t* tries_out)
 {
     if (!c || count < 0 || cap < 0 || (cap && !photons_out)) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "emit_photons: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "emit_photons: no scene uploaded");
     const long long total = (long long)count * c->S.n_light;
     if (tries_out) *tries_out = 0;
     if (total == 0) return 0;
@@ -103,7 +156,7 @@ int gi_build_photon_map(gi_ctx* c, int32_t n, const double* photons, const doubl
 {
     if (!c || n < 0 || (n && !photons)) return GI_E_INVALID;
     c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "build_photon_map: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "build_photon_map: no scene uploaded");
     HIP_TRY(c, hipSetDevice(c->device));
     double box[6];
     frame_box(c, box6, box);
@@ -116,7 +169,7 @@ int gi_trace_photons(gi_ctx* c, int32_t count, int32_t max_depth, uint64_t seed,
 {
     if (!c || count < 0) return GI_E_INVALID;
     c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "trace_photons: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "trace_photons: no scene uploaded");
     const long long total = (long long)count * c->S.n_light;
     if (tries_out) *tries_out = 0;
     if (total > 0x7fffffffLL) return fail(c, GI_E_INVALID, "trace_photons: count too large");
@@ -159,11 +212,11 @@ int gi_debug_photon_tables(gi_ctx* c, int32_t* n_node, int32_t* n_range, int32_t
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const Scene& S = c->S;
     if (n_node) *n_node = S.n_pnode;
-    if (n_range) *n_range = S.n_pnode > 0 ? c->n_prange : 0;
+    if (n_range) *n_range = S.n_pnode > 0 ? c->photons.n_prange : 0;
     if (n_photon) *n_photon = S.n_photon;
     if (S.n_pnode <= 0) return GI_OK;
     if (nodes128) HIP_TRY(c, hipMemcpy(nodes128, S.pnodes, (size_t)S.n_pnode * sizeof(PNode), hipMemcpyDeviceToHost));
-    if (ranges2) HIP_TRY(c, hipMemcpy(ranges2, S.pranges, (size_t)c->n_prange * sizeof(PRange), hipMemcpyDeviceToHost));
+    if (ranges2) HIP_TRY(c, hipMemcpy(ranges2, S.pranges, (size_t)c->photons.n_prange * sizeof(PRange), hipMemcpyDeviceToHost));
     if (pos3 && S.n_photon) HIP_TRY(c, hipMemcpy(pos3, S.ph_pos, (size_t)S.n_photon * 24, hipMemcpyDeviceToHost));
     if (dircol6 && S.n_photon) HIP_TRY(c, hipMemcpy(dircol6, S.ph_dircol, (size_t)S.n_photon * 48, hipMemcpyDeviceToHost));
     return GI_OK;
@@ -247,7 +300,7 @@ int gi_debug_gather_pass(gi_ctx* c, int32_t n, const double* q6, int32_t kernel,
 int gi_debug_leaf_order(gi_ctx* c, int32_t n, const double* rays, int32_t cap, int32_t* leaf_out, int32_t* n_out)
 {
     if (!c || n < 0 || cap < 1 || (n && (!rays || !leaf_out || !n_out))) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "leaf_order: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "leaf_order: no scene uploaded");
     if (n == 0) return GI_OK;
     const size_t N = (size_t)n;
     Entry e(c, "leaf_order");
@@ -295,3 +348,5 @@ int gi_halton_index(gi_ctx* c, int32_t width, int32_t height, int32_t n, const u
     uint32_t* d_o = e.out(out, N);
     return e.run([&] { hipLaunchKernelGGL(k_halton_index, GI_GRID(n), 0, c->stream, make_halton_enum((unsigned)width, (unsigned)height), n, d_i, d_o); });
 }
+
+}  // extern "C"

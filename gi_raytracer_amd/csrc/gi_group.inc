@@ -1,5 +1,5 @@
-// gi_group.inc -- several GPUs from one process (gi_group_*).  Included by gi_kernels.hip at the end of its extern "C" block, which this file
-// leaves once for its C++ helpers.
+// gi_group.inc -- several GPUs from one process (gi_group_*).  Included by gi_kernels.hip last: a group drives whole contexts
+// through their C entries.
 //
 // ================================================================================================= several GPUs from one process
 // The reference parallelises RayTracer::run over image rows with OpenMP (include/raytracer.h:93).  A group does the same over the GPUs of a
@@ -12,7 +12,6 @@ struct gi_group {
     std::vector<DevBuf<int32_t>> d_spp;
     std::string err;
 };
-}  // extern "C" (C++ helpers below)
 #include <thread>
 namespace {
 int group_fail(gi_group* g, int code, const std::string& m) { if (g) g->err = m; return code; }
@@ -186,3 +185,5 @@ int gi_group_render_device(gi_group* g, const gi_render_params* p, int32_t strip
                             return GI_OK;
                         });
 }
+
+}  // extern "C"

@@ -1,15 +1,16 @@
-// gi_kernels.hip -- gfx950 kernels + the C ABI of include/gi_hip.h.
+// gi_kernels.hip -- the gfx950 kernels of the renderer; the C ABI of include/gi_hip.h is in the .inc files included at the end.
 //
 // Kernels (all one ray / one pixel per lane, 64-wide waves, scene tables read through L1/L2):
 //   k_render     the pixel loop of RayTracer::run with the whole path inside (include/raytracer.h:93-160,167-579)
 //   k_trace / k_visible / k_gather / k_radiance   function-level entry points (parity tests, public C++ methods)
 //   k_emit       RayTracer::tracePhotons (include/raytracer.h:582-715), one (photon index, light) per lane
-// Host side of this file: device layouts (8 direction-ordered copies of the octree, leaf-ordered photons, Halton tables)
-// and the gi_* entry points.  No CPU fallback exists: every entry needs a HIP device.
+// This file holds kernels only.  The host side -- the context, the scheduler and the gi_* entry points -- is in the .inc files listed at its end,
+// which also hold the kernels of the sort, the photon-map build and the auxiliary passes.  No CPU fallback exists: every entry needs a HIP device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -305,18 +306,6 @@ __device__ __forceinline__ void pool_begin(const PathPool& pool, size_t slot, co
     r.stream = sample; r.depth = 0; r.pad_[0] = 0u; r.pad_[1] = 0u;
     pool.ray[slot] = r;
 }
-static PathPool make_path_pool(void* base, size_t n)
-{
-    PathPool P;
-    char* b = static_cast<char*>(base);
-    P.ray = reinterpret_cast<PoolRay*>(b); b += n * sizeof(PoolRay);
-    P.hit = reinterpret_cast<PoolHit*>(b); b += n * sizeof(PoolHit);
-    P.thru = reinterpret_cast<PoolThru*>(b); b += n * sizeof(PoolThru);
-    P.gath = reinterpret_cast<PoolGath*>(b); b += n * sizeof(PoolGath);
-    P.L = reinterpret_cast<double*>(b);
-    return P;
-}
-
 __device__ __forceinline__ uint32_t wave_append(unsigned int* counter, bool pred)
 {
     const unsigned long long mask = __ballot(pred);
@@ -1579,49 +1568,6 @@ __global__ __launch_bounds__(GI_BLOCK) void k_pix_wanting(Frame F, const PixRec*
     }
 }
 
-// First-hit feature buffers (gi_render_features_*; gi_device.h: aov_sample): one lane per pixel of this rank's rows in the 8x8-tile order of
-// st_pixel_xy, so a wave is a tile and all its lanes are on the same sample index s -- rays as coherent as the new paths of k_st_trace, on the same
-// records in LDS and the same wave-uniform leaves.  A lane loops over s (Halton index of sample s = that of sample 0 + s * inc), keeps its eight
-// sums in registers and writes once: no queue, no sort, no per-sample buffer, no atomics, and nothing of the path pool.
-// out [local_rows][w][8] = albedo rgb, normal xyz, depth, coverage: the f64 sums in ascending s, divided once by n.  ids [local_rows][w][2]
-// (optional) = entity and material of sample 0's hit, -1 on a miss.
-#ifndef GI_AOV_BLOCK
-// One workgroup per CU next to the 160 KB of records and boxes, as k_st_trace -- but of 512 lanes: the lane keeps a pixel's eight sums and the
-// frame constants next to the walk, which at the 128 registers of a 1024-lane workgroup spills 408 B per lane (wide triangle instance); at 512
-// it fits in 227 without scratch.  Measured on the benchmark frame (caustics 1920x1080, n = 256): 1024 lanes 76.0 ms, 512 lanes 66.5 ms.
-#define GI_AOV_BLOCK 512
-#endif
-template <int FEAT, int WIDE>
-__global__ __launch_bounds__(GI_AOV_BLOCK) void k_aov(Scene S, Frame F, uint32_t n_pix, int32_t n, void* out, int out_f64, int32_t* ids)
-{
-    const typename LdsSrc<WIDE>::type N = LdsSrc<WIDE>::stage_for_trace(S);   // ends with a barrier
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pix) return;
-    int x, ly;
-    st_pixel_xy(F, p, x, ly);
-    uint32_t idx = halton_index(F.he, 0u, (uint32_t)x, (uint32_t)global_row(F, ly));
-    double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int32_t ent0 = -1, mat0 = -1;
-    for (int32_t s = 0; s < n; s++, idx += F.he.inc) {
-        AovSample a;
-        if (!aov_sample<FEAT>(S, N, F, F.seed, idx, a)) continue;
-        sum[0] += a.albedo.x; sum[1] += a.albedo.y; sum[2] += a.albedo.z;
-        sum[3] += a.normal.x; sum[4] += a.normal.y; sum[5] += a.normal.z;
-        sum[6] += a.depth; sum[7] += 1.0;
-        if (s == 0) { ent0 = a.ent; mat0 = a.mat; }
-    }
-    const size_t o = (size_t)ly * F.w + x;
-    const double dn = (double)n;
-    if (out_f64) {
-        double* q = (double*)out + o * 8;
-        for (int k = 0; k < 8; k++) q[k] = sum[k] / dn;
-    } else {
-        float* q = (float*)out + o * 8;
-        for (int k = 0; k < 8; k++) q[k] = (float)(sum[k] / dn);
-    }
-    if (ids) { ids[o * 2] = ent0; ids[o * 2 + 1] = mat0; }
-}
-
 __global__ __launch_bounds__(GI_BLOCK) void k_trace(Scene S, int n, const double* rays, int32_t* hit, int32_t* ent, double* res)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1728,731 +1674,17 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
     if (i < n) out[i] = halton_index(he, sxy[i * 3], sxy[i * 3 + 1], sxy[i * 3 + 2]);
 }
 
-// ================================================================================================= host side
-#include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
-
-#include "gi_stream.inc"   // StreamGrids, StreamWork, STG_*: what the context holds of the scheduler
-
-struct gi_ctx {
-    int device = 0;
-    StreamGrids grids;                // launch grids of the streaming kernels on this context's device
-    hipStream_t stream = nullptr;
-    std::string err;
-    bool have_scene = false;
-    Scene S{};
-    DevBuf<TNode> d_tnodes;
-    DevBuf<WNode> d_wnodes;
-    DevBuf<TexD> d_texs;
-    DevBuf<TriUV> d_tri_uv;
-    DevBuf<unsigned char> d_tex_pixels;
-    DevBuf<double> d_tex_lut;
-    DevBuf<int32_t> d_wleaf_id;
-    DevBuf<float> d_cboxes;           // content boxes of the wide records' children
-    DevBuf<uint32_t> d_cuse;
-    SceneSwitches sw;                 // gi_set_wide_nodes, gi_set_content_culling, gi_set_entity_boxes, GI_CLIP_BOXES, GI_WALK_CUT (apply_switches)
-    bool flat_candidates = true;      // GI_FLAT_CANDIDATES=0: k_st_gather finds a leaf's k-th candidate through its range list, no k_st_gather_wave
-    DevBuf<uint32_t> d_pcand_off;
-    DevBuf<double> d_pcand, d_pcand_dc;
-    uint32_t gather_wave_below = 200000u;    // GI_GATHER_WAVE_BELOW: gather passes with fewer queries give every query a wave (k_st_gather_wave)
-    bool descent_jump = true;         // GI_DESCENT_JUMP=0: the fast descent of the gather keys starts at the root
-    DevBuf<int32_t> d_pjump;          // its jump table (gi_device.h: gather_find_leaf_fast)
-    DevBuf<double> d_pjump_aux;
-    bool sort_cont = true;            // GI_SORT_CONT=0: continuing rays stay in queue order
-    bool sort_shade = true;           // GI_SORT_SHADE=0: the shade stage takes a pass of continuing rays in the order the trace stage left them
-    int sort_shade_lo = 5;            // GI_SORT_SHADE_LO: lowest slot bit that sort looks at (32 neighbouring records = 7 KB stay in the trace stage's order)
-    int sort_lo_bit = 0;              // GI_SORT_LO_BIT: lowest key bit the sort of the continuing rays looks at (27-bit key: octant, 18 Morton bits, 6 direction bits)
-    uint32_t refill_min = 32;         // GI_REFILL_MIN: idle lanes of a wave that make k_st_trace hand out new rays (64: lockstep waves)
-    bool pn_planes_ok = false;        // the uploaded photon octree qualifies for the one-record-per-level descent
-    int32_t n_prange = 0;             // entries of d_pranges in use
-    DevBuf<int32_t> d_refs;
-    DevBuf<LeafTri> d_leaf_tris;
-    DevBuf<double> d_leaf_boxes;          // every leaf reference's own box (gi_device.h: entity_survivors)
-    DevBuf<double> d_trace_boxes;         // the closest-hit walk's boxes (gi_device.h: trace_wide_step)
-    DevBuf<float> d_tcboxes;              // and the content boxes made of them
-    DevBuf<uint32_t> d_tcuse;
-    bool lights_clear = false;            // of the scene last uploaded: no entity within a light's radius + the shadow bias of it (gi_layout.h)
-    double cut_margin = -1;               // of the scene last uploaded
-    bool scene_clipped = false;           // its trace boxes differ from the whole ones
-    DevBuf<TriGeom> d_tris;
-    DevBuf<TriShade> d_shade;
-    DevBuf<Mat> d_mats;
-    DevBuf<LightD> d_lights;
-    DevBuf<FogD> d_fogs;
-    DevBuf<double> d_fog_grid;
-    DevBuf<PNode> d_pnodes;
-    DevBuf<PRange> d_pranges;
-    DevBuf<int32_t> d_pleaf_rank, d_prank_leaf, d_n_pleaf;
-    DevBuf<PDescent> d_pdescent;
-    bool pdescent_ready = false, pjump_ready = false;   // d_pdescent / d_pjump hold the tables of the current photon map (apply_switches)
-    bool fast_descent = true;         // GI_FAST_DESCENT=0: every gather query walks the full photon-octree records
-    DevBuf<double> d_ph_pos, d_ph_dircol;
-    DevBuf<HaltonDim> d_hdims;
-    DevBuf<uint16_t> d_htable;
-    DevBuf<unsigned int> d_tile_counter;
-    DevBuf<Counters> d_counters;
-    // wavefront pipeline workspaces (grown on demand, kept between frames)
-    DevBuf<uint32_t> d_pixtab;               // k_pixel_table of the frame being rendered
-    DevBuf<unsigned char> d_spool;        // paths of the streaming pipeline: field arrays (PathPool), GI_POOL_BYTES_PER_SLOT each
-    size_t spool_slots = 0;
-    DevBuf<PixRec> d_pix;
-    // a progressive session (gi_progressive_*): the pixel records it owns between steps -- everything else a step uses is the shared scratch above and below
-    struct Progressive {
-        bool open = false;
-        gi_render_params rp{};
-        Frame F{};                    // make_frame(rp): max_samples is the session's own
-        int schedule = 0;             // 0: refill pipeline, records in st_pixel_xy order; 1: synchronous rounds, records in padded 8x8 tiles (wf_pixel_xy)
-        int32_t sample_end = 0;       // E: every pixel has been offered samples [0, E)
-        uint32_t n_rec = 0;
-        DevBuf<PixRec> pix;
-    } prog;
-    DevBuf<unsigned int> d_wfcnt;    // rounds (render_adaptive): [0] paths started by k_ad_gen, [1] pixels still wanting samples
-    unsigned int* h_wfcnt = nullptr;  // pinned host mirror of d_wfcnt
-    DevBuf<double> d_lbuf;            // streaming variant: per-sample radiance of the current chunk
-    DevBuf<unsigned long long> d_slot_sample;
-    StreamWork work;                     // queues, keys and scratch of the stream passes (gi_stream.inc)
-    DevBuf<StreamCtl> d_ctl;
-    DevBuf<ShadowQ> d_shq;               // shadow queries the shade stage put off (one light, wide records): entry i belongs to item i of the shade queue
-    bool defer_shadows = true;           // GI_DEFER_SHADOWS=0: the shade kernel walks its shadow segments itself
-    DevBuf<unsigned int> d_blkcnt;       // per-workgroup append counters [QC_KINDS][GI_MAX_PRODUCER_BLOCKS], 128 bytes apart
-    DevBuf<uint32_t> d_segs;             // segment start of every producer workgroup
-    DevBuf<uint32_t> d_rs_hist;          // gi_sort.inc: [digit][workgroup] counters of a radix pass
-    bool rs_attr_set = false;
-    StreamCtl* h_ctl = nullptr;
-    size_t lbuf_bytes_max = (size_t)16 << 30;
-    // per-stage device time of the last streaming frame (HIP events around every launch, same stream)
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<int> ev_stage;        // stage id of event pair k (events 2k, 2k+1)
-    size_t ev_used = 0;
-    bool stage_timing = true;
-    float stage_ms[STG_COUNT_MAX] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int render_mode = 0;              // 0 streaming passes (fixed spp) or rounds (adaptive), 1 megakernel, 2 synchronous rounds always (gi_set_render_mode)
-    size_t pool_slots_max = (size_t)1 << 30;    // upper bound on paths in flight; the actual pool is also bounded by free HBM (render_streaming)
-    uint32_t finish_threshold = 1u << 17;   // GI_FINISH_THRESHOLD: paths left when the finisher takes over
-    bool sample_identity = true;      // GI_SAMPLE_IDENTITY=0: the stream passes always keep the slot -> sample table, also where it would be the identity (stream_samples)
-    bool keep_free_list = false;      // GI_KEEP_FREE_LIST=1: the stream passes write the free list in every pass, also where nothing will read it (stream_passes)
-    bool early_miss = true;           // GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (stream_passes)
-    uint32_t early_turns = 4;         // GI_EARLY_MISS_TURNS: turns of the walk that probe may take before it gives the ray to the trace stage
-    uint32_t wave_factor = 0;         // GI_WAVE_FACTOR: finisher stages with at most this many paths per resident wave run one path per wave; 0 = by the size of the frame (stream_passes)
-    uint32_t coop_factor = 4;         // finisher stages with at most 4 x coop_factor x (resident waves) paths run one path per group of 16 lanes (at most 2 x: one per wave)
-    // finisher stages {paths per wave (0: spread evenly over the resident waves), max vertices}; the last stage runs to MAX_DEPTH.
-    // Measured on the default frame (tools/stripe_probe.py): one full-wave stage 60 ms, this plan 51 ms; on 1/8 of the rows 40 -> 30 ms.
-    std::vector<std::pair<int, int>> finish_plan = {{0, 1}, {0, 1}, {0, 1}, {0, 1}, {0, 2}, {0, 2}, {0, 4}, {0, 8}, {0, GI_MAX_DEPTH + 1}};
-    DevBuf<unsigned int> d_fin_cnt;
-    EventTimer t_frame;               // around the kernels of the last gi_render_* / gi_progressive_step_* call
-    int last_launches = 0;
-    EventTimer t_feat;                // the feature pass (gi_render_features_*) keeps its own: it leaves the frame's times (t_frame, ev_pool) alone
-    int aov_lds_refused = -1;         // -1: the k_aov instances were not asked for their LDS yet; else as StreamGrids::lds_refused
-    // the denoiser (gi_denoise_*, gi_denoise.inc): a timer of its own again, and its scratch -- the guide records [h][w][8] and two colour
-    // buffers [h][w][3], f64, sized on first use and kept
-    EventTimer t_dn;
-    DevBuf<double> d_dn_guides, d_dn_a, d_dn_b;
-    // the guided upsampler (gi_upsample_*, gi_upsample.inc): a timer of its own; its low frame is packed into the denoiser's scratch (dn_reserve)
-    EventTimer t_up;
-    // the occlusion pass (gi_render_occlusion_*, gi_occlusion.inc): a timer of its own, and the answer of its kernels' LDS request (as aov_lds_refused)
-    EventTimer t_ao;
-    int ao_lds_refused = -1;
-    bool count_enabled = false;       // gi_set_counters(ctx, 1): the megakernel counts the reference's visits (per-node walk)
-    bool count_stream = false;        // gi_set_counters(ctx, 2): the streaming kernels count what they execute (StreamCounters)
-    DevBuf<StreamCounters> d_stream_cnt;
-    unsigned long long stream_shaded = 0;   // shaded hits of the last counted frame (sum of the shade queues' lengths)
-    Counters last_counters{};
-    int n_cu = 256;
-};
-
-namespace {
-
-int fail(gi_ctx* c, int code, const std::string& msg)
-{
-    if (c) c->err = msg;
-    return code;
-}
-#define HIP_TRY(c, expr)                                                                                     \
-    do {                                                                                                     \
-        hipError_t e__ = (expr);                                                                             \
-        if (e__ != hipSuccess) return fail((c), GI_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
-    } while (0)
-
-// The photon map's box: the caller's, or the scene's
-void frame_box(const gi_ctx* c, const double* box6, double* out)
-{
-    for (int k = 0; k < 3; k++) { out[k] = box6 ? box6[k] : c->S.root_bmin[k]; out[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
-}
-
-// A frame of npix pixels that `render(d_out, d_spp)` leaves in scratch of this call, copied to the caller's arrays (gi_render_host, gi_progressive_step_host)
-template <class Render>
-int frame_to_host(gi_ctx* c, const char* what, size_t npix, void* h_out, int out_is_f64, int32_t* h_spp, Render render)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = npix * 3 * (out_is_f64 ? 8 : 4);
-    DevBuf<unsigned char> d_out;
-    DevBuf<int32_t> d_spp;
-    HIP_TRY(c, d_out.alloc(bytes));
-    if (h_spp) HIP_TRY(c, d_spp.alloc(npix));
-    const int rc = render((void*)d_out.p, d_spp.p);
-    return rc != GI_OK ? rc : finish_to_host(c, what, {{h_out, d_out.p, bytes}, to_host(h_spp, d_spp, npix)});
-}
-
-// The device side of a function-level entry (gi_entries.inc), after its argument and state checks.  in() uploads a caller's array, out() allocates a
-// result and notes where it goes (h == nullptr: an optional output nobody asked for -- the kernel still writes it), scratch() is memory of this
-// call alone; each takes the element count, once.  run(launch) launches (unless a buffer failed), asks for the launch's status, waits for the
-// stream and copies the results back in the order of the out() calls.  launch returns nothing, or a failure it has recorded with fail().
-struct Entry {
-    gi_ctx* c;
-    const char* what;
-    hipError_t e;
-    DevBuf<unsigned char> buf[16];
-    ToHost outs[6];
-    int n_buf = 0, n_out = 0;
-    Entry(gi_ctx* c_, const char* what_) : c(c_), what(what_), e(hipSetDevice(c_->device)) {}
-    template <class T> T* scratch(size_t count)
-    {
-        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].alloc(count * sizeof(T)) : hipErrorOutOfMemory;
-        return e == hipSuccess ? reinterpret_cast<T*>(buf[n_buf++].p) : nullptr;
-    }
-    template <class T> const T* in(const T* h, size_t count)
-    {
-        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].upload(reinterpret_cast<const unsigned char*>(h), count * sizeof(T)) : hipErrorOutOfMemory;
-        return e == hipSuccess ? reinterpret_cast<const T*>(buf[n_buf++].p) : nullptr;
-    }
-    template <class T> T* out(T* h, size_t count)
-    {
-        T* d = scratch<T>(count);
-        if (d && n_out == 6) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) outs[n_out++] = ToHost{h, d, count * sizeof(T)};
-        return d;
-    }
-    template <class Launch> int run(Launch launch)
-    {
-        if (e == hipSuccess) {
-            if constexpr (std::is_void<decltype(launch())>::value) launch();
-            else if (const int rc = launch()) return rc;
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) return fail(c, GI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return finish_to_host(c, what, outs, (size_t)n_out);
-    }
-};
-
-}  // namespace
-
-__global__ __launch_bounds__(1024) void k_rs_scan(uint32_t* ghist, uint32_t total);   // gi_sort.inc
-// The Scene fields that follow the context's switches, from the uploaded tables and the switches alone (gi_layout.h: apply_scene_switches, which
-// the CPU suite's emulator calls too).  Every upload, every change of the photon map and every gi_set_* of a switch ends here, and nothing else
-// assigns these fields.
-static void apply_switches(gi_ctx* c)
-{
-    SceneTables T;
-    T.wnodes = c->d_wnodes.p; T.cboxes = c->d_cboxes.p; T.n_cboxes = c->d_cboxes.n;
-    T.leaf_boxes = c->d_leaf_boxes.p; T.trace_boxes = c->d_trace_boxes.p;
-    T.tcboxes = c->d_tcboxes.p; T.n_tcboxes = c->d_tcboxes.n; T.tcuse = c->d_tcuse.p;
-    T.cut_margin = c->cut_margin; T.clipped = c->scene_clipped; T.lights_clear = c->lights_clear;
-    T.pn_planes_ok = c->pn_planes_ok;
-    T.pdescent = c->pdescent_ready ? c->d_pdescent.p : nullptr;   // (build_photon_tables)
-    T.pjump = c->pjump_ready ? c->d_pjump.p : nullptr;
-    apply_scene_switches(c->S, T, c->sw);
-}
-
-// The tables derived from the photon map c->S points at: the sort key of the gather queries (k_pleaf_rank), the leaves' candidate lists and, for a
-// map that qualifies whatever the switches are now, the split records of the fast descent and its jump table (apply_switches decides on their use)
-static int build_photon_tables(gi_ctx* c)
-{
-    Scene& S = c->S;
-    S.pleaf_rank = nullptr; S.prank_leaf = nullptr; S.n_pleaf = 0; S.pcand_off = nullptr; S.pcand = nullptr; S.pcand_dc = nullptr;
-    c->pdescent_ready = false; c->pjump_ready = false;
-    if (S.n_pnode <= 0) return GI_OK;
-    if (c->d_pleaf_rank.n < (size_t)S.n_pnode) { HIP_TRY(c, c->d_pleaf_rank.alloc((size_t)S.n_pnode)); HIP_TRY(c, c->d_prank_leaf.alloc((size_t)S.n_pnode)); }
-    if (!c->d_n_pleaf.p) HIP_TRY(c, c->d_n_pleaf.alloc(1));
-    hipLaunchKernelGGL(k_pleaf_rank, dim3(1), dim3(1024), 0, c->stream, S.pnodes, S.n_pnode, c->d_pleaf_rank.p, c->d_prank_leaf.p, c->d_n_pleaf.p);
-    HIP_TRY(c, hipGetLastError());
-    int32_t n = 0;
-    HIP_TRY(c, hipMemcpyAsync(&n, c->d_n_pleaf.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    S.pleaf_rank = c->d_pleaf_rank.p; S.prank_leaf = c->d_prank_leaf.p; S.n_pleaf = n;
-    S.pcand_off = nullptr; S.pcand = nullptr; S.pcand_dc = nullptr;
-    if (c->flat_candidates && n > 0) {
-        if (c->d_pcand_off.n < (size_t)n + 1) HIP_TRY(c, c->d_pcand_off.alloc((size_t)n + 1));
-        hipLaunchKernelGGL(k_pcand_count, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c->stream, S.pnodes, c->d_prank_leaf.p, n, c->d_pcand_off.p);
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, c->stream, c->d_pcand_off.p, (uint32_t)n + 1u);
-        HIP_TRY(c, hipGetLastError());
-        uint32_t total = 0;
-        HIP_TRY(c, hipMemcpyAsync(&total, c->d_pcand_off.p + n, sizeof total, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (total > 0 && total < 0x7fffffffu) {
-            if (c->d_pcand.n < (size_t)total * 3) { HIP_TRY(c, c->d_pcand.alloc((size_t)total * 3)); HIP_TRY(c, c->d_pcand_dc.alloc((size_t)total * 6)); }
-            hipLaunchKernelGGL(k_pcand_fill, dim3(1024), dim3(256), 0, c->stream, S.pnodes, S.pranges, S.ph_pos, S.ph_dircol, c->d_prank_leaf.p, n, c->d_pcand_off.p, c->d_pcand.p, c->d_pcand_dc.p);
-            HIP_TRY(c, hipGetLastError());
-            S.pcand_off = c->d_pcand_off.p; S.pcand = c->d_pcand.p; S.pcand_dc = c->d_pcand_dc.p;
-        }
-    }
-    // the split records of the descent and the map's own box (gather_find_leaf_fast); the one-record-per-level layout only (children from the parent's planes)
-    if (c->fast_descent && c->pn_planes_ok) {
-        if (c->d_pdescent.n < (size_t)S.n_pnode) HIP_TRY(c, c->d_pdescent.alloc((size_t)S.n_pnode));
-        hipLaunchKernelGGL(k_pdescent, dim3((unsigned)((S.n_pnode + 255) / 256)), dim3(256), 0, c->stream, S.pnodes, S.n_pnode, c->d_pdescent.p);
-        HIP_TRY(c, hipGetLastError());
-        PNode root;
-        HIP_TRY(c, hipMemcpyAsync(&root, S.pnodes, sizeof(PNode), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 3; k++) { S.pmap_bmin[k] = root.bmin[k]; S.pmap_bmax[k] = root.bmax[k]; }
-        c->pdescent_ready = true;
-        if (c->descent_jump) {
-            double ext = 0.0, host[7];
-            for (int k = 0; k < 3; k++) { ext = std::max(ext, root.bmax[k] - root.bmin[k]); S.pjump_cell[k] = (root.bmax[k] - root.bmin[k]) / (double)GI_PJUMP_N; S.pjump_inv[k] = (double)GI_PJUMP_N / (root.bmax[k] - root.bmin[k]); }
-            bool ok = ext > 0.0;
-            for (int k = 0; k < 3; k++) { host[k] = root.bmin[k]; host[3 + k] = S.pjump_cell[k]; if (!(S.pjump_cell[k] > 0.0) || !std::isfinite(S.pjump_inv[k])) ok = false; }
-            if (ok) {
-                if (c->d_pjump.n < (size_t)GI_PJUMP_N * GI_PJUMP_N * GI_PJUMP_N) HIP_TRY(c, c->d_pjump.alloc((size_t)GI_PJUMP_N * GI_PJUMP_N * GI_PJUMP_N));
-                if (c->d_pjump_aux.n < 8) HIP_TRY(c, c->d_pjump_aux.alloc(8));
-                host[6] = 0.0;                                                    // (as an int: the "bad" flag)
-                HIP_TRY(c, hipMemcpyAsync(c->d_pjump_aux.p, host, sizeof host, hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(k_pjump, dim3((unsigned)((GI_PJUMP_N * GI_PJUMP_N * GI_PJUMP_N + 255) / 256)), dim3(256), 0, c->stream, c->d_pdescent.p, c->d_pjump_aux.p, c->d_pjump_aux.p + 3, 1e-12 * ext, c->d_pjump.p, reinterpret_cast<int*>(c->d_pjump_aux.p + 6));
-                HIP_TRY(c, hipGetLastError());
-                int bad = 1;
-                HIP_TRY(c, hipMemcpyAsync(&bad, c->d_pjump_aux.p + 6, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                c->pjump_ready = !bad;
-            }
-        }
-    }
-    return GI_OK;
-}
-
-// A photon map now in d_pnodes / d_pranges / d_ph_pos / d_ph_dircol (gi_upload_photons, build_photon_map_on_device): the scene reads it from there
-static int install_photon_map(gi_ctx* c, int32_t n_node, int32_t n_photon, int32_t n_prange, bool planes_ok)
-{
-    Scene& S = c->S;
-    S.pnodes = c->d_pnodes.p; S.pranges = c->d_pranges.p; S.ph_pos = c->d_ph_pos.p; S.ph_dircol = c->d_ph_dircol.p;
-    S.n_pnode = n_node; S.n_photon = n_photon;
-    c->n_prange = n_prange;
-    c->pn_planes_ok = planes_ok;
-    const int rc = build_photon_tables(c);
-    apply_switches(c);
-    return rc;
-}
-
-// no photon map (a fresh PhotonMap): gather queries find nothing
-static void clear_photon_map(gi_ctx* c)
-{
-    Scene& S = c->S;
-    S.pnodes = nullptr; S.ph_pos = nullptr; S.ph_dircol = nullptr; S.n_pnode = 0; S.n_photon = 0; S.n_pleaf = 0;
-    c->pdescent_ready = false; c->pjump_ready = false;
-    apply_switches(c);
-}
-
-#include "gi_sort.inc"
-#include "gi_photon_build.inc"
-#include "gi_denoise.inc"
-#include "gi_upsample.inc"
-#include "gi_occlusion.inc"
-
-static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
-static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
-static constexpr size_t kLdsWideBoxes = (size_t)GI_LDS_WIDE_BOXES_BYTES;   // wide records + their content boxes: k_st_trace / k_st_shadow, one 1024-thread workgroup per CU
-
-// The instances of the k_st_* kernels with their dynamic LDS: every instance of a family is named once, in its table; its selector picks the
-// instance a launch runs (FEAT = scene_feat / scene_trace_feat, gi_device.h), and stream_grids walks the same tables.
-template <class Fn> struct StKernel { Fn fn; size_t lds; };
-using TraceK = StKernel<decltype(&k_st_trace<0, 0>)>;
-using ShadeK = StKernel<decltype(&k_st_shade<0, 0, 0>)>;
-using ShadowK = StKernel<decltype(&k_st_shadow<0, 0>)>;
-using FinishK = StKernel<decltype(&k_st_finish<0, 0, 0>)>;
-// k_st_trace<FEAT, WIDE>: FEAT 0, spheres, textures x per-node, wide; then the counting instance
-static constexpr TraceK kTrace[] = {
-    {k_st_trace<0, 0>, kLdsNodes}, {k_st_trace<0, 1>, kLdsWideBoxes}, {k_st_trace<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_st_trace<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
-    {k_st_trace<7, 0>, kLdsNodes}, {k_st_trace<7, 1>, kLdsWideBoxes}, {k_st_trace<0, 1, true>, kLdsWideBoxes}};
-static TraceK st_trace(int feat, bool wide, bool counting) { return counting ? kTrace[6] : kTrace[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
-// k_st_shade<FEAT, WIDE, DEFER>: FEAT 0, spheres, fog, textures x per-node, wide, wide with the shadow walks put off (one light; several lights)
-// (the one-light form stages the trace stage's records and content boxes for the probe of the next ray: its LDS, one 512-thread workgroup per CU as before)
-static constexpr ShadeK kShade[] = {
-    {k_st_shade<0, 0, 0>, kLdsNodes}, {k_st_shade<0, 1, 0>, kLdsNodes}, {k_st_shade<0, 1, 1>, kLdsWideBoxes}, {k_st_shade<0, 1, 2>, kLdsNodes},
-    {k_st_shade<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_shade<GI_FEAT_SPHERES, 1, 1>, kLdsWideBoxes}, {k_st_shade<GI_FEAT_SPHERES, 1, 2>, kLdsNodes},
-    {k_st_shade<3, 0, 0>, kLdsNodes}, {k_st_shade<3, 1, 0>, kLdsNodes}, {k_st_shade<3, 1, 1>, kLdsWideBoxes}, {k_st_shade<3, 1, 2>, kLdsNodes},
-    {k_st_shade<7, 0, 0>, kLdsNodes}, {k_st_shade<7, 1, 0>, kLdsNodes}, {k_st_shade<7, 1, 1>, kLdsWideBoxes}, {k_st_shade<7, 1, 2>, kLdsNodes}};
-static int feat_row(int feat) { return feat == 7 ? 3 : (feat == 3 ? 2 : feat); }   // the levels 0, spheres, fog, textures
-static ShadeK st_shade(int feat, bool wide, int defer) { return kShade[feat_row(feat) * 4 + (wide ? 1 + defer : 0)]; }
-// k_st_shadow<FEAT, MULTI>: FEAT 0, spheres, fog, textures x one light, several lights; then the counting instances (one light, several)
-static constexpr ShadowK kShadow[] = {
-    {k_st_shadow<0, 0>, kLdsWideBoxes}, {k_st_shadow<0, 1>, kLdsWideBoxes}, {k_st_shadow<GI_FEAT_SPHERES, 0>, kLdsWideBoxes}, {k_st_shadow<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
-    {k_st_shadow<3, 0>, kLdsWideBoxes}, {k_st_shadow<3, 1>, kLdsWideBoxes}, {k_st_shadow<7, 0>, kLdsWideBoxes}, {k_st_shadow<7, 1>, kLdsWideBoxes},
-    {k_st_shadow<0, 0, true>, kLdsWideBoxes}, {k_st_shadow<0, 1, true>, kLdsWideBoxes}};
-static ShadowK st_shadow(int feat, bool many, bool counting) { return kShadow[(counting ? 4 : feat_row(feat)) * 2 + (many ? 1 : 0)]; }
-// k_st_finish<FEAT, WIDE, MODE>: FEAT 0, spheres, fog, textures x per-node, wide: a path per lane, a path per wave, a path per group of 16 lanes
-static constexpr FinishK kFinish[] = {
-    {k_st_finish<0, 0, 0>, kLdsNodes}, {k_st_finish<0, 1, 0>, kLdsNodes}, {k_st_finish<0, 1, 1>, kLdsFinishCoop}, {k_st_finish<0, 1, 2>, kLdsFinishCoop},
-    {k_st_finish<GI_FEAT_SPHERES, 0, 0>, kLdsNodes}, {k_st_finish<GI_FEAT_SPHERES, 1, 0>, kLdsNodes}, {k_st_finish<GI_FEAT_SPHERES, 1, 1>, kLdsFinishCoop}, {k_st_finish<GI_FEAT_SPHERES, 1, 2>, kLdsFinishCoop},
-    {k_st_finish<3, 0, 0>, kLdsNodes}, {k_st_finish<3, 1, 0>, kLdsNodes}, {k_st_finish<3, 1, 1>, kLdsFinishCoop}, {k_st_finish<3, 1, 2>, kLdsFinishCoop},
-    {k_st_finish<7, 0, 0>, kLdsNodes}, {k_st_finish<7, 1, 0>, kLdsNodes}, {k_st_finish<7, 1, 1>, kLdsFinishCoop}, {k_st_finish<7, 1, 2>, kLdsFinishCoop}};
-static FinishK st_finish(int feat, bool wide, int mode) { return kFinish[feat_row(feat) * 4 + (wide ? 1 + mode : 0)]; }
-// k_aov<FEAT, WIDE> (the feature pass): FEAT 0, spheres, textures x per-node, wide -- the rows of kTrace, with the same LDS
-using AovK = StKernel<decltype(&k_aov<0, 0>)>;
-static constexpr AovK kAov[] = {
-    {k_aov<0, 0>, kLdsNodes}, {k_aov<0, 1>, kLdsWideBoxes}, {k_aov<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_aov<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
-    {k_aov<7, 0>, kLdsNodes}, {k_aov<7, 1>, kLdsWideBoxes}};
-static AovK aov_kernel(int feat, bool wide) { return kAov[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
-// k_st_gather / k_st_gather_wave<COUNT>: no template argument of the scene's, no dynamic LDS
-static auto st_gather(bool counting) { return counting ? k_st_gather<true> : k_st_gather<false>; }
-static auto st_gather_wave(bool counting) { return counting ? k_st_gather_wave<true> : k_st_gather_wave<false>; }
-
-// more than 64 KB of dynamic LDS has to be asked for, per kernel (and per device: the attribute belongs to the loaded code object); a refusal
-// (a part with less LDS than gfx950's 160 KB per CU) would make every later launch of the kernel fail: it is kept to be reported by name
-template <class K, size_t N> static void ask_for_lds(const K (&ks)[N], int& refused)
-{
-    for (const K& k : ks)
-        if (k.lds > 64 * 1024 && hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) != hipSuccess) refused = (int)k.lds;
-}
-
-extern "C" {
-
-int gi_create(gi_ctx** out, int device_ordinal)
-{
-    if (!out) return GI_E_INVALID;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return GI_E_NO_DEVICE;
-    if (device_ordinal < 0 || device_ordinal >= n) return GI_E_INVALID;
-    if (hipSetDevice(device_ordinal) != hipSuccess) return GI_E_NO_DEVICE;
-    gi_ctx* c = new gi_ctx();
-    c->device = device_ordinal;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) c->n_cu = prop.multiProcessorCount;
-    std::vector<HaltonDim> dims;
-    std::vector<uint16_t> table;
-    build_halton_tables(dims, table);
-    if (c->d_hdims.upload(dims) != hipSuccess || c->d_htable.upload(table) != hipSuccess || c->d_tile_counter.alloc(1) != hipSuccess ||
-        c->d_counters.alloc(1) != hipSuccess) {
-        delete c;
-        return GI_E_HIP;
-    }
-    c->S.hdims = c->d_hdims.p;
-    c->S.htable = c->d_htable.p;
-    if (const char* e = getenv("GI_LBUF_MAX_BYTES")) c->lbuf_bytes_max = (size_t)strtoull(e, nullptr, 0);   // per-sample radiance buffer: frames beyond it run in sample chunks
-    if (const char* e = getenv("GI_COOP_FACTOR")) c->coop_factor = (uint32_t)strtoul(e, nullptr, 0);
-    if (const char* e = getenv("GI_WAVE_FACTOR")) c->wave_factor = std::min<uint32_t>((uint32_t)strtoul(e, nullptr, 0), 0xffffu);
-    if (const char* e = getenv("GI_EARLY_MISS")) c->early_miss = atoi(e) != 0;
-    if (const char* e = getenv("GI_EARLY_MISS_TURNS")) c->early_turns = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    if (const char* e = getenv("GI_SAMPLE_IDENTITY")) c->sample_identity = atoi(e) != 0;
-    if (const char* e = getenv("GI_KEEP_FREE_LIST")) c->keep_free_list = atoi(e) != 0;
-    if (const char* e = getenv("GI_SORT_CONT")) c->sort_cont = atoi(e) != 0;
-    if (const char* e = getenv("GI_DESCENT_JUMP")) c->descent_jump = atoi(e) != 0;
-    if (const char* e = getenv("GI_FLAT_CANDIDATES")) c->flat_candidates = atoi(e) != 0;
-    if (const char* e = getenv("GI_GATHER_WAVE_BELOW")) c->gather_wave_below = (uint32_t)strtoul(e, nullptr, 10);
-    if (const char* e = getenv("GI_SORT_SHADE")) c->sort_shade = atoi(e) != 0;
-    if (const char* e = getenv("GI_SORT_SHADE_LO")) c->sort_shade_lo = std::max(0, atoi(e));
-    if (const char* e = getenv("GI_SORT_LO_BIT")) c->sort_lo_bit = std::min(26, std::max(0, atoi(e)));
-    if (const char* e = getenv("GI_DEFER_SHADOWS")) c->defer_shadows = atoi(e) != 0;
-    if (const char* e = getenv("GI_FAST_DESCENT")) c->fast_descent = atoi(e) != 0;
-    if (const char* e = getenv("GI_ENTITY_BOXES")) c->sw.entity_boxes = atoi(e) != 0;
-    if (const char* e = getenv("GI_CLIP_BOXES")) c->sw.clip_boxes = atoi(e) != 0;
-    if (const char* e = getenv("GI_WALK_CUT")) c->sw.walk_cut = atoi(e) != 0;
-    if (const char* e = getenv("GI_REFILL_MIN")) c->refill_min = (uint32_t)std::min(64, std::max(1, atoi(e)));
-    if (const char* e = getenv("GI_FINISH_THRESHOLD")) c->finish_threshold = (uint32_t)strtoul(e, nullptr, 0);   // tuning knobs
-    if (const char* e = getenv("GI_FINISH_PLAN")) {   // "lanes:vertices,lanes:vertices,..."
-        std::vector<std::pair<int, int>> plan;
-        for (const char* q = e; *q;) {
-            int l = 0, b = 0, used = 0;
-            if (sscanf(q, "%d:%d%n", &l, &b, &used) != 2 || l < 0 || l > 64 || b < 1) { plan.clear(); break; }
-            plan.push_back({l, b});
-            q += used;
-            if (*q == ',') q++;
-        }
-        if (!plan.empty()) c->finish_plan = plan;
-    }
-    *out = c;
-    return GI_OK;
-}
-
-void gi_destroy(gi_ctx* c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    if (c->h_wfcnt) (void)hipHostFree(c->h_wfcnt);
-    if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    for (EventTimer* t : {&c->t_frame, &c->t_feat, &c->t_dn, &c->t_up, &c->t_ao}) t->destroy();
-    delete c;
-}
-
-const char* gi_last_error(const gi_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-int gi_set_stream(gi_ctx* c, void* s)
-{
-    if (!c) return GI_E_INVALID;
-    c->stream = (hipStream_t)s;
-    return GI_OK;
-}
-
-int gi_upload_scene(gi_ctx* c, const gi_scene_desc* d)
-{
-    if (!c) return GI_E_INVALID;
-    c->prog.open = false;   // a progressive session belongs to the scene and photon map it began on
-    HostScene H;
-    std::string err;
-    if (!layout_scene(d, H, err)) return fail(c, GI_E_INVALID, err);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_tnodes.upload(H.tnodes));
-    HIP_TRY(c, c->d_wnodes.upload(H.wnodes));
-    HIP_TRY(c, c->d_wleaf_id.upload(H.wleaf_id));
-    HIP_TRY(c, c->d_cboxes.upload(H.cboxes));
-    HIP_TRY(c, c->d_cuse.upload(H.cuse));
-    HIP_TRY(c, c->d_texs.upload(H.texs));
-    HIP_TRY(c, c->d_tri_uv.upload(H.tri_uv));
-    HIP_TRY(c, c->d_tex_pixels.upload(H.tex_pixels));
-    HIP_TRY(c, c->d_tex_lut.upload(H.tex_lut));
-    HIP_TRY(c, c->d_refs.upload(H.refs));
-    HIP_TRY(c, c->d_leaf_tris.upload(H.leaf_tris));
-    HIP_TRY(c, c->d_leaf_boxes.upload(H.leaf_boxes));
-    HIP_TRY(c, c->d_trace_boxes.upload(H.trace_boxes));
-    HIP_TRY(c, c->d_tcboxes.upload(H.tcboxes));
-    HIP_TRY(c, c->d_tcuse.upload(H.tcuse));
-    c->cut_margin = H.cut_margin;
-    c->scene_clipped = H.clipped;
-    c->lights_clear = H.lights_clear;
-    HIP_TRY(c, c->d_tris.upload(H.tris));
-    HIP_TRY(c, c->d_shade.upload(H.shade));
-    HIP_TRY(c, c->d_mats.upload(H.mats));
-    HIP_TRY(c, c->d_lights.upload(H.lights));
-    HIP_TRY(c, c->d_fogs.upload(H.fogs));
-    HIP_TRY(c, c->d_fog_grid.upload(H.fog_grid));
-    Scene& S = c->S;
-    S.tnodes = c->d_tnodes.p; S.leaf_refs = c->d_refs.p; S.leaf_tris = c->d_leaf_tris.p; S.tris = c->d_tris.p; S.shade = c->d_shade.p;
-    S.mats = c->d_mats.p; S.lights = c->d_lights.p;
-    S.n_node = H.n_node; S.n_tri = H.n_tri; S.n_light = H.n_light;
-    for (int k = 0; k < 3; k++) { S.root_bmin[k] = H.tnodes[0].bmin[k]; S.root_bmax[k] = H.tnodes[0].bmax[k]; }
-    S.n_wnode = (int32_t)H.wnodes.size();
-    S.wleaf_id = c->d_wleaf_id.p;
-    S.cuse = c->d_cuse.p;
-    S.tri_uv = c->d_tri_uv.p; S.texs = c->d_texs.p; S.tex_pixels = c->d_tex_pixels.p; S.tex_lut = c->d_tex_lut.p; S.n_tex = H.n_tex();
-    S.has_spheres = 0;
-    S.fogs = c->d_fogs.p; S.fog_grid = c->d_fog_grid.p; S.n_fog = H.n_fog();
-    for (const TriGeom& g : H.tris) if (g.flags & 4u) S.has_spheres = 1;
-    for (int k = 0; k < 3; k++) S.ambient[k] = H.ambient[k];
-    // the photon map stays as it is: the reference keeps a valid map when the scene is edited and rebuilt (include/raytracer.h:56-72);
-    // RayTracer::setScene, which allocates a fresh PhotonMap (include/raytracer.h:38), is gi_upload_scene + gi_clear_photons
-    c->have_scene = true;
-    apply_switches(c);
-    return GI_OK;
-}
-
-int gi_clear_photons(gi_ctx* c)
-{
-    if (!c) return GI_E_INVALID;
-    c->prog.open = false;
-    clear_photon_map(c);
-    return GI_OK;
-}
-
-int gi_upload_photons(gi_ctx* c, const gi_photon_map_desc* d)
-{
-    if (!c || !d) return GI_E_INVALID;
-    c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "upload_photons: no scene");
-    HostPhotons H;
-    std::string err;
-    if (!layout_photons(d, H, err)) return fail(c, GI_E_INVALID, err);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (H.n_node == 0) {
-        clear_photon_map(c);
-        return GI_OK;
-    }
-    HIP_TRY(c, c->d_pnodes.upload(H.nodes));
-    HIP_TRY(c, c->d_pranges.upload(H.ranges));
-    HIP_TRY(c, c->d_ph_pos.upload(H.pos));
-    HIP_TRY(c, c->d_ph_dircol.upload(H.dircol));
-    return install_photon_map(c, H.n_node, H.n_photon, (int32_t)H.ranges.size(), H.planes_ok);
-}
-
-int gi_local_rows(const gi_render_params* p) { return local_rows(p); }
-
-#include "gi_stream.inc"   // the scheduler: stream_samples, run_rounds, stream_passes and what the render entries below choose between
-
-int gi_render_device(gi_ctx* c, const gi_render_params* p, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
-{
-    if (!c || !d_out) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "render: no scene uploaded");
-    Frame F;
-    std::string ferr;
-    if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
-    if (cancel && *cancel) return fail(c, GI_E_CANCELLED, "render: cancelled");
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->t_frame.reset(); c->last_launches = 0;
-    if (F.local_rows == 0) return GI_OK;
-    if (c->render_mode == 1 || c->count_enabled) return render_megakernel(c, F, d_out, out_is_f64, d_spp);
-    if (c->count_stream && !uses_refill_schedule(c, F))
-        return fail(c, GI_E_STATE, "render: the streaming work counters (gi_set_counters 2) belong to fixed-sample-count frames of the wavefront pipeline");
-    if (uses_refill_schedule(c, F)) return render_streaming(c, F, d_out, out_is_f64, d_spp, cancel);
-    return render_adaptive(c, F, d_out, out_is_f64, d_spp, cancel);
-}
-
-int gi_set_wide_nodes(gi_ctx* c, int enable)
-{
-    if (!c) return GI_E_INVALID;
-    c->sw.wide = enable != 0;
-    apply_switches(c);
-    return (c->S.wnodes ? 1 : 0) | (c->S.pn_planes ? 2 : 0);
-}
-
-int gi_set_content_culling(gi_ctx* c, int enable)
-{
-    if (!c) return GI_E_INVALID;
-    c->sw.cull = enable != 0;
-    apply_switches(c);
-    return c->S.cboxes ? 1 : 0;
-}
-
-int gi_set_entity_boxes(gi_ctx* c, int enable)
-{
-    if (!c) return GI_E_INVALID;
-    c->sw.entity_boxes = enable != 0;
-    apply_switches(c);
-    return c->S.leaf_boxes ? 1 : 0;
-}
-
-int gi_set_render_mode(gi_ctx* c, int mode)
-{
-    if (!c || mode < 0 || mode > 2) return GI_E_INVALID;
-    c->render_mode = mode;
-    return GI_OK;
-}
-
-int gi_set_pool_slots(gi_ctx* c, int64_t slots)
-{
-    if (!c || slots < 64) return GI_E_INVALID;
-    c->pool_slots_max = (size_t)slots;
-    return GI_OK;
-}
-
-int gi_last_render_ms(gi_ctx* c, float* ms, int32_t* n_launches)
-{
-    if (!c) return GI_E_INVALID;
-    float frame_ms = 0;
-    HIP_TRY(c, c->t_frame.read(&frame_ms));
-    for (int k = 0; k < STG_COUNT_MAX; k++) c->stage_ms[k] = 0;
-    const bool debug_stages = getenv("GI_DEBUG_STAGES") != nullptr;   // read at every call
-    for (size_t k = 0; k + 1 < c->ev_used + 1 && k / 2 < c->ev_stage.size() && k + 1 < c->ev_pool.size() && k < c->ev_used; k += 2) {
-        float t = 0;
-        if (hipEventElapsedTime(&t, c->ev_pool[k], c->ev_pool[k + 1]) == hipSuccess) c->stage_ms[c->ev_stage[k / 2]] += t;
-        if (debug_stages) fprintf(stderr, "[stage] %d %.3f ms\n", c->ev_stage[k / 2], t);
-    }
-    if (ms) *ms = frame_ms;
-    if (n_launches) *n_launches = c->last_launches;
-    return GI_OK;
-}
-
-int gi_last_stage_ms(gi_ctx* c, float* out8)
-{
-    if (!c || !out8) return GI_E_INVALID;
-    int rc = gi_last_render_ms(c, nullptr, nullptr);
-    if (rc) return rc;
-    for (int k = 0; k < 8; k++) out8[k] = c->stage_ms[k];
-    out8[STG_SHADE] += c->stage_ms[STG_SHADOW];   // the shade stage of the 8-entry form includes the shadow walks it put off
-    return GI_OK;
-}
-
-int gi_last_kernel_ms(gi_ctx* c, float* out10)
-{
-    if (!c || !out10) return GI_E_INVALID;
-    int rc = gi_last_render_ms(c, nullptr, nullptr);
-    if (rc) return rc;
-    for (int k = 0; k < STG_COUNT_MAX; k++) out10[k] = c->stage_ms[k];
-    return GI_OK;
-}
-
-int gi_set_counters(gi_ctx* c, int enable)
-{
-    if (!c || enable < 0 || enable > 2) return GI_E_INVALID;
-    c->count_enabled = enable == 1;
-    c->count_stream = enable == 2;
-    return GI_OK;
-}
-int gi_get_stream_counters(gi_ctx* c, int64_t* out17 /* [19] */)
-{
-    if (!c || !out17) return GI_E_INVALID;
-    if (!c->d_stream_cnt.p) return fail(c, GI_E_STATE, "stream counters: no counted frame was rendered (gi_set_counters(ctx, 2), fixed sample count)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    StreamCounters h;
-    HIP_TRY(c, hipMemcpy(&h, c->d_stream_cnt.p, sizeof h, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 6; k++) { out17[k] = (int64_t)h.trace[k]; out17[7 + k] = (int64_t)h.shadow[k]; }
-    out17[6] = (int64_t)h.trace_rays; out17[13] = (int64_t)h.shadow_rays;
-    out17[14] = (int64_t)h.gather_queries; out17[15] = (int64_t)h.gather_cand; out17[16] = (int64_t)c->stream_shaded;
-    out17[17] = (int64_t)h.trace[6]; out17[18] = (int64_t)h.shadow[6];
-    return GI_OK;
-}
-int gi_get_counters(gi_ctx* c, int64_t* out8)
-{
-    if (!c || !out8) return GI_E_INVALID;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    Counters h;
-    HIP_TRY(c, hipMemcpy(&h, c->d_counters.p, sizeof h, hipMemcpyDeviceToHost));
-    out8[0] = (int64_t)h.v_trace; out8[1] = (int64_t)h.v_shadow; out8[2] = (int64_t)h.tri; out8[3] = (int64_t)h.shaded;
-    out8[4] = (int64_t)h.pcand; out8[5] = (int64_t)h.traces; out8[6] = (int64_t)h.shadows; out8[7] = (int64_t)h.gathers;
-    return GI_OK;
-}
-
-int gi_render_host(gi_ctx* c, const gi_render_params* p, void* h_out, int out_is_f64, int32_t* h_spp, volatile const int* cancel)
-{
-    if (!c || !h_out || !p) return GI_E_INVALID;
-    const size_t npix = (size_t)gi_local_rows(p) * (size_t)std::max(p->width, 0);
-    if (npix == 0) return GI_OK;
-    return frame_to_host(c, "render_host", npix, h_out, out_is_f64, h_spp,
-                         [&](void* d_out, int32_t* d_spp) { return gi_render_device(c, p, d_out, out_is_f64, d_spp, cancel); });
-}
-
-#include "gi_progressive.inc"
-
-// ---- first-hit feature buffers (an addition: the reference renders radiance only; the values are those RayTracer::radiance holds after trace()
-// of the primary ray, include/raytracer.h:186-210)
-int gi_render_features_device(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* d_out, int out_is_f64, int32_t* d_ids)
-{
-    if (!c) return GI_E_INVALID;
-    c->t_feat.reset();
-    if (!d_out) return GI_E_INVALID;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "render_features: no scene uploaded");
-    Frame F;
-    std::string ferr;
-    if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
-    if (n_samples < 1) return fail(c, GI_E_INVALID, "render_features: n_samples must be at least 1");
-    // Halton index of sample s = (offset of the pixel < inc) + s * inc, in 32 bits as in the beauty pass
-    if ((unsigned long long)n_samples * F.he.inc > (1ull << 32))
-        return fail(c, GI_E_INVALID, "render_features: n_samples = " + std::to_string(n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
-                                     " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (F.local_rows == 0) return GI_OK;
-    if (c->aov_lds_refused < 0) { c->aov_lds_refused = 0; ask_for_lds(kAov, c->aov_lds_refused); }
-    if (c->aov_lds_refused) return fail(c, GI_E_HIP, "render_features: the device refused " + std::to_string(c->aov_lds_refused) + " bytes of dynamic LDS per workgroup");
-    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
-    const AovK k = aov_kernel(scene_trace_feat(c->S), c->S.wnodes != nullptr);
-    HIP_TRY(c, c->t_feat.begin(c->stream));
-    hipLaunchKernelGGL(k.fn, dim3((n_pix + GI_AOV_BLOCK - 1) / GI_AOV_BLOCK), dim3(GI_AOV_BLOCK), k.lds, c->stream, c->S, F, n_pix, n_samples, d_out, out_is_f64, d_ids);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_feat.end(c->stream));
-    return GI_OK;
-}
-
-int gi_render_features_host(gi_ctx* c, const gi_render_params* p, int32_t n_samples, void* h_out, int out_is_f64, int32_t* h_ids)
-{
-    if (!c) return GI_E_INVALID;
-    c->t_feat.reset();
-    if (!h_out || !p) return GI_E_INVALID;
-    const size_t npix = (size_t)gi_local_rows(p) * (size_t)std::max(p->width, 0);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = npix * 8 * (out_is_f64 ? 8 : 4);
-    DevBuf<unsigned char> d_out;
-    DevBuf<int32_t> d_ids;
-    HIP_TRY(c, d_out.alloc(bytes));
-    if (h_ids) HIP_TRY(c, d_ids.alloc(npix * 2));
-    const int rc = gi_render_features_device(c, p, n_samples, d_out.p, out_is_f64, d_ids.p);
-    return rc != GI_OK ? rc : finish_to_host(c, "render_features_host", {{h_out, d_out.p, bytes}, to_host(h_ids, d_ids, npix * 2)}, &c->t_feat);
-}
-
-int gi_last_features_ms(gi_ctx* c, float* ms)
-{
-    if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->t_feat.read(ms));
-    return GI_OK;
-}
-
-#include "gi_entries.inc"
-
-#include "gi_group.inc"
-
-}  // extern "C"
+// ================================================================================================= host side, and the kernels that stand with it
+#include "gi_context.inc"        // gi_ctx and its parts: scene, photon map, tuning, stage clock, stream workspaces, auxiliary passes
+#include "gi_instances.inc"      // the kernel instances with dynamic LDS, their tables and selectors
+#include "gi_sort.inc"           // the radix sort of the queues: kernels and rs_sort_pairs
+#include "gi_photon_build.inc"   // the photon map built on the device: kernels and build_photon_map_on_device
+#include "gi_stream.inc"         // the scheduler: stream_samples, run_rounds, stream_passes
+#include "gi_api.inc"            // create / destroy, uploads, setters, the frame, its timers and counters
+#include "gi_progressive.inc"    // progressive sessions (gi_progressive_*)
+#include "gi_denoise.inc"        // the a-trous denoiser: kernels and gi_denoise_*
+#include "gi_upsample.inc"       // the guided upsampler: kernel and gi_upsample_*
+#include "gi_features.inc"       // first-hit feature buffers: k_aov and gi_render_features_*; the host frame of the per-pixel passes
+#include "gi_occlusion.inc"      // ambient occlusion: k_ao and gi_render_occlusion_*
+#include "gi_entries.inc"        // function-level entries (parity tests, public C++ methods) and the debug entries
+#include "gi_group.inc"          // one frame over several devices (gi_group_*)

@@ -1,5 +1,5 @@
 // gi_occlusion.inc -- the ambient-occlusion / bent-normal pass (gi_render_occlusion_*; an addition: the reference has none).  Included by
-// gi_kernels.hip after gi_upsample.inc.  The definition is stated in include/gi_hip.h; the per-sample functions are ao_first_hit() and ao_segments()
+// gi_kernels.hip behind gi_features.inc, whose host frame of a per-pixel pass it shares (pixel_pass_frame, pixel_pass, pixel_pass_to_host).  The definition is stated in include/gi_hip.h; the per-sample functions are ao_first_hit() and ao_segments()
 // in gi_device.h.
 //
 // One kernel, k_ao<FEAT, WIDE>, of k_aov's shape: one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, a lane loops over its
@@ -12,9 +12,6 @@
 // (Scene::cboxes, valid for any walk), because the n_dirs any-hit walks of a sample read them and its one closest-hit walk does not have to: that one
 // takes the tables k_aov's takes (Scene::tcboxes, cut to the leaves) through L2 where the two differ.  The segments end anywhere, not at a light, so
 // the any-hit walk uses the whole entities' boxes (Scene::leaf_boxes), as gi_visible does, never the ones cut for segments that end at a light.
-#ifndef GI_AO_BLOCK
-#define GI_AO_BLOCK 512     // as GI_AOV_BLOCK: one workgroup per CU next to the records, 256 registers per lane
-#endif
 template <int FEAT, int WIDE>
 __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n_pix, int32_t n, int32_t n_dirs, double radius, void* out, int out_f64)
 {
@@ -52,14 +49,6 @@ __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n
 
 namespace {
 
-// k_ao<FEAT, WIDE>: FEAT 0, spheres, textures x per-node, wide -- the rows of k_aov, with the same LDS
-struct AoK { decltype(&k_ao<0, 0>) fn; size_t lds; };
-constexpr size_t kAoLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode), kAoLdsWide = (size_t)GI_LDS_WIDE_BOXES_BYTES;
-constexpr AoK kAo[] = {
-    {k_ao<0, 0>, kAoLdsNodes}, {k_ao<0, 1>, kAoLdsWide}, {k_ao<GI_FEAT_SPHERES, 0>, kAoLdsNodes}, {k_ao<GI_FEAT_SPHERES, 1>, kAoLdsWide},
-    {k_ao<7, 0>, kAoLdsNodes}, {k_ao<7, 1>, kAoLdsWide}};
-AoK ao_kernel(int feat, bool wide) { return kAo[(feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0)]; }
-
 // false + message when the parameters are not the header's
 bool ao_check(const gi_occlusion_params* p, std::string& err)
 {
@@ -84,59 +73,37 @@ void gi_occlusion_default_params(gi_occlusion_params* p)
 int gi_render_occlusion_device(gi_ctx* c, const gi_render_params* p, const gi_occlusion_params* op, void* d_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_ao.reset();
+    c->ao.timer.reset();
     if (!p || !d_out) return fail(c, GI_E_INVALID, "render_occlusion: null frame parameters or output pointer");
     std::string err;
     if (!ao_check(op, err)) return fail(c, GI_E_INVALID, err);
-    if (!c->have_scene) return fail(c, GI_E_STATE, "render_occlusion: no scene uploaded");
     Frame F;
-    if (!make_frame(p, F, err)) return fail(c, GI_E_INVALID, err);
-    // Halton index of sample s = (offset of the pixel < inc) + s * inc, in 32 bits as in the beauty pass
-    if ((unsigned long long)op->n_samples * F.he.inc > (1ull << 32))
-        return fail(c, GI_E_INVALID, "render_occlusion: n_samples = " + std::to_string(op->n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
-                                     " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (F.local_rows == 0) return GI_OK;
-    if (c->ao_lds_refused < 0) {
-        c->ao_lds_refused = 0;
-        for (const AoK& k : kAo)
-            if (k.lds > 64 * 1024 && hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds) != hipSuccess) c->ao_lds_refused = (int)k.lds;
-    }
-    if (c->ao_lds_refused) return fail(c, GI_E_HIP, "render_occlusion: the device refused " + std::to_string(c->ao_lds_refused) + " bytes of dynamic LDS per workgroup");
+    if (const int rc = pixel_pass_frame(c, "render_occlusion", p, F)) return rc;
     double radius = op->radius;
     if (radius == 0.0) {   // a tenth of the diagonal of the scene's root box
         const double dx = c->S.root_bmax[0] - c->S.root_bmin[0], dy = c->S.root_bmax[1] - c->S.root_bmin[1], dz = c->S.root_bmax[2] - c->S.root_bmin[2];
         radius = 0.1 * sqrt((dx * dx + dy * dy) + dz * dz);
     }
-    const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
-    const AoK k = ao_kernel(scene_trace_feat(c->S), c->S.wnodes != nullptr);
-    HIP_TRY(c, c->t_ao.begin(c->stream));
-    hipLaunchKernelGGL(k.fn, dim3((n_pix + GI_AO_BLOCK - 1) / GI_AO_BLOCK), dim3(GI_AO_BLOCK), k.lds, c->stream, c->S, F, n_pix, op->n_samples, op->n_dirs, radius, d_out, out_is_f64);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_ao.end(c->stream));
-    return GI_OK;
+    return pixel_pass(c, c->ao, "render_occlusion", F, op->n_samples, kAo, GI_AO_BLOCK, [&](const AoK& k, dim3 grid, dim3 block, uint32_t n_pix) {
+        hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, n_pix, op->n_samples, op->n_dirs, radius, d_out, out_is_f64);
+    });
 }
 
 int gi_render_occlusion_host(gi_ctx* c, const gi_render_params* p, const gi_occlusion_params* op, void* h_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_ao.reset();
+    c->ao.timer.reset();
     if (!p || !h_out) return fail(c, GI_E_INVALID, "render_occlusion: null frame parameters or output pointer");
     std::string err;
     if (!ao_check(op, err)) return fail(c, GI_E_INVALID, err);
-    const size_t npix = (size_t)std::max(gi_local_rows(p), 0) * (size_t)std::max(p->width, 0);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = npix * 4 * (out_is_f64 ? 8 : 4);
-    DevBuf<unsigned char> d_out;
-    HIP_TRY(c, d_out.alloc(bytes));
-    const int rc = gi_render_occlusion_device(c, p, op, d_out.p, out_is_f64);
-    return rc != GI_OK ? rc : finish_to_host(c, "render_occlusion_host", {{h_out, d_out.p, bytes}}, &c->t_ao);
+    return pixel_pass_to_host(c, c->ao, "render_occlusion_host", p, 4, h_out, out_is_f64, nullptr,
+                              [&](void* d_out, int32_t*) { return gi_render_occlusion_device(c, p, op, d_out, out_is_f64); });
 }
 
 int gi_last_occlusion_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->t_ao.read(ms));
+    HIP_TRY(c, c->ao.timer.read(ms));
     return GI_OK;
 }
 

@@ -1,4 +1,4 @@
-// gi_photon_build.inc -- the photon octree built on the device (part of gi_kernels.hip: needs gi_ctx).
+// gi_photon_build.inc -- the photon octree built on the device (included by gi_kernels.hip behind gi_sort.inc: needs gi_ctx, gi_context.inc).
 //
 // Replaces PhotonMap::push_back x n + PhotonMap::rebuild / PhotonMap::Node::partition (include/photonMap.cpp:24-47,137-192) and the
 // flattening that gi_upload_photons does on the host, for photons that are already on the device (RayTracer::tracePhotons -> k_emit) or
@@ -250,20 +250,20 @@ int build_photon_map_on_device(gi_ctx* c, const double* d_ph, int32_t n, const d
     DevBuf<uint32_t> d_src;
     DevBuf<int32_t> d_leaf_rec, d_leaf_first, d_leaf_cnt;
     HIP_TRY(c, d_src.upload(src)); HIP_TRY(c, d_leaf_rec.upload(leaf_rec)); HIP_TRY(c, d_leaf_first.upload(leaf_first)); HIP_TRY(c, d_leaf_cnt.upload(leaf_cnt));
-    HIP_TRY(c, c->d_ph_pos.alloc((size_t)n_final * 3)); HIP_TRY(c, c->d_ph_dircol.alloc((size_t)n_final * 6));
-    hipLaunchKernelGGL(k_pb_gather, dim3(grid), dim3(256), 0, st, d_ph, d_order[cur].p, d_src.p, (uint32_t)n_final, c->d_ph_pos.p, c->d_ph_dircol.p);
-    HIP_TRY(c, c->d_pnodes.upload(recs));
+    HIP_TRY(c, c->photons.d_ph_pos.alloc((size_t)n_final * 3)); HIP_TRY(c, c->photons.d_ph_dircol.alloc((size_t)n_final * 6));
+    hipLaunchKernelGGL(k_pb_gather, dim3(grid), dim3(256), 0, st, d_ph, d_order[cur].p, d_src.p, (uint32_t)n_final, c->photons.d_ph_pos.p, c->photons.d_ph_dircol.p);
+    HIP_TRY(c, c->photons.d_pnodes.upload(recs));
     // candidate ranges: count per leaf, offsets in depth-first leaf order (the order layout_photons assigns them in), fill
-    hipLaunchKernelGGL(k_pb_neighbours, dim3(grid), dim3(256), 0, st, c->d_pnodes.p, d_leaf_rec.p, (uint32_t)leaf_rec.size(), d_leaf_first.p, d_leaf_cnt.p, (PRange*)nullptr, 0);
-    HIP_TRY(c, hipMemcpyAsync(recs.data(), c->d_pnodes.p, recs.size() * sizeof(PNode), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_pb_neighbours, dim3(grid), dim3(256), 0, st, c->photons.d_pnodes.p, d_leaf_rec.p, (uint32_t)leaf_rec.size(), d_leaf_first.p, d_leaf_cnt.p, (PRange*)nullptr, 0);
+    HIP_TRY(c, hipMemcpyAsync(recs.data(), c->photons.d_pnodes.p, recs.size() * sizeof(PNode), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     // layout_photons visits the leaves in the builder's pre-order; the segment order is the same depth-first order
     int32_t n_rng = 0;
     for (int32_t r : leaf_rec) { recs[(size_t)r].nb_off = n_rng; n_rng += recs[(size_t)r].u.lf.nb_cnt; }
-    HIP_TRY(c, hipMemcpyAsync(c->d_pnodes.p, recs.data(), recs.size() * sizeof(PNode), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, c->d_pranges.alloc((size_t)std::max(n_rng, 1)));
-    HIP_TRY(c, hipMemsetAsync(c->d_pranges.p, 0, (size_t)std::max(n_rng, 1) * sizeof(PRange), st));
-    hipLaunchKernelGGL(k_pb_neighbours, dim3(grid), dim3(256), 0, st, c->d_pnodes.p, d_leaf_rec.p, (uint32_t)leaf_rec.size(), d_leaf_first.p, d_leaf_cnt.p, c->d_pranges.p, 1);
+    HIP_TRY(c, hipMemcpyAsync(c->photons.d_pnodes.p, recs.data(), recs.size() * sizeof(PNode), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, c->photons.d_pranges.alloc((size_t)std::max(n_rng, 1)));
+    HIP_TRY(c, hipMemsetAsync(c->photons.d_pranges.p, 0, (size_t)std::max(n_rng, 1) * sizeof(PRange), st));
+    hipLaunchKernelGGL(k_pb_neighbours, dim3(grid), dim3(256), 0, st, c->photons.d_pnodes.p, d_leaf_rec.p, (uint32_t)leaf_rec.size(), d_leaf_first.p, d_leaf_cnt.p, c->photons.d_pranges.p, 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
     return install_photon_map(c, N, n_final, std::max(n_rng, 1), planes_ok);

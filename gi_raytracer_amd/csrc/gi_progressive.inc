@@ -1,5 +1,5 @@
-// gi_progressive.inc -- progressive render sessions (gi_progressive_*).  Included by gi_kernels.hip inside its extern "C" block, after the frame
-// entries whose bodies a step runs (stream_samples, run_rounds).
+// gi_progressive.inc -- progressive render sessions (gi_progressive_*).  Included by gi_kernels.hip behind gi_api.inc: a step
+// runs the bodies of the frame entries (stream_samples, run_rounds, gi_stream.inc).
 //
 // ---- progressive sessions (an addition: the reference renders a frame in one piece).  The session owns its pixel records (c->prog.pix); a step runs
 // the bodies of the one-shot frame on them -- stream_samples over [E, E') for a fixed sample count, run_rounds with the cap E' otherwise -- so a
@@ -31,11 +31,13 @@ int prog_open(gi_ctx* c, const gi_render_params& rp, const Frame& F, int schedul
 }
 }  // namespace
 
+extern "C" {
+
 int gi_progressive_begin(gi_ctx* c, const gi_render_params* p)
 {
     if (!c) return GI_E_INVALID;
     c->prog.open = false;
-    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_begin: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "progressive_begin: no scene uploaded");
     Frame F;
     std::string ferr;
     if (!make_frame(p, F, ferr)) return fail(c, GI_E_INVALID, ferr);
@@ -76,11 +78,11 @@ int gi_progressive_step_device(gi_ctx* c, int32_t n_samples, void* d_out, int ou
     const int32_t e0 = g.sample_end, e1 = (int32_t)std::min<long long>((long long)e0 + n_samples, g.F.max_samples);
     if (e1 == e0) {                 // nothing to take: the frame as the records hold it
         hipStream_t st = c->stream;
-        c->ev_used = 0; c->ev_stage.clear();
+        c->clock.restart();
         HIP_TRY(c, c->t_frame.begin(st));
-        stage_begin(c, STG_ACCUM);
+        c->clock.begin(STG_ACCUM, st);
         hipLaunchKernelGGL(k_pix_resolve, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, st, g.F, g.pix.p, g.n_rec, g.schedule, d_out, out_is_f64, d_spp);
-        stage_end(c);
+        c->clock.end(st);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, c->t_frame.end(st));
         c->last_launches = 1;
@@ -123,12 +125,12 @@ int gi_progressive_status(gi_ctx* c, int32_t* sample_end, int64_t* pixels_wantin
         *pixels_wanting = 0;
         if (g.n_rec) {
             HIP_TRY(c, hipSetDevice(c->device));
-            if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
-            HIP_TRY(c, hipMemsetAsync(c->d_wfcnt.p, 0, sizeof(unsigned int), c->stream));
-            hipLaunchKernelGGL(k_pix_wanting, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, c->stream, g.F, g.pix.p, g.n_rec, g.schedule, c->d_wfcnt.p);
+            if (!c->st.d_wfcnt.p) HIP_TRY(c, c->st.d_wfcnt.alloc(2));
+            HIP_TRY(c, hipMemsetAsync(c->st.d_wfcnt.p, 0, sizeof(unsigned int), c->stream));
+            hipLaunchKernelGGL(k_pix_wanting, dim3(std::min<uint32_t>((g.n_rec + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)stream_grids(c).pix)), dim3(GI_BLOCK), 0, c->stream, g.F, g.pix.p, g.n_rec, g.schedule, c->st.d_wfcnt.p);
             HIP_TRY(c, hipGetLastError());
             unsigned int n = 0;
-            HIP_TRY(c, hipMemcpyAsync(&n, c->d_wfcnt.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(&n, c->st.d_wfcnt.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             *pixels_wanting = (int64_t)n;
         }
@@ -189,7 +191,7 @@ int gi_progressive_restore(gi_ctx* c, const void* h_blob, int64_t n_bytes)
     const uint32_t n_rec = prog_records(F, h.schedule);
     if (h.n_records != n_rec || n_bytes != (int64_t)sizeof h + (int64_t)n_rec * (int64_t)sizeof(PixRec))
         return fail(c, GI_E_INVALID, "progressive_restore: " + std::to_string(n_bytes) + " bytes, a checkpoint of this frame has " + std::to_string(sizeof h + (size_t)n_rec * sizeof(PixRec)) + " (truncated?)");
-    if (!c->have_scene) return fail(c, GI_E_STATE, "progressive_restore: no scene uploaded");
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "progressive_restore: no scene uploaded");
     if (c->count_enabled) return fail(c, GI_E_STATE, "progressive_restore: sessions run on the streaming passes, not with the megakernel's work counters (gi_set_counters 1)");
     if (h.n_entity != c->S.n_tri || h.n_node != c->S.n_node || h.n_photon != c->S.n_photon)
         return fail(c, GI_E_STATE, "progressive_restore: the checkpoint was taken on another scene or photon map (entities, nodes, photons " + std::to_string(h.n_entity) + ", " + std::to_string(h.n_node) + ", " +
@@ -204,3 +206,5 @@ int gi_progressive_restore(gi_ctx* c, const void* h_blob, int64_t n_bytes)
     c->prog.open = true;
     return GI_OK;
 }
+
+}  // extern "C"

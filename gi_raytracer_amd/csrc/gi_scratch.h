@@ -47,6 +47,10 @@ struct EventTimer {
     hipEvent_t a = nullptr, b = nullptr;
     float ms = 0;
     bool pending = false;                        // a and b were recorded and not read yet
+    EventTimer() = default;
+    EventTimer(const EventTimer&) = delete;      // one owner per pair of events
+    EventTimer& operator=(const EventTimer&) = delete;
+    ~EventTimer() { destroy(); }
     void reset() { ms = 0; pending = false; }
     hipError_t begin(hipStream_t st)
     {

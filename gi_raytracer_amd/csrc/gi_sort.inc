@@ -238,7 +238,7 @@ static int rs_sort_pairs(gi_ctx* c, const uint32_t* keys_in, uint32_t* keys_out,
     const int passes = (total_bits + 8) / 9;
     // one workgroup per CU, fewer when the input has fewer tiles than that (the last passes of a frame sort a few thousand pairs)
     const int grid = (int)std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)std::min(c->n_cu, GI_MAX_PRODUCER_BLOCKS), (n + GI_RS_TILE - 1) / GI_RS_TILE));
-    if (!c->rs_attr_set) { HIP_TRY(c, hipFuncSetAttribute((const void*)k_rs_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GI_RS_LDS_BYTES)); c->rs_attr_set = true; }
+    if (!c->st.rs_attr_set) { HIP_TRY(c, hipFuncSetAttribute((const void*)k_rs_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GI_RS_LDS_BYTES)); c->st.rs_attr_set = true; }
     const uint32_t* src_k = keys_in;
     const uint32_t* src_v = vals_in;
     int shift = begin_bit;

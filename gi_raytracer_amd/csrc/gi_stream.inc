@@ -1,68 +1,12 @@
-// gi_stream.inc -- the host side of the streaming pipeline: which k_st_* kernel runs when, on which queue.  Host code only; the kernels, their
-// instance tables and selectors (st_trace, st_shade, ...) are gi_kernels.hip's.  Included by gi_kernels.hip twice: before gi_ctx for the types the
-// context holds by value (the first part below), and inside its extern "C" block, where the render entries stand, for the scheduler itself.
+// gi_stream.inc -- the host side of the streaming pipeline: which k_st_* kernel runs when, on which queue.  Host code only; the kernels are
+// gi_kernels.hip's, their instance tables and selectors (st_trace, st_shade, ...) gi_instances.inc's, the workspaces (StreamState, StreamWork,
+// kStreamWork) and the stage clock gi_context.inc's.  Included by gi_kernels.hip behind gi_sort.inc; the render entries that choose between the
+// schedules are in gi_api.inc.
 //
 //   stream_samples   fixed sample count: chunks of samples through the pool, freed slots refilled with the next samples (ChunkRefill)
 //   run_rounds       adaptive sampling and render mode 2: synchronous rounds, k_ad_gen prepares the paths of a round (RoundRefill)
 //   stream_passes    the pass loop both run: kPassStages in order, until few enough paths are left for the finisher (finish_tail)
-//   plan_pool        (gi_layout.h) how many paths are in flight: the memory budget per slot, which kStreamWork below must stay within
-#ifndef GI_STREAM_TYPES
-#define GI_STREAM_TYPES
-
-struct StreamGrids { int lds_refused = 0; int pix = 0, trace = 0, shade = 0, shadow = 0, gather = 0, accum = 0, finish = 0, ad_gen = 0, ad_accum = 0, compact = 0; };
-
-// stages of the per-stage device times (gi_last_kernel_ms; gi_last_stage_ms folds STG_SHADOW into STG_SHADE)
-#define STG_COUNT_MAX 10
-enum { STG_REGEN = 0, STG_TRACE, STG_SHADE, STG_SORT, STG_GATHER, STG_FINISH, STG_ACCUM, STG_OTHER, STG_SHADOW, STG_COUNT };
-
-// Workspaces of the stream passes, in 32-bit words, grown on demand for P paths in flight and kept between frames (stream_alloc, kStreamWork).
-// A name after `&` is a second role of the buffer it refers to.  The roles of one buffer cannot overlap in time because every launch of a pass goes
-// to the context's one stream in the order of kPassStages: the trace stage's staging queues are read by its compaction before the shade kernel
-// appends to them again; the shade sort's iota, sorted queue and places are last read by the shade kernel, and the compaction behind that kernel
-// is the first to write the gather queries into the same buffers, which the gather of this pass reads before the next pass sorts its shade queue.
-struct StreamWork {
-    using Buf = DevBuf<uint32_t>;
-    Buf q_new;                                        // paths a round prepared (k_ad_gen); the refill of a chunk starts its samples in the trace kernel
-    Buf q_cont_a, q_cont_b;                           // continuing rays in coherence order: a pass reads one (in) while its last sort fills the other (out)
-    Buf q_shade;                                      // hits of the trace stage
-    Buf q_gather;                                     // no reader at present (the gather queries go straight to gather_slots / gather_keys); part of the budget
-    Buf q_free_a, q_free_b;                           // freed slots: written by a pass (out), handed to new samples by the refill of the next (in)
-    Buf gather_keys, gather_slots;                    // the gather queries of a pass in queue order: photon-map leaf, path slot
-    Buf gather_keys_sorted, gather_slots_sorted;      // ... in leaf order
-    Buf& shade_iota = gather_slots;                   // the shade sort: 0, 1, 2, ...
-    Buf& shade_sorted = gather_keys_sorted;           //   the shade queue in slot order
-    Buf& shade_places = gather_slots_sorted;          //   where each item stood in the trace stage's order
-    Buf cont_keys, cont_keys_sorted;                  // coherence keys of the continuing rays
-    Buf stage_hits, stage_free_trace;                 // staging queues the producers append to, one segment per workgroup (k_st_compact closes the gaps): trace stage
-    Buf& stage_cont_slots = stage_hits;               //   shade stage: continuing slot
-    Buf& stage_cont_keys = stage_free_trace;          //   its coherence key
-    Buf stage_gather_slots, stage_free_shade;         //   gather slot, freed slot
-    Buf stage_gather_pos;                             //   gather position (3 doubles per entry)
-    Buf cont_slots;                                   // continuing slots in queue order
-    Buf sort_scratch;                                 // gi_sort.inc ping-pongs through one more copy of keys and values (sort_pairs)
-};
-// what stream_alloc gives every workspace, in words: per path slot, and on top of that.  Staging segments are laid out as if every chunk of a
-// producer's loop were full: up to one chunk of slack.
-struct StreamWorkItem { StreamWork::Buf StreamWork::* buf; uint32_t per_slot, fixed; };
-static constexpr StreamWorkItem kStreamWork[] = {
-    {&StreamWork::q_new, 1, 0}, {&StreamWork::q_cont_a, 1, 0}, {&StreamWork::q_cont_b, 1, 0}, {&StreamWork::q_shade, 1, 0}, {&StreamWork::q_gather, 1, 0},
-    {&StreamWork::q_free_a, 1, 0}, {&StreamWork::q_free_b, 1, 0},
-    {&StreamWork::gather_keys, 1, 0}, {&StreamWork::gather_slots, 1, 0}, {&StreamWork::gather_keys_sorted, 1, 0}, {&StreamWork::gather_slots_sorted, 1, 0},
-    {&StreamWork::cont_keys, 1, 0}, {&StreamWork::cont_keys_sorted, 1, 0},
-    {&StreamWork::stage_hits, 1, 4096}, {&StreamWork::stage_free_trace, 1, 4096}, {&StreamWork::stage_gather_slots, 1, 4096}, {&StreamWork::stage_free_shade, 1, 4096},
-    {&StreamWork::stage_gather_pos, 6, 6 * 4096},
-    {&StreamWork::cont_slots, 1, 0}, {&StreamWork::sort_scratch, 2, 0}};
-constexpr size_t stream_work_bytes_per_slot()
-{
-    size_t words = 0;
-    for (const StreamWorkItem& w : kStreamWork) words += w.per_slot;
-    return words * sizeof(uint32_t);
-}
-// the pool is sized from gi_layout.h's budget per slot (plan_pool): a workspace added here without a term there would overcommit memory
-static_assert(stream_work_bytes_per_slot() + sizeof(unsigned long long) /* d_slot_sample */ <= kBudgetWorkBytes, "kStreamWork allocates more per slot than plan_pool budgets");
-
-#else  // ---------------------------------------------------------------------------------------------------------- the scheduler
-
+//   plan_pool        (gi_layout.h) how many paths are in flight: the memory budget per slot, which kStreamWork (gi_context.inc) must stay within
 static int grid_for(gi_ctx* c, const void* kernel, size_t dyn_lds = 0, int block = GI_BLOCK)
 {
     int per_cu = 0;
@@ -72,41 +16,26 @@ static int grid_for(gi_ctx* c, const void* kernel, size_t dyn_lds = 0, int block
 
 static int render_megakernel(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp)
 {
-    HIP_TRY(c, hipMemsetAsync(c->d_tile_counter.p, 0, sizeof(unsigned int), c->stream));
-    if (c->count_enabled) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(Counters), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->st.d_tile_counter.p, 0, sizeof(unsigned int), c->stream));
+    if (c->count_enabled) HIP_TRY(c, hipMemsetAsync(c->st.d_counters.p, 0, sizeof(Counters), c->stream));
     const int grid = c->n_cu * 2;
     HIP_TRY(c, c->t_frame.begin(c->stream));
     if (c->count_enabled)
-        hipLaunchKernelGGL(k_render<true>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
+        hipLaunchKernelGGL(k_render<true>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->st.d_tile_counter.p, c->st.d_counters.p);
     else
-        hipLaunchKernelGGL(k_render<false>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->d_tile_counter.p, c->d_counters.p);
+        hipLaunchKernelGGL(k_render<false>, dim3(grid), dim3(GI_BLOCK), 0, c->stream, c->S, F, d_out, out_is_f64, d_spp, c->st.d_tile_counter.p, c->st.d_counters.p);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, c->t_frame.end(c->stream));
     c->last_launches = 1;
     return GI_OK;
 }
 
-static void stage_begin(gi_ctx* c, int stage)
-{
-    if (!c->stage_timing) return;
-    if (c->ev_used + 2 > c->ev_pool.size()) {
-        for (int k = 0; k < 2; k++) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; c->ev_pool.push_back(e); }
-    }
-    c->ev_stage.push_back(stage);
-    (void)hipEventRecord(c->ev_pool[c->ev_used], c->stream);
-}
-static void stage_end(gi_ctx* c)
-{
-    if (!c->stage_timing || c->ev_used + 2 > c->ev_pool.size()) return;
-    (void)hipEventRecord(c->ev_pool[c->ev_used + 1], c->stream);
-    c->ev_used += 2;
-}
 // One timed stage of a frame: an event pair around its launches, and every launch counted where it is made (n_launches of gi_last_render_ms).
-extern "C++" struct TimedStage {
+struct TimedStage {
     gi_ctx* c;
     int& launches;
-    TimedStage(gi_ctx* c_, int stage, int& launches_) : c(c_), launches(launches_) { stage_begin(c, stage); }
-    ~TimedStage() { stage_end(c); }
+    TimedStage(gi_ctx* c_, int stage, int& launches_) : c(c_), launches(launches_) { c->clock.begin(stage, c->stream); }
+    ~TimedStage() { c->clock.end(c->stream); }
     template <class K, class... A> void launch(K kernel, dim3 grid, dim3 block, size_t lds, const A&... args)
     {
         hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, args...);
@@ -116,7 +45,7 @@ extern "C++" struct TimedStage {
 
 static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process may drive several devices (gi_group_*)
 {
-    StreamGrids& g = c->grids;
+    StreamGrids& g = c->st.grids;
     if (!g.trace) {
         auto grid_of = [&](const auto& k, int block) { return grid_for(c, (const void*)k.fn, k.lds, block); };
         ask_for_lds(kTrace, g.lds_refused); ask_for_lds(kShade, g.lds_refused); ask_for_lds(kShadow, g.lds_refused); ask_for_lds(kFinish, g.lds_refused);
@@ -143,28 +72,29 @@ static void launch_gather(gi_ctx* c, bool wave, bool counting, const PathPool& p
         hipLaunchKernelGGL(st_gather(counting), dim3(stream_grids(c).gather), dim3(GI_BLOCK), 0, c->stream, c->S, pool, keys, vals, n, slot_sample, sample0, lbuf, sc);
 }
 // a few lights, wide records: the shadow walks of the shade stage run in a kernel of their own (ShadowQ)
-static bool defers_shadows(const gi_ctx* c) { return c->defer_shadows && c->S.wnodes != nullptr && c->S.n_light >= 1 && c->S.n_light <= 4; }   // one query per light and shaded hit
+static bool defers_shadows(const gi_ctx* c) { return c->tune.defer_shadows && c->S.wnodes != nullptr && c->S.n_light >= 1 && c->S.n_light <= 4; }   // one query per light and shaded hit
 
-// everything the pass loop needs for P paths in flight (the radiance buffer is the caller's)
-// need_table: the caller's passes read slot_sample (sample_of); a chunk whose samples are all in flight at once does without it
+hipError_t StreamState::alloc(uint32_t P, bool need_table, int n_shadow)
+{
+    hipError_t e = hipSuccess;
+    auto grow = [&e](auto& buf, size_t need) { if (e == hipSuccess && buf.n < need) e = buf.alloc(need); };
+    auto once = [&e](auto& buf, size_t count) { if (e == hipSuccess && !buf.p) e = buf.alloc(count); };
+    if (spool_slots < P) { grow(d_spool, (size_t)P * GI_POOL_BYTES_PER_SLOT); if (e == hipSuccess) spool_slots = P; }
+    if (need_table) grow(d_slot_sample, P);
+    for (const StreamWorkItem& w : kStreamWork) grow(work.*w.buf, (size_t)P * w.per_slot + w.fixed);
+    grow(d_shq, (size_t)P * (size_t)n_shadow);
+    once(d_blkcnt, (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE);
+    once(d_segs, GI_MAX_PRODUCER_BLOCKS);
+    once(d_rs_hist, (size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS);
+    once(d_ctl, 1);
+    once(h_ctl, 1);
+    return e;
+}
 static int stream_alloc(gi_ctx* c, uint32_t P, bool need_table)
 {
-    if (c->spool_slots < P) { HIP_TRY(c, c->d_spool.alloc((size_t)P * GI_POOL_BYTES_PER_SLOT)); c->spool_slots = P; }
-    if (need_table && c->d_slot_sample.n < P) HIP_TRY(c, c->d_slot_sample.alloc(P));
-    for (const StreamWorkItem& w : kStreamWork) {
-        StreamWork::Buf& buf = c->work.*w.buf;
-        const size_t need = (size_t)P * w.per_slot + w.fixed;
-        if (buf.n < need) HIP_TRY(c, buf.alloc(need));
-    }
-    if (defers_shadows(c) && c->d_shq.n < (size_t)P * (size_t)c->S.n_light) HIP_TRY(c, c->d_shq.alloc((size_t)P * (size_t)c->S.n_light));
-    if (!c->d_blkcnt.p) HIP_TRY(c, c->d_blkcnt.alloc((size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE));
-    if (!c->d_segs.p) HIP_TRY(c, c->d_segs.alloc(GI_MAX_PRODUCER_BLOCKS));
-    if (!c->d_rs_hist.p) HIP_TRY(c, c->d_rs_hist.alloc((size_t)GI_RS_MAXBINS * GI_MAX_PRODUCER_BLOCKS));
-    if (!c->d_ctl.p) HIP_TRY(c, c->d_ctl.alloc(1));
-    if (!c->h_ctl) HIP_TRY(c, hipHostMalloc((void**)&c->h_ctl, sizeof(StreamCtl), hipHostMallocDefault));
+    HIP_TRY(c, c->st.alloc(P, need_table, defers_shadows(c) ? c->S.n_light : 0));
     return GI_OK;
 }
-
 // ---- the new paths of a pass.  A schedule's refill is asked once per pass, with the slots the pass before freed (q_free == nullptr: slots
 // 0 .. n_free - 1), and answers with everything the pass needs to know: paths it has prepared in work.q_new, samples the trace kernel is to start
 // itself (gen.n_gen of them), and whether it will start no more after these.
@@ -256,7 +186,7 @@ static int passes_begin(Passes& p)
     // of the benchmark frame on 8 GPUs (66 M samples): its tail is a larger part of it and holds fewer paths, and a lone path's gather is the wave
     // routine's: up to 32 (a 1/8 share 60.6 ms against 64.0; tools/fin_share.sh)
     const bool small_frame = (unsigned long long)F.w * (unsigned long long)F.local_rows * (unsigned long long)std::max(F.max_samples, 1) < 200000000ull;
-    p.wave_factor = c->wave_factor ? c->wave_factor : ((small_frame && c->S.pcand) ? 32u : 2u);
+    p.wave_factor = c->tune.wave_factor ? c->tune.wave_factor : ((small_frame && c->S.pcand) ? 32u : 2u);
     p.G = &stream_grids(c);
     if (p.G->lds_refused) return fail(c, GI_E_HIP, "render: the device refused " + std::to_string(p.G->lds_refused) + " bytes of dynamic LDS per workgroup (the traversal kernels are laid out for gfx950's 160 KB per CU)");
     p.wide = c->S.wnodes != nullptr;
@@ -270,10 +200,10 @@ static int passes_begin(Passes& p)
     // frame (its trace_rays are compared with culling on and off).  With it a path that does not continue is released by the shade stage even
     // with a gather pending (k_st_shade).
     const bool no_ambient = c->S.ambient[0] == 0.0 && c->S.ambient[1] == 0.0 && c->S.ambient[2] == 0.0;
-    p.early_turns = (c->early_miss && p.wide && defers_shadows(c) && c->S.n_light == 1 && c->S.cboxes != nullptr && c->S.n_fog == 0 && no_ambient && !p.counting) ? c->early_turns : 0u;
-    p.pool = make_path_pool(c->d_spool.p, c->spool_slots);
-    p.sc = p.counting ? c->d_stream_cnt.p : nullptr;
-    p.shq = defers_shadows(c) ? c->d_shq.p : nullptr;
+    p.early_turns = (c->tune.early_miss && p.wide && defers_shadows(c) && c->S.n_light == 1 && c->S.cboxes != nullptr && c->S.n_fog == 0 && no_ambient && !p.counting) ? c->tune.early_turns : 0u;
+    p.pool = make_path_pool(c->st.d_spool.p, c->st.spool_slots);
+    p.sc = p.counting ? c->st.d_stream_cnt.p : nullptr;
+    p.shq = defers_shadows(c) ? c->st.d_shq.p : nullptr;
     return GI_OK;
 }
 
@@ -281,15 +211,15 @@ static int passes_begin(Passes& p)
 static int sort_pairs(TimedStage& stage, const uint32_t* keys_in, uint32_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out, uint32_t n, const uint32_t* n_dev, int begin_bit, int end_bit)
 {
     gi_ctx* c = stage.c;
-    uint32_t* const tk = c->work.sort_scratch.p;
+    uint32_t* const tk = c->st.work.sort_scratch.p;
     stage.launches++;
-    return rs_sort_pairs(c, keys_in, keys_out, vals_in, vals_out, tk, tk + n, n, n_dev, begin_bit, end_bit, c->d_rs_hist.p);
+    return rs_sort_pairs(c, keys_in, keys_out, vals_in, vals_out, tk, tk + n, n, n_dev, begin_bit, end_bit, c->st.d_rs_hist.p);
 }
 
 // The jobs of the two compactions of a pass.  Behind the trace stage: hits -> the shade queue, finished paths -> the head of the free list.
 static CompactJob trace_compact_job(const Passes& p)
 {
-    const StreamWork& w = p.c->work;
+    const StreamWork& w = p.c->st.work;
     CompactJob job;
     memset(&job, 0, sizeof job);
     job.st[0] = {w.stage_hits.p, w.q_shade.p, 1}; job.n_streams[0] = 1; job.kind[0] = QC_SHADE; job.total_field[0] = 0;
@@ -300,7 +230,7 @@ static CompactJob trace_compact_job(const Passes& p)
 // Behind the shade stage, streams in queue order: [0] continuing slot, [1] its coherence key, [2] gather slot, [3] gather position (3 doubles = 6 words), [4] freed slot
 static CompactJob shade_compact_job(const Passes& p)
 {
-    const StreamWork& w = p.c->work;
+    const StreamWork& w = p.c->st.work;
     const Scene& S = p.c->S;
     CompactJob job;
     memset(&job, 0, sizeof job);
@@ -316,7 +246,7 @@ static CompactJob shade_compact_job(const Passes& p)
 }
 static int clear_block_counters(gi_ctx* c)   // the producers' per-workgroup append counters, before each of the two producing kernels
 {
-    HIP_TRY(c, hipMemsetAsync(c->d_blkcnt.p, 0, (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE * sizeof(unsigned int), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->st.d_blkcnt.p, 0, (size_t)QC_KINDS * GI_MAX_PRODUCER_BLOCKS * GI_CNT_STRIDE * sizeof(unsigned int), c->stream));
     return GI_OK;
 }
 
@@ -325,19 +255,19 @@ static int clear_block_counters(gi_ctx* c)   // the producers' per-workgroup app
 static int finish_tail(Passes& p)
 {
     gi_ctx* c = p.c;
-    if (c->d_fin_cnt.n < 16) HIP_TRY(c, c->d_fin_cnt.alloc(16));
-    HIP_TRY(c, hipMemsetAsync(c->d_fin_cnt.p, 0, 16 * sizeof(unsigned int), c->stream));
+    if (c->st.d_fin_cnt.n < 16) HIP_TRY(c, c->st.d_fin_cnt.alloc(16));
+    HIP_TRY(c, hipMemsetAsync(c->st.d_fin_cnt.p, 0, 16 * sizeof(unsigned int), c->stream));
     const uint32_t* fq_in = p.cont_in;
     uint32_t* fq_out = p.cont_out;
-    const size_t n_stage = std::min<size_t>(c->finish_plan.size(), 15);
+    const size_t n_stage = std::min<size_t>(c->tune.finish_plan.size(), 15);
     for (size_t k = 0; k < n_stage; k++) {
-        const int lanes = c->finish_plan[k].first, vertices = k + 1 == n_stage ? GI_MAX_DEPTH + 1 : c->finish_plan[k].second;
-        const unsigned int* n_in_dev = k == 0 ? nullptr : c->d_fin_cnt.p + (k - 1);
+        const int lanes = c->tune.finish_plan[k].first, vertices = k + 1 == n_stage ? GI_MAX_DEPTH + 1 : c->tune.finish_plan[k].second;
+        const unsigned int* n_in_dev = k == 0 ? nullptr : c->st.d_fin_cnt.p + (k - 1);
         TimedStage stage(c, STG_FINISH, p.launches);
         for (int mode = 0; mode < ((p.wide && lanes <= 0) ? 3 : 1); mode++) {   // a path per lane; then, of what that left, a path per wave and a path per group of 16 lanes
             const FinishK fin_k = st_finish(p.feat, p.wide, mode);
             stage.launch(fin_k.fn, dim3(p.G->finish), dim3(GI_FINISH_BLOCK), fin_k.lds, c->S, p.F.seed, p.pool, p.slot_sample, p.sample0,
-                         fq_in, n_in_dev, p.n_cont, lanes, vertices, fq_out, c->d_fin_cnt.p + k, p.lbuf, (p.wave_factor << 16) | (c->coop_factor & 0xffffu));
+                         fq_in, n_in_dev, p.n_cont, lanes, vertices, fq_out, c->st.d_fin_cnt.p + k, p.lbuf, (p.wave_factor << 16) | (c->tune.coop_factor & 0xffffu));
         }
         uint32_t* t = const_cast<uint32_t*>(fq_in); fq_in = fq_out; fq_out = t;
     }
@@ -348,20 +278,20 @@ static int finish_tail(Passes& p)
 static int trace_stage(Passes& p)
 {
     gi_ctx* c = p.c;
-    const StreamWork& w = c->work;
+    const StreamWork& w = c->st.work;
     const StreamGrids& G = *p.G;
-    HIP_TRY(c, hipMemsetAsync(c->d_ctl.p, 0, sizeof(StreamCtl), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->st.d_ctl.p, 0, sizeof(StreamCtl), c->stream));
     // The free list of this pass has one reader, the refill of the next.  Once the refill has started its last sample (`exhausted`, told with the
     // paths of this pass: this pass still reads the previous list, nobody reads the one it would write; rounds never hand a freed slot out again) the
     // kernels get no free queue and skip its appends, the compaction leaves the queue out, and n_free stays 0.  GI_KEEP_FREE_LIST=1: written always.
-    p.want_free = c->keep_free_list || !p.nw.exhausted;
+    p.want_free = c->tune.keep_free_list || !p.nw.exhausted;
     p.free_out = p.want_free ? (p.ping ? w.q_free_b.p : w.q_free_a.p) : nullptr;
     if (G.trace > GI_MAX_PRODUCER_BLOCKS || G.shade > GI_MAX_PRODUCER_BLOCKS) return fail(c, GI_E_STATE, "render: more producer workgroups than per-workgroup counters");
     if (const int rc = clear_block_counters(c)) return rc;
     const TraceK trace_k = st_trace(p.trace_feat, p.wide, p.counting);
     TimedStage(c, STG_TRACE, p.launches).launch(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, c->S, p.F.seed, p.pool, p.slot_sample, p.sample0, p.nw.gen, w.q_new.p, p.nw.n_prepared,
-                                                p.cont_in, p.n_cont, c->d_blkcnt.p, c->d_segs.p, w.stage_hits.p, p.want_free ? w.stage_free_trace.p : nullptr, p.lbuf, c->refill_min, p.sc);
-    TimedStage(c, STG_OTHER, p.launches).launch(k_st_compact, dim3(G.compact), dim3(256), 0, c->S, trace_compact_job(p), c->d_blkcnt.p, c->d_segs.p, (uint32_t)G.trace, c->d_ctl.p);
+                                                p.cont_in, p.n_cont, c->st.d_blkcnt.p, c->st.d_segs.p, w.stage_hits.p, p.want_free ? w.stage_free_trace.p : nullptr, p.lbuf, c->tune.refill_min, p.sc);
+    TimedStage(c, STG_OTHER, p.launches).launch(k_st_compact, dim3(G.compact), dim3(256), 0, c->S, trace_compact_job(p), c->st.d_blkcnt.p, c->st.d_segs.p, (uint32_t)G.trace, c->st.d_ctl.p);
     return GI_OK;
 }
 
@@ -371,17 +301,17 @@ static int trace_stage(Passes& p)
 static int shade_sort_stage(Passes& p)
 {
     gi_ctx* c = p.c;
-    const StreamWork& w = c->work;
+    const StreamWork& w = c->st.work;
     p.shade_queue = w.q_shade.p;
     p.shade_places = nullptr;
-    if (!(c->sort_shade && p.n_cont > 0)) return GI_OK;
+    if (!(c->tune.sort_shade && p.n_cont > 0)) return GI_OK;
     int sbits = 1;
-    while ((1ull << sbits) < (unsigned long long)c->spool_slots) sbits++;
+    while ((1ull << sbits) < (unsigned long long)c->st.spool_slots) sbits++;
     const uint32_t bound = p.n_new + p.n_cont;      // every item of the trace stage may have hit something
     int uncounted = 0;                              // n_launches has never included this stage: the figure stays comparable with earlier frames'
     TimedStage stage(c, STG_SORT, uncounted);
     stage.launch(k_iota, dim3(std::min<uint32_t>((bound + 1023u) / 1024u, 4096u)), dim3(1024), 0, w.shade_iota.p, bound);
-    if (const int rc = sort_pairs(stage, w.q_shade.p, w.shade_sorted.p, w.shade_iota.p, w.shade_places.p, bound, reinterpret_cast<const uint32_t*>(&c->d_ctl.p->n_shade), std::min(c->sort_shade_lo, sbits - 1), sbits)) return rc;
+    if (const int rc = sort_pairs(stage, w.q_shade.p, w.shade_sorted.p, w.shade_iota.p, w.shade_places.p, bound, reinterpret_cast<const uint32_t*>(&c->st.d_ctl.p->n_shade), std::min(c->tune.sort_shade_lo, sbits - 1), sbits)) return rc;
     p.shade_queue = w.shade_sorted.p;
     p.shade_places = w.shade_places.p;
     return GI_OK;
@@ -392,23 +322,23 @@ static int shade_sort_stage(Passes& p)
 static int shade_stage(Passes& p)
 {
     gi_ctx* c = p.c;
-    const StreamWork& w = c->work;
+    const StreamWork& w = c->st.work;
     const StreamGrids& G = *p.G;
     if (const int rc = clear_block_counters(c)) return rc;
     const bool many = c->S.n_light > 1;
     const ShadeK shade_k = st_shade(p.feat, p.wide, p.shq ? (many ? 2 : 1) : 0);
-    TimedStage(c, STG_SHADE, p.launches).launch(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, c->S, p.F.seed, p.pool, p.slot_sample, p.sample0, p.shade_queue, c->d_ctl.p, c->d_blkcnt.p, c->d_segs.p,
+    TimedStage(c, STG_SHADE, p.launches).launch(shade_k.fn, dim3(G.shade), dim3(GI_SHADE_BLOCK), shade_k.lds, c->S, p.F.seed, p.pool, p.slot_sample, p.sample0, p.shade_queue, c->st.d_ctl.p, c->st.d_blkcnt.p, c->st.d_segs.p,
                                                 w.stage_cont_slots.p, w.stage_cont_keys.p, w.stage_gather_slots.p, reinterpret_cast<double*>(w.stage_gather_pos.p), p.want_free ? w.stage_free_shade.p : nullptr,
                                                 p.lbuf, p.shq, p.shade_places, p.early_turns);
     if (p.shq) {
         const ShadowK shadow_k = st_shadow(p.feat, many, p.counting);
-        TimedStage(c, STG_SHADOW, p.launches).launch(shadow_k.fn, dim3(G.shadow), dim3(GI_SHADOW_BLOCK), shadow_k.lds, c->S, p.F.seed, p.pool, p.shq, c->d_ctl.p, p.lbuf, c->refill_min, p.sc);
+        TimedStage(c, STG_SHADOW, p.launches).launch(shadow_k.fn, dim3(G.shadow), dim3(GI_SHADOW_BLOCK), shadow_k.lds, c->S, p.F.seed, p.pool, p.shq, c->st.d_ctl.p, p.lbuf, c->tune.refill_min, p.sc);
     }
-    TimedStage(c, STG_OTHER, p.launches).launch(k_st_compact, dim3(G.compact), dim3(256), 0, c->S, shade_compact_job(p), c->d_blkcnt.p, c->d_segs.p, (uint32_t)G.shade, c->d_ctl.p);
-    HIP_TRY(c, hipMemcpyAsync(c->h_ctl, c->d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, c->stream));
+    TimedStage(c, STG_OTHER, p.launches).launch(k_st_compact, dim3(G.compact), dim3(256), 0, c->S, shade_compact_job(p), c->st.d_blkcnt.p, c->st.d_segs.p, (uint32_t)G.shade, c->st.d_ctl.p);
+    HIP_TRY(c, hipMemcpyAsync(c->st.h_ctl.p, c->st.d_ctl.p, sizeof(StreamCtl), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    p.n_gather = c->h_ctl->n_gather; p.n_cont = c->h_ctl->n_cont; p.n_free = c->h_ctl->n_free;
-    if (p.counting) c->stream_shaded += c->h_ctl->n_shade;
+    p.n_gather = c->st.h_ctl.p->n_gather; p.n_cont = c->st.h_ctl.p->n_cont; p.n_free = c->st.h_ctl.p->n_free;
+    if (p.counting) c->stream_shaded += c->st.h_ctl.p->n_shade;
     return GI_OK;
 }
 
@@ -416,14 +346,14 @@ static int shade_stage(Passes& p)
 static int gather_stage(Passes& p)
 {
     gi_ctx* c = p.c;
-    const StreamWork& w = c->work;
+    const StreamWork& w = c->st.work;
     if (!(c->S.n_pnode > 0 && p.n_gather > 0)) return GI_OK;
     {
         TimedStage stage(c, STG_SORT, p.launches);
         if (const int rc = sort_pairs(stage, w.gather_keys.p, w.gather_keys_sorted.p, w.gather_slots.p, w.gather_slots_sorted.p, p.n_gather, nullptr, 0, photon_key_bits(c->S))) return rc;
     }
     TimedStage stage(c, STG_GATHER, p.launches);
-    launch_gather(c, c->S.pcand && p.n_gather < c->gather_wave_below, p.counting, p.pool, w.gather_keys_sorted.p, w.gather_slots_sorted.p, p.n_gather, p.slot_sample, p.sample0, p.lbuf, p.sc);
+    launch_gather(c, c->S.pcand && p.n_gather < c->tune.gather_wave_below, p.counting, p.pool, w.gather_keys_sorted.p, w.gather_slots_sorted.p, p.n_gather, p.slot_sample, p.sample0, p.lbuf, p.sc);
     p.launches++;
     return GI_OK;
 }
@@ -432,11 +362,11 @@ static int gather_stage(Passes& p)
 static int cont_sort_stage(Passes& p)
 {
     gi_ctx* c = p.c;
-    const StreamWork& w = c->work;
+    const StreamWork& w = c->st.work;
     if (p.n_cont == 0) return GI_OK;
     TimedStage stage(c, STG_SORT, p.launches);
-    if (c->sort_cont) {
-        return sort_pairs(stage, w.cont_keys.p, w.cont_keys_sorted.p, w.cont_slots.p, p.cont_out, p.n_cont, nullptr, c->sort_lo_bit, 27);
+    if (c->tune.sort_cont) {
+        return sort_pairs(stage, w.cont_keys.p, w.cont_keys_sorted.p, w.cont_slots.p, p.cont_out, p.n_cont, nullptr, c->tune.sort_lo_bit, 27);
     }
     HIP_TRY(c, hipMemcpyAsync(p.cont_out, w.cont_slots.p, (size_t)p.n_cont * 4, hipMemcpyDeviceToDevice, c->stream));   // GI_SORT_CONT=0: queue order (tuning aid), counted like the sort
     p.launches++;
@@ -448,7 +378,7 @@ static void print_pass(const Passes& p)   // GI_DEBUG_WF
     fprintf(stderr, "[st] new %u cont %u free %u gather %u\n", p.n_new, p.n_cont, p.n_free, p.n_gather);
     if (!p.counting) return;
     StreamCounters h;   // what this pass executed (tuning aid): cumulative counters, printed per pass
-    if (hipMemcpy(&h, p.c->d_stream_cnt.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
+    if (hipMemcpy(&h, p.c->st.d_stream_cnt.p, sizeof h, hipMemcpyDeviceToHost) == hipSuccess)
         fprintf(stderr, "[cnt] trace rays %llu walks %llu records %llu boxes %llu cboxes %llu leaves %llu eboxes %llu tris %llu | shadow rays %llu records %llu boxes %llu cboxes %llu leaves %llu eboxes %llu tris %llu | gather q %llu cand %llu\n",
                 h.trace_rays, h.trace[0], h.trace[1], h.trace[2], h.trace[3], h.trace[4], h.trace[6], h.trace[5], h.shadow_rays, h.shadow[1], h.shadow[2], h.shadow[3], h.shadow[4], h.shadow[6], h.shadow[5], h.gather_queries, h.gather_cand);
 }
@@ -467,9 +397,9 @@ static int stream_passes(gi_ctx* c, const Frame& F, unsigned long long* slot_sam
         p.nw = refill.next(p.n_free, p.free_in);
         p.n_new = p.nw.n_prepared + p.nw.gen.n_gen;
         if (p.n_new + p.n_cont == 0) break;
-        p.cont_out = p.ping ? c->work.q_cont_b.p : c->work.q_cont_a.p;
-        p.cont_in = p.ping ? c->work.q_cont_a.p : c->work.q_cont_b.p;
-        if (p.nw.exhausted && p.n_new == 0 && p.n_cont <= c->finish_threshold && !p.counting) return finish_tail(p);   // (a counted frame runs its stragglers through the counting passes)
+        p.cont_out = p.ping ? c->st.work.q_cont_b.p : c->st.work.q_cont_a.p;
+        p.cont_in = p.ping ? c->st.work.q_cont_a.p : c->st.work.q_cont_b.p;
+        if (p.nw.exhausted && p.n_new == 0 && p.n_cont <= c->tune.finish_threshold && !p.counting) return finish_tail(p);   // (a counted frame runs its stragglers through the counting passes)
         for (auto stage : kPassStages)
             if (const int rc = stage(p)) return rc;
         p.free_in = p.free_out;
@@ -492,8 +422,8 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
     // paths in flight and samples per chunk: gi_layout.h's budget, of free memory plus what this context holds already and would re-use
     size_t free_b = 0, total_b = 0;
     const bool mem_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-    const size_t held = c->d_spool.n + c->d_lbuf.n * 8 + (c->work.q_new.n + c->work.q_free_b.n) * 4 * 7 + c->d_shq.n * sizeof(ShadowQ);
-    const PoolPlan plan = plan_pool(mem_known, free_b, held, n_pix, spp, c->pool_slots_max, c->lbuf_bytes_max, defers_shadows(c) ? c->S.n_light : 0);
+    const size_t held = c->st.d_spool.n + c->st.d_lbuf.n * 8 + (c->st.work.q_new.n + c->st.work.q_free_b.n) * 4 * 7 + c->st.d_shq.n * sizeof(ShadowQ);
+    const PoolPlan plan = plan_pool(mem_known, free_b, held, n_pix, spp, c->tune.pool_slots_max, c->tune.lbuf_bytes_max, defers_shadows(c) ? c->S.n_light : 0);
     const uint32_t P = plan.P;
     const int chunk = plan.chunk;
     // The sample table.  A chunk of ns samples per pixel whose n_pix * ns samples all fit the pool is started whole by the first pass: refill hands
@@ -501,31 +431,31 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
     // later.  The table would be the identity plus sample0 for the whole chunk, so the kernels are given none (sample_of) -- 8 bytes per sample less
     // to write in the trace stage and a scattered read less per gather query.  Decided per chunk (fits); the table is allocated when the largest
     // chunk of this call needs it, and stays in the budget per slot either way: a later call may need it.  GI_SAMPLE_IDENTITY=0: always a table.
-    auto fits = [&](int ns) { return c->sample_identity && (size_t)P >= (size_t)n_pix * (size_t)ns; };
+    auto fits = [&](int ns) { return c->tune.sample_identity && (size_t)P >= (size_t)n_pix * (size_t)ns; };
     int rc = stream_alloc(c, P, !fits(chunk));
     if (rc) return rc;
-    if (c->d_lbuf.n < (size_t)n_pix * chunk * 3) HIP_TRY(c, c->d_lbuf.alloc((size_t)n_pix * chunk * 3));
+    if (c->st.d_lbuf.n < (size_t)n_pix * chunk * 3) HIP_TRY(c, c->st.d_lbuf.alloc((size_t)n_pix * chunk * 3));
     const StreamGrids& G = stream_grids(c);
     hipStream_t st = c->stream;
     int launches = 0;
-    c->ev_used = 0; c->ev_stage.clear();
+    c->clock.restart();
     if (c->count_stream) {
-        if (!c->d_stream_cnt.p) HIP_TRY(c, c->d_stream_cnt.alloc(1));
-        HIP_TRY(c, hipMemsetAsync(c->d_stream_cnt.p, 0, sizeof(StreamCounters), st));
+        if (!c->st.d_stream_cnt.p) HIP_TRY(c, c->st.d_stream_cnt.alloc(1));
+        HIP_TRY(c, hipMemsetAsync(c->st.d_stream_cnt.p, 0, sizeof(StreamCounters), st));
         c->stream_shaded = 0;
     }
     HIP_TRY(c, c->t_frame.begin(st));
     if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
-    if (c->d_pixtab.n < n_pix) HIP_TRY(c, c->d_pixtab.alloc(n_pix));
-    hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->d_pixtab.p);
+    if (c->st.d_pixtab.n < n_pix) HIP_TRY(c, c->st.d_pixtab.alloc(n_pix));
+    hipLaunchKernelGGL(k_pixel_table, dim3(G.pix), dim3(GI_BLOCK), 0, st, F, n_pix, c->st.d_pixtab.p);
     launches++;
     for (int s0 = s_begin; s0 < s_end; s0 += chunk) {
         const int ns = std::min(chunk, s_end - s0);
-        ChunkRefill refill(F, c->d_pixtab.p, n_pix, s0, ns);
+        ChunkRefill refill(F, c->st.d_pixtab.p, n_pix, s0, ns);
         if (debug_wf) fprintf(stderr, "[st] chunk of %d samples: pool %u slots, sample table %s\n", ns, P, fits(ns) ? "off" : "on");
-        rc = stream_passes(c, F, fits(ns) ? nullptr : c->d_slot_sample.p, refill.sample0, c->d_lbuf.p, P, refill, debug_wf, cancel, launches);   // pass 0: every slot is free
+        rc = stream_passes(c, F, fits(ns) ? nullptr : c->st.d_slot_sample.p, refill.sample0, c->st.d_lbuf.p, P, refill, debug_wf, cancel, launches);   // pass 0: every slot is free
         if (rc) return rc;
-        TimedStage(c, STG_ACCUM, launches).launch(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, F, pix, c->d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp);
+        TimedStage(c, STG_ACCUM, launches).launch(k_st_accum, dim3(G.accum), dim3(GI_BLOCK), 0, F, pix, c->st.d_lbuf.p, n_pix, ns, d_out, out_is_f64, d_spp);
         if (s_done) *s_done = s0 + ns;
     }
     HIP_TRY(c, hipGetLastError());
@@ -537,8 +467,8 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
 static int render_streaming(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
     const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
-    return stream_samples(c, F, c->d_pix.p, 0, F.max_samples, true, d_out, out_is_f64, d_spp, cancel, nullptr);
+    if (c->st.d_pix.n < n_pix) HIP_TRY(c, c->st.d_pix.alloc(n_pix));
+    return stream_samples(c, F, c->st.d_pix.p, 0, F.max_samples, true, d_out, out_is_f64, d_spp, cancel, nullptr);
 }
 
 // Adaptive sampling (min_samples != max_samples, include/raytracer.h:108-148), and every frame of render mode 2: synchronous rounds --
@@ -554,40 +484,40 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
     if (!rounds_fit(F)) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
     const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (wf_pixel_xy)
     const bool debug_wf = getenv("GI_DEBUG_WF") != nullptr;   // read at every call
-    int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->pool_slots_max, 0xfffffff0ull) / n_pix));
+    int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->tune.pool_slots_max, 0xfffffff0ull) / n_pix));
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
     const size_t slots = (size_t)n_pix * (size_t)B;
     int rc = stream_alloc(c, (uint32_t)slots, true);   // k_ad_gen names every path's place in the radiance buffer
     if (rc) return rc;
-    if (c->d_lbuf.n < slots * 3) HIP_TRY(c, c->d_lbuf.alloc(slots * 3));
-    if (!c->d_wfcnt.p) HIP_TRY(c, c->d_wfcnt.alloc(2));
-    if (!c->h_wfcnt) HIP_TRY(c, hipHostMalloc((void**)&c->h_wfcnt, 2 * sizeof(unsigned int), hipHostMallocDefault));
+    if (c->st.d_lbuf.n < slots * 3) HIP_TRY(c, c->st.d_lbuf.alloc(slots * 3));
+    if (!c->st.d_wfcnt.p) HIP_TRY(c, c->st.d_wfcnt.alloc(2));
+    HIP_TRY(c, c->st.h_wfcnt.alloc(2));
     const StreamGrids& G = stream_grids(c);
     hipStream_t st = c->stream;
-    unsigned int* cnt = c->d_wfcnt.p;
+    unsigned int* cnt = c->st.d_wfcnt.p;
     int launches = 0;
-    c->ev_used = 0; c->ev_stage.clear();
+    c->clock.restart();
     HIP_TRY(c, c->t_frame.begin(st));
     if (init) { hipLaunchKernelGGL(k_pix_init, dim3(G.pix), dim3(GI_BLOCK), 0, st, pix, n_pix); launches++; }
     bool any = F.max_samples > 0 && F.min_samples > 0;
     if (!any) {   // 0 samples per pixel still has to write the initial colour
         HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
+        hipLaunchKernelGGL(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, st, F, pix, c->st.d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
         launches++;
     }
     while (any) {
         if (cancel && *cancel) { c->last_launches = launches; return fail(c, GI_E_CANCELLED, "render: cancelled"); }
         HIP_TRY(c, hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned int), st));
-        TimedStage(c, STG_REGEN, launches).launch(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, c->S, F, pix, make_path_pool(c->d_spool.p, c->spool_slots), c->d_slot_sample.p, n_pix, B, c->work.q_new.p, cnt + 0);
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt, cnt, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        TimedStage(c, STG_REGEN, launches).launch(k_ad_gen, dim3(G.ad_gen), dim3(GI_BLOCK), 0, c->S, F, pix, make_path_pool(c->st.d_spool.p, c->st.spool_slots), c->st.d_slot_sample.p, n_pix, B, c->st.work.q_new.p, cnt + 0);
+        HIP_TRY(c, hipMemcpyAsync(c->st.h_wfcnt.p, cnt, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        RoundRefill refill(F, c->h_wfcnt[0]);      // paths started by this round, already in the new-path queue
-        rc = stream_passes(c, F, c->d_slot_sample.p, 0ull, c->d_lbuf.p, 0u, refill, debug_wf, cancel, launches);
+        RoundRefill refill(F, c->st.h_wfcnt.p[0]);      // paths started by this round, already in the new-path queue
+        rc = stream_passes(c, F, c->st.d_slot_sample.p, 0ull, c->st.d_lbuf.p, 0u, refill, debug_wf, cancel, launches);
         if (rc) return rc;
-        TimedStage(c, STG_ACCUM, launches).launch(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, F, pix, c->d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
-        HIP_TRY(c, hipMemcpyAsync(c->h_wfcnt + 1, cnt + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        TimedStage(c, STG_ACCUM, launches).launch(k_ad_accum, dim3(G.ad_accum), dim3(GI_BLOCK), 0, F, pix, c->st.d_lbuf.p, n_pix, B, d_out, out_is_f64, d_spp, cnt + 1);
+        HIP_TRY(c, hipMemcpyAsync(c->st.h_wfcnt.p + 1, cnt + 1, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
-        any = c->h_wfcnt[1] > 0;
+        any = c->st.h_wfcnt.p[1] > 0;
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, c->t_frame.end(st));
@@ -598,12 +528,11 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
 static int render_adaptive(gi_ctx* c, const Frame& F, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
     const uint32_t n_pix = rounds_records(F);
-    if (c->d_pix.n < n_pix) HIP_TRY(c, c->d_pix.alloc(n_pix));
-    return run_rounds(c, F, c->d_pix.p, true, d_out, out_is_f64, d_spp, cancel);
+    if (c->st.d_pix.n < n_pix) HIP_TRY(c, c->st.d_pix.alloc(n_pix));
+    return run_rounds(c, F, c->st.d_pix.p, true, d_out, out_is_f64, d_spp, cancel);
 }
 
 // fixed sample count: the streaming pool with path regeneration (the refill schedule); adaptive sampling: rounds (sample-order decisions) on the
 // same passes; mode 2: rounds for every frame, a second schedule of the fixed-spp frames
 static bool uses_refill_schedule(const gi_ctx* c, const Frame& F) { return c->render_mode == 0 && F.min_samples == F.max_samples && F.max_samples > 0; }
 
-#endif

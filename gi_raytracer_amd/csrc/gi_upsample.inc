@@ -163,7 +163,7 @@ int gi_upsample_device(gi_ctx* c, const gi_upsample_params* p, const void* d_low
                        const void* d_features, int features_is_f64, void* d_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_up.reset();
+    c->up.timer.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!d_low_color || !d_low_features || !d_features || !d_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
@@ -172,20 +172,20 @@ int gi_upsample_device(gi_ctx* c, const gi_upsample_params* p, const void* d_low
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = dn_reserve(c, n_low);
     if (rc != GI_OK) return rc;
-    HIP_TRY(c, c->t_up.begin(c->stream));
+    HIP_TRY(c, c->up.timer.begin(c->stream));
     const int demod = p->demodulate != 0;
     hipLaunchKernelGGL(k_dn_pack, dim3((unsigned)((n_low * 8 + 255) / 256)), dim3(256), 0, c->stream, n_low, d_low_color, low_color_is_f64, d_low_features, low_features_is_f64, demod,
-                       c->d_dn_a.p, c->d_dn_guides.p);
+                       c->dn.d_a.p, c->dn.d_guides.p);
     UpGrid G;
     G.w = p->width; G.h = p->height; G.wl = p->low_width; G.hl = p->low_height; G.S = p->factor;
     G.tiles_x = (p->width + GI_UP_TX - 1) / GI_UP_TX;
     const int tiles_y = (p->height + GI_UP_TY - 1) / GI_UP_TY;
     DnInv inv;
     inv.c = 0.0; inv.n = dn_inv(p->sigma_normal, 1.0); inv.z = dn_inv(p->sigma_depth, 1.0); inv.a = dn_inv(p->sigma_albedo, 1.0);
-    hipLaunchKernelGGL(k_up_sample, dim3((unsigned)((size_t)G.tiles_x * tiles_y)), dim3(GI_UP_BLOCK), 0, c->stream, G, inv, c->d_dn_a.p, c->d_dn_guides.p, d_features, features_is_f64,
+    hipLaunchKernelGGL(k_up_sample, dim3((unsigned)((size_t)G.tiles_x * tiles_y)), dim3(GI_UP_BLOCK), 0, c->stream, G, inv, c->dn.d_a.p, c->dn.d_guides.p, d_features, features_is_f64,
                        demod, d_out, out_is_f64);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, c->t_up.end(c->stream));
+    HIP_TRY(c, c->up.timer.end(c->stream));
     return GI_OK;
 }
 
@@ -193,7 +193,7 @@ int gi_upsample_host(gi_ctx* c, const gi_upsample_params* p, const void* h_low_c
                      const void* h_features, int features_is_f64, void* h_out, int out_is_f64)
 {
     if (!c) return GI_E_INVALID;
-    c->t_up.reset();
+    c->up.timer.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
     if (!h_low_color || !h_low_features || !h_features || !h_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
@@ -207,13 +207,13 @@ int gi_upsample_host(gi_ctx* c, const gi_upsample_params* p, const void* h_low_c
     if (e == hipSuccess) e = d_out.alloc(ob);
     if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("upsample_host: ") + hipGetErrorString(e));
     const int rc = gi_upsample_device(c, p, d_color.p, low_color_is_f64, d_low.p, low_features_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
-    return rc != GI_OK ? rc : finish_to_host(c, "upsample_host", {{h_out, d_out.p, ob}}, &c->t_up);
+    return rc != GI_OK ? rc : finish_to_host(c, "upsample_host", {{h_out, d_out.p, ob}}, &c->up.timer);
 }
 
 int gi_last_upsample_ms(gi_ctx* c, float* ms)
 {
     if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->t_up.read(ms));
+    HIP_TRY(c, c->up.timer.read(ms));
     return GI_OK;
 }
 

@@ -1,6 +1,6 @@
 """The free list of the stream passes has one reader: the refill of the next pass, which hands freed slots to samples that have not been started.
 From the pass in which the last sample is started (and in every pass of an adaptive round or of render mode 2) nothing reads it, so the kernels get
-no free queue, the compaction leaves the queue out and the pass reports 0 freed slots (gi_kernels.hip: stream_passes).  GI_KEEP_FREE_LIST=1 writes
+no free queue, the compaction leaves the queue out and the pass reports 0 freed slots (gi_stream.inc: trace_stage).  GI_KEEP_FREE_LIST=1 writes
 it in every pass as before.  Which slots are listed where nobody looks is bookkeeping, not arithmetic: every frame here is compared byte for byte
 with the same frame of a context that keeps the list.  What the passes did is read off the per-pass line of GI_DEBUG_WF, so a default context that
 quietly kept the list, or one that dropped it while samples were still waiting for a slot, fails here too."""
