@@ -358,7 +358,7 @@ struct gi_ctx {
         bool open = false;
         gi_render_params rp{};
         Frame F{};                    // make_frame(rp): max_samples is the session's own
-        int schedule = 0;             // 0: refill pipeline, records in st_pixel_xy order; 1: synchronous rounds, records in padded 8x8 tiles (wf_pixel_xy)
+        int schedule = 0;             // 0: refill pipeline, records in st_pixel_xy order; 1: synchronous rounds, records in padded 8x8 tiles (tile_pixel_xy)
         int32_t sample_end = 0;       // E: every pixel has been offered samples [0, E)
         uint32_t n_rec = 0;
         DevBuf<PixRec> pix;

@@ -25,9 +25,6 @@
 using namespace gi;
 
 #define GI_BLOCK 256
-#ifndef GI_EXP_SHADE
-#define GI_EXP_SHADE 0
-#endif
 
 // ================================================================================================= kernels
 // A pixel of the adaptive loop between launches (streaming and round-based renderers), as PixelState plus n = samples started this round.
@@ -318,8 +315,8 @@ __device__ __forceinline__ uint32_t wave_append(unsigned int* counter, bool pred
     return base + (unsigned int)__popcll(mask & ((1ull << lane) - 1ull));
 }
 
-// pixel index -> (x, local row): 8x8 tiles so that the 64 lanes of a wave start neighbouring pixels
-__device__ __forceinline__ bool wf_pixel_xy(const Frame& F, uint32_t i, int& x, int& ly)
+// record of the rounds schedule -> (x, local row): padded 8x8 tiles, so that the 64 lanes of a wave start neighbouring pixels; false for a padding record
+__device__ __forceinline__ bool tile_pixel_xy(const Frame& F, uint32_t i, int& x, int& ly)
 {
     const int tiles_x = (F.w + 7) >> 3;
     const uint32_t tile = i >> 6, t = i & 63u;
@@ -377,7 +374,7 @@ __global__ __launch_bounds__(GI_BLOCK) void k_ad_gen(Scene S, Frame F, PixRec* p
     for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_round; i0 += gridDim.x * blockDim.x) {
         const uint32_t i = i0 + lane;
         int x = 0, ly = 0, n = 0, s0 = 0;
-        const bool inside = i < n_pix && wf_pixel_xy(F, i, x, ly);
+        const bool inside = i < n_pix && tile_pixel_xy(F, i, x, ly);
         if (inside) {
             const int s = pix[i].s, samps = pix[i].samps;
             if (s < F.max_samples && samps < F.min_samples) {
@@ -418,7 +415,7 @@ __global__ __launch_bounds__(GI_BLOCK) void k_ad_accum(Frame F, PixRec* pix, con
         const uint32_t i = i0 + lane;
         bool wants = false;
         int x, ly;
-        if (i < n_pix && wf_pixel_xy(F, i, x, ly)) {
+        if (i < n_pix && tile_pixel_xy(F, i, x, ly)) {
             PixRec r = pix[i];
             PixelState ps = pixrec_to_state(r);
             for (int k = 0; k < r.n && pixel_wants_sample(ps, F); k++) pixel_add_sample(ps, F, ld3(lbuf + ((size_t)i * B + k) * 3));
@@ -459,6 +456,10 @@ __host__ __device__ __forceinline__ uint32_t seg_start(uint32_t b, uint32_t n_in
     const uint32_t lo = b < extra ? b : extra;
     return (lo * (full + 1) + (b - lo) * full) * bs;
 }
+// The u-th item of this workgroup's share, in its own numbering (what its LDS counter hands out), as an index into the input queue: the workgroup's
+// chunks of cs items are those of the grid-stride loop above, gridDim.x chunks apart.  One contract, three parties: seg_start counts these same chunks
+// (as full) to place the workgroup's output segment, and k_st_compact reads the segments back through segs[] -- all must agree on cs and the grid.
+__device__ __forceinline__ uint32_t chunk_item(uint32_t u, uint32_t cs) { return ((u / cs) * gridDim.x + blockIdx.x) * cs + u % cs; }
 
 // a finished path gives its slot back (its radiance is already in the per-sample buffer: the stages accumulate there)
 __device__ __forceinline__ void st_release(uint32_t slot, uint32_t* q_free, unsigned int* n_free, bool finished)
@@ -519,6 +520,20 @@ __global__ void k_pixel_table(Frame F, uint32_t n_pix, uint32_t* out)
 // the others walk on -- a wave no longer runs at the pace of its longest ray with the other lanes switched off (closed scenes: a third
 // of the lanes were active per leaf step).  Waves of new paths (neighbouring pixels, leaves shared through the scalar cache) stay in
 // lockstep: refill_min = 64 for them.  The workgroup's items are those of the grid-stride loop, so seg_start still bounds its output.
+// The refill step of those waves (k_st_trace, k_st_shadow), by all 64 lanes once the kernel has decided to refill: the idle lanes (~busy) take the next items of the
+// workgroup's share with one LDS atomic.  base: the first of them, wave-uniform; u: this lane's (chunk_item's numbering; idle lanes only, check it against total).
+struct HandOut { uint32_t base, u; };
+__device__ __forceinline__ HandOut hand_out(unsigned long long busy, unsigned int* s_next, uint32_t total, uint32_t lane, bool& more)
+{
+    const unsigned long long want = ~busy;
+    const uint32_t nw = (uint32_t)__popcll(want);
+    const int leader = __ffsll((long long)want) - 1;
+    unsigned int base = 0;
+    if ((int)lane == leader) base = atomicAdd(s_next, nw);
+    base = (unsigned int)__shfl((int)base, leader);
+    more = base + nw < total;
+    return HandOut{base, base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull))};
+}
 template <int FEAT, int WIDE, bool COUNT = false>
 __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t seed, PathPool pool, unsigned long long* slot_sample, unsigned long long sample0,
                                                        GenArgs g, const uint32_t* q_a, uint32_t n_a, const uint32_t* q_b, uint32_t n_b, unsigned int* bc, uint32_t* segs,
@@ -623,19 +638,12 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
                 }
                 pend = false;
                 if (more) {
-                    const unsigned long long want = ~busy;
-                    const uint32_t nw = (uint32_t)__popcll(want);
-                    unsigned int base = 0;
-                    if (lane == (uint32_t)(__ffsll((long long)want) - 1)) base = atomicAdd(s_next, nw);
-                    base = (unsigned int)__shfl((int)base, __ffsll((long long)want) - 1);
-                    more = base + nw < total;
+                    const HandOut f = hand_out(busy, s_next, total, lane, more);
                     // first item this fetch hands out: new paths run in lockstep, continuing ones refill
-                    const uint32_t i_first = ((base / bs) * gridDim.x + blockIdx.x) * bs + base % bs;
-                    thr = i_first < g.n_gen ? 64u : refill_min;
+                    thr = chunk_item(f.base, bs) < g.n_gen ? 64u : refill_min;
                     if (!walking) {
-                        const uint32_t u = base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
-                        const uint32_t i = ((u / bs) * gridDim.x + blockIdx.x) * bs + u % bs;
-                        if (u < total && i < n_in) {
+                        const uint32_t i = chunk_item(f.u, bs);
+                        if (f.u < total && i < n_in) {
                             item = i;
                             if constexpr (COUNT) n_rays++;
                             fetch(i, slot, ray, stream, depth);
@@ -733,7 +741,7 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
             u = (uint32_t)__shfl((int)b, 0);
         }
         if (u >= total) break;
-        const uint32_t i = ((u / cs) * gridDim.x + blockIdx.x) * cs + u % cs + lane;
+        const uint32_t i = chunk_item(u, cs) + lane;
         int fl = 0;
         bool valid = i < n_in;
         uint32_t slot = 0;
@@ -862,17 +870,10 @@ __global__ __launch_bounds__(GI_SHADOW_BLOCK) void k_st_shadow(Scene S, uint64_t
                 pend = false;
             }
             if (more) {
-                const unsigned long long want = ~busy;
-                const uint32_t nw = (uint32_t)__popcll(want);
-                const int leader = __ffsll((long long)want) - 1;
-                unsigned int base = 0;
-                if ((int)lane == leader) base = atomicAdd(s_next, nw);
-                base = (unsigned int)__shfl((int)base, leader);
-                more = base + nw < total;
+                const HandOut f = hand_out(busy, s_next, total, lane, more);
                 if (!walking) {
-                    const uint32_t u = base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull));
-                    const uint32_t i = ((u / bs) * gridDim.x + blockIdx.x) * bs + u % bs;
-                    if (u < total && i < n_in && shq[(size_t)i * nl].live) {
+                    const uint32_t i = chunk_item(f.u, bs);
+                    if (f.u < total && i < n_in && shq[(size_t)i * nl].live) {
                         li = nl - 1u;
                         const ShadowQ& e = shq[(size_t)i * nl + li];
                         item = i;
@@ -1154,7 +1155,7 @@ __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S
         if (lane == 0) u = atomicAdd(&s_next, 64u);
         u = (unsigned int)__shfl((int)u, 0);
         if (u >= total) break;
-        const uint32_t i = ((u / cs) * gridDim.x + blockIdx.x) * cs + u % cs + lane;
+        const uint32_t i = chunk_item(u, cs) + lane;
         const bool valid = i < n_in;
         const uint32_t rank = valid ? keys[i] : 0xffffffffu;                       // rank of the query's leaf among the leaves with candidates
         const bool has_leaf = valid && rank < (uint32_t)S.n_pleaf;
@@ -1537,13 +1538,13 @@ __global__ __launch_bounds__(GI_BLOCK) void k_st_accum(Frame F, PixRec* pix, con
 }
 
 // Progressive sessions (gi_progressive_*): the frame as the pixel records hold it, nothing folded.  One lane per record, consecutive lanes read
-// consecutive 72-byte records; tiled = 0: the records are in st_pixel_xy order (fixed schedule), 1: in padded 8x8 tiles (rounds, wf_pixel_xy),
+// consecutive 72-byte records; tiled = 0: the records are in st_pixel_xy order (fixed schedule), 1: in padded 8x8 tiles (rounds, tile_pixel_xy),
 // whose padding records have no pixel.
 __global__ __launch_bounds__(GI_BLOCK) void k_pix_resolve(Frame F, const PixRec* pix, uint32_t n_rec, int tiled, void* out, int out_f64, int32_t* out_spp)
 {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_rec; i += gridDim.x * blockDim.x) {
         int x, ly;
-        if (tiled) { if (!wf_pixel_xy(F, i, x, ly)) continue; }
+        if (tiled) { if (!tile_pixel_xy(F, i, x, ly)) continue; }
         else st_pixel_xy(F, i, x, ly);
         const PixRec r = pix[i];
         pixel_write(F, x, ly, pixrec_to_state(r), out, out_f64, out_spp);
@@ -1558,7 +1559,7 @@ __global__ __launch_bounds__(GI_BLOCK) void k_pix_wanting(Frame F, const PixRec*
         const uint32_t i = i0 + lane;
         int x, ly;
         bool wants = false;
-        if (i < n_rec && (!tiled || wf_pixel_xy(F, i, x, ly))) {
+        if (i < n_rec && (!tiled || tile_pixel_xy(F, i, x, ly))) {
             const int2 ss = *reinterpret_cast<const int2*>(&pix[i].samps);   // samps and s, adjacent and 8-byte aligned in the 72-byte record
             PixelState ps;
             ps.samps = ss.x; ps.s = ss.y;                                      // the two fields the rule reads

@@ -482,7 +482,7 @@ static bool rounds_fit(const Frame& F) { return (size_t)((F.w + 7) >> 3) * (size
 static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d_out, int out_is_f64, int32_t* d_spp, volatile const int* cancel)
 {
     if (!rounds_fit(F)) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
-    const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (wf_pixel_xy)
+    const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (tile_pixel_xy)
     const bool debug_wf = getenv("GI_DEBUG_WF") != nullptr;   // read at every call
     int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->tune.pool_slots_max, 0xfffffff0ull) / n_pix));
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
