@@ -214,6 +214,111 @@ def two_light_scene(with_glass=True):
     return s.rebuild()
 
 
+# the lights of many_lights_scene: different sides and heights, distinct colours and radii (the first n are used)
+MANY_LIGHTS = [((-2.5, 4.0, 1.5), (9, 7, 5), 0.10), ((3.0, 3.5, 2.0), (3, 5, 9), 0.15), ((0.4, 3.0, -3.2), (6, 9, 4), 0.05), ((-3.6, 2.4, -0.8), (8, 3, 7), 0.20),
+               ((3.4, 2.0, -1.6), (4, 8, 8), 0.12), ((0.3, 5.0, 3.0), (7, 7, 2), 0.08)]
+# thin slabs: a canopy over the front of the left block, one over the right block's front, a wall at the left, a wall at the back; the canopies' tops are the highest y
+MANY_LIGHTS_SLABS = [((-2.1, 1.45, 0.2), (-0.2, 1.5, 1.9)), ((0.2, 1.45, -0.1), (2.2, 1.5, 1.6)), ((-2.7, 0.001, -1.6), (-2.65, 1.4, 1.2)), ((-2.2, 0.001, -1.65), (2.4, 1.4, -1.6))]
+SHADOW_BIAS = 1e-4      # include/raytracer.h: the shadow segment starts at hit + SHADOW_BIAS * normal
+
+
+def many_lights_scene(n_lights, emitter=False, fog=False):
+    """two_light_scene(False)'s floor and blocks (diffuse only) under the first n_lights of MANY_LIGHTS, with thin slabs between them so that which
+    lights a vertex sees differs from vertex to vertex: two canopies whose top faces are the scene's highest (a shadow segment that starts on one
+    misses the scene's box), a wall at the left and a mirror wall at the back (no glass: nothing refracts).  The reference keeps the share of the LAST visible light of a vertex, so a walk
+    from the last light down stops at another light in every part of the picture (many_lights_census counts the parts).  emitter: the left block
+    has diffuse and emissive colour, so a vertex on it carries A0 beside its queries; fog: a HeightFog slab over the right half of the floor, which the
+    segments from there cross and the ones from the left do not; it reaches above the right canopy, so that the segments which miss the scene's box are
+    answered by the medium."""
+    s = gi.Scene()
+    white = s.add_material(1, 1, 1, (0.8, 0.8, 0.8)); grey = s.add_material(1, 1, 1, (0.5, 0.5, 0.55))
+    red = s.add_material(1, 1, 1, (0.8, 0.3, 0.2), (0.6, 0.45, 0.1) if emitter else (0, 0, 0))
+    quad = lambda a, b, c, d: [[a, b, c], [a, c, d]]
+    tris, mats = [], []
+    def box(lo, hi, m):
+        (x0, y0, z0), (x1, y1, z1) = lo, hi
+        f = [((x0, y0, z0), (x1, y0, z0), (x1, y1, z0), (x0, y1, z0)), ((x0, y0, z1), (x0, y1, z1), (x1, y1, z1), (x1, y0, z1)),
+             ((x0, y0, z0), (x0, y1, z0), (x0, y1, z1), (x0, y0, z1)), ((x1, y0, z0), (x1, y0, z1), (x1, y1, z1), (x1, y1, z0)),
+             ((x0, y1, z0), (x1, y1, z0), (x1, y1, z1), (x0, y1, z1)), ((x0, y0, z0), (x0, y0, z1), (x1, y0, z1), (x1, y0, z0))]
+        for a, b, c, d in f:                             # wound so that the normals point outwards (two_light_scene's point inwards: its blocks' faces
+            tris.extend(quad(a, d, c, b)); mats.extend([m, m])   # start their shadow segments inside the block and see no light at all)
+    tris.extend(quad((-4, 0, -4), (-4, 0, 4), (4, 0, 4), (4, 0, -4))); mats.extend([white, white])
+    # a foot under the floor, as in large_alpha_scene: with the floor ON the root box's lower face a vertex there (y = +-1e-16) gathers or not by the last
+    # bit of the bounce that led to it (device libm against glibc) -- seen on the MI355X without the foot: 34 of 5 184 pixels, RMSE 6e-5 .. 1.5e-4 with
+    # a photon map and 1e-18 without one, the same bits in every schedule
+    tris.extend(quad((-0.5, -0.37, -0.5), (-0.5, -0.37, 0.5), (0.5, -0.37, 0.5), (0.5, -0.37, -0.5))); mats.extend([white, white])
+    box((-1.6, 0.001, -0.4), (-0.6, 1.0, 0.6), red)
+    box((0.5, 0.001, -0.7), (1.5, 1.2, 0.3), white)
+    mirror = s.add_material(0, 1, 1, (0.9, 0.9, 0.9))    # opaque; reflect() is +, * only, the same bits with every libm.  The photon map keeps
+    for k, (lo, hi) in enumerate(MANY_LIGHTS_SLABS):     # caustic photons only: without a specular surface no photon would be stored at all
+        box(lo, hi, mirror if k == 3 else grey)
+    s.add_triangles(np.array(tris, float), mat_idx=mats)
+    for pos, col, rad in MANY_LIGHTS[:n_lights]:
+        s.add_light(pos, col, rad)
+    if fog:
+        s.add_height_fog((2.0, 1.0, 0.5), (3.6, 2.0, 5.0), (0.8, 0.85, 1.0), 4, 0.5, 4)    # x 0.2 .. 3.8, y 0 .. 2: the right canopy's top lies in it
+    s.set_camera((0.2, 2.2, 5.5), (0, 0.5, 0))
+    return s.rebuild()
+
+
+MANY_LIGHTS_NAMES = {"three_lights": (3, False, False), "four_lights": (4, False, False), "five_lights": (5, False, False), "six_lights": (6, False, False),
+                     "four_lights_emitter": (4, True, False), "three_lights_fog": (3, False, True)}
+
+
+def _segment_meets_box(a, b, lo, hi):
+    """Whether the segments a[i] -> b[i] touch the box [lo, hi] (slab test in numpy)."""
+    d = b - a
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t0, t1 = (lo - a) / d, (hi - a) / d
+    par = d == 0
+    tn = np.where(par, np.where((a >= lo) & (a <= hi), -np.inf, np.inf), np.minimum(t0, t1))
+    tf = np.where(par, np.where((a >= lo) & (a <= hi), np.inf, -np.inf), np.maximum(t0, t1))
+    return np.maximum(tn.max(axis=1), 0.0) <= np.minimum(tf.min(axis=1), 1.0)
+
+
+def many_lights_census(scene, w=96, h=54):
+    """Which branches of the several-lights shadow path a frame of `scene` reaches, from the oracle alone: the first hits of the w x h sample-0 primary
+    rays, and whether the segment from hit + SHADOW_BIAS * normal to each light's centre is free.  Returns the number of hit vertices per class:
+      last            the last light is visible (the first query asked answers the item)
+      second_last     the last light is hidden, the one before it visible (one step of k_st_shadow's loop)
+      earlier         (3+ lights) the last two are hidden and an earlier one is visible (two or more steps)
+      light0_only     (4 lights) lights 3, 2 and 1 are hidden, light 0 is visible
+      none            every light is hidden
+      outside_box     the segment starts outside the scene's root box (above a top face at its highest y): no walk begins
+      emitter_lit / emitter_dark   the hit is on an emitting surface, with a visible light / with none
+      fog_crossed / fog_missed   the segment to the winning (last visible) light crosses the medium's box / does not
+      fog_outside_box            it crosses the medium's box and starts outside the scene's root box"""
+    o = oracle_for(scene)
+    t = scene.tables()
+    lights = t["lights"][:, :3]
+    n = len(lights)
+    rays = np.array([o.primary_ray(w, h, 0, x, y)[1] for y in range(h) for x in range(w)])
+    hit, ent, res, _ = o.trace(rays)
+    k = hit > 0
+    org = res[k, :3] + SHADOW_BIAS * res[k, 3:6]
+    vis = np.stack([o.visible(np.concatenate([org, np.broadcast_to(l, org.shape)], 1))[0] > 0 for l in lights], 1)
+    root = o.octree()[0][0]
+    assert np.all(lights[:, 1] > root[4])                      # every light hangs above the box: a segment that starts above it never enters it
+    out = {"vertices": int(k.sum()), "last": int(vis[:, -1].sum()), "second_last": int((~vis[:, -1] & vis[:, -2]).sum()), "none": int((~vis.any(1)).sum()),
+           "outside_box": int((org[:, 1] > root[4]).sum())}
+    if n >= 3:
+        out["earlier"] = int((~vis[:, -1] & ~vis[:, -2] & vis[:, :-2].any(1)).sum())
+    if n == 4:
+        out["light0_only"] = int((~vis[:, 1:].any(1) & vis[:, 0]).sum())
+    emits = (t["mats"][:, 6:9] != 0).any(1)[t["tri_mat"]][ent[k]]
+    if (t["mats"][:, 6:9] != 0).any():
+        out["emitter_lit"] = int((emits & vis.any(1)).sum())
+        out["emitter_dark"] = int((emits & ~vis.any(1)).sum())
+    if len(t["fog"]):
+        f = t["fog"][0]
+        win = n - 1 - np.argmax(vis[:, ::-1], axis=1)          # the last visible light (rows without one are masked out below)
+        crossed = _segment_meets_box(org, lights[win], f[:3] - 0.5 * f[3:6], f[:3] + 0.5 * f[3:6])
+        out["fog_crossed"] = int((vis.any(1) & crossed).sum())
+        out["fog_missed"] = int((vis.any(1) & ~crossed).sum())
+        out["fog_outside_box"] = int((crossed & (org[:, 1] > root[4])).sum())      # no walk begins and the medium alone answers, light after light
+    return out
+
+
 def coplanar_scene():
     """Entities that lie in one plane and overlap (a patch on the floor of a room, a panel in its ceiling -- what a Cornell box's light is): a ray into the
     overlap meets two entities at exactly the same distance and RayTracer::trace keeps the one it asks first (include/raytracer.h:446-472, strict <).
@@ -365,6 +470,7 @@ def alpha_case(opacity=0.5, textured=False):
 
 _NAMED = {"large_alpha": lambda: alpha_case(), "large_alpha_tex": lambda: alpha_case(textured=True),
           "two_lights": lambda: two_light_scene(False), "two_lights_glass": lambda: two_light_scene(True)}
+_NAMED.update({name: (lambda args=args: many_lights_scene(*args)) for name, args in MANY_LIGHTS_NAMES.items()})
 
 
 def named_scene(name):

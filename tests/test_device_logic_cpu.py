@@ -205,3 +205,38 @@ def test_two_lights_match_oracle():
     pc.check_emission(rt, scene, 1000)
     rmse, img, ref = pc.check_render(rt, scene, 48, 27, 4, 2000)
     assert rmse < 1e-12 and img.mean() > 1e-3
+
+
+MANY_LIGHTS = ["three_lights", "four_lights", "five_lights", "four_lights_emitter", "three_lights_fog"]
+
+
+@pytest.mark.parametrize("name", MANY_LIGHTS)
+def test_many_lights_scenes_reach_every_branch(name):
+    """The census of pc.many_lights_census, from the oracle alone: every class of vertex the several-lights shadow path treats differently (the
+    first light asked wins; one step of k_st_shadow's loop; two or more; light 0 after all the others; no light; a segment that misses the scene's
+    box; an emitting surface lit and dark; a segment through the medium and one beside it) holds at least 20 of a 96 x 54 frame's first hits.
+    These are conditions on the scenes: a comparison of frames over them cannot pass for want of cases."""
+    n, emitter, fog = pc.MANY_LIGHTS_NAMES[name]
+    scene = pc.named_scene(name)
+    assert scene.desc().n_light == n and scene.desc().n_fog == int(fog) and scene.desc().n_tri < 100
+    census = pc.many_lights_census(scene)
+    print(name, census)
+    want = ["last", "second_last", "earlier", "none", "outside_box"] + (["light0_only"] if n == 4 else []) + (["emitter_lit", "emitter_dark"] if emitter else [])
+    want += ["fog_crossed", "fog_missed", "fog_outside_box"] if fog else []
+    assert set(want) <= set(census)
+    for k in want:
+        assert census[k] >= 20, (k, census)
+
+
+@pytest.mark.parametrize("name", MANY_LIGHTS)
+def test_many_lights_match_oracle(name):
+    """Three, four and five lights, an emitting block, a medium: the CPU build of the device code (which walks every light inline, the form the
+    streaming passes fall back to from five lights on) against the oracle, photons from every light.  glibc on both sides and no glass: the
+    two-light test's bound."""
+    scene = pc.named_scene(name)
+    rt = el.EmulRayTracer().setScene(scene)
+    _, ph = pc.check_emission(rt, scene, 1000)
+    assert len(ph) > 200 * scene.desc().n_light          # the mirror wall sends photons of every light into the map
+    rmse, img, ref = pc.check_render(rt, scene, 48, 27, 4, 2000)
+    print(name, "rmse", rmse, "mean", float(img.mean()), "photons of 1000 indices", len(ph))
+    assert rmse < 1e-12 and img.mean() > 1e-3

@@ -53,6 +53,17 @@ def test_benchmark_frame_bound_by_memory(free_gib, held_gib):
         assert P == 519136986
 
 
+def test_benchmark_frame_with_four_deferred_lights_bound_by_memory():
+    """Four lights put off four ShadowQ per slot: 356 + 4 x 96 = 740 bytes instead of 452.  With 128 GiB free the benchmark frame is bound by memory
+    (149 938 999 slots of its 530 841 600 samples), and by fewer slots than with one light (245 475 353, the case above): the stride of d_shq is in the budget."""
+    assert POOL_RECORD + 124 + 4 * SHADOW_Q == 740
+    P, chunk = _plan(free_b=128 * GIB, **dict(BENCH, lights=4))
+    assert (P, chunk) == _parent(True, 128 * GIB, 0, 1920 * 1080, 256, SLOTS_MAX, LBUF_MAX, 4)
+    assert P == (int(float(128 * GIB) * 0.90) - 1920 * 1080 * 256 * 24) // 740 == 149938999 < 1920 * 1080 * 256 and chunk == 256
+    assert P < _plan(free_b=128 * GIB, **BENCH)[0] == 245475353
+    assert P * 740 + 1920 * 1080 * 256 * 24 <= int(float(128 * GIB) * 0.90)          # the pool and the radiance buffer fit what was offered
+
+
 def test_small_frame_and_a_pool_of_a_third():
     assert _plan(**SMALL) == (24576, 8)
     assert _plan(slots_max=24576 // 3 + 1, **SMALL) == (8193, 8)
