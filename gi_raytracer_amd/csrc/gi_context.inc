@@ -57,9 +57,7 @@ struct SceneStore {
     DevBuf<double> d_trace_boxes;         // the closest-hit walk's boxes (gi_device.h: trace_wide_step)
     DevBuf<float> d_tcboxes;              // and the content boxes made of them
     DevBuf<uint32_t> d_tcuse;
-    bool lights_clear = false;            // of the scene last uploaded: no entity within a light's radius + the shadow bias of it (gi_layout.h)
-    double cut_margin = -1;               // of the scene last uploaded
-    bool scene_clipped = false;           // its trace boxes differ from the whole ones
+    WalkCuts cuts;                        // of the scene last uploaded: what it allows the walks' short cuts (gi_layout.h)
     DevBuf<TriGeom> d_tris;
     DevBuf<TriShade> d_shade;
     DevBuf<Mat> d_mats;
@@ -81,7 +79,7 @@ struct SceneStore {
         up(d_refs, H.refs); up(d_leaf_tris, H.leaf_tris); up(d_leaf_boxes, H.leaf_boxes); up(d_trace_boxes, H.trace_boxes);
         up(d_tcboxes, H.tcboxes); up(d_tcuse, H.tcuse);
         if (e != hipSuccess) return e;
-        cut_margin = H.cut_margin; scene_clipped = H.clipped; lights_clear = H.lights_clear;
+        cuts = H.walk_cuts();
         up(d_tris, H.tris); up(d_shade, H.shade); up(d_mats, H.mats); up(d_lights, H.lights); up(d_fogs, H.fogs); up(d_fog_grid, H.fog_grid);
         if (e != hipSuccess) return e;
         S.tnodes = d_tnodes.p; S.leaf_refs = d_refs.p; S.leaf_tris = d_leaf_tris.p; S.tris = d_tris.p; S.shade = d_shade.p;
@@ -394,7 +392,7 @@ static void apply_switches(gi_ctx* c)
     T.wnodes = s.d_wnodes.p; T.cboxes = s.d_cboxes.p; T.n_cboxes = s.d_cboxes.n;
     T.leaf_boxes = s.d_leaf_boxes.p; T.trace_boxes = s.d_trace_boxes.p;
     T.tcboxes = s.d_tcboxes.p; T.n_tcboxes = s.d_tcboxes.n; T.tcuse = s.d_tcuse.p;
-    T.cut_margin = s.cut_margin; T.clipped = s.scene_clipped; T.lights_clear = s.lights_clear;
+    T.set_walk_cuts(s.cuts);
     T.pn_planes_ok = ph.pn_planes_ok;
     T.pdescent = ph.pdescent_ready ? ph.d_pdescent.p : nullptr;
     T.pjump = ph.pjump_ready ? ph.d_pjump.p : nullptr;

@@ -40,7 +40,7 @@ struct Emul {
         T.wnodes = hs.wnodes.data(); T.cboxes = hs.cboxes.data(); T.n_cboxes = hs.cboxes.size();
         T.leaf_boxes = hs.leaf_boxes.data(); T.trace_boxes = hs.trace_boxes.data();
         T.tcboxes = hs.tcboxes.data(); T.n_tcboxes = hs.tcboxes.size(); T.tcuse = hs.tcuse.data();
-        T.cut_margin = hs.cut_margin; T.clipped = hs.clipped; T.lights_clear = hs.lights_clear;
+        T.set_walk_cuts(hs.walk_cuts());
         T.pn_planes_ok = hp.planes_ok;
         SceneSwitches sw;
         sw.wide = wide; sw.cull = cull;
@@ -68,17 +68,43 @@ void emul_scene_views(Emul* e, int32_t* ids10, double* cut_margin)
     ids10[9] = S.pn_planes;
     *cut_margin = S.cut_margin;
 }
+// The raw storage of every table layout_scene / layout_photons left behind, in the order of tests/test_layout_tables_cpu.py: TABLES, and the
+// scalars beside them in the order of SCALARS there (every one a value a double holds exactly).  -1: no such table.
+int emul_layout_table(Emul* e, int which, const void** p, uint64_t* n_bytes)
+{
+    const HostScene& s = e->hs;
+    const HostPhotons& ph = e->hp;
+    int k = 0;
+    auto is = [&](const auto& v) { if (which != k++) return false; *p = v.data(); *n_bytes = v.size() * sizeof(v[0]); return true; };
+    const bool found = is(s.tnodes) || is(s.wnodes) || is(s.wleaf_id) || is(s.cboxes) || is(s.cuse) || is(s.refs) || is(s.leaf_tris) || is(s.leaf_boxes) ||
+                       is(s.trace_boxes) || is(s.tcboxes) || is(s.tcuse) || is(s.worder) || is(s.tris) || is(s.shade) || is(s.tri_uv) || is(s.mats) ||
+                       is(s.lights) || is(s.fogs) || is(s.fog_grid) || is(s.texs) || is(s.tex_pixels) || is(s.tex_lut) ||
+                       is(ph.nodes) || is(ph.ranges) || is(ph.pos) || is(ph.dircol);
+    return found ? 0 : -1;
+}
+void emul_layout_scalars(Emul* e, double* out14)
+{
+    const HostScene& s = e->hs;
+    const HostPhotons& ph = e->hp;
+    const double v[14] = {(double)s.n_node, (double)s.n_tri, (double)s.n_light, (double)s.n_tex(), (double)s.n_fog(), s.ambient[0], s.ambient[1], s.ambient[2],
+                          s.cut_margin, (double)s.clipped, (double)s.lights_clear, (double)ph.planes_ok, (double)ph.n_photon, (double)ph.n_node};
+    for (int k = 0; k < 14; k++) out14[k] = v[k];
+}
 const char* emul_error(Emul* e) { return e->err.c_str(); }
 int emul_upload_scene(Emul* e, const gi_scene_desc* d)
 {
-    if (!layout_scene(d, e->hs, e->err)) return GI_E_INVALID;
+    HostScene H;                        // beside the bound scene, as gi_upload_scene does: a refused descriptor leaves that one as it was
+    if (!layout_scene(d, H, e->err)) return GI_E_INVALID;
+    e->hs = std::move(H);
     e->hp = HostPhotons();
     e->bind();
     return 0;
 }
 int emul_upload_photons(Emul* e, const gi_photon_map_desc* d)
 {
-    if (!layout_photons(d, e->hp, e->err)) return GI_E_INVALID;
+    HostPhotons H;                      // (as emul_upload_scene)
+    if (!layout_photons(d, H, e->err)) return GI_E_INVALID;
+    e->hp = std::move(H);
     e->bind();
     return 0;
 }
