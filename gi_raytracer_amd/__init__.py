@@ -67,6 +67,11 @@ class OcclusionParams(C.Structure):
     _fields_ = [("n_samples", C.c_int32), ("n_dirs", C.c_int32), ("radius", C.c_double)]
 
 
+class Lens(C.Structure):
+    """gi_lens (include/gi_hip.h): the thin lens of a context; radius 0 is the pinhole."""
+    _fields_ = [("radius", C.c_double), ("rotation", C.c_double), ("blades", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -85,6 +90,7 @@ ABI_SYMBOLS = [
     "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
+    "gi_lens_default", "gi_set_lens", "gi_get_lens", "gi_lens_vertices", "gi_group_set_lens", "gi_debug_primary_rays", "gi_focus_distance",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
     "gih_add_texture", "gih_add_material_tex", "gih_load_png", "gih_free",
@@ -166,6 +172,14 @@ def lib():
     L.gi_progressive_save.argtypes = [vp, vp, C.c_int64]
     L.gi_progressive_restore.argtypes = [vp, vp, C.c_int64]
     L.gi_progressive_end.argtypes = [vp]
+    L.gi_lens_default.argtypes = [C.POINTER(Lens)]
+    L.gi_lens_default.restype = None
+    L.gi_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.gi_get_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.gi_lens_vertices.argtypes = [C.POINTER(Lens), _dp]
+    L.gi_group_set_lens.argtypes = [vp, C.POINTER(Lens)]
+    L.gi_debug_primary_rays.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, _up, _dp]
+    L.gi_focus_distance.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, C.c_int32, _dp]
     L.gi_group_create.argtypes = [C.POINTER(vp), C.c_int32, _ip]
     L.gi_group_destroy.argtypes = [vp]
     L.gi_group_size.argtypes = [vp]
@@ -473,24 +487,74 @@ def occlusion_params(n=None, dirs=None, radius=None, width=None, height=None):
     return p
 
 
-def _whole(name, v):
-    """An integer argument of occlusion_params: ValueError for anything that is not a whole number an int32 holds."""
+def _whole(name, v, what="occlusion"):
+    """An integer argument of occlusion_params / lens_params: ValueError for anything that is not a whole number an int32 holds."""
     try:
         i = int(v)
     except (TypeError, ValueError, OverflowError):
-        raise ValueError(f"occlusion: {name} must be a whole number, got {v!r}") from None
+        raise ValueError(f"{what}: {name} must be a whole number, got {v!r}") from None
     if i != v or not -2 ** 31 <= i < 2 ** 31:
-        raise ValueError(f"occlusion: {name} must be a whole number, got {v!r}")
+        raise ValueError(f"{what}: {name} must be a whole number, got {v!r}")
     return i
+
+
+LENS_BLADES = range(3, 17)
+
+
+def lens_params(radius=None, blades=None, rotation=None):
+    """gi_lens_default (radius 0 = the pinhole, 6 blades, rotation 0) with any of radius (scene units), blades, rotation (radians) set.  No device
+    needed.  ValueError for what gi_set_lens would refuse: a negative, NaN or infinite radius, blades outside 3 .. 16, a rotation that is not finite."""
+    l = Lens()
+    lib().gi_lens_default(C.byref(l))
+    if radius is not None:
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError(f"lens: radius must be a number, got {radius!r}") from None
+        if not (0.0 <= radius < float("inf")):
+            raise ValueError(f"lens: radius must be finite and >= 0 (0: the pinhole), got {radius}")
+        l.radius = radius
+    if blades is not None:
+        l.blades = _whole("blades", blades, "lens")
+    if rotation is not None:
+        try:
+            rotation = float(rotation)
+        except (TypeError, ValueError):
+            raise ValueError(f"lens: rotation must be a number, got {rotation!r}") from None
+        if not (-float("inf") < rotation < float("inf")):
+            raise ValueError(f"lens: rotation must be finite (radians), got {rotation}")
+        l.rotation = rotation
+    if l.blades not in LENS_BLADES:
+        raise ValueError(f"lens: blades must be {LENS_BLADES[0]} .. {LENS_BLADES[-1]}, got {l.blades}")
+    return l
+
+
+def lens_vertices(lens):
+    """gi_lens_vertices: the aperture polygon's unit vertices [blades + 1][2] as the kernels read them (the last a copy of the first).  No device."""
+    xy = np.zeros((lens.blades + 1 if 0 <= lens.blades <= 64 else 1, 2))
+    if lib().gi_lens_vertices(C.byref(lens), _p(xy)) != GI_OK:
+        raise ValueError("lens_vertices: not a lens gi_set_lens accepts")
+    return xy
+
+
+def lens_tag(lens):
+    """The lens tag of a checkpoint header (include/gi_hip.h): 0 for a pinhole, else the low 32 bits of 64-bit FNV-1a over the 24 bytes of gi_lens,
+    0 replaced by 1."""
+    if not lens.radius > 0:
+        return 0
+    h = 0xcbf29ce484222325
+    for b in bytes(lens):
+        h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return (h & 0xFFFFFFFF) or 1
 
 
 # The header of a progressive checkpoint (include/gi_hip.h: gi_progressive_save), little-endian, 192 bytes; the 72-byte pixel records follow.
 CHECKPOINT_MAGIC = b"GIPROGR\0"
 CHECKPOINT_VERSION = 1
-CHECKPOINT_HEADER = "<8sII11d7i4xdQiiQIIiiii"
+CHECKPOINT_HEADER = "<8sII11d7i4xdQiiQIIiiiI"
 CHECKPOINT_RECORD_BYTES = 72
 _CHECKPOINT_FIELDS = ("width", "height", "stripe_h", "stripe_rank", "stripe_world", "min_samples", "max_samples", "noise_thresh", "seed",
-                      "schedule", "sample_end", "n_records", "record_bytes", "reserved0", "n_entity", "n_node", "n_photon", "reserved1")
+                      "schedule", "sample_end", "n_records", "record_bytes", "reserved0", "n_entity", "n_node", "n_photon", "lens_tag")
 
 
 def parse_checkpoint_header(blob):
@@ -505,6 +569,7 @@ def parse_checkpoint_header(blob):
     h = {"magic": v[0], "version": v[1], "header_bytes": v[2], "cam_pos": v[3:6], "cam_up": v[6:9], "cam_forward": v[9:12],
          "sensor_diag": v[12], "focal_dist": v[13]}
     h.update(zip(_CHECKPOINT_FIELDS, v[14:]))
+    h["reserved1"] = h["lens_tag"]      # the field's name before it became the lens tag
     if h["version"] != CHECKPOINT_VERSION or h["header_bytes"] != n or h["record_bytes"] != CHECKPOINT_RECORD_BYTES:
         raise ValueError(f"checkpoint: version {h['version']}, header {h['header_bytes']} bytes, records of {h['record_bytes']} bytes: not this format")
     if len(blob) != n + h["n_records"] * CHECKPOINT_RECORD_BYTES:
@@ -622,6 +687,12 @@ class RayTracerGroup:
             scene.build_photon_map(photons)
             pd = scene.photon_desc()
             self._check(self.L.gi_group_upload_photons(self.h, C.byref(pd)), "group upload_photons")
+        return self
+
+    def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
+        """gi_group_set_lens: the thin lens of every member context (RayTracer.set_lens)."""
+        l = lens if lens is not None else lens_params(radius, blades, rotation)
+        self._check(self.L.gi_group_set_lens(self.h, C.byref(l)), "group set_lens")
         return self
 
     def run(self, params, stripe_h=16, first_stripe=0, n_stripes=None, f64=True, frame=None):
@@ -911,6 +982,48 @@ class RayTracer:
         ms = C.c_float()
         self._check(self.L.gi_last_occlusion_ms(self.h, C.byref(ms)), "last_occlusion_ms")
         return ms.value
+
+    def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
+        """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,
+        run_features, run_occlusion, run_upsampled.  radius in scene units (0: the pinhole), blades 3 .. 16, rotation in radians; or a Lens.  The
+        plane focal_dist in front of the camera stays sharp (focus_at moves it).  ValueError for bad values, before the library is called; GiError
+        (code -4) while a progressive session is open.  Returns self."""
+        l = lens if lens is not None else lens_params(radius, blades, rotation)
+        self._check(self.L.gi_set_lens(self.h, C.byref(l)), "set_lens")
+        return self
+
+    @property
+    def lens(self):
+        """gi_get_lens: the context's lens (radius 0, 6 blades, rotation 0 until set_lens)."""
+        l = Lens()
+        self._check(self.L.gi_get_lens(self.h, C.byref(l)), "get_lens")
+        return l
+
+    def primary_rays(self, p, idx):
+        """gi_debug_primary_rays: rays [n][6] = origin, unit direction of the samples with Halton indices idx of the frame p (from params), under
+        the context's lens."""
+        idx = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+        rays = np.zeros((len(idx), 6))
+        self._check(self.L.gi_debug_primary_rays(self.h, C.byref(p), len(idx), _p(idx, _up), _p(rays)), "primary_rays")
+        return rays
+
+    def focus_distance(self, w, h, x, y, **kw):
+        """gi_focus_distance: the distance, along cam_forward, of the first surface behind the centre of pixel (x, y) of a w x h frame, seen through
+        the pinhole; None on a miss.  focus_at(that) makes it the sharp plane."""
+        p = self.params(w, h, **kw)
+        d = C.c_double()
+        rc = self._check(self.L.gi_focus_distance(self.h, C.byref(p), int(x), int(y), C.byref(d)), "focus_distance")
+        return None if rc == 1 else d.value
+
+    def focus_at(self, dist):
+        """Move the sharp plane to `dist` in front of the camera: sensor_diag and focal_dist are both multiplied by dist / focal_dist, so the field
+        of view is kept.  Returns self."""
+        dist = float(dist)
+        if not (0.0 < dist < float("inf")):
+            raise ValueError(f"focus_at: the distance must be finite and > 0, got {dist}")
+        k = dist / self.focal_dist
+        self.sensor_diag, self.focal_dist = self.sensor_diag * k, self.focal_dist * k
+        return self
 
     def run_upsampled(self, w, h, factor, feature_samples, denoise=False, f64=True, **kw):
         """A w x h frame from a (w / factor) x (h / factor) render: `run` at the reduced size with **kw (min_samples, max_samples, noise_thresh,

@@ -6,6 +6,7 @@
                                [--progressive N [--time-limit SECONDS] [--checkpoint FILE]]
                                [--upsample S [--upsample-pfm LOW.pfm]]
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
+                               [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -25,6 +26,11 @@ reduced-size render itself.  Not together with --progressive.
 --occlusion PREFIX (one more addition) also writes the ambient occlusion of the frame, at --width x --height: PREFIX.open.pfm (one channel, 1 = nothing
 within the radius) and PREFIX.bent.pfm (three channels, the mean free direction).  --occlusion-samples N samples per pixel and --occlusion-dirs K
 segments per sample (default 16 and 16), --occlusion-radius R their length (default 0: a tenth of the scene box's diagonal).
+--aperture R (a further addition) renders through a thin lens of radius R (scene units; 0 = the pinhole) instead of the reference's pinhole: depth
+of field.  --blades N (3 .. 16, default 6) and --blade-rotation DEG shape the aperture, a regular polygon.  The plane that stays sharp is the
+camera's sensor plane, focal_dist in front of it; --focus D moves it to distance D, --focus-pixel X Y to the first surface behind the centre of
+that pixel (the field of view is kept).  Every other flag renders under the lens: --features, --occlusion, --progressive (a checkpoint resumes
+only under the lens it was written with), --denoise, --upsample.
 """
 import argparse
 import os
@@ -64,7 +70,20 @@ def parser():
     ap.add_argument("--occlusion-samples", type=int, default=None, metavar="N", help="with --occlusion: samples per pixel (default 16)")
     ap.add_argument("--occlusion-dirs", type=int, default=None, metavar="K", help="with --occlusion: segments per sample, 1 .. 64 (default 16)")
     ap.add_argument("--occlusion-radius", type=float, default=None, metavar="R", help="with --occlusion: length of a segment (default 0: a tenth of the scene box's diagonal)")
+    ap.add_argument("--aperture", type=float, default=None, metavar="R", help="render through a thin lens of radius R in scene units (0: the pinhole)")
+    ap.add_argument("--blades", type=int, default=None, metavar="N", help="with --aperture: blades of the aperture, 3 .. 16 (default 6)")
+    ap.add_argument("--blade-rotation", type=float, default=None, metavar="DEG", help="with --aperture: rotation of the aperture in degrees (default 0)")
+    ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: distance of the plane that stays sharp (default: the camera's focal distance)")
+    ap.add_argument("--focus-pixel", type=int, nargs=2, default=None, metavar=("X", "Y"), help="with --aperture: focus on the first surface behind the centre of this pixel")
     return ap
+
+
+def lens_of(a):
+    """The Lens the --aperture flags ask for (ValueError for bad values), or None without --aperture."""
+    if a.aperture is None:
+        return None
+    import math
+    return gi.lens_params(radius=a.aperture, blades=a.blades, rotation=None if a.blade_rotation is None else math.radians(a.blade_rotation))
 
 
 def check_args(ap, a):
@@ -86,6 +105,18 @@ def check_args(ap, a):
             gi.occlusion_params(**occlusion_kwargs(a), width=a.width, height=a.height)
         except ValueError as e:
             ap.error(f"--occlusion: {e}")
+    if a.aperture is None and (a.blades is not None or a.blade_rotation is not None or a.focus is not None or a.focus_pixel is not None):
+        ap.error("--blades, --blade-rotation, --focus and --focus-pixel need --aperture R")
+    if a.focus is not None and a.focus_pixel is not None:
+        ap.error("--focus D and --focus-pixel X Y do not go together")
+    if a.focus is not None and not 0 < a.focus < float("inf"):
+        ap.error("--focus D: a finite distance > 0")
+    if a.focus_pixel is not None and not (0 <= a.focus_pixel[0] < a.width and 0 <= a.focus_pixel[1] < a.height):
+        ap.error(f"--focus-pixel X Y: a pixel of the {a.width} x {a.height} frame")
+    try:
+        lens_of(a)
+    except ValueError as e:
+        ap.error(f"--aperture: {e}")
     if a.upsample is not None:
         if a.progressive is not None:
             ap.error("--upsample and --progressive do not go together")
@@ -191,7 +222,18 @@ def main(argv=None):
     if n_photons > 0 and scene.desc().n_light > 0:
         stored = len(rt.tracePhotons(n_photons)[0])
     t1 = time.time()
-    feat = ""
+    feat = lens_note = ""
+    lens = lens_of(a)
+    if lens is not None:
+        if a.focus_pixel is not None:
+            d = rt.focus_distance(a.width, a.height, *a.focus_pixel)
+            if d is None or not d > 0:
+                raise SystemExit(f"--focus-pixel {a.focus_pixel[0]} {a.focus_pixel[1]}: no surface behind that pixel")
+            rt.focus_at(d)
+        elif a.focus is not None:
+            rt.focus_at(a.focus)
+        rt.set_lens(lens=lens)
+        lens_note = f"; lens radius {lens.radius:g}, {lens.blades} blades, sharp at {rt.focal_dist:g}"
     S = a.upsample
     if a.progressive:
         lin, spp, feat = render_progressive(a, rt)
@@ -235,7 +277,7 @@ def main(argv=None):
         feat += f"; occlusion {rt.last_occlusion_ms():.2f} ms -> {a.occlusion}.open.pfm, {a.occlusion}.bent.pfm"
     n = int(spp.sum())
     print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / spp.size:.1f} spp), {stored} photons stored; "
-          f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{feat}")
+          f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{lens_note}{feat}")
     return 0
 
 

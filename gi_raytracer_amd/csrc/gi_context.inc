@@ -366,6 +366,12 @@ struct gi_ctx {
     Tuning tune;
     StageClock clock;
     StreamState st;
+    // the thin lens (gi_set_lens): what the caller set, and the aperture's vertices on the device.  S.lens_* follow it (set_lens, gi_lens.inc);
+    // uploads of scenes and photons leave them alone
+    struct LensState {
+        gi_lens lens{0.0, 0.0, 6, 0};
+        DevBuf<double> d_verts;       // [GI_LENS_MAX_BLADES + 1][2], allocated by the first lens with a radius
+    } lens;
     AuxPass feat, ao, up;             // gi_render_features_*, gi_render_occlusion_*, gi_upsample_*
     DenoisePass dn;                   // gi_denoise_*
 };

@@ -171,6 +171,10 @@ struct Scene {
     const int32_t* pjump;     // [N][N][N] (y, z, x; N = GI_PJUMP_N) the node the descent of a position in that cell of the map's box has reached after GI_PJUMP_BITS levels (or its leaf); null = not used
     double pjump_cell[3], pjump_inv[3];   // a cell's size per axis and its inverse
     double cut_margin;        // >= 0: a closest-hit walk looks no further than its best hit plus this (trace_wide_step, cut_behind_hit); < 0: it walks on as the reference does
+    // the thin lens (gi_set_lens; an addition).  The context's, not the scene's: uploads leave these three alone.  lens_radius == 0: a pinhole
+    const double* lens_verts; // [lens_blades + 1][2] the aperture polygon's unit vertices, the last a copy of the first (gi_lens_vertices, host libm)
+    double lens_radius;
+    int32_t lens_blades;
 };
 // the feature levels of the GI_FEAT_* bits
 inline int scene_feat(const Scene& S) { return S.n_tex > 0 ? 7 : (S.n_fog > 0 ? 3 : (S.has_spheres ? GI_FEAT_SPHERES : 0)); }
@@ -2209,21 +2213,47 @@ struct Frame {
     uint64_t seed;
     int32_t stripe_h, stripe_rank, stripe_world, local_rows;
 };
-// primary ray of sample s of pixel (x,y): include/raytracer.h:112-129 (FOCAL_BLUR == 0)
-GI_HD Ray primary_ray_at(const Scene& S, const Frame& F, uint32_t idx);
+// primary ray of sample s of pixel (x,y): include/raytracer.h:112-129 (FOCAL_BLUR == 0), and the thin lens that stands in for FOCAL_BLUR (an addition)
+template <bool LENS = true> GI_HD Ray primary_ray_at(const Scene& S, const Frame& F, uint32_t idx);
 GI_HD Ray primary_ray(const Scene& S, const Frame& F, int s, int x, int y, uint32_t& idx)
 {
     idx = halton_index(F.he, (uint32_t)s, (uint32_t)x, (uint32_t)y);
     return primary_ray_at(S, F, idx);
 }
-GI_HD Ray primary_ray_at(const Scene& S, const Frame& F, uint32_t idx)   // the ray of the sample with Halton index idx (the index names the pixel too: Halton_enum)
+// the point of the sensor plane at (dx, dy) pixels from the frame's top left corner: the plane that stays sharp under a lens
+GI_HD V3 pixel_pos(const Frame& F, double dx, double dy)
+{
+    return F.screen_center + (F.sw * (dx / F.w - .5)) * F.right - (F.sh * (dy / F.h - .5)) * F.cam_up;
+}
+// The eye of the sample with Halton index idx on a lens of S.lens_radius > 0 (gi_hip.h: gi_set_lens states the order of operations): a point drawn
+// uniformly by area from the regular polygon S.lens_verts in the plane of F.right and F.cam_up.  u0 picks the blade's triangle (centre, v_k, v_k+1)
+// and the distance from the centre, u1 the place between the two vertices.  IEEE operations only -- the vertices were computed on the host.
+enum { P_LENS_U = 34, P_LENS_V = 35 };  // RNG purposes of the two numbers (seed, stream idx, depth 0, a = 0)
+GI_HD V3 lens_eye(const Scene& S, const Frame& F, uint32_t idx)
+{
+    const Rng rng = rng_make(F.seed, idx);   // depth 0
+    const double u0 = rng_draw(rng, P_LENS_U);
+    const double u1 = rng_draw(rng, P_LENS_V);
+    const int32_t B = S.lens_blades;
+    const double ub = u0 * B;
+    int32_t k = (int32_t)ub;
+    if (k > B - 1) k = B - 1;
+    const double r = sqrt(ub - k);
+    const double* v = S.lens_verts + 2 * k;
+    const double lx = r * ((1 - u1) * v[0] + u1 * v[2]);
+    const double ly = r * ((1 - u1) * v[1] + u1 * v[3]);
+    return F.cam_pos + (S.lens_radius * lx) * F.right + (S.lens_radius * ly) * F.cam_up;
+}
+// LENS = false: an instance that is launched for pinholes only and carries no code for the lens (k_st_trace, where the branch cost registers)
+template <bool LENS> GI_HD Ray primary_ray_at(const Scene& S, const Frame& F, uint32_t idx)   // the ray of the sample with Halton index idx (the index names the pixel too: Halton_enum)
 {
     double xr = halton_sample(S, 0, idx);
     double yr = halton_sample(S, 1, idx);
     double dx = (float)((float)xr * F.he.scale_x);
     double dy = (float)((float)yr * F.he.scale_y);
-    V3 pixelPos = F.screen_center + (F.sw * (dx / F.w - .5)) * F.right - (F.sh * (dy / F.h - .5)) * F.cam_up;
+    V3 pixelPos = pixel_pos(F, dx, dy);
     V3 eyePos = F.cam_pos;
+    if (LENS && S.lens_radius > 0) eyePos = lens_eye(S, F, idx);   // uniform per launch; a pinhole makes no draw
     return make_ray(eyePos, normalize(pixelPos - eyePos));
 }
 // adaptive per-pixel loop state: include/raytracer.h:102-148

@@ -82,6 +82,12 @@ int gi_group_clear_photons(gi_group* g)
     for (gi_ctx* c : g->ctx) gi_clear_photons(c);
     return GI_OK;
 }
+int gi_group_set_lens(gi_group* g, const gi_lens* l)
+{
+    if (!g) return GI_E_INVALID;
+    for (gi_ctx* c : g->ctx) { const int rc = gi_set_lens(c, l); if (rc) return group_fail(g, rc, gi_last_error(c)); }
+    return GI_OK;
+}
 int gi_group_upload_photons(gi_group* g, const gi_photon_map_desc* d)
 {
     if (!g) return GI_E_INVALID;

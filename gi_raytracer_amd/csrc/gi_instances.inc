@@ -35,8 +35,11 @@ static int feat_row(int feat) { return feat == 7 ? 3 : (feat == 3 ? 2 : feat); }
 // k_st_trace<FEAT, WIDE>: the first-hit rows; then the counting instance
 static constexpr TraceK kTrace[] = {
     {k_st_trace<0, 0>, kLdsNodes}, {k_st_trace<0, 1>, kLdsWideBoxes}, {k_st_trace<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_st_trace<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
-    {k_st_trace<7, 0>, kLdsNodes}, {k_st_trace<7, 1>, kLdsWideBoxes}, {k_st_trace<0, 1, true>, kLdsWideBoxes}};
-static TraceK st_trace(int feat, bool wide, bool counting) { return counting ? kTrace[6] : kTrace[first_hit_row(feat, wide)]; }
+    {k_st_trace<7, 0>, kLdsNodes}, {k_st_trace<7, 1>, kLdsWideBoxes}, {k_st_trace<0, 1, true>, kLdsWideBoxes},
+    // the first-hit rows again for a context with a thin lens (gi_set_lens): the pinhole's instances carry no code for it
+    {k_st_trace<0, 0, false, true>, kLdsNodes}, {k_st_trace<0, 1, false, true>, kLdsWideBoxes}, {k_st_trace<GI_FEAT_SPHERES, 0, false, true>, kLdsNodes},
+    {k_st_trace<GI_FEAT_SPHERES, 1, false, true>, kLdsWideBoxes}, {k_st_trace<7, 0, false, true>, kLdsNodes}, {k_st_trace<7, 1, false, true>, kLdsWideBoxes}};
+static TraceK st_trace(int feat, bool wide, bool counting, bool lens) { return counting ? kTrace[6] : kTrace[(lens ? 7 : 0) + first_hit_row(feat, wide)]; }
 // k_st_shade<FEAT, WIDE, DEFER>: FEAT 0, spheres, fog, textures x per-node, wide, wide with the shadow walks put off (one light; several lights)
 // (the one-light form stages the trace stage's records and content boxes for the probe of the next ray: its LDS, one 512-thread workgroup per CU as before)
 static constexpr ShadeK kShade[] = {

@@ -534,7 +534,7 @@ __device__ __forceinline__ HandOut hand_out(unsigned long long busy, unsigned in
     more = base + nw < total;
     return HandOut{base, base + (uint32_t)__popcll(want & ((1ull << lane) - 1ull))};
 }
-template <int FEAT, int WIDE, bool COUNT = false>
+template <int FEAT, int WIDE, bool COUNT = false, bool LENS = false>   // LENS: new paths start on the thin lens (launched only when the context has one)
 __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t seed, PathPool pool, unsigned long long* slot_sample, unsigned long long sample0,
                                                        GenArgs g, const uint32_t* q_a, uint32_t n_a, const uint32_t* q_b, uint32_t n_b, unsigned int* bc, uint32_t* segs,
                                                        uint32_t* q_shade, uint32_t* q_free, double* lbuf, uint32_t refill_min, StreamCounters* sc)
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(GI_TRACE_BLOCK) void k_st_trace(Scene S, uint64_t s
             if ((unsigned long long)srel * g.n_pix > rel) srel--;
             else if ((unsigned long long)(srel + 1u) * g.n_pix <= rel) srel++;
             stream = g.pixtab[rel - srel * g.n_pix] + (uint32_t)(g.s_begin + (int)srel) * g.F.he.inc;        // halton_index(he, s, x, y) = its value for s = 0 + s * inc
-            ray = primary_ray_at(S, g.F, stream);
+            ray = primary_ray_at<LENS || COUNT>(S, g.F, stream);
             depth = 0;
         } else {
             slot = i - g.n_gen < n_a ? q_a[i - g.n_gen] : q_b[i - g.n_gen - n_a];
@@ -1688,4 +1688,5 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
 #include "gi_features.inc"       // first-hit feature buffers: k_aov and gi_render_features_*; the host frame of the per-pixel passes
 #include "gi_occlusion.inc"      // ambient occlusion: k_ao and gi_render_occlusion_*
 #include "gi_entries.inc"        // function-level entries (parity tests, public C++ methods) and the debug entries
+#include "gi_lens.inc"           // the thin lens: gi_set_lens, its vertex table, gi_debug_primary_rays, gi_focus_distance
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

@@ -809,6 +809,35 @@ inline bool layout_photons(const gi_photon_map_desc* d, HostPhotons& H, std::str
     return true;
 }
 
+// ---- the thin lens (gi_hip.h: gi_set_lens).  What gi_set_lens accepts; the aperture polygon's vertices as the kernels read them; the checkpoint's tag.
+#define GI_LENS_MIN_BLADES 3
+#define GI_LENS_MAX_BLADES 16
+inline bool lens_valid(const gi_lens* l)
+{
+    return l && std::isfinite(l->radius) && l->radius >= 0 && std::isfinite(l->rotation) && l->blades >= GI_LENS_MIN_BLADES && l->blades <= GI_LENS_MAX_BLADES && l->reserved == 0;
+}
+// xy [blades + 1][2]: v_k = (cos, sin)(rotation + (2 pi k) / blades) with the host's libm, the last a copy of the first
+inline void lens_vertices(const gi_lens& l, double* xy)
+{
+    for (int k = 0; k < l.blades; k++) {
+        const double th = l.rotation + (2.0 * GI_PI * k) / l.blades;
+        xy[2 * k] = std::cos(th); xy[2 * k + 1] = std::sin(th);
+    }
+    xy[2 * l.blades] = xy[0]; xy[2 * l.blades + 1] = xy[1];
+}
+// 0 for a pinhole, else the low 32 bits of 64-bit FNV-1a over radius, rotation, blades, reserved as they lie in memory (24 bytes, little-endian), 0 -> 1
+inline uint32_t lens_tag(const gi_lens& l)
+{
+    if (!(l.radius > 0)) return 0u;
+    unsigned char b[24];
+    static_assert(sizeof(gi_lens) == 24, "gi_lens is 24 bytes without padding");
+    memcpy(b, &l, 24);
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int k = 0; k < 24; k++) { h ^= b[k]; h *= 0x100000001b3ull; }
+    const uint32_t t = (uint32_t)h;
+    return t ? t : 1u;
+}
+
 inline int local_rows(const gi_render_params* p)
 {
     if (!p || p->stripe_h <= 0 || p->stripe_world <= 0 || p->height <= 0) return 0;

@@ -12,7 +12,8 @@ struct ProgBlobHeader {            // little-endian, 192 bytes; the pixel record
     int32_t schedule, sample_end;
     uint64_t n_records;
     uint32_t record_bytes, reserved0;
-    int32_t n_entity, n_node, n_photon, reserved1;
+    int32_t n_entity, n_node, n_photon;
+    uint32_t lens_tag;             // 0: pinhole (gi_layout.h: lens_tag)
 };
 static_assert(sizeof(gi_render_params) == 136 && sizeof(ProgBlobHeader) == 192 && sizeof(PixRec) == 72, "checkpoint layout (include/gi_hip.h)");
 const char kProgMagic[8] = {'G', 'I', 'P', 'R', 'O', 'G', 'R', '\0'};
@@ -162,6 +163,7 @@ int gi_progressive_save(gi_ctx* c, void* h_blob, int64_t cap_bytes)
     h.schedule = g.schedule; h.sample_end = g.sample_end;
     h.n_records = g.n_rec; h.record_bytes = (uint32_t)sizeof(PixRec);
     h.n_entity = c->S.n_tri; h.n_node = c->S.n_node; h.n_photon = c->S.n_photon;
+    h.lens_tag = lens_tag(c->lens.lens);
     memcpy(h_blob, &h, sizeof h);
     if (g.n_rec) {
         HIP_TRY(c, hipSetDevice(c->device));
@@ -191,6 +193,8 @@ int gi_progressive_restore(gi_ctx* c, const void* h_blob, int64_t n_bytes)
     const uint32_t n_rec = prog_records(F, h.schedule);
     if (h.n_records != n_rec || n_bytes != (int64_t)sizeof h + (int64_t)n_rec * (int64_t)sizeof(PixRec))
         return fail(c, GI_E_INVALID, "progressive_restore: " + std::to_string(n_bytes) + " bytes, a checkpoint of this frame has " + std::to_string(sizeof h + (size_t)n_rec * sizeof(PixRec)) + " (truncated?)");
+    if (h.lens_tag != lens_tag(c->lens.lens))
+        return fail(c, GI_E_INVALID, "progressive_restore: the checkpoint was taken under another lens (tag " + std::to_string(h.lens_tag) + ", the context's lens has " + std::to_string(lens_tag(c->lens.lens)) + "): gi_set_lens first");
     if (!c->scene.have_scene) return fail(c, GI_E_STATE, "progressive_restore: no scene uploaded");
     if (c->count_enabled) return fail(c, GI_E_STATE, "progressive_restore: sessions run on the streaming passes, not with the megakernel's work counters (gi_set_counters 1)");
     if (h.n_entity != c->S.n_tri || h.n_node != c->S.n_node || h.n_photon != c->S.n_photon)

@@ -49,7 +49,7 @@ static const StreamGrids& stream_grids(gi_ctx* c)   // per context: one process 
     if (!g.trace) {
         auto grid_of = [&](const auto& k, int block) { return grid_for(c, (const void*)k.fn, k.lds, block); };
         ask_for_lds(kTrace, g.lds_refused); ask_for_lds(kShade, g.lds_refused); ask_for_lds(kShadow, g.lds_refused); ask_for_lds(kFinish, g.lds_refused);
-        g.pix = grid_for(c, (const void*)k_pix_init); g.trace = grid_of(st_trace(7, true, false), GI_TRACE_BLOCK);
+        g.pix = grid_for(c, (const void*)k_pix_init); g.trace = grid_of(st_trace(7, true, false, false), GI_TRACE_BLOCK);
         g.shade = grid_of(st_shade(7, true, 0), GI_SHADE_BLOCK); g.shadow = grid_of(st_shadow(7, true, false), GI_SHADOW_BLOCK); g.gather = grid_for(c, (const void*)st_gather(false)); g.accum = grid_for(c, (const void*)k_st_accum);
         g.compact = grid_for(c, (const void*)k_st_compact, 0, 256); g.finish = grid_of(st_finish(7, true, 0), GI_FINISH_BLOCK); g.ad_gen = grid_for(c, (const void*)k_ad_gen); g.ad_accum = grid_for(c, (const void*)k_ad_accum);
     }
@@ -288,7 +288,7 @@ static int trace_stage(Passes& p)
     p.free_out = p.want_free ? (p.ping ? w.q_free_b.p : w.q_free_a.p) : nullptr;
     if (G.trace > GI_MAX_PRODUCER_BLOCKS || G.shade > GI_MAX_PRODUCER_BLOCKS) return fail(c, GI_E_STATE, "render: more producer workgroups than per-workgroup counters");
     if (const int rc = clear_block_counters(c)) return rc;
-    const TraceK trace_k = st_trace(p.trace_feat, p.wide, p.counting);
+    const TraceK trace_k = st_trace(p.trace_feat, p.wide, p.counting, c->S.lens_radius > 0);
     TimedStage(c, STG_TRACE, p.launches).launch(trace_k.fn, dim3(G.trace), dim3(GI_TRACE_BLOCK), trace_k.lds, c->S, p.F.seed, p.pool, p.slot_sample, p.sample0, p.nw.gen, w.q_new.p, p.nw.n_prepared,
                                                 p.cont_in, p.n_cont, c->st.d_blkcnt.p, c->st.d_segs.p, w.stage_hits.p, p.want_free ? w.stage_free_trace.p : nullptr, p.lbuf, c->tune.refill_min, p.sc);
     TimedStage(c, STG_OTHER, p.launches).launch(k_st_compact, dim3(G.compact), dim3(256), 0, c->S, trace_compact_job(p), c->st.d_blkcnt.p, c->st.d_segs.p, (uint32_t)G.trace, c->st.d_ctl.p);

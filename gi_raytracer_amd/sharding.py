@@ -5,6 +5,8 @@ The reference parallelises the frame over image rows with `#pragma omp parallel 
 STRIPE_H rows dealt round-robin to the ranks (interleaved, because the cost of a row depends strongly on what it sees); every
 rank renders its stripes into one compact [local_rows][w][3] buffer; one gather (RCCL over xGMI when the tensors live on the
 GPUs, gloo in the CPU tests) brings them to rank 0, which puts the rows back in frame order.  No other collective is needed.
+A thin lens (RayTracer.set_lens) is state of a rank's own context, like its scene: every rank sets the same lens before it renders, and the
+stripes then assemble to the frame one rank renders under that lens.
 """
 import numpy as np
 

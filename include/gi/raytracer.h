@@ -204,6 +204,27 @@ class RayTracer {
         return true;
     }
 
+    // ---- ADDITION (the reference's camera is a pinhole: FOCAL_BLUR == 0): a thin lens for every frame and pass of this RayTracer -- run(),
+    // renderFeatures, renderOcclusion -- on every device it renders on (gi_set_lens / gi_group_set_lens; include/gi_hip.h states the definition).
+    // radius in scene units (0: the pinhole again), blades 3 .. 16, rotation in radians.  The plane that stays sharp is the camera's sensor plane,
+    // focalDist in front of it.  false with last_error() set when the lens is refused (the lens then stays as it was) or no device is usable.
+    bool setLens(double radius, int blades = 6, double rotation = 0)
+    {
+        if (!ensure_context()) return false;
+        gi_lens l;
+        l.radius = radius; l.rotation = rotation; l.blades = blades; l.reserved = 0;
+        return check(_st->group ? gi_group_set_lens(_st->group, &l) : gi_set_lens(_st->ctx, &l)) == 0;
+    }
+    // ---- ADDITION: move the sharp plane to `dist` in front of the camera.  sensorDiag and focalDist are both multiplied by dist / focalDist, so the
+    // field of view is kept.  false for a distance that is not finite and > 0 (the camera is then left alone).
+    bool focusAt(double dist)
+    {
+        if (!(dist > 0) || !(dist < INFINITY)) return false;
+        const double k = dist / _camera.focalDist;
+        _camera.sensorDiag = _camera.sensorDiag * k; _camera.focalDist = _camera.focalDist * k;
+        return true;
+    }
+
     // ---- ADDITION (the reference has no such member): ambient occlusion and bent normals of the w x h frame run() renders (include/gi_hip.h states
     // the definition): per pixel the share of the segments above the first hit that meet nothing within the radius, and their mean direction.
     // op = nullptr: gi_occlusion_default_params (16 samples, 16 directions, a tenth of the scene box's diagonal).  gi_render_occlusion_host on the

@@ -412,7 +412,7 @@ int gi_kat(gi_ctx*, int32_t what, int32_t n, const double* in, int32_t in_stride
  *       stripe_h, stripe_rank, stripe_world, min_samples, max_samples), 4 bytes 0, f64 noise_thresh, u64 seed
  *   152 i32 schedule (0 refill pipeline: records in 8x8-tile order without padding; 1 rounds: whole 8x8 tiles, padding records included)
  *   156 i32 E   160 u64 record count   168 u32 record bytes (72)   172 u32 0
- *   176 i32 entities, i32 octree nodes, i32 stored photons of the scene it was taken on (a weak fingerprint), i32 0
+ *   176 i32 entities, i32 octree nodes, i32 stored photons of the scene it was taken on (a weak fingerprint), u32 lens tag (0: pinhole; gi_set_lens)
  *   192 the records as they lie on the device: f64 colour[3], lastCol[3], var, i32 samps, s, n (scratch of a round), 0
  *   restore opens a session from a blob, on the blob's schedule.  GI_E_INVALID: bad magic, version, sizes, truncation; GI_E_STATE: no scene, or
  *   the fingerprint differs.  THE CALLER uploads the same scene and the same photons first (same photon seed and count): the fingerprint only
@@ -428,6 +428,50 @@ int gi_progressive_state_bytes(gi_ctx*, int64_t* n_bytes);
 int gi_progressive_save(gi_ctx*, void* h_blob, int64_t cap_bytes);
 int gi_progressive_restore(gi_ctx*, const void* h_blob, int64_t n_bytes);
 int gi_progressive_end(gi_ctx*);
+
+/* Thin-lens camera: depth of field with a bladed aperture -- an ADDITION.  The reference's camera is a pinhole (FOCAL_BLUR == 0 at compile time,
+ * include/raytracer.h:112-129); its formula for a non-zero FOCAL_BLUR moves the eye by the two Halton numbers that also place the sample in the pixel,
+ * which shears the projection instead of blurring it, and is not mirrored.  Here the eye of every primary ray is drawn from an aperture in the plane
+ * of `right` = normalize(cross(cam_forward, cam_up)) and cam_up -- the vectors the sensor plane is spanned by -- and the sensor plane, focal_dist in
+ * front of cam_pos, is the plane that stays sharp.  The lens is state of the context, not a field of gi_render_params: every pass that makes primary
+ * rays (gi_render_* in all render modes, gi_progressive_*, gi_render_features_*, gi_render_occlusion_*, gi_group_render_*) runs under it, and it
+ * outlives scene and photon uploads.
+ * The aperture is a regular polygon of `blades` vertices, v_k = (cos(rotation + 2 pi k / blades), sin(rotation + 2 pi k / blades)), k = 0 .. blades,
+ * v_blades a copy of v_0, computed ONCE on the host with the host's libm (gi_lens_vertices; theta_k = rotation + (2 pi k) / blades in double) and
+ * read by the kernels from a table: the device side is IEEE operations only (+ - * /, sqrt, compares) and can be restated bit for bit
+ * (tests/lens_expect.py).  Per sample with Halton index idx, in this order, B = blades:
+ *   u0 = draw(seed, stream idx, depth 0, purpose 34, a = 0),  u1 = the same with purpose 35   (f64 draws; DESIGN.md "RNG contract", gi_kat 8)
+ *   k = min((int)(u0 B), B - 1),  f = u0 B - k,  r = sqrt(f)
+ *   l = r ((1 - u1) v_k + u1 v_k+1)                     per component; uniform by area over the polygon
+ *   eyePos = (cam_pos + (radius l.x) right) + (radius l.y) cam_up
+ *   pixelPos as for the pinhole;  dir = normalize(pixelPos - eyePos)
+ * radius == 0 is the pinhole: no draw is made and nothing is added to the eye, so a context that was never given a lens and one that was given
+ * {0, any valid blades and rotation} produce the same bits everywhere.  The depth of gi_render_features_* stays length(hit - ray.origin), from the
+ * eye on the lens.
+ * gi_lens_default: radius 0, rotation 0, 6 blades.
+ * gi_set_lens: radius in scene units, finite and >= 0; blades 3 .. 16; rotation finite, in radians; reserved 0 -- anything else (or a null
+ *   pointer): GI_E_INVALID, and the lens stays as it was.  GI_E_STATE while a progressive session is open (its samples so far were taken under the
+ *   lens it began with).  gi_get_lens returns what was set (the default on a fresh context).
+ * gi_lens_vertices: host only, no device: xy [blades + 1][2]; GI_E_INVALID for a lens gi_set_lens would refuse.
+ * gi_group_set_lens: the lens of every member context.
+ * Checkpoints: the header word at offset 188 (reserved1 so far) is the lens tag: 0 for a pinhole -- pinhole checkpoints keep their bytes -- else
+ *   the low 32 bits of 64-bit FNV-1a over the 24 bytes of gi_lens, 0 replaced by 1.  gi_progressive_restore returns GI_E_INVALID when the blob's tag is not
+ *   that of the context's lens: as with scene and photons, the caller sets the lens first.
+ * gi_debug_primary_rays: rays [n][6] = origin, unit direction of the samples with the given Halton indices of the frame `params`, under the
+ *   context's lens -- what every pass above traces.  No scene is needed.
+ * gi_focus_distance: autofocus.  The PINHOLE ray through the centre of pixel (x, y) of the frame (dx = x + .5, dy = y + .5) is traced as a primary
+ *   ray is (RayTracer::trace; alpha test with seed params->seed, stream 0, depth 0); *dist = length(hit - cam_pos) dot(dir, cam_forward), the distance
+ *   of the plane through the hit that is parallel to the sensor.  Returns 1 and leaves *dist alone on a miss.  GI_E_INVALID: a pixel outside the
+ *   frame, bad parameters, a null pointer; GI_E_STATE: no scene.  A caller makes that plane the sharp one by scaling sensor_diag and focal_dist by
+ *   dist / focal_dist: the field of view stays. */
+typedef struct gi_lens { double radius; double rotation; int32_t blades; int32_t reserved; } gi_lens;
+void gi_lens_default(gi_lens*);
+int gi_set_lens(gi_ctx*, const gi_lens*);
+int gi_get_lens(gi_ctx*, gi_lens*);
+int gi_lens_vertices(const gi_lens*, double* xy /*[blades + 1][2]*/);
+int gi_group_set_lens(gi_group*, const gi_lens*);
+int gi_debug_primary_rays(gi_ctx*, const gi_render_params*, int32_t n, const uint32_t* idx, double* rays /*[n][6]*/);
+int gi_focus_distance(gi_ctx*, const gi_render_params*, int32_t x, int32_t y, double* dist);
 
 #ifdef __cplusplus
 }
