@@ -439,13 +439,25 @@ def low_frame_size(w, h, factor):
     return w // factor, h // factor
 
 
+def _filter_array(a):
+    """An input of denoise / upsample as a contiguous float32 or float64 array; of a dict of run_features, its features."""
+    a = np.asarray(a["features"] if isinstance(a, dict) else a)
+    return np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+
+
+def _fill_params(p, kw, ints, floats, what):
+    """Sets the fields of p that kw names: those in `ints` as int, those in `floats` as float; TypeError for any other name."""
+    for k, v in kw.items():
+        if k not in ints + floats:
+            raise TypeError(f"{what}: unknown parameter {k!r}")
+        setattr(p, k, int(v) if k in ints else float(v))
+    return p
+
+
 def upsample_arrays(low_color, low_features, features, factor):
     """The three inputs of RayTracer.upsample as contiguous float32 / float64 arrays (dicts of run_features are accepted for the features);
     ValueError unless low_color is [hl][wl][3], low_features [hl][wl][8], features [h][w][8] with wl = ceil(w / factor), hl = ceil(h / factor)."""
-    def arr(a):
-        a = np.asarray(a["features"] if isinstance(a, dict) else a)
-        return np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
-    low_color, low_features, features = arr(low_color), arr(low_features), arr(features)
+    low_color, low_features, features = _filter_array(low_color), _filter_array(low_features), _filter_array(features)
     factor = int(factor)
     if factor not in UPSAMPLE_FACTORS:
         raise ValueError(f"upsample: factor must be {UPSAMPLE_FACTORS[0]} .. {UPSAMPLE_FACTORS[-1]}, got {factor}")
@@ -861,33 +873,29 @@ class RayTracer:
         """The feature pass into device memory; out_ptr ([rows][w][8]) and ids_ptr ([rows][w][2] int32, optional) are raw device pointers."""
         self._check(self.L.gi_render_features_device(self.h, C.byref(p), int(n), C.c_void_p(out_ptr), 1 if f64 else 0, C.c_void_p(ids_ptr) if ids_ptr else None), "render_features_device")
 
+    def _last_ms(self, name):
+        """gi_last_<name>_ms of an auxiliary pass."""
+        ms = C.c_float()
+        self._check(getattr(self.L, f"gi_last_{name}_ms")(self.h, C.byref(ms)), f"last_{name}_ms")
+        return ms.value
+
     def last_features_ms(self):
         """gi_last_features_ms: device time of the last feature pass (last_render_ms / last_kernel_ms keep the last frame's)."""
-        ms = C.c_float()
-        self._check(self.L.gi_last_features_ms(self.h, C.byref(ms)), "last_features_ms")
-        return ms.value
+        return self._last_ms("features")
 
     def denoise_params(self, w, h, **kw):
         """gi_denoise_default_params with width, height and any of iterations, demodulate, sigma_color, sigma_normal, sigma_depth, sigma_albedo set."""
         p = DenoiseParams()
         self.L.gi_denoise_default_params(C.byref(p))
         p.width, p.height = int(w), int(h)
-        for k, v in kw.items():
-            if k not in ("iterations", "demodulate", "sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"):
-                raise TypeError(f"denoise: unknown parameter {k!r}")
-            setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
-        return p
+        return _fill_params(p, kw, ("iterations", "demodulate"), ("sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"), "denoise")
 
     def denoise(self, color, features, f64=None, **kw):
         """The edge-avoiding a-trous denoiser (gi_denoise_host; an addition, the reference has no denoiser) on a whole frame: color [h][w][3] as
         `run` returns it, features [h][w][8] as `run_features` returns them (its dict is accepted too), each float32 or float64.  Returns
         [h][w][3], float64 unless f64=False (default: the colour's type).  **kw: iterations (0 .. 8), demodulate, sigma_color, sigma_normal,
         sigma_depth, sigma_albedo; the formula is stated in include/gi_hip.h.  Needs no scene."""
-        if isinstance(features, dict):
-            features = features["features"]
-        color, features = np.asarray(color), np.asarray(features)
-        color = np.ascontiguousarray(color, np.float32 if color.dtype == np.float32 else np.float64)
-        features = np.ascontiguousarray(features, np.float32 if features.dtype == np.float32 else np.float64)
+        color, features = _filter_array(color), _filter_array(features)
         if color.ndim != 3 or color.shape[2] != 3 or features.shape != color.shape[:2] + (8,):
             raise ValueError(f"denoise: color [h][w][3] and features [h][w][8] expected, got {color.shape} and {features.shape}")
         if f64 is None:
@@ -908,9 +916,7 @@ class RayTracer:
 
     def last_denoise_ms(self):
         """gi_last_denoise_ms: device time of the last denoiser pass (the frame's and the feature pass's times keep theirs)."""
-        ms = C.c_float()
-        self._check(self.L.gi_last_denoise_ms(self.h, C.byref(ms)), "last_denoise_ms")
-        return ms.value
+        return self._last_ms("denoise")
 
     def upsample_params(self, w, h, factor, **kw):
         """gi_upsample_default_params with the full size w x h, the factor, the low size (the ceilings) and any of demodulate, sigma_normal,
@@ -920,11 +926,7 @@ class RayTracer:
         p.width, p.height, p.factor = int(w), int(h), int(factor)
         if p.factor > 0:
             p.low_width, p.low_height = -(-p.width // p.factor), -(-p.height // p.factor)
-        for k, v in kw.items():
-            if k not in ("demodulate", "sigma_normal", "sigma_depth", "sigma_albedo"):
-                raise TypeError(f"upsample: unknown parameter {k!r}")
-            setattr(p, k, int(v) if k == "demodulate" else float(v))
-        return p
+        return _fill_params(p, kw, ("demodulate",), ("sigma_normal", "sigma_depth", "sigma_albedo"), "upsample")
 
     def upsample(self, low_color, low_features, features, factor, f64=None, **kw):
         """The guided upsampler (gi_upsample_host; an addition, the reference has none): a full-size frame [h][w][3] from low_color [hl][wl][3] as `run`
@@ -951,9 +953,7 @@ class RayTracer:
 
     def last_upsample_ms(self):
         """gi_last_upsample_ms: device time of the last upsampler pass (the frame's, the feature pass's and the denoiser's times keep theirs)."""
-        ms = C.c_float()
-        self._check(self.L.gi_last_upsample_ms(self.h, C.byref(ms)), "last_upsample_ms")
-        return ms.value
+        return self._last_ms("upsample")
 
     def occlusion_params(self, **kw):
         """The module's occlusion_params: n, dirs, radius (and width, height for the Halton cap) -> gi_occlusion_params; ValueError for bad values."""
@@ -979,9 +979,7 @@ class RayTracer:
 
     def last_occlusion_ms(self):
         """gi_last_occlusion_ms: device time of the last occlusion pass (the frame's and the other passes' times keep theirs)."""
-        ms = C.c_float()
-        self._check(self.L.gi_last_occlusion_ms(self.h, C.byref(ms)), "last_occlusion_ms")
-        return ms.value
+        return self._last_ms("occlusion")
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
         """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,

@@ -7,6 +7,7 @@
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
 //   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler
+// Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
 struct gi_ctx;
@@ -383,6 +384,57 @@ int fail(gi_ctx* c, int code, const std::string& msg)
     if (c) c->err = msg;
     return code;
 }
+
+// gi_last_<pass>_ms: the device time of the pass's last call (EventTimer::read)
+template <class Pass> int pass_ms(gi_ctx* c, Pass gi_ctx::*pass, float* ms)
+{
+    if (!c || !ms) return GI_E_INVALID;
+    HIP_TRY(c, (c->*pass).timer.read(ms));
+    return GI_OK;
+}
+
+// The device side of a host-pointer entry, after its argument and state checks.  in() uploads a caller's array, out() allocates a
+// result and notes where it goes (h == nullptr: an optional output nobody asked for -- the kernel still writes it), scratch() is memory of this
+// call alone; each takes the element count, once.  run(launch) launches (unless a buffer failed), asks for the launch's status, waits for the
+// stream and copies the results back in the order of the out() calls.  launch returns nothing, or a failure it has recorded with fail().
+// timer: the pass's, where the launch is a timed pass (finish_to_host: a call that fails at its end has no time to report).
+struct Entry {
+    gi_ctx* c;
+    const char* what;
+    EventTimer* timer;
+    hipError_t e;
+    DevBuf<unsigned char> buf[16];
+    ToHost outs[6];
+    int n_buf = 0, n_out = 0;
+    Entry(gi_ctx* c_, const char* what_, EventTimer* timer_ = nullptr) : c(c_), what(what_), timer(timer_), e(hipSetDevice(c_->device)) {}
+    template <class T> T* scratch(size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].alloc(count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> const T* in(const T* h, size_t count)
+    {
+        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].upload(reinterpret_cast<const unsigned char*>(h), count * sizeof(T)) : hipErrorOutOfMemory;
+        return e == hipSuccess ? reinterpret_cast<const T*>(buf[n_buf++].p) : nullptr;
+    }
+    template <class T> T* out(T* h, size_t count)
+    {
+        T* d = scratch<T>(count);
+        if (d && n_out == 6) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) outs[n_out++] = ToHost{h, d, count * sizeof(T)};
+        return d;
+    }
+    template <class Launch> int run(Launch launch)
+    {
+        if (e == hipSuccess) {
+            if constexpr (std::is_void<decltype(launch())>::value) launch();
+            else if (const int rc = launch()) return rc;
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return fail(c, GI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return finish_to_host(c, what, outs, (size_t)n_out, timer);
+    }
+};
 
 }  // namespace
 

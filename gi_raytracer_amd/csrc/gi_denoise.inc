@@ -6,19 +6,20 @@
 //               level) and the level-invariant guide record [h][w][8] (albedo, normal, depth, coverage: 64 B, one half cache line);
 //   k_dn_level  one level, one lane per pixel, 25 taps from LDS.  A level of step s is a dense 5 x 5 filter on each of the s^2 interleaved
 //               sub-lattices x = ox + s lx, y = oy + s ly, so a workgroup takes a 32 x 16 tile of ONE sub-lattice with a halo of two lattice
-//               cells: 36 x 20 = 720 cells whatever s is.  The cells sit in LDS as 11 planes of doubles (structure of arrays), so the 32 lanes
-//               of a row read 32 consecutive doubles per ds_read_b64: no bank conflicts.  Cells outside the frame get a NaN colour and are
-//               then skipped by the same test that skips non-finite input.  The last level multiplies by the modulation and stores in the
-//               caller's type;
+//               cells: 36 x 20 = 720 cells whatever s is.  The cells sit in LDS as a GuideTile, so the 32 lanes of a row read 32 consecutive
+//               doubles per ds_read_b64: no bank conflicts.  The last level multiplies by the modulation and stores in the caller's type;
 //   k_dn_copy   iterations = 0: out = colour, converted.
+// What this file shares with the guided upsampler (gi_upsample.inc), each written once here: on the device GuideTile (the LDS tile: its size, its
+// two staging loops, its cell reader), TapSum (the weighted sum over the taps) and dn_store3 (three values in the caller's type), beside k_dn_pack
+// and guide_diff() in gi_device.h; on the host filter_size_check / filter_sigma_check and the two refusals behind them, dn_inv and dn_reserve.
+// The host-pointer forms are an Entry with the pass's timer and the timer reads are pass_ms (both gi_context.inc).
 // Workgroups that share a neighbourhood run next to each other: the sub-lattice index is the fastest part of blockIdx.x, so at large steps the
 // s^2 workgroups that read one region of the frame (each a 1/s^2 sample of its cache lines) are in flight together and the lines come from L2.
 #define GI_DN_TX 32
 #define GI_DN_TY 16
 #define GI_DN_HX (GI_DN_TX + 4)
 #define GI_DN_HY (GI_DN_TY + 4)
-#define GI_DN_CELLS (GI_DN_HX * GI_DN_HY)       // 720
-#define GI_DN_PLANE 724                         // plane stride in doubles: = 4 mod 16, so the loader's 8 components of a cell fall on different banks (2-way at worst)
+#define GI_DN_PLANE 724                         // plane stride in doubles, for 36 x 20 = 720 cells (GuideTile: = 4 mod 16)
 #define GI_DN_BLOCK (GI_DN_TX * GI_DN_TY)       // 512
 #define GI_DN_MAX_ITERATIONS 8
 
@@ -53,91 +54,135 @@ __global__ __launch_bounds__(256) void k_dn_copy(size_t n, const void* color, in
     if (i < n) dn_store(out, out_f64, i, dn_load(color, color_f64, i));
 }
 
-__device__ __forceinline__ DnPix dn_cell(const double* lds, int cell)
+// The LDS tile both image filters take their taps from: HX x HY cells (a workgroup's pixels and their halo) as 11 planes of doubles (structure
+// of arrays): colour 0..2, then the guide record -- albedo 3..5, normal 6..8, depth 9, coverage 10.  PLANE is the plane stride in doubles, = 4 mod
+// 16, so that the loader's 8 components of a cell fall on different banks (2-way at worst).
+template <int HX, int HY, int PLANE>
+struct GuideTile {
+    static constexpr int CELLS = HX * HY, DOUBLES = 11 * PLANE;
+    // Stages the tile from colour [h][w][3] and guides [h][w][8] (f64) with the GI_DN_BLOCK lanes of the workgroup and ends with a barrier.
+    // pixel_of_cell(cx, cy, x, y) names the frame pixel of halo cell (cx, cy).  A cell outside the frame gets a NaN colour, so the test that skips
+    // non-finite input skips it, and zero guides.  Colour goes double by double, the guides in 4 pairs of doubles per cell (16-byte loads).
+    template <class PixelOfCell>
+    static __device__ __forceinline__ void fill(double* lds, const double* __restrict__ colour, const double* __restrict__ guides, int w, int h, PixelOfCell pixel_of_cell)
+    {
+        for (int idx = threadIdx.x; idx < CELLS * 3; idx += GI_DN_BLOCK) {
+            const int cell = idx / 3, k = idx - cell * 3;
+            int x, y;
+            pixel_of_cell(cell % HX, cell / HX, x, y);
+            const bool in = x >= 0 && x < w && y >= 0 && y < h;
+            lds[k * PLANE + cell] = in ? colour[((size_t)y * w + x) * 3 + k] : __builtin_nan("");
+        }
+        for (int idx = threadIdx.x; idx < CELLS * 4; idx += GI_DN_BLOCK) {
+            const int cell = idx >> 2, k = (idx & 3) * 2;
+            int x, y;
+            pixel_of_cell(cell % HX, cell / HX, x, y);
+            double2 v = make_double2(0.0, 0.0);
+            if (x >= 0 && x < w && y >= 0 && y < h) v = *(const double2*)(guides + ((size_t)y * w + x) * 8 + k);
+            lds[(3 + k) * PLANE + cell] = v.x;
+            lds[(4 + k) * PLANE + cell] = v.y;
+        }
+        __syncthreads();
+    }
+    static __device__ __forceinline__ DnPix cell(const double* lds, int i)
+    {
+        DnPix q;
+        q.c = v3(lds[i], lds[PLANE + i], lds[2 * PLANE + i]);
+        q.a = v3(lds[3 * PLANE + i], lds[4 * PLANE + i], lds[5 * PLANE + i]);
+        q.n = v3(lds[6 * PLANE + i], lds[7 * PLANE + i], lds[8 * PLANE + i]);
+        q.z = lds[9 * PLANE + i];
+        q.cov = lds[10 * PLANE + i];
+        return q;
+    }
+};
+
+// The weighted colour sum of a pixel's taps.  A skipped tap (ok false, wq 0) still adds an exact 0.0, never 0 * its NaN.
+struct TapSum {
+    V3 num = v3(0, 0, 0);
+    double den = 0.0;
+    __device__ __forceinline__ void add(const DnPix& q, double wq, bool ok)
+    {
+        num.x += wq * (ok ? q.c.x : 0.0);
+        num.y += wq * (ok ? q.c.y : 0.0);
+        num.z += wq * (ok ? q.c.z : 0.0);
+        den += wq;
+    }
+    __device__ __forceinline__ V3 mean() const { return v3(num.x / den, num.y / den, num.z / den); }   // for den > 0
+};
+
+__device__ __forceinline__ void dn_store3(void* p, int is_f64, size_t o, V3 v)
 {
-    DnPix q;
-    q.c = v3(lds[cell], lds[GI_DN_PLANE + cell], lds[2 * GI_DN_PLANE + cell]);
-    q.a = v3(lds[3 * GI_DN_PLANE + cell], lds[4 * GI_DN_PLANE + cell], lds[5 * GI_DN_PLANE + cell]);
-    q.n = v3(lds[6 * GI_DN_PLANE + cell], lds[7 * GI_DN_PLANE + cell], lds[8 * GI_DN_PLANE + cell]);
-    q.z = lds[9 * GI_DN_PLANE + cell];
-    q.cov = lds[10 * GI_DN_PLANE + cell];
-    return q;
+    dn_store(p, is_f64, o, v.x);
+    dn_store(p, is_f64, o + 1, v.y);
+    dn_store(p, is_f64, o + 2, v.z);
 }
+
+using DnTile = GuideTile<GI_DN_HX, GI_DN_HY, GI_DN_PLANE>;
 
 // src, dst: [h][w][3] f64 demodulated colour; guides [h][w][8] f64.  last: dst is not written; out (type out_f64) gets colour * modulation.
 __global__ __launch_bounds__(GI_DN_BLOCK) void k_dn_level(DnGrid G, DnInv inv, const double* __restrict__ src, const double* __restrict__ guides, double* __restrict__ dst,
                                                           int last, int demodulate, void* out, int out_f64)
 {
-    __shared__ double lds[11 * GI_DN_PLANE];
+    __shared__ double lds[DnTile::DOUBLES];
     const int s = 1 << G.log2s;
     const uint32_t sub = blockIdx.x & (uint32_t)(s * s - 1);
     const uint32_t tile = blockIdx.x >> (2 * G.log2s);
     const int ox = (int)(sub & (uint32_t)(s - 1)), oy = (int)(sub >> G.log2s);
     const int lx0 = (int)(tile % (uint32_t)G.tiles_x) * GI_DN_TX - 2, ly0 = (int)(tile / (uint32_t)G.tiles_x) * GI_DN_TY - 2;   // lattice cell of halo cell (0, 0)
-    // colour: 720 cells x 3 doubles
-    for (int idx = threadIdx.x; idx < GI_DN_CELLS * 3; idx += GI_DN_BLOCK) {
-        const int cell = idx / 3, k = idx - cell * 3;
-        const int x = ox + s * (lx0 + cell % GI_DN_HX), y = oy + s * (ly0 + cell / GI_DN_HX);
-        const bool in = x >= 0 && x < G.w && y >= 0 && y < G.h;
-        lds[k * GI_DN_PLANE + cell] = in ? src[((size_t)y * G.w + x) * 3 + k] : __builtin_nan("");
-    }
-    // guides: 720 cells x 4 pairs of doubles (16-byte loads); record = albedo 0..2, normal 3..5, depth 6, coverage 7 -> planes 3 .. 10
-    for (int idx = threadIdx.x; idx < GI_DN_CELLS * 4; idx += GI_DN_BLOCK) {
-        const int cell = idx >> 2, k = (idx & 3) * 2;
-        const int x = ox + s * (lx0 + cell % GI_DN_HX), y = oy + s * (ly0 + cell / GI_DN_HX);
-        double2 v = make_double2(0.0, 0.0);
-        if (x >= 0 && x < G.w && y >= 0 && y < G.h) v = *(const double2*)(guides + ((size_t)y * G.w + x) * 8 + k);
-        lds[(3 + k) * GI_DN_PLANE + cell] = v.x;
-        lds[(4 + k) * GI_DN_PLANE + cell] = v.y;
-    }
-    __syncthreads();
+    DnTile::fill(lds, src, guides, G.w, G.h, [=](int cx, int cy, int& x, int& y) { x = ox + s * (lx0 + cx); y = oy + s * (ly0 + cy); });
     const int tx = threadIdx.x & (GI_DN_TX - 1), ty = threadIdx.x / GI_DN_TX;
     const int x = ox + s * (lx0 + 2 + tx), y = oy + s * (ly0 + 2 + ty);
     if (x >= G.w || y >= G.h) return;
-    const DnPix p = dn_cell(lds, (ty + 2) * GI_DN_HX + tx + 2);
+    const DnPix p = DnTile::cell(lds, (ty + 2) * GI_DN_HX + tx + 2);
     const bool p_ok = dn_finite(p.c);
     const double p_c2 = dn_sq3(p.c);
     const double h5[5] = {1.0 / 16.0, 1.0 / 4.0, 3.0 / 8.0, 1.0 / 4.0, 1.0 / 16.0};
-    V3 num = v3(0, 0, 0);
-    double den = 0.0;
+    TapSum sum;
 #pragma unroll
     for (int dy = 0; dy < 5; dy++) {
 #pragma unroll
         for (int dx = 0; dx < 5; dx++) {
-            const DnPix q = dn_cell(lds, (ty + dy) * GI_DN_HX + tx + dx);
+            const DnPix q = DnTile::cell(lds, (ty + dy) * GI_DN_HX + tx + dx);
             const bool ok = dn_finite(q.c);        // outside the frame (NaN from the loader) or a non-finite input: skipped
-            const double wq = ok ? dn_tap_weight(p, p_c2, p_ok, q, inv, h5[dy] * h5[dx]) : 0.0;
-            num.x += wq * (ok ? q.c.x : 0.0);
-            num.y += wq * (ok ? q.c.y : 0.0);
-            num.z += wq * (ok ? q.c.z : 0.0);
-            den += wq;
+            sum.add(q, ok ? dn_tap_weight(p, p_c2, p_ok, q, inv, h5[dy] * h5[dx]) : 0.0, ok);
         }
     }
-    V3 r = v3(0, 0, 0);
-    if (den > 0.0) r = v3(num.x / den, num.y / den, num.z / den);
+    const V3 r = sum.den > 0.0 ? sum.mean() : v3(0, 0, 0);
     const size_t o = ((size_t)y * G.w + x) * 3;
-    if (last) {
-        dn_store(out, out_f64, o, r.x * dn_modulation(p.a.x, demodulate));
-        dn_store(out, out_f64, o + 1, r.y * dn_modulation(p.a.y, demodulate));
-        dn_store(out, out_f64, o + 2, r.z * dn_modulation(p.a.z, demodulate));
-    } else {
-        dst[o] = r.x; dst[o + 1] = r.y; dst[o + 2] = r.z;
-    }
+    if (last) dn_store3(out, out_f64, o, v3(r.x * dn_modulation(p.a.x, demodulate), r.y * dn_modulation(p.a.y, demodulate), r.z * dn_modulation(p.a.z, demodulate)));
+    else dn_store3(dst, 1, o, r);
 }
 
 namespace {
 
-// false + message when the parameters are not the header's
+// ---- what the entries of an image filter `name` ("denoise", "upsample") refuse in the same words.  A *_check gives false + message when the
+// parameters are not the header's; the two refusals below it come behind that check, the pixel limit in the device form only.
+bool filter_size_check(const char* name, int w, int h, std::string& err)
+{
+    if (w >= 1 && h >= 1) return true;
+    err = std::string(name) + ": width and height must be at least 1, got " + std::to_string(w) + " x " + std::to_string(h);
+    return false;
+}
+bool filter_sigma_check(const char* name, const char* const* names, const double* values, int n, std::string& err)
+{
+    for (int k = 0; k < n; k++)
+        if (!(values[k] >= 0.0)) { err = std::string(name) + ": " + names[k] + " must be >= 0 (0 switches the term off), got " + std::to_string(values[k]); return false; }
+    return true;
+}
+int filter_null_pointer(gi_ctx* c, const char* name) { return fail(c, GI_E_INVALID, std::string(name) + ": null colour, feature or output pointer"); }
+int filter_pixel_limit(gi_ctx* c, const char* name, size_t n_pix)
+{
+    return n_pix > ((size_t)1 << 28) ? fail(c, GI_E_INVALID, std::string(name) + ": frames beyond 2^28 pixels are not supported") : GI_OK;
+}
+
 bool dn_check(const gi_denoise_params* p, std::string& err)
 {
     if (!p) { err = "denoise: null parameters"; return false; }
-    if (p->width < 1 || p->height < 1) { err = "denoise: width and height must be at least 1, got " + std::to_string(p->width) + " x " + std::to_string(p->height); return false; }
+    if (!filter_size_check("denoise", p->width, p->height, err)) return false;
     if (p->iterations < 0 || p->iterations > GI_DN_MAX_ITERATIONS) { err = "denoise: iterations must be 0 .. " + std::to_string(GI_DN_MAX_ITERATIONS) + ", got " + std::to_string(p->iterations); return false; }
     const double sg[4] = {p->sigma_color, p->sigma_normal, p->sigma_depth, p->sigma_albedo};
     const char* names[4] = {"sigma_color", "sigma_normal", "sigma_depth", "sigma_albedo"};
-    for (int k = 0; k < 4; k++)
-        if (!(sg[k] >= 0.0)) { err = std::string("denoise: ") + names[k] + " must be >= 0 (0 switches the term off), got " + std::to_string(sg[k]); return false; }
-    return true;
+    return filter_sigma_check("denoise", names, sg, 4, err);
 }
 
 double dn_inv(double sigma, double scale) { return sigma != 0.0 ? scale / (sigma * sigma) : 0.0; }
@@ -176,9 +221,9 @@ int gi_denoise_device(gi_ctx* c, const gi_denoise_params* p, const void* d_color
     c->dn.timer.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
-    if (!d_color || !d_features || !d_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
+    if (!d_color || !d_features || !d_out) return filter_null_pointer(c, "denoise");
     const size_t n_pix = (size_t)p->width * (size_t)p->height;
-    if (n_pix > ((size_t)1 << 28)) return fail(c, GI_E_INVALID, "denoise: frames beyond 2^28 pixels are not supported");
+    if (const int rc = filter_pixel_limit(c, "denoise", n_pix)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const int it = p->iterations;
     if (it > 0) {
@@ -221,24 +266,15 @@ int gi_denoise_host(gi_ctx* c, const gi_denoise_params* p, const void* h_color, 
     c->dn.timer.reset();
     std::string err;
     if (!dn_check(p, err)) return fail(c, GI_E_INVALID, err);
-    if (!h_color || !h_features || !h_out) return fail(c, GI_E_INVALID, "denoise: null colour, feature or output pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
+    if (!h_color || !h_features || !h_out) return filter_null_pointer(c, "denoise");
     const size_t n_pix = (size_t)p->width * (size_t)p->height;
-    const size_t cb = n_pix * 3 * (color_is_f64 ? 8 : 4), fb = n_pix * 8 * (features_is_f64 ? 8 : 4), ob = n_pix * 3 * (out_is_f64 ? 8 : 4);
-    DevBuf<unsigned char> d_color, d_feat, d_out;
-    hipError_t e = d_color.upload((const unsigned char*)h_color, cb);
-    if (e == hipSuccess) e = d_feat.upload((const unsigned char*)h_features, fb);
-    if (e == hipSuccess) e = d_out.alloc(ob);
-    if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("denoise_host: ") + hipGetErrorString(e));
-    const int rc = gi_denoise_device(c, p, d_color.p, color_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
-    return rc != GI_OK ? rc : finish_to_host(c, "denoise_host", {{h_out, d_out.p, ob}}, &c->dn.timer);
+    Entry e(c, "denoise_host", &c->dn.timer);
+    const unsigned char* d_color = e.in((const unsigned char*)h_color, n_pix * 3 * (color_is_f64 ? 8 : 4));
+    const unsigned char* d_feat = e.in((const unsigned char*)h_features, n_pix * 8 * (features_is_f64 ? 8 : 4));
+    unsigned char* d_out = e.out((unsigned char*)h_out, n_pix * 3 * (out_is_f64 ? 8 : 4));
+    return e.run([&] { return gi_denoise_device(c, p, d_color, color_is_f64, d_feat, features_is_f64, d_out, out_is_f64); });
 }
 
-int gi_last_denoise_ms(gi_ctx* c, float* ms)
-{
-    if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->dn.timer.read(ms));
-    return GI_OK;
-}
+int gi_last_denoise_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::dn, ms); }
 
 }  // extern "C"

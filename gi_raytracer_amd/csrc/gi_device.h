@@ -2360,18 +2360,27 @@ struct DnInv { double c, n, z, a; };             // 4^level / sigma_color^2, 1 /
 GI_HD double dn_sq3(V3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }
 GI_HD bool dn_finite(V3 c) { return fabs(c.x) <= 1.7976931348623157e308 && fabs(c.y) <= 1.7976931348623157e308 && fabs(c.z) <= 1.7976931348623157e308; }
 GI_HD double dn_modulation(double albedo, int demodulate) { return demodulate ? (albedo > GI_DN_ALBEDO_FLOOR ? albedo : GI_DN_ALBEDO_FLOOR) : 1.0; }
+// The three guide terms of a tap, shared by both filters' weights: squared normal difference, squared relative depth difference (0 unless
+// z_p + z_q > 0), squared albedo difference plus squared coverage difference.
+struct GuideDiff { double dn, dz, da; };
+GI_HD GuideDiff guide_diff(const DnPix& p, const DnPix& q)
+{
+    GuideDiff g;
+    g.dn = dn_sq3(p.n - q.n);
+    const double dcov = p.cov - q.cov;
+    g.da = dn_sq3(p.a - q.a) + dcov * dcov;
+    const double zs = p.z + q.z;
+    g.dz = 0.0;
+    if (zs > 0.0) { const double r = (p.z - q.z) / zs; g.dz = r * r; }
+    return g;
+}
 // weight of tap q for the centre p: hh = h[dy] h[dx]; p_c2 = |c_p|^2; p_ok = the centre's colour is finite (else the colour term is 0).
 // The caller skips taps outside the frame and taps whose colour is not finite.
 GI_HD double dn_tap_weight(const DnPix& p, double p_c2, bool p_ok, const DnPix& q, const DnInv& inv, double hh)
 {
     const double dc = p_ok ? dn_sq3(p.c - q.c) / (p_c2 + (dn_sq3(q.c) + GI_DN_DC_EPS)) : 0.0;
-    const double dn = dn_sq3(p.n - q.n);
-    const double dcov = p.cov - q.cov;
-    const double da = dn_sq3(p.a - q.a) + dcov * dcov;
-    const double zs = p.z + q.z;
-    double dz = 0.0;
-    if (zs > 0.0) { const double r = (p.z - q.z) / zs; dz = r * r; }
-    const double d = ((dc * inv.c + dn * inv.n) + dz * inv.z) + da * inv.a;
+    const GuideDiff g = guide_diff(p, q);
+    const double d = ((dc * inv.c + g.dn * inv.n) + g.dz * inv.z) + g.da * inv.a;
     const double t = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
     return hh * (t * t);
 }
@@ -2379,13 +2388,8 @@ GI_HD double dn_tap_weight(const DnPix& p, double p_c2, bool p_ok, const DnPix& 
 // colour term, d = (dn inv_n + dz inv_z) + da inv_a (inv.c is not read); hh = ty tx, the tent.
 GI_HD double up_tap_weight(const DnPix& p, const DnPix& q, const DnInv& inv, double hh)
 {
-    const double dn = dn_sq3(p.n - q.n);
-    const double dcov = p.cov - q.cov;
-    const double da = dn_sq3(p.a - q.a) + dcov * dcov;
-    const double zs = p.z + q.z;
-    double dz = 0.0;
-    if (zs > 0.0) { const double r = (p.z - q.z) / zs; dz = r * r; }
-    const double d = (dn * inv.n + dz * inv.z) + da * inv.a;
+    const GuideDiff g = guide_diff(p, q);
+    const double d = (g.dn * inv.n + g.dz * inv.z) + g.da * inv.a;
     const double e = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
     return hh * (e * e);
 }

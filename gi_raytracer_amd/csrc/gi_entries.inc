@@ -1,5 +1,5 @@
 // gi_entries.inc -- the function-level and debug entries of the C ABI: host arrays in, one kernel (or one pass), host arrays out.  Included by
-// gi_kernels.hip behind the passes.  Each reads: argument and state checks, buffers (Entry, below:
+// gi_kernels.hip behind the passes.  Each reads: argument and state checks, buffers (Entry, gi_context.inc:
 // element counts once per buffer), the launch, and Entry::run copies the outputs back in the order they were named.
 namespace {
 
@@ -8,47 +8,6 @@ void frame_box(const gi_ctx* c, const double* box6, double* out)
 {
     for (int k = 0; k < 3; k++) { out[k] = box6 ? box6[k] : c->S.root_bmin[k]; out[3 + k] = box6 ? box6[3 + k] : c->S.root_bmax[k]; }
 }
-
-// The device side of a function-level entry, after its argument and state checks.  in() uploads a caller's array, out() allocates a
-// result and notes where it goes (h == nullptr: an optional output nobody asked for -- the kernel still writes it), scratch() is memory of this
-// call alone; each takes the element count, once.  run(launch) launches (unless a buffer failed), asks for the launch's status, waits for the
-// stream and copies the results back in the order of the out() calls.  launch returns nothing, or a failure it has recorded with fail().
-struct Entry {
-    gi_ctx* c;
-    const char* what;
-    hipError_t e;
-    DevBuf<unsigned char> buf[16];
-    ToHost outs[6];
-    int n_buf = 0, n_out = 0;
-    Entry(gi_ctx* c_, const char* what_) : c(c_), what(what_), e(hipSetDevice(c_->device)) {}
-    template <class T> T* scratch(size_t count)
-    {
-        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].alloc(count * sizeof(T)) : hipErrorOutOfMemory;
-        return e == hipSuccess ? reinterpret_cast<T*>(buf[n_buf++].p) : nullptr;
-    }
-    template <class T> const T* in(const T* h, size_t count)
-    {
-        if (e == hipSuccess) e = n_buf < 16 ? buf[n_buf].upload(reinterpret_cast<const unsigned char*>(h), count * sizeof(T)) : hipErrorOutOfMemory;
-        return e == hipSuccess ? reinterpret_cast<const T*>(buf[n_buf++].p) : nullptr;
-    }
-    template <class T> T* out(T* h, size_t count)
-    {
-        T* d = scratch<T>(count);
-        if (d && n_out == 6) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) outs[n_out++] = ToHost{h, d, count * sizeof(T)};
-        return d;
-    }
-    template <class Launch> int run(Launch launch)
-    {
-        if (e == hipSuccess) {
-            if constexpr (std::is_void<decltype(launch())>::value) launch();
-            else if (const int rc = launch()) return rc;
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) return fail(c, GI_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return finish_to_host(c, what, outs, (size_t)n_out);
-    }
-};
 
 }  // namespace
 

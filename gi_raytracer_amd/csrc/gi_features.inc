@@ -115,11 +115,6 @@ int gi_render_features_host(gi_ctx* c, const gi_render_params* p, int32_t n_samp
                               [&](void* d_out, int32_t* d_ids) { return gi_render_features_device(c, p, n_samples, d_out, out_is_f64, d_ids); });
 }
 
-int gi_last_features_ms(gi_ctx* c, float* ms)
-{
-    if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->feat.timer.read(ms));
-    return GI_OK;
-}
+int gi_last_features_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::feat, ms); }
 
 }  // extern "C"

@@ -100,11 +100,6 @@ int gi_render_occlusion_host(gi_ctx* c, const gi_render_params* p, const gi_occl
                               [&](void* d_out, int32_t*) { return gi_render_occlusion_device(c, p, op, d_out, out_is_f64); });
 }
 
-int gi_last_occlusion_ms(gi_ctx* c, float* ms)
-{
-    if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->ao.timer.read(ms));
-    return GI_OK;
-}
+int gi_last_occlusion_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::ao, ms); }
 
 }  // extern "C"

@@ -1,23 +1,21 @@
 // gi_upsample.inc -- the guided (joint-bilateral) upsampler (gi_upsample_*; an addition: the reference has none).  Included by gi_kernels.hip after
-// gi_denoise.inc, whose pack kernel, LDS cell reader and scratch it uses.  The formula is stated in include/gi_hip.h; the per-tap function is
-// up_tap_weight() in gi_device.h.
+// gi_denoise.inc, whose pack kernel, LDS tile (GuideTile), tap sum, typed store, parameter checks and scratch it uses (listed there).  The formula
+// is stated in include/gi_hip.h; the per-tap function is up_tap_weight() in gi_device.h.
 //
 // Two kernels on the context's stream, no atomics, no host sync between them:
 //   k_dn_pack    on the LOW frame: widens and demodulates its colour and widens its guide records into the denoiser's scratch (f64);
 //   k_up_sample  one lane per FULL pixel; a workgroup takes a 32 x 16 tile of full pixels.  The taps of pixel x are the low columns X0(x) - 1 ..
 //                X0(x) + 2 with X0(x) = floor((2x + 1 - S) / 2S), and X0(x0 + 31) - X0(x0) <= ceil(31 / S) <= 16, so the tile's low-size footprint is
-//                at most 20 x 12 cells (S = 2; fewer for larger S, the rest of the 240 cells are loaded and not read).  The cells sit in LDS as 11
-//                planes of doubles (structure of arrays, as in k_dn_level): the 32 lanes of a tile row read at most 32 / S + 1 different, consecutive
-//                doubles per ds_read_b64 -- neighbours share a cell, which is a broadcast, not a conflict.  Cells outside the low frame get a NaN
-//                colour and are skipped by the test that skips non-finite input.  After the barrier each lane reads its own full-size guide record
+//                at most 20 x 12 cells (S = 2; fewer for larger S, the rest of the 240 cells are loaded and not read).  The cells sit in LDS as a
+//                GuideTile, as in k_dn_level: the 32 lanes of a tile row read at most 32 / S + 1 different, consecutive doubles per ds_read_b64 --
+//                neighbours share a cell, which is a broadcast, not a conflict.  After the barrier each lane reads its own full-size guide record
 //                (32 or 64 B; consecutive lanes read consecutive records) straight from global memory, runs the 16 taps out of LDS and stores once
 //                in the caller's type.
 #define GI_UP_TX 32
 #define GI_UP_TY 16
 #define GI_UP_HX (GI_UP_TX / 2 + 4)             // 20: the S = 2 footprint
 #define GI_UP_HY (GI_UP_TY / 2 + 4)             // 12
-#define GI_UP_CELLS (GI_UP_HX * GI_UP_HY)       // 240
-#define GI_UP_PLANE 244                         // plane stride in doubles: = 4 mod 16, as GI_DN_PLANE, for the loader's 8 components of a cell
+#define GI_UP_PLANE 244                         // plane stride in doubles, for 20 x 12 = 240 cells (GuideTile: = 4 mod 16)
 #define GI_UP_BLOCK (GI_UP_TX * GI_UP_TY)       // 512
 #define GI_UP_MIN_FACTOR 2
 #define GI_UP_MAX_FACTOR 8
@@ -26,42 +24,18 @@ struct UpGrid { int32_t w, h, wl, hl, S, tiles_x; };
 
 __device__ __forceinline__ int up_floor_div(int a, int b) { const int q = a / b; return (a % b < 0) ? q - 1 : q; }   // b > 0
 
-__device__ __forceinline__ DnPix up_cell(const double* lds, int cell)
-{
-    DnPix q;
-    q.c = v3(lds[cell], lds[GI_UP_PLANE + cell], lds[2 * GI_UP_PLANE + cell]);
-    q.a = v3(lds[3 * GI_UP_PLANE + cell], lds[4 * GI_UP_PLANE + cell], lds[5 * GI_UP_PLANE + cell]);
-    q.n = v3(lds[6 * GI_UP_PLANE + cell], lds[7 * GI_UP_PLANE + cell], lds[8 * GI_UP_PLANE + cell]);
-    q.z = lds[9 * GI_UP_PLANE + cell];
-    q.cov = lds[10 * GI_UP_PLANE + cell];
-    return q;
-}
+using UpTile = GuideTile<GI_UP_HX, GI_UP_HY, GI_UP_PLANE>;
+static_assert(GI_UP_BLOCK == GI_DN_BLOCK, "GuideTile::fill strides by the denoiser's workgroup size");
 
 // lc [hl][wl][3] f64 demodulated low colour and lg [hl][wl][8] f64 low guides (k_dn_pack's output); feat [h][w][8] and out [h][w][3] in the caller's types
 __global__ __launch_bounds__(GI_UP_BLOCK) void k_up_sample(UpGrid G, DnInv inv, const double* __restrict__ lc, const double* __restrict__ lg, const void* __restrict__ feat, int feat_f64,
                                                            int demodulate, void* __restrict__ out, int out_f64)
 {
-    __shared__ double lds[11 * GI_UP_PLANE];
+    __shared__ double lds[UpTile::DOUBLES];
     const int S2 = 2 * G.S, S4 = 4 * G.S;
     const int fx0 = (int)(blockIdx.x % (uint32_t)G.tiles_x) * GI_UP_TX, fy0 = (int)(blockIdx.x / (uint32_t)G.tiles_x) * GI_UP_TY;
     const int lx0 = up_floor_div(2 * fx0 + 1 - G.S, S2) - 1, ly0 = up_floor_div(2 * fy0 + 1 - G.S, S2) - 1;     // low pixel of halo cell (0, 0)
-    // colour: 240 cells x 3 doubles
-    for (int idx = threadIdx.x; idx < GI_UP_CELLS * 3; idx += GI_UP_BLOCK) {
-        const int cell = idx / 3, k = idx - cell * 3;
-        const int X = lx0 + cell % GI_UP_HX, Y = ly0 + cell / GI_UP_HX;
-        const bool in = X >= 0 && X < G.wl && Y >= 0 && Y < G.hl;
-        lds[k * GI_UP_PLANE + cell] = in ? lc[((size_t)Y * G.wl + X) * 3 + k] : __builtin_nan("");
-    }
-    // guides: 240 cells x 4 pairs of doubles (16-byte loads); record = albedo 0..2, normal 3..5, depth 6, coverage 7 -> planes 3 .. 10
-    for (int idx = threadIdx.x; idx < GI_UP_CELLS * 4; idx += GI_UP_BLOCK) {
-        const int cell = idx >> 2, k = (idx & 3) * 2;
-        const int X = lx0 + cell % GI_UP_HX, Y = ly0 + cell / GI_UP_HX;
-        double2 v = make_double2(0.0, 0.0);
-        if (X >= 0 && X < G.wl && Y >= 0 && Y < G.hl) v = *(const double2*)(lg + ((size_t)Y * G.wl + X) * 8 + k);
-        lds[(3 + k) * GI_UP_PLANE + cell] = v.x;
-        lds[(4 + k) * GI_UP_PLANE + cell] = v.y;
-    }
-    __syncthreads();
+    UpTile::fill(lds, lc, lg, G.wl, G.hl, [=](int cx, int cy, int& X, int& Y) { X = lx0 + cx; Y = ly0 + cy; });
     const int x = fx0 + (int)(threadIdx.x & (GI_UP_TX - 1)), y = fy0 + (int)(threadIdx.x / GI_UP_TX);
     if (x >= G.w || y >= G.h) return;
     const size_t pix = (size_t)y * G.w + x;
@@ -91,36 +65,29 @@ __global__ __launch_bounds__(GI_UP_BLOCK) void k_up_sample(UpGrid G, DnInv inv, 
         const int nx = abs(S2 * (X0 - 1 + i) - Nx);
         tx[i] = nx < S4 ? (double)(S4 - nx) / r4 : 0.0;
     }
-    V3 num = v3(0, 0, 0);
-    double den = 0.0;
+    TapSum sum;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const int ny = abs(S2 * (Y0 - 1 + j) - Ny);
         const double ty = ny < S4 ? (double)(S4 - ny) / r4 : 0.0;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            const DnPix q = up_cell(lds, (cy + j) * GI_UP_HX + cx + i);
+            const DnPix q = UpTile::cell(lds, (cy + j) * GI_UP_HX + cx + i);
             const bool ok = dn_finite(q.c);        // outside the low frame (NaN from the loader) or a non-finite input: skipped
-            const double wq = ok ? up_tap_weight(p, q, inv, ty * tx[i]) : 0.0;
-            num.x += wq * (ok ? q.c.x : 0.0);
-            num.y += wq * (ok ? q.c.y : 0.0);
-            num.z += wq * (ok ? q.c.z : 0.0);
-            den += wq;
+            sum.add(q, ok ? up_tap_weight(p, q, inv, ty * tx[i]) : 0.0, ok);
         }
     }
     const V3 mf = v3(dn_modulation(p.a.x, demodulate), dn_modulation(p.a.y, demodulate), dn_modulation(p.a.z, demodulate));
     V3 r = v3(0, 0, 0);
-    if (den > 0.0) {
-        r = v3((num.x / den) * mf.x, (num.y / den) * mf.y, (num.z / den) * mf.z);
+    if (sum.den > 0.0) {
+        r = sum.mean() * mf;
     } else {
         // every tap rejected: the nearest low pixel.  x / S is X0 or X0 + 1, so it is one of the taps' cells; it lies inside the low frame, so a NaN there is the input's
         const int Xn = min(x / G.S, G.wl - 1), Yn = min(y / G.S, G.hl - 1);
-        const DnPix q = up_cell(lds, (Yn - ly0) * GI_UP_HX + (Xn - lx0));
-        if (dn_finite(q.c)) r = v3(q.c.x * mf.x, q.c.y * mf.y, q.c.z * mf.z);
+        const DnPix q = UpTile::cell(lds, (Yn - ly0) * GI_UP_HX + (Xn - lx0));
+        if (dn_finite(q.c)) r = q.c * mf;
     }
-    dn_store(out, out_f64, pix * 3, r.x);
-    dn_store(out, out_f64, pix * 3 + 1, r.y);
-    dn_store(out, out_f64, pix * 3 + 2, r.z);
+    dn_store3(out, out_f64, pix * 3, r);
 }
 
 namespace {
@@ -129,7 +96,7 @@ namespace {
 bool up_check(const gi_upsample_params* p, std::string& err)
 {
     if (!p) { err = "upsample: null parameters"; return false; }
-    if (p->width < 1 || p->height < 1) { err = "upsample: width and height must be at least 1, got " + std::to_string(p->width) + " x " + std::to_string(p->height); return false; }
+    if (!filter_size_check("upsample", p->width, p->height, err)) return false;
     if (p->factor < GI_UP_MIN_FACTOR || p->factor > GI_UP_MAX_FACTOR) {
         err = "upsample: factor must be " + std::to_string(GI_UP_MIN_FACTOR) + " .. " + std::to_string(GI_UP_MAX_FACTOR) + ", got " + std::to_string(p->factor);
         return false;
@@ -142,9 +109,7 @@ bool up_check(const gi_upsample_params* p, std::string& err)
     }
     const double sg[3] = {p->sigma_normal, p->sigma_depth, p->sigma_albedo};
     const char* names[3] = {"sigma_normal", "sigma_depth", "sigma_albedo"};
-    for (int k = 0; k < 3; k++)
-        if (!(sg[k] >= 0.0)) { err = std::string("upsample: ") + names[k] + " must be >= 0 (0 switches the term off), got " + std::to_string(sg[k]); return false; }
-    return true;
+    return filter_sigma_check("upsample", names, sg, 3, err);
 }
 
 }  // namespace
@@ -166,9 +131,9 @@ int gi_upsample_device(gi_ctx* c, const gi_upsample_params* p, const void* d_low
     c->up.timer.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
-    if (!d_low_color || !d_low_features || !d_features || !d_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
+    if (!d_low_color || !d_low_features || !d_features || !d_out) return filter_null_pointer(c, "upsample");
     const size_t n_pix = (size_t)p->width * (size_t)p->height, n_low = (size_t)p->low_width * (size_t)p->low_height;
-    if (n_pix > ((size_t)1 << 28)) return fail(c, GI_E_INVALID, "upsample: frames beyond 2^28 pixels are not supported");
+    if (const int rc = filter_pixel_limit(c, "upsample", n_pix)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const int rc = dn_reserve(c, n_low);
     if (rc != GI_OK) return rc;
@@ -196,25 +161,16 @@ int gi_upsample_host(gi_ctx* c, const gi_upsample_params* p, const void* h_low_c
     c->up.timer.reset();
     std::string err;
     if (!up_check(p, err)) return fail(c, GI_E_INVALID, err);
-    if (!h_low_color || !h_low_features || !h_features || !h_out) return fail(c, GI_E_INVALID, "upsample: null colour, feature or output pointer");
-    HIP_TRY(c, hipSetDevice(c->device));
+    if (!h_low_color || !h_low_features || !h_features || !h_out) return filter_null_pointer(c, "upsample");
     const size_t n_pix = (size_t)p->width * (size_t)p->height, n_low = (size_t)p->low_width * (size_t)p->low_height;
-    const size_t cb = n_low * 3 * (low_color_is_f64 ? 8 : 4), lb = n_low * 8 * (low_features_is_f64 ? 8 : 4), fb = n_pix * 8 * (features_is_f64 ? 8 : 4), ob = n_pix * 3 * (out_is_f64 ? 8 : 4);
-    DevBuf<unsigned char> d_color, d_low, d_feat, d_out;
-    hipError_t e = d_color.upload((const unsigned char*)h_low_color, cb);
-    if (e == hipSuccess) e = d_low.upload((const unsigned char*)h_low_features, lb);
-    if (e == hipSuccess) e = d_feat.upload((const unsigned char*)h_features, fb);
-    if (e == hipSuccess) e = d_out.alloc(ob);
-    if (e != hipSuccess) return fail(c, GI_E_HIP, std::string("upsample_host: ") + hipGetErrorString(e));
-    const int rc = gi_upsample_device(c, p, d_color.p, low_color_is_f64, d_low.p, low_features_is_f64, d_feat.p, features_is_f64, d_out.p, out_is_f64);
-    return rc != GI_OK ? rc : finish_to_host(c, "upsample_host", {{h_out, d_out.p, ob}}, &c->up.timer);
+    Entry e(c, "upsample_host", &c->up.timer);
+    const unsigned char* d_color = e.in((const unsigned char*)h_low_color, n_low * 3 * (low_color_is_f64 ? 8 : 4));
+    const unsigned char* d_low = e.in((const unsigned char*)h_low_features, n_low * 8 * (low_features_is_f64 ? 8 : 4));
+    const unsigned char* d_feat = e.in((const unsigned char*)h_features, n_pix * 8 * (features_is_f64 ? 8 : 4));
+    unsigned char* d_out = e.out((unsigned char*)h_out, n_pix * 3 * (out_is_f64 ? 8 : 4));
+    return e.run([&] { return gi_upsample_device(c, p, d_color, low_color_is_f64, d_low, low_features_is_f64, d_feat, features_is_f64, d_out, out_is_f64); });
 }
 
-int gi_last_upsample_ms(gi_ctx* c, float* ms)
-{
-    if (!c || !ms) return GI_E_INVALID;
-    HIP_TRY(c, c->up.timer.read(ms));
-    return GI_OK;
-}
+int gi_last_upsample_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::up, ms); }
 
 }  // extern "C"

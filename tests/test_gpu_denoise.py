@@ -35,7 +35,7 @@ def report(tag, got, want):
     print(f"{tag}: {bad} of {got.size} values differ" + (f", largest relative error {np.nanmax(rel):.3e}" if bad else ""))
 
 
-@pytest.mark.parametrize("w,h", [(1, 1), (3, 2), (37, 29), (96, 72), (200, 131)])
+@pytest.mark.parametrize("w,h", [(1, 1), (3, 2), (37, 29), (96, 72), (200, 131), (32, 16), (33, 17), (65, 33)])
 def test_synthetic_frames_match_the_expectation(rt0, w, h):
     noisy, feat, _ = de.synthetic(w, h, seed=w + h)
     for it in range(1, 7):

@@ -43,7 +43,7 @@ def reduced(w, h, factor, seed=1, noise=0.5):
     return ue.box_reduce(noisy, factor), ue.box_reduce(feat, factor), feat
 
 
-@pytest.mark.parametrize("w,h,factor", [(1, 1, 2), (3, 2, 2), (37, 29, 2), (37, 29, 3), (37, 29, 4), (70, 37, 2), (200, 131, 3), (64, 32, 8)])
+@pytest.mark.parametrize("w,h,factor", [(1, 1, 2), (3, 2, 2), (37, 29, 2), (37, 29, 3), (37, 29, 4), (70, 37, 2), (200, 131, 3), (64, 32, 8), (33, 17, 5), (65, 33, 7), (9, 9, 8), (32, 16, 2)])
 def test_synthetic_frames_match_the_expectation(rt0, w, h, factor):
     low, low_feat, feat = reduced(w, h, factor, seed=w + h)
     assert low.shape[:2] == ue.low_size(w, h, factor)[::-1]
