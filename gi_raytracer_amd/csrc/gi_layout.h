@@ -198,7 +198,7 @@ inline RefRange node_refs(const gi_scene_desc* d, int n) { return {d->node_ent_o
 // the bit of a child's slot that says "high side" on axis ax: x = bit 0, z = bit 1, y = bit 2 (include/octree.cpp:321-328)
 inline int axis_slot_bit(int ax) { return ax == 0 ? 0 : (ax == 1 ? 2 : 1); }
 inline bool entity_is_sphere(const gi_scene_desc* d, int e) { return d->ent_kind && d->ent_kind[e] == 1; }
-// The exact box of entity e (sphere: centre P[0..2] -+ radius P[3]; triangle: its vertices), nothing added.  Not gi_host.cpp: entity_box, which
+// The exact box of entity e (sphere: centre P[0..2] -+ radius P[3]; triangle: its vertices), nothing added.  Not gi_host_geom.inc: entity_box, which
 // is the reference's box with its EPSILON growth and decides which leaves refer to the entity.
 inline void entity_bounds(const gi_scene_desc* d, int e, double* lo, double* hi)
 {

@@ -1,6 +1,7 @@
 // include/gi/octree.h -- the scene container of the reference (include/octree.h:17-65) for its callers: loaders and generators push entities,
 // lights and atmosphere entities; RayTracer::setScene takes the pointer.  rebuild() (include/octree.cpp:53-119) hands the entities to the
-// host tree builder (gi_raytracer_amd/csrc/gi_host.cpp: the reference's light-cone precompute and Octree::Node::partition, node for node),
+// host tree builder (gi_raytracer_amd/csrc/gi_host_scene.inc: build_octree, the reference's light-cone precompute, and gi_host_tree.inc: its
+// Octree::Node::partition, node for node, as the EntityRule of the one partition that also builds the photon tree),
 // keeps the flattened tables for the upload to the GPU and mirrors the tree into `_root` (Node: box, entity pointers, eight children), so
 // that code walking `_root` sees the reference's structure.  intersect / intersectSorted / atmosphere* are host-side queries over `_root`
 // for such callers; the renderer never uses them -- its traversal is the HIP kernels' walk over the uploaded tables.

@@ -1,5 +1,11 @@
 """Host-side feeders of the product (gi_raytracer_amd/csrc/gi_host.cpp) against dumps of the reference's own loader,
 Octree::rebuild and PhotonMap::rebuild (tests/golden/scene_*.npz).  Everything is exact."""
+import ctypes as C
+import glob
+import os
+import re
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -30,6 +36,178 @@ def test_loader_octree_photon_map_identical_to_reference(golden, name):
         assert np.array_equal(p["node_bbox"], fx["pm_bbox"])
         assert np.array_equal(np.where(p["node_child"][:, 0] >= 0, p["node_child"][:, 0], -1), fx["pm_firstchild"])
         assert np.array_equal(p["node_off"], fx["pm_off"]) and np.array_equal(p["node_idx"], fx["pm_idx"])
+
+
+CSRC = os.path.join(pc.ROOT, "gi_raytracer_amd", "csrc")
+_dp = C.POINTER(C.c_double)
+
+
+def _p(a):
+    return a.ctypes.data_as(_dp)
+
+
+def _max_photons_per_leaf():
+    """kMaxPhotonsPerLeaf as the host builder's source states it (gi_host.cpp and the pieces it includes)."""
+    for path in sorted(glob.glob(os.path.join(CSRC, "gi_host*"))):
+        m = re.search(r"\bkMaxPhotonsPerLeaf\s*=\s*(\d+)\s*;", open(path).read())
+        if m:
+            return int(m.group(1))
+    raise AssertionError("kMaxPhotonsPerLeaf not found in the host builder's source")
+
+
+PM_BOX = np.array([-1.0, -2.0, -3.0, 2.0, 1.5, 4.0])
+K = _max_photons_per_leaf()
+
+
+def _cloud(shape, n):
+    lo, hi = PM_BOX[:3], PM_BOX[3:]
+    ph = np.random.RandomState(n * 7 + len(shape)).rand(n, 9)
+    ph[:, :3] = lo + ph[:, :3] * (hi - lo)
+    if shape == "point":
+        ph[:, :3] = [0.3, 0.4, 0.5]
+    elif shape == "mid_face":
+        ph[::2, 0] = lo[0] + .5 * (hi[0] - lo[0])          # the root's mid plane, as the builder computes it: these belong to the upper octants
+    return ph
+
+
+def _photon_map_in_box(scene, box, ph):
+    box, ph = np.ascontiguousarray(box, np.float64), np.ascontiguousarray(ph, np.float64).reshape(-1, 9)
+    assert scene.L.gih_build_photon_map_in_box(scene.h, _p(box), len(ph), _p(ph) if len(ph) else None) == 0
+    return scene.photon_tables()
+
+
+def _subtree_sizes(child):
+    size = np.ones(len(child), np.int64)
+    for i in range(len(child) - 1, -1, -1):                 # pre-order: every child has a larger number than its parent
+        size[i] += size[child[i][child[i] >= 0]].sum()
+    return size
+
+
+@pytest.mark.parametrize("n", [0, 1, K, K + 1, 5000])
+@pytest.mark.parametrize("shape", ["uniform", "point", "mid_face"])
+def test_photon_tree_invariants(shape, n):
+    """The photon octree over a cloud in PM_BOX, checked by numpy alone: every photon is listed exactly once, by a leaf whose half-open box
+    holds it; an inner node lists nothing and has all eight children, numbered in pre-order (the first is the node's number + 1, each next
+    one follows the subtree of the one before: consecutive numbers wherever the children are leaves); node 0 is the box given; the
+    offsets do not decrease and end at n.
+
+    shape "point" with more than K photons: the reference's PhotonMap::Node::partition, which the builder follows node for node, splits
+    such a cloud until its cell is a few rounding steps wide, where the octants hold the photons no more, and lists them in no leaf
+    (0 references, 457 nodes, for 17 and for 5000 photons; the parent commit gives the same).  "Exactly once" and "ends at n" cannot hold
+    there; what holds is asserted: no photon is listed twice, and the offsets end at the number of references."""
+    ph = _cloud(shape, n)
+    t = _photon_map_in_box(gi.Scene(), PM_BOX, ph)
+    child, off, idx, box = t["node_child"], t["node_off"], t["node_idx"], t["node_bbox"]
+    print(f"{shape} n={n}: {len(box)} nodes, {len(idx)} references")
+    assert np.array_equal(t["photons"], ph) and np.array_equal(box[0], PM_BOX)
+    assert off[0] == 0 and (np.diff(off) >= 0).all() and len(off) == len(box) + 1
+    inner = (child >= 0).any(axis=1)
+    assert (child[inner] >= 0).all() and (np.diff(off)[inner] == 0).all()
+    size = _subtree_sizes(child)
+    ids = np.nonzero(inner)[0]
+    assert np.array_equal(child[inner][:, 0], ids + 1)
+    assert np.array_equal(child[inner][:, 1:], child[inner][:, :-1] + size[child[inner][:, :-1]])
+    assert np.array_equal(child[inner][:, 7] + size[child[inner][:, 7]], ids + size[ids]) and size[0] == len(box)
+    leaf_of_ref = np.repeat(np.arange(len(box)), np.diff(off))
+    o, b = ph[idx, :3], box[leaf_of_ref]
+    assert ((o >= b[:, :3]) & (o < b[:, 3:])).all()
+    assert off[-1] == len(idx) and len(np.unique(idx)) == len(idx) and (len(idx) == 0 or (0 <= idx.min() and idx.max() < n))
+    if not (shape == "point" and n > K):
+        assert np.array_equal(np.sort(idx), np.arange(n)) and off[-1] == n
+
+
+@pytest.mark.parametrize("name", ["test_scene", "spheres"])
+def test_scene_tree_leaves_list_exactly_the_entities_that_touch_them(name):
+    """For every leaf and every entity: the leaf lists the entity if and only if the closed overlap of the two boxes holds and the
+    entity's own cell test (gih_entity_overlaps_box) says 1.  Children of a frozen node (a node that kept more than 3/4 of its entities
+    per child on average) are leaves, and no child pointer refers to an empty node."""
+    s = pc.load_scene(name)
+    L, t = s.L, s.tables()
+    child, off, idx, box = t["node_child"], t["node_ent_off"], t["node_ent_idx"], t["node_bbox"]
+    kind, pos = t["ent_kind"], np.ascontiguousarray(t["tri_pos"].reshape(-1, 9))
+    assert 0 in kind and (1 in kind or name != "spheres")        # triangles in both scenes, spheres in the second
+    ebox = np.zeros((len(kind), 6))
+    for e in range(len(kind)):
+        assert L.gih_entity_bbox(int(kind[e]), _p(pos[e]), _p(ebox[e])) == 0
+    inner = (child >= 0).any(axis=1)
+    listed = np.zeros((len(box), len(kind)), bool)
+    listed[np.repeat(np.arange(len(box)), np.diff(off)), idx] = True
+    assert not listed[inner].any()
+    # touch[i][e]: entity e passes both tests against the box of node i; the cell test runs only where the boxes overlap
+    touch = ((box[:, None, :3] <= ebox[None, :, 3:]) & (box[:, None, 3:] >= ebox[None, :, :3])).all(axis=2)
+    pairs = np.argwhere(touch)
+    for i, e in pairs:
+        touch[i, e] = L.gih_entity_overlaps_box(int(kind[e]), _p(pos[e]), _p(box[i])) == 1
+    print(f"{name}: {len(box)} nodes, {int((~inner).sum())} leaves, {len(kind)} entities, {len(pairs)} cell tests")
+    assert np.array_equal(listed[~inner], touch[~inner])
+    kids = child[child >= 0]
+    assert (inner[kids] | (np.diff(off)[kids] > 0)).all()
+    # what a node was handed: everything for the root, below it what the parent was handed and what passes the child's tests; a node
+    # that hands its eight children more than 3/4 of that on average is frozen
+    have = np.zeros_like(touch)
+    have[0] = True
+    for i in np.nonzero(inner)[0]:
+        c = child[i][child[i] >= 0]
+        have[c] = have[i] & touch[c]
+        if have[c].sum() / 8 > 0.75 * have[i].sum():
+            assert not inner[c].any(), i
+
+
+def test_photon_map_in_box_leaves_the_scene_tree_alone(golden):
+    s = pc.load_scene("caustics")
+    before = s.tables()
+    ph = golden("scene_caustics")["photons"][:3000]
+    box = np.r_[ph[:, :3].min(axis=0) - .5, ph[:, :3].max(axis=0) + .25]
+    assert not np.array_equal(box, before["node_bbox"][0])
+    p = _photon_map_in_box(s, box, ph)
+    after = s.tables()
+    assert all(np.array_equal(before[k], after[k]) for k in before)
+    assert np.array_equal(p["node_bbox"][0], box)
+    s.build_photon_map(ph)                                    # over the scene's root box again, not over the box left behind
+    assert np.array_equal(s.photon_tables()["node_bbox"][0], before["node_bbox"][0])
+
+
+def test_box_mesh_and_fog_grid_match_the_scn_keywords(tmp_path):
+    """gih_box_mesh and gih_fog_grid, which need no scene, give what the `box` and `heightFog` lines of a scene file give."""
+    L = gi.lib()
+    boxes = [((0.5, 1, -2), (1, 2, 3), (0.1, -0.7, 2.5)), ((-3, 0, 0), (.25, .5, 4), (0, 0, 0))]
+    fogs = [((0, 0, 0), (1, 2, 1), (1, 1, 1), .5, .25, 2), ((1, -1, 2), (2, 0, 3), (.5, .6, .7), 1.5, .75, 3)]
+    meshes, grids = [], []
+    for b in boxes:
+        out = np.zeros(108)
+        assert L.gih_box_mesh(*[_p(np.array(v, float)) for v in b], _p(out)) == 12
+        meshes.append(out.reshape(12, 3, 3))
+    for f in fogs:
+        par = np.array([*f[0], *f[1], *f[2], *f[3:]], float)
+        n = L.gih_fog_grid(_p(par), C.c_uint64(gi.DEFAULT_SEED), None, 0)
+        g = np.zeros(n)
+        assert n == (f[1][0] + 1) * (f[1][1] + 1) * (f[1][2] + 1) * f[5] ** 3 and L.gih_fog_grid(_p(par), C.c_uint64(gi.DEFAULT_SEED), _p(g), n) == n
+        grids.append(g)
+    scn = tmp_path / "parts.scn"
+    lines = ["colorTex 0 0 0", "colorTex 1 1 1", "mat 1 0 1 1 1"]
+    lines += ["box " + " ".join(repr(float(x)) for v in b for x in v) + " 0" for b in boxes]
+    lines += ["heightFog " + " ".join(repr(float(x)) for x in [*f[0], *f[1], *f[2], *f[3:]]) for f in fogs[:1]]
+    scn.write_text("\n".join(lines) + "\n")
+    t = gi.Scene.load(str(scn)).rebuild().tables()
+    assert np.array_equal(t["tri_pos"], np.concatenate(meshes))
+    assert np.array_equal(t["fog_grid"], grids[0])
+    # a second fog of a scene continues the scene's counter, so only a scene's first grid equals the stand-alone one
+    scn.write_text("\n".join(lines[:3] + ["heightFog " + " ".join(repr(float(x)) for x in [*f[0], *f[1], *f[2], *f[3:]]) for f in fogs[1:]]) + "\n")
+    assert np.array_equal(gi.Scene.load(str(scn)).rebuild().tables()["fog_grid"], grids[1])
+
+
+def test_host_builders_under_sanitizers(tmp_path):
+    """tests/host_builders/host_builders.cpp, a program of its own over gi_host.cpp built with the address and undefined-behaviour
+    sanitizers: every scene file, both tree builders, the descriptors, the single-object entries and the loaders' error paths."""
+    exe = str(tmp_path / "host_builders")
+    # the loaders leave fscanf's result unchecked, as the reference's do: -Wno-unused-result
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-g", "-Wall", "-Werror", "-Wno-unused-result", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                    "-fno-omit-frame-pointer", os.path.join(pc.ROOT, "tests", "host_builders", "host_builders.cpp"), os.path.join(CSRC, "gi_host.cpp"), "-lz", "-o", exe], check=True)
+    work = tmp_path / "work"
+    work.mkdir()
+    r = subprocess.run([exe, pc.ROOT, str(work)] + [pc.SCN[k] for k in sorted(pc.SCN)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("host_builders ok"), r.stdout + r.stderr
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr
 
 
 def test_settings_defaults_and_scene_overrides():
