@@ -87,7 +87,7 @@ ABI_SYMBOLS = [
     "gi_denoise_default_params", "gi_denoise_device", "gi_denoise_host", "gi_last_denoise_ms",
     "gi_upsample_default_params", "gi_upsample_device", "gi_upsample_host", "gi_last_upsample_ms",
     "gi_occlusion_default_params", "gi_render_occlusion_device", "gi_render_occlusion_host", "gi_last_occlusion_ms", "gi_set_render_mode", "gi_set_wide_nodes", "gi_set_content_culling", "gi_set_entity_boxes", "gi_set_pool_slots", "gi_last_render_ms", "gi_last_stage_ms", "gi_last_kernel_ms", "gi_set_counters", "gi_get_counters", "gi_get_stream_counters", "gi_trace", "gi_visible",
-    "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
+    "gi_gather", "gi_radiance", "gi_emit_photons", "gi_halton_sample", "gi_halton_index", "gi_debug_leaf_order", "gi_debug_sort_pairs", "gi_debug_find_leaves", "gi_debug_gather_pass", "gi_debug_walk", "gi_kat", "gi_visible_rays", "gi_build_photon_map", "gi_trace_photons", "gi_debug_photon_tables", "gi_clear_photons", "gi_group_clear_photons",
     "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
     "gi_lens_default", "gi_set_lens", "gi_get_lens", "gi_lens_vertices", "gi_group_set_lens", "gi_debug_primary_rays", "gi_focus_distance",
@@ -158,6 +158,8 @@ def lib():
     L.gi_debug_sort_pairs.argtypes = [vp, C.c_int32, _up, _up, C.c_int32, C.c_int32, _up, _up]
     L.gi_debug_find_leaves.argtypes = [vp, C.c_int32, _dp, _ip, _ip]
     L.gi_debug_gather_pass.argtypes = [vp, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, _up, _up, C.POINTER(C.c_int64)]
+    L.gi_debug_walk.argtypes = [vp, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _ip, _ip, _dp]
+    L.gi_visible_rays.argtypes = [vp, C.c_int32, _dp, _dp, _ip]
     L.gi_kat.argtypes = [vp, C.c_int32, C.c_int32, _dp, C.c_int32, _dp]
     L.gi_clear_photons.argtypes = [vp]
     L.gi_group_clear_photons.argtypes = [vp]
@@ -1114,6 +1116,30 @@ class RayTracer:
         vis = np.zeros(len(q), np.int32)
         self._check(self.L.gi_visible(self.h, len(q), _p(q), _p(vis, _ip)), "visible")
         return vis
+
+    def visible_rays(self, rays, mt):
+        """gi_visible_rays: RayTracer::visible with the reference's own arguments, rays [n][6] = origin, unit direction, mt [n] = squared length."""
+        rays = _f64(rays).reshape(-1, 6); mt = _f64(mt).reshape(-1)
+        assert len(mt) == len(rays)
+        vis = np.zeros(len(rays), np.int32)
+        self._check(self.L.gi_visible_rays(self.h, len(rays), _p(rays), _p(mt), _p(vis, _ip)), "visible_rays")
+        return vis
+
+    def debug_walk(self, rays, mt=None, form=0, lds=True):
+        """gi_debug_walk: rays [n][6] through the walk forms the passes run (form 0 a ray per lane, 1 per wave, 2 per group of 16 lanes; lds: the
+        records and content boxes staged in LDS or read from global memory).  mt None: closest hit, returns (hit, ent, res) as trace();
+        mt [n]: any hit below that squared length, returns vis as visible_rays()."""
+        rays = _f64(rays).reshape(-1, 6)
+        n = len(rays)
+        hit = np.zeros(n, np.int32)
+        if mt is not None:
+            mt = _f64(mt).reshape(-1)
+            assert len(mt) == n
+            self._check(self.L.gi_debug_walk(self.h, n, _p(rays), _p(mt), int(form), 1 if lds else 0, _p(hit, _ip), None, None), "debug_walk")
+            return hit
+        ent = np.zeros(n, np.int32); res = np.zeros((n, 8))
+        self._check(self.L.gi_debug_walk(self.h, n, _p(rays), None, int(form), 1 if lds else 0, _p(hit, _ip), _p(ent, _ip), _p(res)), "debug_walk")
+        return hit, ent, res
 
     def samplePhotons(self, q):
         q = _f64(q).reshape(-1, 6)

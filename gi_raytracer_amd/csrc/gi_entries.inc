@@ -256,6 +256,34 @@ int gi_debug_gather_pass(gi_ctx* c, int32_t n, const double* q6, int32_t kernel,
     return rc;
 }
 
+int gi_debug_walk(gi_ctx* c, int32_t n, const double* rays, const double* mt, int32_t form, int32_t lds, int32_t* hit_or_vis, int32_t* ent, double* res8)
+{
+    if (!c || n < 0 || form < 0 || form > 2 || lds < 0 || lds > 1 || (n && (!rays || !hit_or_vis || (!mt && (!ent || !res8))))) return GI_E_INVALID;
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "debug_walk: no scene uploaded");
+    if (!c->S.wnodes) return fail(c, GI_E_STATE, "debug_walk: the scene has no wide records (or gi_set_wide_nodes(0))");
+    if (n == 0) return GI_OK;
+    // k_debug_walk<FEAT, FORM, ANY>: the level stage_trace picks (textures -> 7, else 3) x the three forms x closest hit, any hit
+    typedef decltype(&k_debug_walk<3, 0, false>) WalkK;
+    static const WalkK kWalk[2][3][2] = {
+        {{k_debug_walk<3, 0, false>, k_debug_walk<3, 0, true>}, {k_debug_walk<3, 1, false>, k_debug_walk<3, 1, true>}, {k_debug_walk<3, 2, false>, k_debug_walk<3, 2, true>}},
+        {{k_debug_walk<7, 0, false>, k_debug_walk<7, 0, true>}, {k_debug_walk<7, 1, false>, k_debug_walk<7, 1, true>}, {k_debug_walk<7, 2, false>, k_debug_walk<7, 2, true>}}};
+    const WalkK fn = kWalk[c->S.n_tex > 0 ? 1 : 0][form][mt ? 1 : 0];
+    const size_t lds_bytes = form == 0 ? (size_t)GI_LDS_WIDE_BOXES_BYTES : (size_t)GI_LDS_BOXES_BYTES(GI_FINISH_COOP_RECORDS);
+    const size_t N = (size_t)n, lanes = N * (form == 0 ? 1 : (form == 1 ? 64 : 16));
+    const unsigned blocks = (unsigned)std::min<size_t>((lanes + GI_DEBUG_WALK_BLOCK - 1) / GI_DEBUG_WALK_BLOCK, 2048);   // the kernel strides over the rest
+    Entry e(c, "debug_walk");
+    const double* d_r = e.in(rays, N * 6);
+    const double* d_m = mt ? e.in(mt, N) : nullptr;
+    int32_t* d_h = e.out(hit_or_vis, N);
+    int32_t* d_e = mt ? nullptr : e.out(ent, N);
+    double* d_o = mt ? nullptr : e.out(res8, N * 8);
+    return e.run([&]() -> int {
+        HIP_TRY(c, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));   // more than 64 KB has to be asked for
+        hipLaunchKernelGGL(fn, dim3(blocks), dim3(GI_DEBUG_WALK_BLOCK), lds_bytes, c->stream, c->S, n, d_r, d_m, lds, d_h, d_e, d_o);
+        return GI_OK;
+    });
+}
+
 int gi_debug_leaf_order(gi_ctx* c, int32_t n, const double* rays, int32_t cap, int32_t* leaf_out, int32_t* n_out)
 {
     if (!c || n < 0 || cap < 1 || (n && (!rays || !leaf_out || !n_out))) return GI_E_INVALID;

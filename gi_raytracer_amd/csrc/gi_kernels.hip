@@ -1611,6 +1611,46 @@ __global__ __launch_bounds__(GI_BLOCK) void k_visible_rays(Scene S, int n, const
     vis[i] = visible(S, sr, mt[i], rng, 0, nullptr) ? 1 : 0;
 }
 
+// gi_debug_walk: caller rays through the walk forms the passes run, with k_trace's / k_visible_rays' keys (rng_make(0, i), P_TRACE_ALPHA, light 0) and
+// k_trace's output.  FORM 0: a ray per lane over the records and content boxes k_st_trace (closest hit) / a shadow kernel without lights to end at
+// (any hit) stages; FORM 1, 2: a ray per wave / per group of 16 lanes over what k_st_finish stages (ray i = group i, every lane of the group holds
+// it, the first writes).  lds = 0: the same source with nothing staged (n_l = n_lc = 0), every record and box from global memory.
+#define GI_DEBUG_WALK_BLOCK 256
+template <int FEAT, int FORM, bool ANY>
+__global__ __launch_bounds__(GI_DEBUG_WALK_BLOCK) void k_debug_walk(Scene S, int n, const double* rays, const double* mt, int lds, int32_t* hit, int32_t* ent, double* res)
+{
+    constexpr uint32_t G = FORM == 1 ? 64u : (FORM == 2 ? 16u : 1u);
+    typedef typename std::conditional<FORM == 0, LdsWide, LdsWideCoop<FORM == 2 ? 16 : 64>>::type Src;
+    const LdsWide L = FORM == 0 ? stage_wide_in_lds(S, true, GI_LDS_WNODES_BIG, ANY ? 0 : 1) : stage_wide_in_lds(S, true, GI_FINISH_COOP_RECORDS);   // ends with a barrier
+    Src N;
+    N.g = L.g; N.cboxes = L.cboxes; N.cuse = L.cuse; N.box_off = L.box_off; N.use_off = L.use_off;
+    N.n_l = lds ? L.n_l : 0; N.n_lc = lds ? L.n_lc : 0;
+    const uint32_t n_groups = gridDim.x * blockDim.x / G;
+    for (uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / G; i < (uint32_t)n; i += n_groups) {   // uniform over a group: its lanes stay together
+        const double* r = rays + (size_t)i * 6;
+        const Ray ray = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+        const Rng rng = rng_make(0, i);
+        const bool writes = (threadIdx.x & (G - 1u)) == 0u;
+        if constexpr (ANY) {
+            const bool vis = visible_nodes<FEAT>(S, N, ray, mt[i], rng, 0, nullptr);
+            if (writes) hit[i] = vis ? 1 : 0;
+        } else {
+            HitRec h;
+            h.tu = 0; h.tv = 0;
+            const bool ok = trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr);
+            if (!writes) continue;
+            hit[i] = ok ? 1 : 0;
+            ent[i] = ok ? h.tri : -1;
+            double* o = res + (size_t)i * 8;
+            if (ok) {
+                const V3 nn = shading_normal(S, h);
+                o[0] = h.pos.x; o[1] = h.pos.y; o[2] = h.pos.z; o[3] = nn.x; o[4] = nn.y; o[5] = nn.z; o[6] = h.u; o[7] = h.v;
+            } else
+                for (int k = 0; k < 8; k++) o[k] = 0;
+        }
+    }
+}
+
 __global__ __launch_bounds__(GI_BLOCK) void k_gather(Scene S, int n, const double* q, double* res3, int32_t* n_cand)
 {
     __shared__ float heap[GI_GATHER_K * GI_BLOCK];

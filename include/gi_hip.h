@@ -381,6 +381,13 @@ int gi_debug_find_leaves(gi_ctx*, int32_t n, const double* pos, int32_t* fast_ou
  * res3 [n][3] = the caustic term of query i (RayTracer::samplePhotons(pos, dir, 32)); keys_out / order_out [n] (optional) = the keys and slots
  * in the order the kernel read them; counters2 (optional) = gather queries and candidates a counting instance counted (0 otherwise).    */
 int gi_debug_gather_pass(gi_ctx*, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2);
+/* gi_debug_walk: caller rays [n][6] (origin, unit direction) through the octree walk in the forms the passes run it, with gi_trace's /
+ * gi_visible_rays' keys (stream = ray index, seed 0, light 0): the same answers, ray by ray.  mt NULL: closest hit, hit_or_vis / ent / res8 as gi_trace
+ * writes them; mt [n] (squared length): any hit below it, hit_or_vis = visible, ent / res8 are not touched.  form: 0 a ray per lane (the loop of the
+ * trace and shadow kernels), 1 a ray per wave, 2 a ray per group of 16 lanes (the finisher's last stages: ray i = group i).  lds: 1 the wide records
+ * and content boxes staged in LDS as those kernels stage them (form 0, closest hit: the closest-hit walk's boxes; else the whole entities'), 0 the
+ * same tables read from global memory.  GI_E_STATE: the scene has no wide records.                                                          */
+int gi_debug_walk(gi_ctx*, int32_t n, const double* rays, const double* mt, int32_t form, int32_t lds, int32_t* hit_or_vis, int32_t* ent, double* res8);
 int gi_kat(gi_ctx*, int32_t what, int32_t n, const double* in, int32_t in_stride, double* out3);
 
 /* Progressive render sessions -- an ADDITION: the reference renders a frame in one piece (its GUI repaints rows as they finish).  A session keeps

@@ -41,6 +41,9 @@ def lib():
         L.emul_rng.restype = C.c_double
         L.emul_set_wide.argtypes = [vp, C.c_int]
         L.emul_set_cull.argtypes = [vp, C.c_int]
+        L.emul_set_entity_boxes.argtypes = [vp, C.c_int]
+        L.emul_visible_rays.argtypes = [vp, C.c_int, _dp, _dp, _ip]
+        L.emul_debug_walk.argtypes = [vp, C.c_int, _dp, _dp, C.c_int, C.c_int, _ip, _ip, _dp]
         L.emul_leaf_order.argtypes = [vp, C.c_int, _dp, C.c_int, _ip, _ip]
         L.emul_kat.argtypes = [C.c_int, C.c_int, _dp, C.c_int, _dp]
         L.emul_pool_plan.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_int64)]
@@ -123,6 +126,24 @@ class EmulRayTracer(gi.RayTracer):
 
     def set_content_culling(self, on):
         return bool(self.E.emul_set_cull(self.h, 1 if on else 0))
+
+    def set_entity_boxes(self, on):
+        return bool(self.E.emul_set_entity_boxes(self.h, 1 if on else 0))
+
+    def visible_rays(self, rays, mt):
+        rays = gi._f64(rays).reshape(-1, 6); mt = gi._f64(mt).reshape(-1); vis = np.zeros(len(rays), np.int32)
+        assert len(mt) == len(rays)
+        self.E.emul_visible_rays(self.h, len(rays), gi._p(rays), gi._p(mt), gi._p(vis, _ip))
+        return vis
+
+    def debug_walk(self, rays, mt=None, form=0, lds=False):
+        """gi_debug_walk's per-lane form over plain memory (form 0, lds False): the only one a CPU has."""
+        rays = gi._f64(rays).reshape(-1, 6); n = len(rays)
+        hit = np.zeros(n, np.int32); ent = np.zeros(n, np.int32); res = np.zeros((n, 8))
+        mt = None if mt is None else gi._f64(mt).reshape(-1)
+        if self.E.emul_debug_walk(self.h, n, gi._p(rays), gi._p(mt), int(form), 1 if lds else 0, gi._p(hit, _ip), gi._p(ent, _ip), gi._p(res)) != 0:
+            raise gi.GiError(f"debug_walk: the CPU build has no form {form} / lds {lds}, or the scene no wide records")
+        return hit if mt is not None else (hit, ent, res)
 
     def trace(self, rays):
         rays = gi._f64(rays).reshape(-1, 6); n = len(rays)

@@ -18,7 +18,7 @@ struct Emul {
     std::vector<uint16_t> htable;
     Scene S{};
     std::string err;
-    bool wide = true, cull = true;
+    bool wide = true, cull = true, entity_boxes = true;
     void bind()
     {
         S.tnodes = hs.tnodes.data(); S.leaf_refs = hs.refs.data(); S.leaf_tris = hs.leaf_tris.data(); S.tris = hs.tris.data(); S.shade = hs.shade.data();
@@ -44,7 +44,7 @@ struct Emul {
         T.pn_planes_ok = hp.planes_ok;
         SceneSwitches sw;
         sw.wide = wide; sw.cull = cull;
-        sw.entity_boxes = !off("GI_ENTITY_BOXES"); sw.clip_boxes = !off("GI_CLIP_BOXES"); sw.walk_cut = !off("GI_WALK_CUT");
+        sw.entity_boxes = entity_boxes && !off("GI_ENTITY_BOXES"); sw.clip_boxes = !off("GI_CLIP_BOXES"); sw.walk_cut = !off("GI_WALK_CUT");
         apply_scene_switches(S, T, sw);
     }
 };
@@ -55,6 +55,7 @@ Emul* emul_create() { Emul* e = new Emul(); build_halton_tables(e->hdims, e->hta
 void emul_destroy(Emul* e) { delete e; }
 int emul_set_wide(Emul* e, int on) { e->wide = on != 0; e->bind(); return (e->S.wnodes != nullptr ? 1 : 0) | (e->S.pn_planes ? 2 : 0); }
 int emul_set_cull(Emul* e, int on) { e->cull = on != 0; e->bind(); return e->S.cboxes != nullptr ? 1 : 0; }
+int emul_set_entity_boxes(Emul* e, int on) { e->entity_boxes = on != 0; e->bind(); return e->S.leaf_boxes != nullptr ? 1 : 0; }
 // which table every Scene field that follows the switches points at (tests/test_scene_views.py): 0 none, 1 wnodes, 2 cboxes, 3 cuse, 4 leaf_boxes,
 // 5 trace_boxes, 6 tcboxes, 7 tcuse, -1 something else; ids10 = wnodes, cboxes, leaf_boxes, trace_boxes, tcboxes, tcuse, shadow_boxes, scboxes, scuse, pn_planes (as it is)
 void emul_scene_views(Emul* e, int32_t* ids10, double* cut_margin)
@@ -132,6 +133,43 @@ int emul_visible(Emul* e, int n, const double* q, int32_t* vis)
         Ray sr = make_ray(o, ld);
         Rng rng = rng_make(0, (uint32_t)i);
         vis[i] = visible(e->S, sr, len2(ld), rng, 0, nullptr);
+    }
+    return 0;
+}
+// gi_visible_rays: the reference's own arguments, origin + unit direction and the squared length
+int emul_visible_rays(Emul* e, int n, const double* rays, const double* mt, int32_t* vis)
+{
+    for (int i = 0; i < n; i++) {
+        const double* r = rays + (size_t)i * 6;
+        Ray sr = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+        Rng rng = rng_make(0, (uint32_t)i);
+        vis[i] = visible(e->S, sr, mt[i], rng, 0, nullptr);
+    }
+    return 0;
+}
+// gi_debug_walk, the form a CPU has: a ray per lane, records from plain memory (form 0, lds 0), called the way k_debug_walk calls the walks -- the
+// level stage_trace picks, the closest-hit walk's content boxes for a closest hit and the whole entities' for any hit.  -1: another form, or no wide records
+int emul_debug_walk(Emul* e, int n, const double* rays, const double* mt, int form, int lds, int32_t* hit, int32_t* ent, double* res)
+{
+    if (form != 0 || lds != 0 || !e->S.wnodes) return -1;
+    const Scene& S = e->S;
+    GlobalWide W;
+    W.g = S.wnodes; W.cboxes = mt ? S.cboxes : S.tcboxes; W.cuse = mt ? S.cuse : S.tcuse;
+    for (int i = 0; i < n; i++) {
+        const double* r = rays + (size_t)i * 6;
+        const Ray ray = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+        const Rng rng = rng_make(0, (uint32_t)i);
+        if (mt) {
+            hit[i] = S.n_tex > 0 ? visible_nodes<7>(S, W, ray, mt[i], rng, 0, nullptr) : visible_nodes<3>(S, W, ray, mt[i], rng, 0, nullptr);
+            continue;
+        }
+        HitRec h;
+        h.tu = 0; h.tv = 0;
+        const bool ok = S.n_tex > 0 ? trace_nodes<7>(S, W, ray, rng, P_TRACE_ALPHA, h, nullptr) : trace_nodes<3>(S, W, ray, rng, P_TRACE_ALPHA, h, nullptr);
+        hit[i] = ok; ent[i] = ok ? h.tri : -1;
+        double* o = res + (size_t)i * 8;
+        if (ok) { V3 nn = shading_normal(S, h); o[0] = h.pos.x; o[1] = h.pos.y; o[2] = h.pos.z; o[3] = nn.x; o[4] = nn.y; o[5] = nn.z; o[6] = h.u; o[7] = h.v; }
+        else for (int k = 0; k < 8; k++) o[k] = 0;
     }
     return 0;
 }

@@ -752,3 +752,570 @@ def check_photon_descent(rt, scene, photons=20000):
     rt.set_wide_nodes(True)
     assert (na > 0).mean() > 0.1 and (na == 0).any()
     assert np.array_equal(na, nbc) and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+# ------------------------------------------------------------------------------------------------ rays aimed at the geometry
+GI_EPSILON = 1e-5                    # gi_device.h / include/entities.h: tri_hit's |det| threshold
+EDGE_RAYS_PER_CLASS = 1600           # (at most 4 000 per class and scene; six classes stay below 24 000 rays per launch)
+
+
+def _unit(v):
+    v = np.asarray(v, float)
+    n = np.sqrt((v * v).sum(-1, keepdims=True))
+    return v / np.where(n == 0, 1.0, n)
+
+
+def _hair(rs, ext, n):
+    """ext * 10**U(-15, -9) with both signs (the range test_quick_descent_of_the_gather_keys_finds_the_same_leaf uses)."""
+    return ext * 10.0 ** rs.uniform(-15, -9, n) * rs.choice([-1.0, 1.0], n)
+
+
+def _edge_origins(rs, lo, hi, n):
+    """A third inside the root box, a third on its faces, a third up to 0.2 extents outside it."""
+    o = lo + (hi - lo) * rs.rand(n, 3)
+    k = np.arange(n) % 3
+    ax, side = rs.randint(3, size=n), rs.randint(2, size=n)
+    face = np.where(side == 0, lo[ax], hi[ax])
+    out = face + (hi - lo)[ax] * rs.uniform(0, 0.2, n) * np.where(side == 0, -1.0, 1.0)
+    rows = np.arange(n)
+    o[rows[k == 1], ax[k == 1]] = face[k == 1]
+    o[rows[k == 2], ax[k == 2]] = out[k == 2]
+    return o
+
+
+def _aim(rs, o, tgt, lo, hi, axis_share=0.2, back_share=0.6):
+    """Rays from o to tgt; a share of them reaches the target along an exact axis direction instead (the other two components 0.0 or -0.0).
+    back_share of the rays whose origin lies outside the root box run the other way, from the target out to that origin: the aimed-at point is
+    then the ray's own origin (t = 0 to rounding), and in a closed room these are the rays that can leave the scene at all."""
+    n = len(tgt)
+    o = o.copy()
+    d = _unit(tgt - o)
+    back = ((o < lo) | (o > hi)).any(1) & (rs.rand(n) < back_share)
+    d[back] = -d[back]
+    o[back] = tgt[back]
+    ax = rs.rand(n) < axis_share
+    for j in np.nonzero(ax)[0]:
+        a, s = rs.randint(3), rs.choice([-1.0, 1.0])
+        dist = (hi - lo)[a] * rs.uniform(0.05, 1.2)
+        o[j] = tgt[j]
+        o[j, a] = tgt[j, a] - s * dist
+        d[j] = rs.choice([0.0, -0.0], 3)
+        d[j, a] = s
+    return np.concatenate([o, d], 1)
+
+
+def _root_box_entered(rays, lo, hi):
+    """BoundingBox::intersect(ray, 0, inf) of the root box as the walks ask it (include/bbox.h:47-73; a NaN from 0 * inf is ignored, and leaving at
+    the first tmax <= tmin equals testing the last): a ray for which this is False is never walked, whatever lies on its line."""
+    with np.errstate(all="ignore"):
+        inv = 1.0 / rays[:, 3:]
+        t0, t1 = (lo - rays[:, :3]) * inv, (hi - rays[:, :3]) * inv
+    t0, t1 = np.where(inv < 0, t1, t0), np.where(inv < 0, t0, t1)
+    tmin, tmax = np.zeros(len(rays)), np.full(len(rays), np.inf)
+    ok = np.ones(len(rays), bool)
+    for a in range(3):
+        tmin = np.where(t0[:, a] > tmin, t0[:, a], tmin)
+        tmax = np.where(t1[:, a] < tmax, t1[:, a], tmax)
+        ok &= ~(tmax <= tmin)
+    return ok
+
+
+def _with_scene_behind(rs, rays, lo, hi, ext, share=0.12):
+    """The same lines with the origin slid forward to where the ray leaves the root box -- on that face to rounding, a hair before or behind it, or up to
+    0.2 extents outside: everything aimed at lies behind the origin (t < 0), and whether a walk begins at all hangs on the root box's own slab test.  In a
+    closed room these are the rays that leave the scene."""
+    rays = rays.copy()
+    rows = np.nonzero((rs.rand(len(rays)) < share) & _root_box_entered(rays, lo, hi))[0]
+    o, d = rays[rows, :3], rays[rows, 3:]
+    with np.errstate(all="ignore"):
+        t1 = np.where(d == 0, np.inf, np.maximum((lo - o) / d, (hi - o) / d))
+    s = t1.min(1)
+    k = np.arange(len(rows)) % 3
+    s = s + np.where(k == 0, 0.0, np.where(k == 1, _hair(rs, ext, len(rows)), ext * rs.uniform(0, 0.2, len(rows))))
+    rays[rows, :3] = o + d * s[:, None]
+    return rays
+
+
+def _leaf_entities(t):
+    """(leaf node, entity) pairs of the scene's octree, grouped per leaf that holds any."""
+    off, idx = t["node_ent_off"], t["node_ent_idx"]
+    return [(k, idx[off[k]:off[k + 1]]) for k in range(len(off) - 1) if off[k + 1] > off[k]]
+
+
+def _tri_boundary_targets(rs, t, n, ext):
+    tri, kind = t["tri_pos"], t["ent_kind"]
+    leaves = [(k, e[kind[e] == 0]) for k, e in _leaf_entities(t)]
+    leaves = [(k, e) for k, e in leaves if len(e)]
+    out = []
+    for j in range(n):
+        _, ents = leaves[j % len(leaves)]                      # triangles from every leaf that holds any, in turn
+        p0, p1, p2 = tri[ents[rs.randint(len(ents))]]
+        e1, e2 = p1 - p0, p2 - p0
+        w = rs.uniform(0.03, 0.97)
+        what = j // len(leaves) % 6 if n >= 6 * len(leaves) else rs.randint(6)
+        u, v = [(0, 0), (1, 0), (0, 1), (w, 0), (0, w), (w, 1 - w)][what]
+        p = p0 + u * e1 + v * e2
+        move = rs.randint(3)                                   # on the boundary; a hair inwards or outwards in the triangle's plane
+        if move:
+            c = (p0 + p1 + p2) / 3.0
+            if what < 3:
+                inward = _unit(c - p)
+            else:
+                a, b = [(p0, p1), (p0, p2), (p1, p2)][what - 3]
+                along = _unit(b - a)
+                inward = c - a
+                inward = _unit(inward - along * (inward * along).sum())
+            p = p + inward * _hair(rs, ext, 1)[0]
+        out.append(p)
+    return np.array(out)
+
+
+def _cut_triangle(p, a, c):
+    """The two points where the plane x_a = c cuts the triangle p [3][3] (None when it does not cross it)."""
+    s = p[:, a] - c
+    pts = []
+    for i, j in ((0, 1), (1, 2), (2, 0)):
+        if (s[i] < 0) != (s[j] < 0):
+            pts.append(p[i] + (p[j] - p[i]) * (s[i] / (s[i] - s[j])))
+    return pts if len(pts) == 2 else None
+
+
+def _leaf_plane_targets(rs, t, n, ext):
+    """Per target: point, the face's axis (the normal), -1 or the second axis for a target on a leaf edge.  None when no entity crosses a face of
+    its leaf (a tree of one leaf)."""
+    tri, kind, bb = t["tri_pos"], t["ent_kind"], t["node_bbox"]
+    pairs = [(k, e) for k, ents in _leaf_entities(t) for e in ents]
+    order = rs.permutation(len(pairs))
+    plane, edge = [], []
+    want_edge = n // 4
+    for rnd in range(8):
+        for j in order:
+            k, e = pairs[j]
+            a = rs.randint(3)
+            c = bb[k, a + 3 * rs.randint(2)]
+            lo, hi = bb[k, :3], bb[k, 3:]
+            if kind[e] == 0:
+                cut = _cut_triangle(tri[e], a, c)
+                if cut is None:
+                    continue
+                P, Q = cut
+                if len(edge) < want_edge:                       # on a leaf edge: where the cut crosses a plane of a second axis
+                    b = (a + 1 + rs.randint(2)) % 3
+                    for c2 in (lo[b], hi[b]):
+                        sP, sQ = P[b] - c2, Q[b] - c2
+                        if (sP < 0) != (sQ < 0):
+                            x = P + (Q - P) * (sP / (sP - sQ))
+                            x[a], x[b] = c, c2
+                            edge.append((x, a, b))
+                            break
+                for _ in range(6):                                  # a point of the cut, on the leaf's own face when the cut reaches it
+                    x = P + (Q - P) * rs.rand()
+                    if ((x >= lo - 1e-9) & (x <= hi + 1e-9)).all():
+                        break
+                x[a] = c
+            else:
+                ctr, rad = tri[e][0], tri[e][1][0]
+                h = c - ctr[a]
+                if abs(h) >= rad:
+                    continue
+                phi, r = rs.uniform(0, 2 * np.pi), np.sqrt(rad * rad - h * h)
+                x = ctr.copy()
+                x[a] = c
+                x[(a + 1) % 3] += r * np.cos(phi)
+                x[(a + 2) % 3] += r * np.sin(phi)
+            plane.append((x, a, -1))
+            if len(plane) >= n - want_edge and len(edge) >= want_edge:
+                break
+        if not plane or (len(plane) >= n - want_edge and len(edge) >= want_edge):
+            break
+    if not plane:
+        return None
+    both = (plane[:n - len(edge[:want_edge])] + edge[:want_edge])[:n]
+    return np.array([b[0] for b in both]), np.array([b[1] for b in both]), np.array([b[2] for b in both])
+
+
+def _leaf_plane_rays(rs, t, n, lo, hi, ext):
+    got = _leaf_plane_targets(rs, t, n, ext)
+    if got is None:
+        return None
+    tgt, ax, _ = got
+    m = len(tgt)
+    rows = np.arange(m)
+    plane = tgt[rows, ax].copy()
+    k = rs.randint(3, size=m)                                   # on the plane, a hair to either side along its normal
+    tgt[rows, ax] += np.where(k == 0, 0.0, _hair(rs, ext, m))
+    o = _edge_origins(rs, lo, hi, m)
+    side = np.where(rs.rand(m) < 0.5, -1.0, 1.0)                # from both sides of the plane
+    o[rows, ax] = plane + side * np.maximum(np.abs(o[rows, ax] - plane), 1e-3 * ext)
+    rays = _aim(rs, o, tgt, lo, hi, axis_share=0.0)
+    normal = rs.rand(m) < 0.25                                  # along the plane's normal
+    for j in np.nonzero(normal)[0]:
+        a = ax[j]
+        rays[j, :3] = tgt[j]
+        rays[j, a] = o[j, a]
+        rays[j, 3:] = rs.choice([0.0, -0.0], 3)
+        rays[j, 3 + a] = 1.0 if o[j, a] < plane[j] else -1.0
+    return rays
+
+
+def _in_plane_rays(rs, t, n, lo, hi, ext):
+    tri, kind = t["tri_pos"], t["ent_kind"]
+    tris = np.nonzero(kind == 0)[0]
+    rays = []
+    for j in range(n):
+        p0, p1, p2 = tri[tris[rs.randint(len(tris))]]
+        e1, e2 = p1 - p0, p2 - p0
+        N = np.cross(e1, e2)
+        if not (N * N).sum() > 0:
+            continue
+        nrm = _unit(N)
+        u = rs.uniform(0.05, 0.9); v = rs.uniform(0.02, 0.95 - u)
+        tgt = p0 + u * e1 + v * e2
+        a, b = rs.uniform(-1.5, 2.5, 2)
+        o = p0 + a * e1 + b * e2
+        d0 = _unit(tgt - o)
+        if j % 3 == 0:                                          # origin and direction in the triangle's plane: det == 0 to rounding
+            rays.append(np.concatenate([o, d0]))
+            continue
+        # tilted out of the plane so that |det| = |d . (e1 x e2)| lands at 1e-3 .. 1e3 times GI_EPSILON, through a point inside the triangle
+        det = GI_EPSILON * 10.0 ** rs.uniform(-3, 3)
+        s = min(det / np.sqrt((N * N).sum()), 0.9)
+        d = _unit(d0 * np.sqrt(1 - s * s) + nrm * s * rs.choice([-1.0, 1.0]))
+        rays.append(np.concatenate([tgt - d * ext * rs.uniform(0.02, 0.5), d]))
+    return np.array(rays)
+
+
+def _sphere_rays(rs, t, n, lo, hi, ext):
+    tri, kind = t["tri_pos"], t["ent_kind"]
+    sph = np.nonzero(kind == 1)[0]
+    if not len(sph):
+        return None
+    org = _edge_origins(rs, lo, hi, n)
+    rays = []
+    for j in range(n):
+        e = sph[rs.randint(len(sph))]
+        c, rad = tri[e][0], tri[e][1][0]
+        o = org[j]
+        rnd = _unit(rs.randn(3))
+        what = j % 8
+        if what in (0, 1):                                      # tangent (r of ent_hit zero) and a hair either side
+            oc = c - o
+            L = np.sqrt((oc * oc).sum())
+            if L <= rad * 1.001:
+                o = c + rnd * rad * rs.uniform(1.5, 4.0); oc = c - o; L = np.sqrt((oc * oc).sum())
+            w = _unit(np.cross(oc, rs.randn(3)))
+            T = c + rad * (-(rad / L) * _unit(oc) + np.sqrt(1 - (rad / L) ** 2) * w)      # the tangent point seen from o
+            if what == 1:
+                T = T + _unit(T - c) * _hair(rs, ext, 1)[0]
+            rays.append(np.concatenate([o, _unit(T - o)]))
+        elif what == 2:                                         # origin on the surface, pointing in / pointing out
+            o = c + rad * rnd
+            d = _unit(rs.randn(3))
+            rays.append(np.concatenate([o, d]))
+        elif what == 3:                                         # origin inside, or at the centre
+            o = c + rad * rnd * (0.0 if j % 16 == 3 else rs.uniform(0, 1))
+            rays.append(np.concatenate([o, _unit(rs.randn(3))]))
+        elif what == 4:                                         # the sphere entirely behind the origin
+            if np.sqrt(((o - c) ** 2).sum()) <= rad * 1.001:
+                o = c + rnd * rad * rs.uniform(1.01, 3.0)
+            rays.append(np.concatenate([o, _unit(_unit(o - c) + 0.8 * rs.randn(3) * rs.rand())]))
+        elif what == 5:                                         # through both poles (ent_uv: asin of the y component)
+            if j % 16 == 5:
+                s = rs.choice([-1.0, 1.0])
+                rays.append(np.array([c[0], c[1] + s * rad * rs.uniform(1.1, 3.0), c[2], rs.choice([0.0, -0.0]), -s, rs.choice([0.0, -0.0])]))
+            else:
+                rays.append(np.concatenate([o, _unit(c + np.array([0, rad, 0]) * rs.choice([-1.0, 1.0]) - o)]))
+        elif what == 6:                                         # the atan2 seam: hit points with z = centre's z on the +x side
+            phi = rs.uniform(-0.5 * np.pi, 0.5 * np.pi)
+            T = c + rad * np.array([np.cos(phi), np.sin(phi), 0.0])
+            rays.append(np.concatenate([o, _unit(T - o)]))
+        else:                                                   # a plain ray at the sphere
+            rays.append(np.concatenate([o, _unit(c + rad * rnd * rs.rand() - o)]))
+    return np.array(rays)
+
+
+def segments_as_rays(q):
+    """Segments q [n][6] = origin, target as gi_visible_rays' arguments, formed the way k_visible / make_ray form them (IEEE +, *, /, sqrt in the
+    same order: the same bits): rays [n][6] = origin, unit direction; mt [n] = squared length.  A segment of length zero has no direction: +x."""
+    q = np.asarray(q, float)
+    ld = q[:, 3:] - q[:, :3]
+    mt = ld[:, 0] * ld[:, 0] + ld[:, 1] * ld[:, 1] + ld[:, 2] * ld[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = ld * (1.0 / np.sqrt(mt))[:, None]
+    d[mt == 0] = (1.0, 0.0, 0.0)
+    return np.concatenate([q[:, :3], d], 1), mt
+
+
+def entity_edge_rays(scene, seed=1, n=EDGE_RAYS_PER_CLASS):
+    """Rays aimed at the geometry instead of at random (adversarial_rays stresses the box arithmetic; these the entity tests and the places where
+    the walks' short cuts are tight): named classes, each [m][6] = origin, unit direction (m <= n); "shadow_ends" is [m][6] = origin, target
+    (segments_as_rays gives the other form).  Built from scene.tables(); from_hits and shadow_ends start from the ORACLE's hit points.
+      tri_boundary  vertices, points on the edges, and the same a hair inwards / outwards in the triangle's plane; triangles of every leaf in turn
+      leaf_plane    a point of an entity on a face plane of a leaf that refers to it, and a hair to either side; from both sides, a share along
+                    the plane's normal, a share with the target on a leaf edge (two planes)
+      in_plane      origin and direction in a triangle's plane (det == 0); tilted so that |det| is 1e-3 .. 1e3 times GI_EPSILON
+      sphere        tangents and a hair either side, origins on the surface / inside / at the centre, the sphere behind the origin, poles, seam
+      from_hits     origins that ARE hit points (no bias): mirrored on, in a random direction, straight back
+      shadow_ends   segments that end at a hit point exactly or a hair before / behind it, that start at one, of length zero and a hair
+    Origins: a third inside the root box, a third on its faces, a third up to 0.2 extents outside; a share of the rays reaches its target along an
+    exact axis direction, a share runs from the target out to the origin, a share has the scene behind it (_aim, _with_scene_behind).
+    A class a scene cannot have (no sphere; a tree of one leaf has no entity crossing a face) is left out."""
+    t = scene.tables()
+    bb = t["node_bbox"][0]
+    lo, hi = bb[:3], bb[3:]
+    ext = float((hi - lo).max())
+    rs = np.random.RandomState(seed)
+    oracle = oracle_for(scene)
+    out = {}
+    tgt = _tri_boundary_targets(rs, t, n, ext)
+    out["tri_boundary"] = _with_scene_behind(rs, _aim(rs, _edge_origins(rs, lo, hi, len(tgt)), tgt, lo, hi), lo, hi, ext)
+    lp = _leaf_plane_rays(rs, t, n, lo, hi, ext)
+    if lp is not None:
+        out["leaf_plane"] = _with_scene_behind(rs, lp, lo, hi, ext)
+    out["in_plane"] = _with_scene_behind(rs, _in_plane_rays(rs, t, n, lo, hi, ext), lo, hi, ext)
+    sp = _sphere_rays(rs, t, n, lo, hi, ext)
+    if sp is not None:
+        out["sphere"] = sp
+    # the oracle's hit points of the classes so far: on the surface to rounding, so the t of the self-intersection is ~ +-1e-16 and its sign decides
+    base = np.concatenate(list(out.values()))
+    hit, _, res, _ = oracle.trace(base)
+    hp, nrm, din = res[hit > 0, :3], res[hit > 0, 3:6], base[hit > 0, 3:]
+    org = base[hit > 0, :3]
+    pick = rs.permutation(len(hp))[:n]
+    k = np.arange(len(pick)) % 3
+    nn = _unit(nrm[pick])
+    mirror = _unit(din[pick] - 2.0 * (din[pick] * nn).sum(1, keepdims=True) * nn)
+    d = np.where((k == 0)[:, None], mirror, np.where((k == 1)[:, None], _unit(rs.randn(len(pick), 3)), -din[pick]))
+    out["from_hits"] = np.concatenate([hp[pick], d], 1)
+    # segments
+    pick = rs.permutation(len(hp))[:n]
+    m = len(pick)
+    k = np.arange(m) % 8
+    o, tg = org[pick].copy(), hp[pick].copy()
+    h = _hair(rs, ext, m)
+    tg[(k == 1) | (k == 2)] += (din[pick] * h[:, None])[(k == 1) | (k == 2)]                 # a hair before or behind the hit point
+    before = (k == 3)                                                                         # ends a (larger) hair before its first blocker
+    tg[before] -= (din[pick] * (ext * 10.0 ** rs.uniform(-9, -3, m))[:, None])[before]
+    start = (k == 4) | (k == 5)                                                               # starts at a hit point (ts == 0)
+    o[start] = hp[pick][start]
+    tg[start] = o[start] + _unit(rs.randn(m, 3))[start] * (ext * rs.uniform(0.01, 1.0, m))[start, None]
+    tg[k == 5] = org[pick][k == 5]                                                            # ... and runs straight back to where the ray came from
+    tg[k == 6] = o[k == 6]                                                                    # mt zero
+    tg[k == 7] = o[k == 7] + (_unit(rs.randn(m, 3)) * np.abs(h)[:, None])[k == 7]             # mt a hair above zero
+    far = (k == 7) & (np.arange(m) % 16 == 15)                                                # (and segments through the hit point to twice as far)
+    tg[far] = o[far] + 2.0 * (hp[pick][far] - o[far])
+    out["shadow_ends"] = np.concatenate([o, tg], 1)
+    for a in out.values():
+        a.setflags(write=False)
+    return out
+
+
+def _ulp_close(a, b, ulps=4):
+    return np.abs(a - b) <= ulps * np.spacing(np.maximum(np.abs(a), np.abs(b)))
+
+
+def brute_force_closest(t, rays, never=None, drawn=None, chunk=256):
+    """Closest hit over ALL entities without an octree, float64 numpy with the formulas of include/entities.h (triangle: :443-490, sphere: :60-101).
+    Returns (hit [n], squared distance of the nearest hit [n], tied [n][n_ent] bool: the entities whose hit point lies within 4 ulp, per coordinate,
+    of the nearest one's, applies [n]).  never [n_ent]: entities whose alpha test accepts no hit (alpha 0, IOR 1): left out.  drawn [n_ent]: entities
+    whose alpha test draws a number per leaf; a ray that meets one of them anywhere is outside what this can say (applies = False)."""
+    tri, kind = t["tri_pos"], t["ent_kind"]
+    never = np.zeros(len(tri), bool) if never is None else never
+    drawn = np.zeros(len(tri), bool) if drawn is None else drawn
+    applies = np.ones(len(rays), bool)
+    p0, e1, e2 = tri[:, 0], tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]
+    is_sph = kind == 1
+    rad = tri[:, 1, 0]
+    n, E = len(rays), len(tri)
+    hit = np.zeros(n, bool); best = np.full(n, np.inf); tied = np.zeros((n, E), bool)
+    dot = lambda a, b: a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+    for s in range(0, n, chunk):
+        o, d = rays[s:s + chunk, None, :3], rays[s:s + chunk, None, 3:]
+        with np.errstate(all="ignore"):
+            p = np.cross(d, e2[None])
+            det = dot(e1[None], p)
+            ok = ~((det < GI_EPSILON) & (det > -GI_EPSILON))
+            inv = 1.0 / det
+            tv = o - p0[None]
+            u = dot(tv, p) * inv
+            ok &= ~((u < 0) | (u > 1))
+            qq = np.cross(tv, e1[None])
+            v = dot(d, qq) * inv
+            ok &= ~((v < 0) | (u + v > 1))
+            tt = dot(e2[None], qq) * inv
+            ok &= ~(tt <= 0)
+            ok &= ~np.isnan(tt)
+            if is_sph.any():
+                oc = tv[:, is_sph]
+                dt = dot(np.broadcast_to(d, oc.shape), oc)
+                r = dt * dt - dot(oc, oc) + (rad * rad)[None, is_sph]
+                sr = np.sqrt(r)
+                t1, t2 = -1 * dt - sr, -1 * dt + sr
+                oks = ~(r < 0) & ~((t1 < 0) & (t2 < 0))
+                ts = np.where(((t1 < t2) & (t1 > 0)) | (t2 < 0), t1, t2)
+                tt[:, is_sph] = ts
+                ok[:, is_sph] = oks
+            applies[s:s + chunk] = ~(ok & drawn[None]).any(1)
+            ok &= ~(never | drawn)[None]
+            hp = o + np.where(ok, tt, 0.0)[..., None] * d
+            diff = hp - o
+            d2 = np.where(ok, dot(diff, diff), np.inf)
+        j = d2.argmin(1)
+        rows = np.arange(len(j))
+        best[s:s + chunk] = d2[rows, j]
+        hit[s:s + chunk] = np.isfinite(d2[rows, j])
+        near = hp[rows, j][:, None, :]
+        tied[s:s + chunk] = ok & _ulp_close(hp, near).all(-1) & hit[s:s + chunk, None]
+    return hit, best, tied, applies
+
+
+_EDGE_CASES = {}
+
+
+def edge_case(scene, key=None, brute=True):
+    """entity_edge_rays(scene) once per session (key: a name to remember it by), with what the CPU alone says about it, read-only: the closest-hit
+    classes as ONE array (a ray's index is its RNG stream: the alpha draws of a launch belong to it) with the oracle's answers and the brute
+    force's, the segments with the oracle's, and per class the shares of both outcomes -- at least 5 % each, from the oracle, before any device is asked."""
+    if key is not None and key in _EDGE_CASES:
+        return _EDGE_CASES[key]
+    oracle, t = oracle_for(scene), scene.tables()
+    sets = entity_edge_rays(scene)
+    names = [n for n in sets if n != "shadow_ends"]
+    c = {"names": names, "rays": np.concatenate([sets[n] for n in names]), "cls": np.concatenate([np.full(len(sets[n]), i) for i, n in enumerate(names)]),
+         "q": sets["shadow_ends"]}
+    rays = c["rays"]
+    c["hit"], c["ent"], c["res"], n_leaves = oracle.trace(rays)
+    c["vis"] = oracle.visible(c["q"])[0]
+    c["seg_rays"], c["mt"] = segments_as_rays(c["q"])
+    k = c["hit"] > 0
+    if brute:
+        # the brute force stands on its own: the oracle's hit is the nearest of all entities (a check of the ray set and of the oracle).  Outside its
+        # reach: a ray that meets an entity whose alpha test draws a number per leaf, and a ray whose walk asks no entity at all -- it misses the root
+        # box by the reference's own slab test or enters no leaf (a ray lying in a face of the root box), whatever lies on its line
+        alpha = alpha_entities(scene)
+        never = alpha & (t["mats"][t["tri_mat"], 1] == 0)                 # alpha = opacity * texture alpha = 0, IOR 1: no hit is ever accepted
+        bh, bd2, tied, applies = brute_force_closest(t, rays, never, alpha & ~never)
+        bb = t["node_bbox"][0]
+        applies = applies & _root_box_entered(rays, bb[:3], bb[3:]) & (n_leaves > 0)
+        od = c["res"][:, :3] - rays[:, :3]
+        od2 = od[:, 0] * od[:, 0] + od[:, 1] * od[:, 1] + od[:, 2] * od[:, 2]
+        bad = np.nonzero(applies & ((bh != k) | (k & ~_ulp_close(od2, np.where(k, bd2, od2)))))[0]
+        assert not len(bad), (len(bad), [(names[c["cls"][i]], rays[i].tolist(), int(c["hit"][i]), int(c["ent"][i]), float(od2[i]), bool(bh[i]), float(bd2[i])) for i in bad[:3]])
+        assert tied[k & applies, c["ent"][k & applies]].all()             # the oracle's own entity is one of the tied ones
+        c["tied"], c["applies"] = tied, applies
+    for i, name in enumerate(names):
+        m = c["cls"] == i
+        share = float(k[m].mean())
+        line = f"  {name:12s} {int(m.sum()):5d} rays: hit {share:.1%}, miss {1 - share:.1%}"
+        if brute:
+            line += f"; {int((applies[m] & (tied[m].sum(1) > 1)).sum())} tied (more than one entity within 4 ulp of the nearest hit point)"
+            line += f"; {int((~applies[m]).sum())} outside the brute force's reach (an alpha draw, or no entity is asked)"
+        print(line)
+        assert 0.05 <= share <= 0.95, (name, share)
+    share = float((c["vis"] > 0).mean())
+    print(f"  {'shadow_ends':12s} {len(c['q']):5d} segments: open {share:.1%}, blocked {1 - share:.1%}")
+    assert 0.05 <= share <= 0.95, ("shadow_ends", share)
+    for a in c.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    if key is not None:
+        _EDGE_CASES[key] = c
+    return c
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64)
+
+
+def check_entity_edges(rt, scene, forms, what="closest", key=None, brute=True, others=()):
+    """Rays aimed at entity edges, leaf planes and tangents (entity_edge_rays) through every form of the walk `rt` has, against the oracle and the
+    brute force.  The bound is equality (the walks use IEEE + - * / sqrt only):
+      * hit flag and hit point bits equal the oracle's for every ray; visibility equals the oracle's for every segment;
+      * the entity is one of the brute force's tied set (hit points within 4 ulp of the nearest), and the oracle's where that set has one member --
+        with it normal, u and v (two triangles that share an edge can place the hit at bitwise the same point; the reference keeps the one it met
+        first and leaves entered at equal t0 may be met in another order: check_leaf_order);
+      * across the device's own forms everything is bit-equal, the entity included: rt.trace / rt.visible / rt.visible_rays with wide records on
+        and off, content culling off, entity boxes off, the contexts in `others` ((name, rt) pairs, e.g. made under GI_CLIP_BOXES=0), and
+        rt.debug_walk for every (form, lds) of `forms`.
+    brute = False (a scene with alpha-tested entities: the draws are per leaf): the oracle and the forms only.  Returns {class: rays compared}."""
+    case = edge_case(scene, key, brute)
+    wide = rt.set_wide_nodes(True)
+    names = ["shadow_ends"] if what == "any" else case["names"]
+    rays = case["seg_rays"] if what == "any" else case["rays"]
+    assert len(rays) <= 24000
+    cls = np.zeros(len(rays), int) if what == "any" else case["cls"]
+
+    def run(r, how):
+        if what == "any":
+            q, mt = case["q"], case["mt"]
+            return {"visible": lambda: (r.visible(q),), "visible_rays": lambda: (r.visible_rays(rays, mt),)}.get(how, lambda: (r.debug_walk(rays, mt, *how),))()
+        return r.trace(rays) if how == "trace" else r.debug_walk(rays, None, *how)
+
+    entries = ["visible", "visible_rays"] if what == "any" else ["trace"]
+    got = {}
+    for e in entries:
+        got[("wide", e)] = run(rt, e)
+    if wide:
+        for f in forms:
+            got[("debug_walk", tuple(f))] = run(rt, tuple(f))
+        rt.set_wide_nodes(False)
+        for e in entries:
+            got[("per node", e)] = run(rt, e)
+        assert rt.set_wide_nodes(True)
+        if rt.set_content_culling(True):
+            rt.set_content_culling(False)
+            for e in entries:
+                got[("no culling", e)] = run(rt, e)
+            rt.set_content_culling(True)
+        if rt.set_entity_boxes(True):
+            rt.set_entity_boxes(False)
+            for e in entries:
+                got[("no entity boxes", e)] = run(rt, e)
+            rt.set_entity_boxes(True)
+    else:
+        assert (scene.tables()["node_child"][0] < 0).all()        # only a tree of one leaf has no wide records: nothing but the plain walk to ask
+        for f in forms:
+            try:
+                run(rt, tuple(f))
+                raise AssertionError("debug_walk answered without wide records")
+            except gi.GiError:
+                pass
+    for name, r in others:
+        for e in entries:
+            got[(name, e)] = run(r, e)
+
+    def describe(i, k):
+        return {"class": names[cls[i]], "row": int(i), "ray": rays[i].tolist(), "form": k, "got": [np.asarray(a)[i].tolist() for a in got[k]]}
+
+    # against the oracle (and the brute force)
+    first = next(iter(got))
+    if what == "any":
+        vis_o = case["vis"]
+        for k, (vis,) in got.items():
+            bad = np.nonzero(vis != vis_o)[0]
+            assert not len(bad), (len(bad), [dict(describe(i, k), oracle=int(vis_o[i])) for i in bad[:3]])
+    else:
+        hit_o, ent_o, res_o = case["hit"], case["ent"], case["res"]
+        tied, applies = (case["tied"], case["applies"]) if brute else (None, None)
+        for k, (hit, ent, res) in got.items():
+            bad = np.nonzero((hit != hit_o) | (_bits(res[:, :3]) != _bits(res_o[:, :3])).any(1))[0]
+            assert not len(bad), (len(bad), [dict(describe(i, k), oracle=[int(hit_o[i]), int(ent_o[i]), res_o[i].tolist()],
+                                                  brute=None if tied is None else np.nonzero(tied[i])[0].tolist()) for i in bad[:3]])
+            h = hit_o > 0
+            if brute:
+                unique = h & (~applies | (tied.sum(1) == 1))
+                member = tied[np.arange(len(ent)), np.where(h, ent, 0)] | ~h | ~applies
+            else:
+                unique, member = h, np.ones(len(ent), bool)
+            same = (ent == ent_o) & (_bits(res[:, 3:6]) == _bits(res_o[:, 3:6])).all(1)   # (columns 6, 7: the device's barycentric u, v; the oracle's are the texture's)
+            bad = np.nonzero(~member | (unique & ~same))[0]
+            assert not len(bad), (len(bad), [dict(describe(i, k), oracle=[int(ent_o[i]), res_o[i].tolist()],
+                                                  brute=None if tied is None else np.nonzero(tied[i])[0].tolist()) for i in bad[:3]])
+    # across the forms: every bit, the entity included
+    for k, v in got.items():
+        for a, b in zip(v, got[first]):
+            bad = np.nonzero((np.asarray(a).reshape(len(rays), -1).view(np.uint64 if a.dtype == np.float64 else a.dtype) !=
+                              np.asarray(b).reshape(len(rays), -1).view(np.uint64 if b.dtype == np.float64 else b.dtype)).any(1))[0]
+            assert not len(bad), (len(bad), [dict(describe(i, k), other=describe(i, first)) for i in bad[:3]])
+    print(f"  {what}: {len(rays)} rays x {len(got)} forms: " + ", ".join(f"{a} {b}" for a, b in got))
+    return {n: int((cls == i).sum()) for i, n in enumerate(names)}
