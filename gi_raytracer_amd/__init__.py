@@ -72,6 +72,14 @@ class Lens(C.Structure):
     _fields_ = [("radius", C.c_double), ("rotation", C.c_double), ("blades", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BakeParams(C.Structure):
+    """gi_bake_params (include/gi_hip.h)."""
+    _fields_ = [("mode", C.c_int32), ("n_samples", C.c_int32), ("stream_base", C.c_uint32), ("seed", C.c_uint64)]
+
+
+BAKE_TEXEL, BAKE_SH9 = 0, 1
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -91,6 +99,7 @@ ABI_SYMBOLS = [
     "gi_progressive_begin", "gi_progressive_step_device", "gi_progressive_step_host", "gi_progressive_status", "gi_progressive_state_bytes",
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
     "gi_lens_default", "gi_set_lens", "gi_get_lens", "gi_lens_vertices", "gi_group_set_lens", "gi_debug_primary_rays", "gi_focus_distance",
+    "gi_bake_default_params", "gi_bake_device", "gi_bake_host", "gi_last_bake_ms", "gi_bake_rays", "gi_bake_fold",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
     "gih_add_texture", "gih_add_material_tex", "gih_load_png", "gih_free",
@@ -182,6 +191,13 @@ def lib():
     L.gi_group_set_lens.argtypes = [vp, C.POINTER(Lens)]
     L.gi_debug_primary_rays.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, _up, _dp]
     L.gi_focus_distance.argtypes = [vp, C.POINTER(RenderParams), C.c_int32, C.c_int32, _dp]
+    L.gi_bake_default_params.argtypes = [C.POINTER(BakeParams)]
+    L.gi_bake_default_params.restype = None
+    L.gi_bake_device.argtypes = [vp, vp, C.c_int32, C.POINTER(BakeParams), vp, C.c_int]
+    L.gi_bake_host.argtypes = [vp, _dp, C.c_int32, C.POINTER(BakeParams), vp, C.c_int]
+    L.gi_last_bake_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.gi_bake_rays.argtypes = [vp, _dp, C.c_int32, C.POINTER(BakeParams), _dp, _up]
+    L.gi_bake_fold.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
     L.gi_group_create.argtypes = [C.POINTER(vp), C.c_int32, _ip]
     L.gi_group_destroy.argtypes = [vp]
     L.gi_group_size.argtypes = [vp]
@@ -426,6 +442,14 @@ def save_ppm(path, lin):
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0]))
         f.write(a.tobytes())
+
+
+def probe_grid(box6, nx, ny, nz):
+    """A regular grid of probe positions inside the box (min xyz, max xyz): the centres of its nx x ny x nz cells, [nz][ny][nx][3]."""
+    b = np.asarray(box6, np.float64).reshape(6)
+    ax = [b[k] + (np.arange(n) + 0.5) * ((b[3 + k] - b[k]) / n) for k, n in enumerate((int(nx), int(ny), int(nz)))]
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x, y, z], -1))
 
 
 UPSAMPLE_FACTORS = range(2, 9)
@@ -982,6 +1006,75 @@ class RayTracer:
     def last_occlusion_ms(self):
         """gi_last_occlusion_ms: device time of the last occlusion pass (the frame's and the other passes' times keep theirs)."""
         return self._last_ms("occlusion")
+
+    def bake_params(self, mode, samples, stream_base=0, seed=None):
+        """gi_bake_params: mode BAKE_TEXEL / BAKE_SH9 (or "texel" / "sh9"), samples per point, the stream index of sample 0 of point 0, the seed
+        (default: the tracer's)."""
+        p = BakeParams()
+        self.L.gi_bake_default_params(C.byref(p))
+        p.mode = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}.get(mode, mode)
+        p.n_samples, p.stream_base = int(samples), int(stream_base)
+        p.seed = self.seed if seed is None else seed
+        return p
+
+    @staticmethod
+    def _bake_points(points, normals=None):
+        pts = _f64(points).reshape(-1, 3)
+        if normals is None:
+            return pts
+        nrm = _f64(normals).reshape(-1, 3)
+        if len(nrm) != len(pts):
+            raise ValueError(f"bake: {len(pts)} points and {len(nrm)} normals")
+        return np.ascontiguousarray(np.concatenate([pts, nrm], 1))
+
+    def _bake(self, rows, bp, f64):
+        n = len(rows)
+        out = np.zeros((n, 3) if bp.mode == BAKE_TEXEL else (n, 9, 3), np.float64 if f64 else np.float32)
+        self._check(self.L.gi_bake_host(self.h, _p(rows), n, C.byref(bp), out.ctypes.data_as(C.c_void_p), 1 if f64 else 0), "bake_host")
+        return out
+
+    def bake_texels(self, points, normals, samples, stream_base=0, seed=None, f64=True):
+        """Lightmap texels (gi_bake_host, GI_BAKE_TEXEL; an addition, the reference starts every path at the camera): per point [n][3] with normal
+        [n][3], the mean over `samples` rays in the diffuse bounce's lobe of the radiance the path tracer finds along them -- the factor a
+        roughness-1 albedo is multiplied by for its indirect term.  Direct light of the lights at the point is not in it.  Returns [n][3].
+        Sample k of point i runs on stream stream_base + i * samples + k; the definition is stated in include/gi_hip.h."""
+        return self._bake(self._bake_points(points, normals), self.bake_params(BAKE_TEXEL, samples, stream_base, seed), f64)
+
+    def bake_probes(self, points, samples, stream_base=0, seed=None, f64=True):
+        """Light probes (gi_bake_host, GI_BAKE_SH9): per point [n][3] the nine real spherical-harmonic coefficients (bands 0 to 2; the order is the
+        header's) of the incident radiance, per colour channel, from `samples` rays uniform over the sphere.  Returns [n][9][3]."""
+        return self._bake(self._bake_points(points), self.bake_params(BAKE_SH9, samples, stream_base, seed), f64)
+
+    def bake_device(self, bp, points_ptr, n_points, out_ptr, f64=False):
+        """A bake on device memory (raw device pointers: points [n][6] or [n][3] f64, out [n][3] or [n][9][3]); bp from bake_params.  The points are
+        not looked at."""
+        self._check(self.L.gi_bake_device(self.h, C.c_void_p(points_ptr), int(n_points), C.byref(bp), C.c_void_p(out_ptr), 1 if f64 else 0), "bake_device")
+
+    def bake_rays(self, points, normals, samples, stream_base=0, seed=None):
+        """gi_bake_rays: the rays a bake's generator makes -- (rays [n * samples][6] = origin, unit direction, streams [n * samples]), sample k of
+        point i in row i * samples + k.  normals None: probes (GI_BAKE_SH9), else texels."""
+        rows = self._bake_points(points, normals)
+        bp = self.bake_params(BAKE_SH9 if normals is None else BAKE_TEXEL, samples, stream_base, seed)
+        rays = np.zeros((len(rows) * bp.n_samples, 6)); streams = np.zeros(len(rows) * bp.n_samples, np.uint32)
+        self._check(self.L.gi_bake_rays(self.h, _p(rows), len(rows), C.byref(bp), _p(rays), _p(streams, _up)), "bake_rays")
+        return rays, streams
+
+    def bake_fold(self, mode, radiance, dirs=None):
+        """gi_bake_fold: the bake's fold kernel on caller data -- radiance [n][samples][3] and, for BAKE_SH9, unit directions [n][samples][3].
+        Returns [n][3] (BAKE_TEXEL) or [n][9][3]."""
+        mode = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}.get(mode, mode)
+        L3 = _f64(radiance)
+        n, ns = L3.shape[:2]
+        d3 = _f64(dirs) if dirs is not None else None
+        if L3.ndim != 3 or L3.shape[2] != 3 or (d3 is not None and d3.shape != L3.shape):
+            raise ValueError("bake_fold: radiance and directions [n][samples][3] expected")
+        out = np.zeros((n, 3) if mode == BAKE_TEXEL else (n, 9, 3))
+        self._check(self.L.gi_bake_fold(self.h, mode, n, ns, _p(d3), _p(L3), _p(out)), "bake_fold")
+        return out
+
+    def last_bake_ms(self):
+        """gi_last_bake_ms: device time of the last bake (the frame's and the other passes' times keep theirs)."""
+        return self._last_ms("bake")
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
         """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,

@@ -7,6 +7,7 @@
                                [--upsample S [--upsample-pfm LOW.pfm]]
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
+    python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -31,6 +32,9 @@ of field.  --blades N (3 .. 16, default 6) and --blade-rotation DEG shape the ap
 camera's sensor plane, focal_dist in front of it; --focus D moves it to distance D, --focus-pixel X Y to the first surface behind the centre of
 that pixel (the field of view is kept).  Every other flag renders under the lens: --features, --occlusion, --progressive (a checkpoint resumes
 only under the lens it was written with), --denoise, --upsample.
+--probes NX NY NZ (an addition as well) renders no frame: it bakes a regular grid of light probes inside the octree's root box, one at the centre
+of each of the NX x NY x NZ cells, with --probe-samples N rays each (default 256), after the photon pass, and writes their spherical-harmonic
+coefficients to -o as a numpy array [NZ][NY][NX][9][3] (float32; include/gi_hip.h: GI_BAKE_SH9).  The frame's flags do not go with it.
 """
 import argparse
 import os
@@ -41,6 +45,7 @@ import gi_raytracer_amd as gi
 
 
 FEATURE_FILES = ("albedo", "normal", "depth", "coverage")
+PROBE_SAMPLES = 256
 
 
 def parser():
@@ -75,6 +80,8 @@ def parser():
     ap.add_argument("--blade-rotation", type=float, default=None, metavar="DEG", help="with --aperture: rotation of the aperture in degrees (default 0)")
     ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: distance of the plane that stays sharp (default: the camera's focal distance)")
     ap.add_argument("--focus-pixel", type=int, nargs=2, default=None, metavar=("X", "Y"), help="with --aperture: focus on the first surface behind the centre of this pixel")
+    ap.add_argument("--probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="bake a grid of light probes in the scene's box instead of a frame; -o gets a .npy [NZ][NY][NX][9][3]")
+    ap.add_argument("--probe-samples", type=int, default=None, metavar="N", help="with --probes: rays per probe (default 256)")
     return ap
 
 
@@ -96,6 +103,18 @@ def check_args(ap, a):
         ap.error("--progressive N: N must be at least 1")
     if a.time_limit is not None and not a.time_limit >= 0:
         ap.error("--time-limit SECONDS: a number >= 0")
+    if a.probes is None and a.probe_samples is not None:
+        ap.error("--probe-samples needs --probes NX NY NZ")
+    if a.probes is not None:
+        if min(a.probes) < 1 or a.probes[0] * a.probes[1] * a.probes[2] >= 2 ** 31:
+            ap.error("--probes NX NY NZ: three numbers >= 1, fewer than 2^31 probes in all")
+        if a.probe_samples is not None and a.probe_samples < 1:
+            ap.error("--probe-samples N: N must be at least 1")
+        if a.probes[0] * a.probes[1] * a.probes[2] * (a.probe_samples or PROBE_SAMPLES) > 2 ** 32:
+            ap.error("--probes: probes x samples must keep the stream index within 32 bits")
+        frame_flags = (a.pfm, a.samples, a.features, a.feature_samples, a.denoise, a.progressive, a.upsample, a.occlusion, a.aperture)
+        if any(f is not None for f in frame_flags):
+            ap.error("--probes renders no frame: only --photons, --probe-samples, --device and -o go with it")
     if a.upsample is None and a.upsample_pfm:
         ap.error("--upsample-pfm needs --upsample S")
     if a.occlusion is None and (a.occlusion_samples is not None or a.occlusion_dirs is not None or a.occlusion_radius is not None):
@@ -141,6 +160,12 @@ def replace_file(path, write):
 def write_bytes(path, data):
     with open(path, "wb") as f:
         f.write(data)
+
+
+def write_npy(path, array):
+    import numpy as np
+    with open(path, "wb") as f:      # (np.save would add ".npy" to a name without it)
+        np.save(f, array)
 
 
 def render_progressive(a, rt):
@@ -222,6 +247,16 @@ def main(argv=None):
     if n_photons > 0 and scene.desc().n_light > 0:
         stored = len(rt.tracePhotons(n_photons)[0])
     t1 = time.time()
+    if a.probes:
+        import numpy as np
+        nx, ny, nz = a.probes
+        ns = a.probe_samples or PROBE_SAMPLES
+        grid = gi.probe_grid(scene.tables()["node_bbox"][0], nx, ny, nz)
+        sh = rt.bake_probes(grid.reshape(-1, 3), ns, f64=False).reshape(nz, ny, nx, 9, 3)
+        replace_file(a.output, lambda t: write_npy(t, sh))
+        print(f"{a.scene}: {nx} x {ny} x {nz} probes of {ns} samples, {stored} photons stored; photon pass {t1 - t0:.2f} s, "
+              f"bake {rt.last_bake_ms():.2f} ms -> {a.output}")
+        return 0
     feat = lens_note = ""
     lens = lens_of(a)
     if lens is not None:

@@ -6,7 +6,7 @@
 //   Tuning        every value taken from the environment when the context is made (from_env), and the two limits the setters change
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
-//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler
+//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake
 // Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
@@ -336,6 +336,11 @@ struct AuxPass {
 struct DenoisePass : AuxPass {
     DevBuf<double> d_guides, d_a, d_b;
 };
+// a bake (gi_bake.inc), with what it keeps beside the stream workspaces: every path's unit direction [slot][3] (probes: the fold's basis is
+// evaluated there) and the sums of a chunk's points between two ranges of samples [terms][points], f64, sized on first use and kept
+struct BakePass : AuxPass {
+    DevBuf<double> d_dirs, d_sums;
+};
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
 struct gi_ctx {
@@ -375,6 +380,7 @@ struct gi_ctx {
     } lens;
     AuxPass feat, ao, up;             // gi_render_features_*, gi_render_occlusion_*, gi_upsample_*
     DenoisePass dn;                   // gi_denoise_*
+    BakePass bake;                    // gi_bake_*
 };
 
 namespace {

@@ -1729,4 +1729,5 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
 #include "gi_occlusion.inc"      // ambient occlusion: k_ao and gi_render_occlusion_*
 #include "gi_entries.inc"        // function-level entries (parity tests, public C++ methods) and the debug entries
 #include "gi_lens.inc"           // the thin lens: gi_set_lens, its vertex table, gi_debug_primary_rays, gi_focus_distance
+#include "gi_bake.inc"           // light baking: k_bake_gen, k_bake_fold and gi_bake_*
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

@@ -252,6 +252,20 @@ class RayTracer {
         return true;
     }
 
+    // ---- ADDITION (the reference's paths all start at the camera): light baking on the context of the per-ray methods (gi_bake_host; include/gi_hip.h
+    // states the definition, and what a bake does not hold: direct light of the lights at the point itself).  Sample k of point i runs on stream
+    // streamBase + i * samples + k under this RayTracer's seed.  false with last_error() set when it cannot run (out is then left alone).
+    // bakeProbes: points [n][3] -> out [n][9][3], the SH coefficients of bands 0 to 2 of the incident radiance, per colour channel.
+    bool bakeProbes(const std::vector<double>& points, int samples, std::vector<double>& out, uint32_t streamBase = 0)
+    {
+        return bake(GI_BAKE_SH9, points, 3, 27, samples, streamBase, out);
+    }
+    // bakeTexels: pointsAndNormals [n][6] = position, normal -> out [n][3], the factor a roughness-1 albedo is multiplied by for its indirect term.
+    bool bakeTexels(const std::vector<double>& pointsAndNormals, int samples, std::vector<double>& out, uint32_t streamBase = 0)
+    {
+        return bake(GI_BAKE_TEXEL, pointsAndNormals, 6, 3, samples, streamBase, out);
+    }
+
     // ---- ADDITION (the reference has no denoiser): the edge-avoiding a-trous filter of gi_denoise_host (include/gi_hip.h states the formula) on a
     // whole frame.  color = [height][width][3] linear radiance of a feat.width x feat.height frame, feat = what renderFeatures filled; out gets
     // [height][width][3].  dp = nullptr: gi_denoise_default_params; else its width / height are overwritten with feat's.  Needs a device, not a
@@ -479,6 +493,19 @@ class RayTracer {
         rp.min_samples = min_samples; rp.max_samples = max_samples; rp.noise_thresh = noise_thresh;
         rp.seed = seed;
         return rp;
+    }
+    bool bake(int mode, const std::vector<double>& rows, size_t row, size_t terms, int samples, uint32_t streamBase, std::vector<double>& out)
+    {
+        if (!ready()) return false;
+        if (rows.size() % row != 0 || rows.size() / row > 0x7fffffffu) { _st->err = "bake: the points are not rows of " + std::to_string(row) + " numbers"; return false; }
+        gi_bake_params p;
+        gi_bake_default_params(&p);
+        p.mode = mode; p.n_samples = samples; p.stream_base = streamBase; p.seed = seed;
+        const size_t n = rows.size() / row;
+        std::vector<double> buf(n * terms + 1);
+        if (check(gi_bake_host(_st->ctx, rows.data(), (int32_t)n, &p, buf.data(), 1)) != 0) return false;
+        out.assign(buf.begin(), buf.begin() + n * terms);
+        return true;
     }
     static gi::Mat mat_of(const Entity* e)
     {

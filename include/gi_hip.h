@@ -480,6 +480,65 @@ int gi_group_set_lens(gi_group*, const gi_lens*);
 int gi_debug_primary_rays(gi_ctx*, const gi_render_params*, int32_t n, const uint32_t* idx, double* rays /*[n][6]*/);
 int gi_focus_distance(gi_ctx*, const gi_render_params*, int32_t x, int32_t y, double* dist);
 
+/* Light baking -- an ADDITION: the reference's paths all start at the camera.  A bake gathers incident light at caller-given points: light probes
+ * (nine spherical-harmonic coefficients per colour channel) and lightmap texels (the diffuse indirect factor), with the renderer's own samplers and
+ * the whole path tracer behind every ray -- the streaming passes gi_render_* runs, fed by a generator of their own instead of a frame.
+ * A bake takes n_points points with n_samples directions each.  Sample k of point i carries the 32-bit Halton / RNG stream index
+ *     stream = stream_base + i * n_samples + k
+ * which plays the part a pixel sample's Halton index plays in the frame: Halton dimensions 0 and 1 at that index, as floats, are the direction's
+ * (u, v) (the frame places the sample in the pixel with them, emission the point on the light); dimensions 2 + 2d and 3 + 2d and the counter RNG
+ * keyed by (seed, stream) drive the path exactly as for a primary ray of that index (DESIGN.md "RNG contract").  A caller that splits a point list
+ * over several calls or devices gives part [a, b) the base stream_base + a * n_samples and gets the rows [a, b) of the whole bake, bit for bit.
+ *   GI_BAKE_TEXEL (lightmap texel): points [n][6] = position P, normal N.
+ *     Nn = N / sqrt((Nx Nx + Ny Ny) + Nz Nz) per component;  O = P + 0.0001 Nn (SHADOW_BIAS);  d = hemisphereSample_cos(Nn, u, v, 2)
+ *     (include/util.cpp:35-58), the lobe of the reference's diffuse bounce (include/raytracer.h:321-379);  the ray is Ray(O, d) (include/ray.h:7-17:
+ *     d is normalised once more).  out [n][3] = the sum over k of L_k, accumulated in ascending k from +0.0, divided by (double) n_samples.
+ *     This is the factor the albedo of a roughness-1 surface is multiplied by for its indirect term in RayTracer::radiance; times pi it is the
+ *     irradiance, up to what fastPrecisePow does to the cosine lobe (include/util.h:113-136).
+ *   GI_BAKE_SH9 (light probe): points [n][3] = position P.
+ *     O = P;  d = randomUnitVec((double) u, (double) v) (include/util.h:183-188), uniform over the sphere.
+ *     out [n][9][3]: acc[j][c] += L_k[c] Y_j(d_k) in ascending k from +0.0, then (acc * 12.566370614359172) / (double) n_samples.
+ *     Y_j is the real SH basis of bands 0 to 2 at the unit direction (x, y, z) the path's record holds, in this order and with these literals:
+ *       Y0 = 0.28209479177387814              Y1 = 0.4886025119029199 y              Y2 = 0.4886025119029199 z
+ *       Y3 = 0.4886025119029199 x             Y4 = 1.0925484305920792 (x y)          Y5 = 1.0925484305920792 (y z)
+ *       Y6 = 0.31539156525252005 (3.0 (z z) - 1.0)    Y7 = 1.0925484305920792 (x z)  Y8 = 0.5462742152960396 (x x - y y)
+ * L_k = RayTracer::radiance(ray, depth 0) (include/raytracer.h:167-276) of that ray under the counter RNG with the call's seed -- gi_radiance on the
+ * rows of gi_bake_rays states it: the first hit's emission, its direct light, its caustic gather, the rest of the path, fog on the way, the ambient
+ * term on a miss.  The fold is IEEE operations only (+ * /) in the order written, compiled without contraction: given the same L_k and d_k it can be
+ * restated bit for bit (tests/bake_expect.py); gi_bake_fold runs it on caller data.
+ * What a bake does NOT hold: the analytic lights are not geometry, so no ray ever hits one -- direct light of the lights at the point itself is not in
+ * the result.  This is the usual indirect-only bake; a consumer adds direct light itself, and gi_visible answers the shadow segment.  The context's
+ * lens plays no part (there is no primary ray), nor does the render mode: a bake always runs the streaming passes.  Points inside geometry are
+ * baked like any other.  There is no gi_group_* form: split the point list.
+ * out is float (out_is_f64 = 0) or double (1), rounded once on store.  Points that do not fit the path pool (gi_set_pool_slots, free memory) run in
+ * chunks, samples that do not fit in ranges of k; the sums stay f64 in ascending k, so the result does not depend on either, nor on the launch.
+ * The path pool, the queues and the per-sample buffer are the shared scratch a frame uses: an open progressive session is left as it is.
+ * GI_E_INVALID: a null pointer (points and out may be null when n_points is 0), a mode other than the two, n_samples < 1, n_points < 0,
+ * stream_base + n_points * n_samples - 1 beyond 32 bits, and -- gi_bake_host and gi_bake_rays, which look at the points -- a position or normal that
+ * is not finite, or a normal 0 0 0.  gi_bake_device does NOT look at its points: they are the caller's device memory.  GI_E_STATE: no scene.
+ * n_points = 0 is GI_OK and writes nothing.  A refused call does not touch the output, and leaves the frame's and the other passes' times alone.
+ * gi_bake_default_params: GI_BAKE_SH9, 256 samples, stream_base 0, seed 0x9E3779B97F4A7C15.
+ * gi_bake_device: DEVICE pointers, asynchronous on the context's stream between its own read-backs; gi_bake_host: HOST pointers.
+ * gi_last_bake_ms: device time of the last bake (HIP events around it); the frame's and the other passes' times are left alone.
+ * Check entries (host pointers): gi_bake_rays gives the rays the generator makes, rays6_out [n_points * n_samples][6] = origin, unit direction
+ * and stream_out [n_points * n_samples], sample k of point i in row i * n_samples + k; no scene is needed.  gi_bake_fold runs the fold kernel on
+ * caller data: dirs3 and L3 [n_points][n_samples][3] (dirs3 may be null for GI_BAKE_TEXEL), out [n_points][3] or [n_points][9][3] double; the samples go
+ * through it in ranges of 16, as those of a bake that does not fit the pool. */
+#define GI_BAKE_TEXEL 0
+#define GI_BAKE_SH9 1
+typedef struct gi_bake_params {
+    int32_t mode;            /* GI_BAKE_TEXEL or GI_BAKE_SH9 */
+    int32_t n_samples;       /* >= 1 directions per point */
+    uint32_t stream_base;    /* stream index of sample 0 of point 0 */
+    uint64_t seed;           /* counter-RNG seed, as gi_render_params::seed */
+} gi_bake_params;
+void gi_bake_default_params(gi_bake_params*);
+int gi_bake_device(gi_ctx*, const double* d_points, int32_t n_points, const gi_bake_params*, void* d_out, int out_is_f64);
+int gi_bake_host(gi_ctx*, const double* points, int32_t n_points, const gi_bake_params*, void* h_out, int out_is_f64);
+int gi_last_bake_ms(gi_ctx*, float* ms);
+int gi_bake_rays(gi_ctx*, const double* points, int32_t n_points, const gi_bake_params*, double* rays6_out, uint32_t* stream_out);
+int gi_bake_fold(gi_ctx*, int32_t mode, int32_t n_points, int32_t n_samples, const double* dirs3, const double* L3, double* out);
+
 #ifdef __cplusplus
 }
 #endif
