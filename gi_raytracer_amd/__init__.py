@@ -80,6 +80,12 @@ class BakeParams(C.Structure):
 BAKE_TEXEL, BAKE_SH9 = 0, 1
 
 
+class LightmapParams(C.Structure):
+    """gi_lightmap_params (include/gi_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_samples", C.c_int32), ("dilate", C.c_int32), ("flip", C.c_int32),
+                ("stream_base", C.c_uint32), ("seed", C.c_uint64)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -100,6 +106,7 @@ ABI_SYMBOLS = [
     "gi_progressive_save", "gi_progressive_restore", "gi_progressive_end",
     "gi_lens_default", "gi_set_lens", "gi_get_lens", "gi_lens_vertices", "gi_group_set_lens", "gi_debug_primary_rays", "gi_focus_distance",
     "gi_bake_default_params", "gi_bake_device", "gi_bake_host", "gi_last_bake_ms", "gi_bake_rays", "gi_bake_fold",
+    "gi_lightmap_default_params", "gi_lightmap_host", "gi_lightmap_device", "gi_last_lightmap_ms", "gi_lightmap_texels", "gi_lightmap_dilate",
     "gi_device_count", "gi_group_create", "gi_group_destroy", "gi_group_size", "gi_group_ctx", "gi_group_last_error", "gi_group_upload_scene", "gi_group_upload_photons", "gi_group_render_host", "gi_group_render_device",
     "gih_scene_create", "gih_scene_destroy", "gih_last_error", "gih_load_scn", "gih_add_material", "gih_add_triangles",
     "gih_add_texture", "gih_add_material_tex", "gih_load_png", "gih_free",
@@ -198,6 +205,13 @@ def lib():
     L.gi_last_bake_ms.argtypes = [vp, C.POINTER(C.c_float)]
     L.gi_bake_rays.argtypes = [vp, _dp, C.c_int32, C.POINTER(BakeParams), _dp, _up]
     L.gi_bake_fold.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]
+    L.gi_lightmap_default_params.argtypes = [C.POINTER(LightmapParams)]
+    L.gi_lightmap_default_params.restype = None
+    L.gi_lightmap_host.argtypes = [vp, C.POINTER(LightmapParams), C.c_int32, _ip, _dp, vp, C.c_int, _ip, _ip]
+    L.gi_lightmap_device.argtypes = [vp, C.POINTER(LightmapParams), C.c_int32, vp, vp, vp, C.c_int, vp, _ip]
+    L.gi_last_lightmap_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.gi_lightmap_texels.argtypes = [vp, C.POINTER(LightmapParams), C.c_int32, _ip, _dp, _ip, _ip, _dp, _ip, C.c_int32]
+    L.gi_lightmap_dilate.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _dp, _ip, _dp]
     L.gi_group_create.argtypes = [C.POINTER(vp), C.c_int32, _ip]
     L.gi_group_destroy.argtypes = [vp]
     L.gi_group_size.argtypes = [vp]
@@ -450,6 +464,18 @@ def probe_grid(box6, nx, ny, nz):
     ax = [b[k] + (np.arange(n) + 0.5) * ((b[3 + k] - b[k]) / n) for k, n in enumerate((int(nx), int(ny), int(nz)))]
     z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
     return np.ascontiguousarray(np.stack([x, y, z], -1))
+
+
+def chart_of_material(scene, material=None):
+    """(ent [n], uv [n][3][2]): the default chart of a lightmap (RayTracer.bake_lightmap) for a scene whose texture coordinates are already an
+    unwrapped atlas -- the scene's own texture coordinates of all triangle entities of that material index, in entity order; None: of all
+    triangles.  Spheres are left out."""
+    t = scene.tables()
+    keep = t["ent_kind"] != 1
+    if material is not None:
+        keep &= t["tri_mat"] == int(material)
+    ent = np.flatnonzero(keep).astype(np.int32)
+    return ent, np.ascontiguousarray(t["tri_uv"][ent], np.float64).reshape(-1, 3, 2)
 
 
 UPSAMPLE_FACTORS = range(2, 9)
@@ -1075,6 +1101,79 @@ class RayTracer:
     def last_bake_ms(self):
         """gi_last_bake_ms: device time of the last bake (the frame's and the other passes' times keep theirs)."""
         return self._last_ms("bake")
+
+    def lightmap_params(self, width, height, samples, dilate=2, flip=False, stream_base=0, seed=None):
+        """gi_lightmap_params: the atlas size, samples per covered texel, dilation passes, whether the normals are negated, the stream index of
+        sample 0 of covered texel 0, the seed (default: the tracer's)."""
+        p = LightmapParams()
+        self.L.gi_lightmap_default_params(C.byref(p))
+        p.width, p.height, p.n_samples, p.dilate, p.flip = int(width), int(height), int(samples), int(dilate), 1 if flip else 0
+        p.stream_base = int(stream_base)
+        p.seed = self.seed if seed is None else seed
+        return p
+
+    @staticmethod
+    def _chart(ent, uv):
+        e = np.ascontiguousarray(ent, np.int32).reshape(-1)
+        c = _f64(uv).reshape(-1, 3, 2)
+        if len(c) != len(e):
+            raise ValueError(f"lightmap: {len(e)} entities and {len(c)} chart triangles")
+        return e, c
+
+    def bake_lightmap(self, ent, uv, width, height, samples, dilate=2, flip=False, stream_base=0, seed=None, f64=True, want_owner=False):
+        """A lightmap atlas (gi_lightmap_host; an addition around the bake): the chart -- ent [n] triangle entities, uv [n][3][2] their chart
+        coordinates in [0, 1]^2, v growing with the row -- rasterised into width x height texels, every covered texel baked as bake_texels does with
+        `samples` rays, the rows put back into the image and the gutters filled by `dilate` passes.  Returns the atlas [height][width][3], or
+        (atlas, owner [height][width] = the chart row of a covered texel or -1, n_covered) with want_owner.  Sample k of the i-th covered texel
+        (ascending y * width + x) runs on stream stream_base + i * samples + k; the definition is stated in include/gi_hip.h.  chart_of_material
+        gives the chart of a scene whose texture coordinates are an atlas already."""
+        e, c = self._chart(ent, uv)
+        p = self.lightmap_params(width, height, samples, dilate, flip, stream_base, seed)
+        atlas = np.zeros((max(p.height, 0), max(p.width, 0), 3), np.float64 if f64 else np.float32)
+        owner = np.full((max(p.height, 0), max(p.width, 0)), -1, np.int32) if want_owner else None
+        n_cov = C.c_int32(0)
+        self._check(self.L.gi_lightmap_host(self.h, C.byref(p), len(e), _p(e, _ip), _p(c), atlas.ctypes.data_as(C.c_void_p), 1 if f64 else 0,
+                                            _p(owner, _ip), C.byref(n_cov)), "lightmap_host")
+        return (atlas, owner, n_cov.value) if want_owner else atlas
+
+    def lightmap_device(self, p, n_chart, ent_ptr, uv_ptr, atlas_ptr, f64=False, owner_ptr=None):
+        """A lightmap on device memory (raw device pointers: ent [n] int32, uv [n][3][2] f64, atlas [h][w][3], owner [h][w] int32 or None); p from
+        lightmap_params.  The chart is not looked at.  Returns n_covered."""
+        n_cov = C.c_int32(0)
+        self._check(self.L.gi_lightmap_device(self.h, C.byref(p), int(n_chart), C.c_void_p(ent_ptr), C.c_void_p(uv_ptr), C.c_void_p(atlas_ptr),
+                                              1 if f64 else 0, C.c_void_p(owner_ptr), C.byref(n_cov)), "lightmap_device")
+        return n_cov.value
+
+    def lightmap_texels(self, ent, uv, width, height, flip=False):
+        """gi_lightmap_texels: the texel table a lightmap bakes -- (owner [height][width], points [n_cov][3], normals [n_cov][3], texel [n_cov]),
+        covered texels in ascending y * width + x."""
+        e, c = self._chart(ent, uv)
+        p = self.lightmap_params(width, height, 1, 0, flip)
+        cap = max(p.width, 0) * max(p.height, 0)
+        owner = np.full((max(p.height, 0), max(p.width, 0)), -1, np.int32)
+        rows = np.zeros((cap, 6)); texel = np.zeros(cap, np.int32)
+        n_cov = C.c_int32(0)
+        self._check(self.L.gi_lightmap_texels(self.h, C.byref(p), len(e), _p(e, _ip), _p(c), _p(owner, _ip), C.byref(n_cov), _p(rows), _p(texel, _ip), cap), "lightmap_texels")
+        n = n_cov.value
+        return owner, np.ascontiguousarray(rows[:n, 0:3]), np.ascontiguousarray(rows[:n, 3:6]), texel[:n].copy()
+
+    def lightmap_dilate(self, values, filled, passes):
+        """gi_lightmap_dilate: the lightmap's gutter dilation on caller data -- values [h][w][3], filled [h][w] (truth values), `passes` 0 .. 64.
+        Returns [h][w][3]; texels still unfilled are 0 0 0."""
+        v = _f64(values)
+        f = np.ascontiguousarray(np.asarray(filled) != 0, np.int32)
+        if v.ndim != 3 or v.shape[2] != 3 or f.shape != v.shape[:2]:
+            raise ValueError("lightmap_dilate: values [h][w][3] and filled [h][w] expected")
+        out = np.zeros(v.shape)
+        self._check(self.L.gi_lightmap_dilate(self.h, v.shape[1], v.shape[0], int(passes), _p(v), _p(f, _ip), _p(out)), "lightmap_dilate")
+        return out
+
+    def last_lightmap_ms(self):
+        """gi_last_lightmap_ms: (device time of the last lightmap, {"raster": .., "bake": .., "dilate": ..} -- raster + rank, bake, scatter + dilate);
+        gi_last_bake_ms, the frame's and the other passes' times keep theirs."""
+        ms, st = C.c_float(0), (C.c_float * 3)()
+        self._check(self.L.gi_last_lightmap_ms(self.h, C.byref(ms), st), "last_lightmap_ms")
+        return ms.value, dict(zip(("raster", "bake", "dilate"), (float(x) for x in st)))
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
         """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,

@@ -8,6 +8,8 @@
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
+    python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
+                               -o OUT.ppm [--pfm OUT.pfm]
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -35,6 +37,10 @@ only under the lens it was written with), --denoise, --upsample.
 --probes NX NY NZ (an addition as well) renders no frame: it bakes a regular grid of light probes inside the octree's root box, one at the centre
 of each of the NX x NY x NZ cells, with --probe-samples N rays each (default 256), after the photon pass, and writes their spherical-harmonic
 coefficients to -o as a numpy array [NZ][NY][NX][9][3] (float32; include/gi_hip.h: GI_BAKE_SH9).  The frame's flags do not go with it.
+--lightmap W H (an addition too) renders no frame either: it bakes a W x H lightmap atlas (include/gi_hip.h: gi_lightmap_*) over the scene's own
+texture coordinates, read as an unwrapped chart (v grows downwards) -- of the triangles of material index --lightmap-material M, or of all triangles
+-- with --lightmap-samples N rays per covered texel (default 256) and --lightmap-dilate D gutter passes (default 2), after the photon pass.  -o gets
+the 8-bit PPM of the display transform, --pfm the linear atlas; one line gives the number of covered texels and the device time.
 """
 import argparse
 import os
@@ -46,6 +52,7 @@ import gi_raytracer_amd as gi
 
 FEATURE_FILES = ("albedo", "normal", "depth", "coverage")
 PROBE_SAMPLES = 256
+LIGHTMAP_SAMPLES = 256
 
 
 def parser():
@@ -82,6 +89,10 @@ def parser():
     ap.add_argument("--focus-pixel", type=int, nargs=2, default=None, metavar=("X", "Y"), help="with --aperture: focus on the first surface behind the centre of this pixel")
     ap.add_argument("--probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="bake a grid of light probes in the scene's box instead of a frame; -o gets a .npy [NZ][NY][NX][9][3]")
     ap.add_argument("--probe-samples", type=int, default=None, metavar="N", help="with --probes: rays per probe (default 256)")
+    ap.add_argument("--lightmap", type=int, nargs=2, default=None, metavar=("W", "H"), help="bake a W x H lightmap atlas over the scene's texture coordinates instead of a frame")
+    ap.add_argument("--lightmap-material", type=int, default=None, metavar="M", help="with --lightmap: only the triangles of this material index (default: all triangles)")
+    ap.add_argument("--lightmap-samples", type=int, default=None, metavar="N", help="with --lightmap: rays per covered texel (default 256)")
+    ap.add_argument("--lightmap-dilate", type=int, default=None, metavar="D", help="with --lightmap: gutter dilation passes, 0 .. 64 (default 2)")
     return ap
 
 
@@ -115,6 +126,23 @@ def check_args(ap, a):
         frame_flags = (a.pfm, a.samples, a.features, a.feature_samples, a.denoise, a.progressive, a.upsample, a.occlusion, a.aperture)
         if any(f is not None for f in frame_flags):
             ap.error("--probes renders no frame: only --photons, --probe-samples, --device and -o go with it")
+    if a.lightmap is None and (a.lightmap_material is not None or a.lightmap_samples is not None or a.lightmap_dilate is not None):
+        ap.error("--lightmap-material, --lightmap-samples and --lightmap-dilate need --lightmap W H")
+    if a.lightmap is not None:
+        w, h = a.lightmap
+        if not (1 <= w <= 8192 and 1 <= h <= 8192):
+            ap.error("--lightmap W H: two numbers from 1 to 8192")
+        if a.lightmap_samples is not None and a.lightmap_samples < 1:
+            ap.error("--lightmap-samples N: N must be at least 1")
+        if a.lightmap_dilate is not None and not 0 <= a.lightmap_dilate <= 64:
+            ap.error("--lightmap-dilate D: D from 0 to 64")
+        if a.lightmap_material is not None and a.lightmap_material < 0:
+            ap.error("--lightmap-material M: a material index >= 0")
+        if w * h * (a.lightmap_samples or LIGHTMAP_SAMPLES) > 2 ** 32:
+            ap.error("--lightmap: texels x samples must keep the stream index within 32 bits")
+        frame_flags = (a.samples, a.features, a.feature_samples, a.denoise, a.progressive, a.upsample, a.occlusion, a.aperture, a.probes)
+        if any(f is not None for f in frame_flags):
+            ap.error("--lightmap renders no frame: only --lightmap-*, --photons, --device, -o and --pfm go with it")
     if a.upsample is None and a.upsample_pfm:
         ap.error("--upsample-pfm needs --upsample S")
     if a.occlusion is None and (a.occlusion_samples is not None or a.occlusion_dirs is not None or a.occlusion_radius is not None):
@@ -256,6 +284,18 @@ def main(argv=None):
         replace_file(a.output, lambda t: write_npy(t, sh))
         print(f"{a.scene}: {nx} x {ny} x {nz} probes of {ns} samples, {stored} photons stored; photon pass {t1 - t0:.2f} s, "
               f"bake {rt.last_bake_ms():.2f} ms -> {a.output}")
+        return 0
+    if a.lightmap:
+        w, h = a.lightmap
+        ns = a.lightmap_samples or LIGHTMAP_SAMPLES
+        ent, uv = gi.chart_of_material(scene, a.lightmap_material)
+        atlas, _, n_cov = rt.bake_lightmap(ent, uv, w, h, ns, dilate=2 if a.lightmap_dilate is None else a.lightmap_dilate, f64=False, want_owner=True)
+        gi.save_ppm(a.output, atlas)
+        if a.pfm:
+            gi.save_pfm(a.pfm, atlas)
+        ms, stages = rt.last_lightmap_ms()
+        print(f"{a.scene}: lightmap {w}x{h}, {len(ent)} chart triangles, {n_cov} texels covered, {ns} samples each, {stored} photons stored; "
+              f"photon pass {t1 - t0:.2f} s, lightmap {ms:.2f} ms (raster {stages['raster']:.2f}, bake {stages['bake']:.2f}, dilate {stages['dilate']:.2f}) -> {a.output}")
         return 0
     feat = lens_note = ""
     lens = lens_of(a)

@@ -151,9 +151,11 @@ struct BakeQuiet {
     ~BakeQuiet() { c->clock.stage_timing = timing; c->count_stream = counting; }
 };
 
-// the bake itself: d_points and d_out on the device, arguments checked
-int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake_params& bp, void* d_out, int out_is_f64)
+// the bake itself: d_points and d_out on the device, arguments checked.  timer: the events around it -- the bake's own, or those of a pass that
+// bakes as one of its stages (gi_lightmap.inc) and leaves gi_last_bake_ms alone
+int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake_params& bp, void* d_out, int out_is_f64, EventTimer* timer = nullptr)
 {
+    EventTimer& tm = timer ? *timer : c->bake.timer;
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t n_samples = (uint32_t)bp.n_samples;
     const int n_shadow = defers_shadows(c) ? c->S.n_light : 0;
@@ -185,7 +187,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
     double* const dirs = bp.mode == GI_BAKE_SH9 ? c->bake.d_dirs.p : nullptr;
     const size_t out_row = (size_t)terms * (out_is_f64 ? 8 : 4);
     int launches = 0;
-    HIP_TRY(c, c->bake.timer.begin(st));
+    HIP_TRY(c, tm.begin(st));
     for (uint32_t i0 = 0; i0 < n_points; i0 += pl.chunk_points) {
         const uint32_t np = std::min(pl.chunk_points, n_points - i0);
         F.w = (int32_t)np;
@@ -202,7 +204,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
                                make_path_pool(c->st.d_spool.p, c->st.spool_slots), c->st.d_slot_sample.p, dirs, c->st.work.q_new.p, c->st.d_wfcnt.p);
             HIP_TRY(c, hipGetLastError());
             RoundRefill refill(F, np * nk);      // every sample of the range starts: the count needs no read-back
-            if (const int rc = stream_passes(c, F, c->st.d_slot_sample.p, 0ull, c->st.d_lbuf.p, 0u, refill, debug_wf, nullptr, launches)) { c->bake.timer.reset(); return rc; }
+            if (const int rc = stream_passes(c, F, c->st.d_slot_sample.p, 0ull, c->st.d_lbuf.p, 0u, refill, debug_wf, nullptr, launches)) { tm.reset(); return rc; }
             const int first = k0 == 0, last = k0 + nk == n_samples;
             void* const out = (char*)d_out + (size_t)i0 * out_row;
             const dim3 grid((np + GI_BLOCK - 1) / GI_BLOCK), block(GI_BLOCK);
@@ -213,7 +215,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
             HIP_TRY(c, hipGetLastError());
         }
     }
-    HIP_TRY(c, c->bake.timer.end(st));
+    HIP_TRY(c, tm.end(st));
     return GI_OK;
 }
 

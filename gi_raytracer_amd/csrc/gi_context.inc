@@ -6,7 +6,7 @@
 //   Tuning        every value taken from the environment when the context is made (from_env), and the two limits the setters change
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
-//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake
+//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake, lightmap
 // Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
@@ -61,6 +61,7 @@ struct SceneStore {
     WalkCuts cuts;                        // of the scene last uploaded: what it allows the walks' short cuts (gi_layout.h)
     DevBuf<TriGeom> d_tris;
     DevBuf<TriShade> d_shade;
+    std::vector<uint32_t> tri_flags;      // TriGeom::flags of every entity, on the host: gi_lightmap_host refuses a chart row that names a sphere
     DevBuf<Mat> d_mats;
     DevBuf<LightD> d_lights;
     DevBuf<FogD> d_fogs;
@@ -83,6 +84,8 @@ struct SceneStore {
         cuts = H.walk_cuts();
         up(d_tris, H.tris); up(d_shade, H.shade); up(d_mats, H.mats); up(d_lights, H.lights); up(d_fogs, H.fogs); up(d_fog_grid, H.fog_grid);
         if (e != hipSuccess) return e;
+        tri_flags.resize(H.tris.size());
+        for (size_t i = 0; i < H.tris.size(); i++) tri_flags[i] = H.tris[i].flags;
         S.tnodes = d_tnodes.p; S.leaf_refs = d_refs.p; S.leaf_tris = d_leaf_tris.p; S.tris = d_tris.p; S.shade = d_shade.p;
         S.mats = d_mats.p; S.lights = d_lights.p;
         S.n_node = H.n_node; S.n_tri = H.n_tri; S.n_light = H.n_light;
@@ -193,18 +196,21 @@ struct Tuning {
 enum { STG_REGEN = 0, STG_TRACE, STG_SHADE, STG_SORT, STG_GATHER, STG_FINISH, STG_ACCUM, STG_OTHER, STG_SHADOW, STG_COUNT };
 
 // Per-stage device time of the last streaming frame: a pair of HIP events around every timed stage, on the frame's stream; the pool of events
-// grows with the longest frame and is kept.
+// grows with the longest frame and is kept.  The sums are computed once per frame: the runtime's answer for one pair of events is not the same
+// number at every call (it was seen to move by a nanosecond between two calls with nothing recorded in between), and a time that nothing has
+// touched must read the same.
 struct StageClock {
     std::vector<hipEvent_t> ev_pool;
     std::vector<int> ev_stage;        // stage id of event pair k (events 2k, 2k+1)
     size_t ev_used = 0;
     bool stage_timing = true;
+    bool summed = false;              // stage_ms holds the sums of the pairs recorded so far: read() has nothing to do
     float stage_ms[STG_COUNT_MAX] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     StageClock() = default;
     StageClock(const StageClock&) = delete;
     StageClock& operator=(const StageClock&) = delete;
     ~StageClock() { for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e); }
-    void restart() { ev_used = 0; ev_stage.clear(); }   // a new frame
+    void restart() { ev_used = 0; ev_stage.clear(); summed = false; }   // a new frame
     void begin(int stage, hipStream_t st)
     {
         if (!stage_timing) return;
@@ -212,6 +218,7 @@ struct StageClock {
             for (int k = 0; k < 2; k++) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; ev_pool.push_back(e); }
         }
         ev_stage.push_back(stage);
+        summed = false;
         (void)hipEventRecord(ev_pool[ev_used], st);
     }
     void end(hipStream_t st)
@@ -221,15 +228,20 @@ struct StageClock {
         ev_used += 2;
     }
     // stage_ms = the sums of the pairs recorded since restart(); debug: a "[stage]" line per pair (GI_DEBUG_STAGES)
+    // (kept once every pair has answered; a pair that is not ready yet is asked again at the next call)
     void read(bool debug)
     {
+        if (summed && !debug) return;
         for (int k = 0; k < STG_COUNT_MAX; k++) stage_ms[k] = 0;
         const size_t n_pairs = std::min({ev_used / 2, ev_stage.size(), ev_pool.size() / 2});
+        bool all = true;
         for (size_t k = 0; k < n_pairs; k++) {
             float t = 0;
             if (hipEventElapsedTime(&t, ev_pool[2 * k], ev_pool[2 * k + 1]) == hipSuccess) stage_ms[ev_stage[k]] += t;
+            else all = false;
             if (debug) fprintf(stderr, "[stage] %d %.3f ms\n", ev_stage[k], t);
         }
+        summed = all;
     }
 };
 
@@ -341,6 +353,15 @@ struct DenoisePass : AuxPass {
 struct BakePass : AuxPass {
     DevBuf<double> d_dirs, d_sums;
 };
+// a lightmap (gi_lightmap.inc): the stage timers beside the pass's own, and its scratch, sized on first use and kept.  work [6 T] f64 holds the
+// texels' points until they are compacted and the two dilation buffers [T][3] after the bake
+struct LightmapPass : AuxPass {
+    EventTimer t_stage[3];            // raster + rank, bake, scatter + dilate
+    DevBuf<int32_t> d_own, d_texel;   // [T] owner row (the raster's atomicMin table, then -1 where not covered); [n_cov] texel of a table row
+    DevBuf<uint32_t> d_rank, d_blk;   // [T] row of a covered texel; covered texels per workgroup, scanned
+    DevBuf<double> d_work, d_points, d_rows;   // d_points [n_cov][6], d_rows [n_cov][3]: the bake's input and output
+    DevBuf<unsigned char> d_fill;     // [2][T] filled flags of the two dilation buffers
+};
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
 struct gi_ctx {
@@ -381,6 +402,7 @@ struct gi_ctx {
     AuxPass feat, ao, up;             // gi_render_features_*, gi_render_occlusion_*, gi_upsample_*
     DenoisePass dn;                   // gi_denoise_*
     BakePass bake;                    // gi_bake_*
+    LightmapPass lm;                  // gi_lightmap_*
 };
 
 namespace {

@@ -1730,4 +1730,5 @@ __global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint3
 #include "gi_entries.inc"        // function-level entries (parity tests, public C++ methods) and the debug entries
 #include "gi_lens.inc"           // the thin lens: gi_set_lens, its vertex table, gi_debug_primary_rays, gi_focus_distance
 #include "gi_bake.inc"           // light baking: k_bake_gen, k_bake_fold and gi_bake_*
+#include "gi_lightmap.inc"       // lightmap atlases: k_lm_raster, k_lm_point, the rank, k_lm_scatter, k_lm_dilate and gi_lightmap_*
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

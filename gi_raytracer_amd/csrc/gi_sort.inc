@@ -98,8 +98,8 @@ __global__ __launch_bounds__(GI_RS_BLOCK) void k_rs_hist(const uint32_t* keys, c
     for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) ghist[(size_t)i * gridDim.x + blockIdx.x] = hist[i];
 }
 
-// exclusive prefix sums over ghist[bin][workgroup] in that order (one workgroup; total <= 512 x 2 048 counters), 8 192 counters at a time through LDS
-// so that the global reads and writes are coalesced
+// exclusive prefix sums over ghist[bin][workgroup] in that order (one workgroup; any total -- the sort's is at most 512 x 2 048 counters, the
+// lightmap's rank passes one count per 256 texels, up to 262 145), 8 192 counters at a time through LDS so that the global reads and writes are coalesced
 __global__ __launch_bounds__(1024) void k_rs_scan(uint32_t* ghist, uint32_t total)
 {
     __shared__ uint32_t buf[8192];

@@ -265,6 +265,27 @@ class RayTracer {
     {
         return bake(GI_BAKE_TEXEL, pointsAndNormals, 6, 3, samples, streamBase, out);
     }
+    // bakeLightmap (gi_lightmap_host): the chart -- ent [n] triangle entities of the uploaded scene, uv [n][3][2] their chart coordinates, v growing
+    // with the row -- rasterised into width x height texels, the covered ones baked as bakeTexels does, put back into the image and dilated `dilate`
+    // times.  atlas gets [height][width][3]; owner (optional) [height][width], the chart row of a covered texel or -1; nCovered (optional) their number.
+    bool bakeLightmap(const std::vector<int32_t>& ent, const std::vector<double>& uv, int width, int height, int samples, std::vector<double>& atlas,
+                      int dilate = 2, bool flip = false, uint32_t streamBase = 0, std::vector<int32_t>* owner = nullptr, int* nCovered = nullptr)
+    {
+        if (!ready()) return false;
+        if (uv.size() != ent.size() * 6 || ent.size() > 0x7fffffffu) { _st->err = "bakeLightmap: uv must hold three coordinate pairs per chart row"; return false; }
+        gi_lightmap_params p;
+        gi_lightmap_default_params(&p);
+        p.width = width; p.height = height; p.n_samples = samples; p.dilate = dilate; p.flip = flip ? 1 : 0; p.stream_base = streamBase; p.seed = seed;
+        const size_t T = width > 0 && height > 0 && width <= 8192 && height <= 8192 ? (size_t)width * (size_t)height : 0;
+        std::vector<double> buf(T * 3 + 1);
+        std::vector<int32_t> own(T + 1);
+        int32_t n = 0;
+        if (check(gi_lightmap_host(_st->ctx, &p, (int32_t)ent.size(), ent.data(), uv.data(), buf.data(), 1, owner ? own.data() : nullptr, &n)) != 0) return false;
+        atlas.assign(buf.begin(), buf.begin() + T * 3);
+        if (owner) owner->assign(own.begin(), own.begin() + T);
+        if (nCovered) *nCovered = n;
+        return true;
+    }
 
     // ---- ADDITION (the reference has no denoiser): the edge-avoiding a-trous filter of gi_denoise_host (include/gi_hip.h states the formula) on a
     // whole frame.  color = [height][width][3] linear radiance of a feat.width x feat.height frame, feat = what renderFeatures filled; out gets

@@ -539,6 +539,66 @@ int gi_last_bake_ms(gi_ctx*, float* ms);
 int gi_bake_rays(gi_ctx*, const double* points, int32_t n_points, const gi_bake_params*, double* rays6_out, uint32_t* stream_out);
 int gi_bake_fold(gi_ctx*, int32_t mode, int32_t n_points, int32_t n_samples, const double* dirs3, const double* L3, double* out);
 
+/* Lightmap atlases -- an ADDITION around the bake: the UV chart of a mesh rasterised into texels, the covered texels baked as GI_BAKE_TEXEL points,
+ * the rows scattered back into an image and the gutters filled, in one device-side pass.  An atlas image comes back, not a point list.
+ * A lightmap is baked for a CHART of n_chart rows.  Row j holds ent[j], an entity index that must be a triangle (0 <= ent < n_tri, not an analytic
+ * sphere), and uv[j][3][2], three finite f64 chart coordinates for the triangle's vertices 0, 1 and 2.  The chart is the caller's, a second UV set:
+ * the scene's texture coordinates play no part on the device.  The same entity may appear in several rows.
+ * The atlas is width x height texels.  Texel (x, y) is in row y from the top and has index t = y * width + x; its centre is
+ *     pu = ((double) x + 0.5) / (double) width,  pv = ((double) y + 0.5) / (double) height
+ * v grows with the row index; there is no wrap and no flip.  All arithmetic below is f64, IEEE + - * / only, in the order written, compiled without
+ * contraction, so that it can be restated bit for bit (tests/lightmap_expect.py).
+ * Coverage.  E(a, b, p) = (b.x - a.x) * (p.y - a.y) - (b.y - a.y) * (p.x - a.x).  For row j with chart vertices a, b, c: area = E(a, b, c),
+ *   e0 = E(b, c, p), e1 = E(c, a, p), e2 = E(a, b, p).  A row with area == 0 or a non-finite area covers nothing.  Otherwise the row covers p iff
+ *   p lies in the row's chart box -- min(a.x, b.x, c.x) <= p.x <= max(a.x, b.x, c.x) and the same in y, plain comparisons, both ends included --
+ *   AND the edge test passes: e0 >= 0 && e1 >= 0 && e2 >= 0 if area > 0, all three <= 0 if area < 0.  Edges are inclusive: a texel centre on an
+ *   edge shared by two rows is claimed by both.  The box is part of the definition, not a short cut: where the three vertices are collinear up to
+ *   rounding the area is a tiny non-zero number and the edge values round to 0 or to its sign all along the line EXTENDED; the box ends such a
+ *   sliver at its vertices.  The OWNER of a texel is the lowest row index that covers it.  Nothing of the result depends on the launch, nor on
+ *   the size of the coordinates: which texels the rasteriser visits for a row is its own business, it applies this test to each.
+ * Point of an owned texel.  b1 = e1 / area, b2 = e2 / area.  With the entity's vertex 0 and edges p0, e1v = p1 - p0, e2v = p2 - p0: per component
+ *   P = (p0 + b1 * e1v) + b2 * e2v.  If the entity interpolates normals (all three vertex normals non-zero), N = ((1 - b1 - b2) * n0 + b1 * n1) + b2 * n2,
+ *   else N = the face normal normalize(cross(p1 - p0, p2 - p0)).  params.flip != 0 negates N.  A texel whose N is 0 0 0 or not finite is NOT COVERED:
+ *   its owner is reported as -1, and no other row inherits it.
+ * Rank.  Covered texels are numbered i = 0 .. n_cov - 1 in ascending t.  points[n_cov][6] = P, N with texel[n_cov] = t is a GI_BAKE_TEXEL point list,
+ *   and the bake is exactly gi_bake_* on it: sample k of covered texel i runs on stream_base + i * n_samples + k, with the same fold, the same
+ *   chunking freedom and the same seed meaning.  Direct light of the analytic lights is not in it, as in every bake.
+ * Scatter and dilation.  The atlas value of a covered texel is its bake row, f64.  Then `dilate` passes run.  In each pass, every texel that is not
+ *   filled at the start of the pass and has at least one filled 8-neighbour takes the sum of its filled neighbours' values, from +0.0 in the order
+ *   (x-1,y-1) (x,y-1) (x+1,y-1) (x-1,y) (x+1,y) (x-1,y+1) (x,y+1) (x+1,y+1), divided by (double) count; neighbours outside the atlas do not exist.
+ *   The texel is filled from the next pass on (a pass reads only the state before it).  Texels still unfilled at the end are 0 0 0.
+ * Outputs: atlas [height][width][3], float (out_is_f64 = 0) or double (1), rounded once on store; optionally owner [height][width] int32, the chart
+ * row of a covered texel and -1 otherwise (dilated texels stay -1); optionally *n_covered.
+ * GI_E_INVALID: a null pointer where one is needed (ent and uv may be null when n_chart is 0, which is GI_OK and gives an all-zero atlas with owner
+ * -1), width or height outside 1 .. 8192, n_samples < 1, dilate outside 0 .. 64, flip other than 0 / 1, n_chart < 0,
+ * stream_base + width * height * n_samples beyond 2^32 (every texel may be covered), and -- the host entries, which look at the chart -- an entity
+ * index out of range, an entity that is a sphere, a non-finite coordinate.  gi_lightmap_device does NOT look at its chart, apart from clamping ent
+ * to the entity tables.  GI_E_STATE: no scene.  A refused call touches no output and no timer.
+ * gi_lightmap_default_params: 256 x 256, 256 samples, dilate 2, flip 0, stream_base 0, seed 0x9E3779B97F4A7C15.
+ * gi_lightmap_device: DEVICE pointers for ent, uv, atlas and owner (n_covered is a host pointer); it waits for the stream once, to size the bake.
+ * Scratch: 58 bytes per texel and 76 per covered texel of device memory, kept by the context for the next call; the host entries give it back when
+ * they return if the atlas has more than 2^22 texels, gi_lightmap_device keeps it until a host entry or gi_destroy frees it.
+ * gi_last_lightmap_ms: device time of the last lightmap, and per stage in stages3 (may be null): raster + rank, bake, scatter + dilate.
+ * gi_last_bake_ms, the frame's and the other passes' times keep their values across a lightmap; an open progressive session is left as it is.
+ * Check entries (host pointers): gi_lightmap_texels gives the texel table -- owner [height][width], *n_covered, points6 [cap][6], texel [cap];
+ * cap < n_covered is GI_E_INVALID, but *n_covered and owner are still written.  gi_lightmap_dilate runs `passes` dilation passes on caller data:
+ * values3 [height][width][3], filled [height][width] (0 / non-zero; the values of unfilled texels are not read), out3 [height][width][3]; no scene needed.
+ * There is no gi_group_* form: split the atlas by rows of covered texels with stream_base, as the bake documents. */
+typedef struct gi_lightmap_params {
+    int32_t width, height;   /* 1 .. 8192 each */
+    int32_t n_samples;       /* >= 1 directions per covered texel */
+    int32_t dilate;          /* 0 .. 64 passes */
+    int32_t flip;            /* 0 / 1: negate the normals */
+    uint32_t stream_base;    /* stream index of sample 0 of covered texel 0 */
+    uint64_t seed;           /* counter-RNG seed, as gi_bake_params::seed */
+} gi_lightmap_params;
+void gi_lightmap_default_params(gi_lightmap_params*);
+int gi_lightmap_host(gi_ctx*, const gi_lightmap_params*, int32_t n_chart, const int32_t* ent, const double* uv, void* h_atlas, int out_is_f64, int32_t* h_owner, int32_t* n_covered);
+int gi_lightmap_device(gi_ctx*, const gi_lightmap_params*, int32_t n_chart, const int32_t* d_ent, const double* d_uv, void* d_atlas, int out_is_f64, int32_t* d_owner, int32_t* n_covered);
+int gi_last_lightmap_ms(gi_ctx*, float* ms, float* stages3);
+int gi_lightmap_texels(gi_ctx*, const gi_lightmap_params*, int32_t n_chart, const int32_t* ent, const double* uv, int32_t* owner, int32_t* n_covered, double* points6, int32_t* texel, int32_t cap);
+int gi_lightmap_dilate(gi_ctx*, int32_t width, int32_t height, int32_t passes, const double* values3, const int32_t* filled, double* out3);
+
 #ifdef __cplusplus
 }
 #endif
