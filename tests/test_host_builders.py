@@ -128,7 +128,7 @@ def test_scene_tree_leaves_list_exactly_the_entities_that_touch_them(name):
     assert 0 in kind and (1 in kind or name != "spheres")        # triangles in both scenes, spheres in the second
     ebox = np.zeros((len(kind), 6))
     for e in range(len(kind)):
-        assert L.gih_entity_bbox(int(kind[e]), _p(pos[e]), _p(ebox[e])) == 0
+        assert L.gih_entity_bbox(kind[e], _p(pos[e]), _p(ebox[e])) == 0
     inner = (child >= 0).any(axis=1)
     listed = np.zeros((len(box), len(kind)), bool)
     listed[np.repeat(np.arange(len(box)), np.diff(off)), idx] = True
@@ -137,7 +137,7 @@ def test_scene_tree_leaves_list_exactly_the_entities_that_touch_them(name):
     touch = ((box[:, None, :3] <= ebox[None, :, 3:]) & (box[:, None, 3:] >= ebox[None, :, :3])).all(axis=2)
     pairs = np.argwhere(touch)
     for i, e in pairs:
-        touch[i, e] = L.gih_entity_overlaps_box(int(kind[e]), _p(pos[e]), _p(box[i])) == 1
+        touch[i, e] = L.gih_entity_overlaps_box(kind[e], _p(pos[e]), _p(box[i])) == 1
     print(f"{name}: {len(box)} nodes, {int((~inner).sum())} leaves, {len(kind)} entities, {len(pairs)} cell tests")
     assert np.array_equal(listed[~inner], touch[~inner])
     kids = child[child >= 0]
@@ -179,9 +179,9 @@ def test_box_mesh_and_fog_grid_match_the_scn_keywords(tmp_path):
         meshes.append(out.reshape(12, 3, 3))
     for f in fogs:
         par = np.array([*f[0], *f[1], *f[2], *f[3:]], float)
-        n = L.gih_fog_grid(_p(par), C.c_uint64(gi.DEFAULT_SEED), None, 0)
+        n = L.gih_fog_grid(_p(par), gi.DEFAULT_SEED, None, 0)
         g = np.zeros(n)
-        assert n == (f[1][0] + 1) * (f[1][1] + 1) * (f[1][2] + 1) * f[5] ** 3 and L.gih_fog_grid(_p(par), C.c_uint64(gi.DEFAULT_SEED), _p(g), n) == n
+        assert n == (f[1][0] + 1) * (f[1][1] + 1) * (f[1][2] + 1) * f[5] ** 3 and L.gih_fog_grid(_p(par), gi.DEFAULT_SEED, _p(g), n) == n
         grids.append(g)
     scn = tmp_path / "parts.scn"
     lines = ["colorTex 0 0 0", "colorTex 1 1 1", "mat 1 0 1 1 1"]
