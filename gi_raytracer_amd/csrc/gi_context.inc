@@ -114,7 +114,7 @@ struct PhotonStore {
     DevBuf<uint32_t> d_pcand_off;                            // build_photon_candidates
     DevBuf<double> d_pcand, d_pcand_dc;
     DevBuf<PDescent> d_pdescent;                             // build_photon_descent
-    DevBuf<int32_t> d_pjump;          // its jump table (gi_device.h: gather_find_leaf_fast)
+    DevBuf<int32_t> d_pjump;          // its jump table (gi_gather.h: gather_find_leaf_fast)
     DevBuf<double> d_pjump_aux;
     bool pdescent_ready = false, pjump_ready = false;   // d_pdescent / d_pjump hold the tables of the current photon map (apply_switches decides on their use)
 };

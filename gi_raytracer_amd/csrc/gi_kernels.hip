@@ -4,6 +4,8 @@
 //   k_render     the pixel loop of RayTracer::run with the whole path inside (include/raytracer.h:93-160,167-579)
 //   k_trace / k_visible / k_gather / k_radiance   function-level entry points (parity tests, public C++ methods)
 //   k_emit       RayTracer::tracePhotons (include/raytracer.h:582-715), one (photon index, light) per lane
+// The photon gather's kernels (k_st_gather, k_st_gather_wave, k_gather, ...) are in gi_gather.inc, included behind k_st_compact; what they share
+// with the per-lane gather is in gi_gather.h (through gi_device.h).
 // This file holds kernels only.  The host side -- the context, the scheduler and the gi_* entry points -- is in the .inc files listed at its end,
 // which also hold the kernels of the sort, the photon-map build and the auxiliary passes.  No CPU fallback exists: every entry needs a HIP device.
 #include <hip/hip_runtime.h>
@@ -1026,23 +1028,6 @@ __global__ __launch_bounds__(256) void k_pjump(const PDescent* pd, const double*
     }
     out[i] = node;
 }
-__global__ void k_find_leaves(Scene S, int32_t n, const double* pos, int32_t* fast, int32_t* full)   // gi_debug_find_leaves
-{
-    for (int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x); i < n; i += (int32_t)(gridDim.x * blockDim.x)) {
-        const V3 p = v3(pos[(size_t)i * 3], pos[(size_t)i * 3 + 1], pos[(size_t)i * 3 + 2]);
-        fast[i] = S.pdescent ? gather_find_leaf_fast(S, p) : -2;
-        full[i] = gather_find_leaf(S, p);
-    }
-}
-// The sort key of a gather query (k_st_compact's gather queue, gi_debug_gather_pass): the rank of the photon-map leaf around the position among the
-// leaves with candidates; n_pleaf, the key past the last leaf, when there is nothing to gather (outside the map, a leaf without candidates)
-__device__ __forceinline__ uint32_t gather_key(const Scene& S, V3 pos)
-{
-    int32_t leaf = S.pdescent ? gather_find_leaf_fast(S, pos) : -2;
-    if (leaf == -2) leaf = gather_find_leaf(S, pos);
-    const int32_t rank = leaf < 0 ? -1 : S.pleaf_rank[leaf];
-    return rank < 0 ? (uint32_t)S.n_pleaf : (uint32_t)rank;
-}
 struct CompactStream { const uint32_t* src; uint32_t* dst; int width; };
 struct CompactJob {
     CompactStream st[5];    // streams of queue A (e.g. slot + key), then queue B, queue C: n_streams[q] streams each
@@ -1119,267 +1104,8 @@ __global__ __launch_bounds__(256) void k_st_compact(Scene S, CompactJob job, con
     }
 }
 
-// Gather queries are sorted by the photon-map leaf that contains them (keys from k_st_compact): queries of one leaf share their candidate
-// photons, so the lanes of a wave read the same photons and run loops of equal length.
-// Queries arrive sorted by leaf, and a leaf typically serves thousands of queries per pass, so most waves hold 64 queries of ONE
-// leaf: such a wave copies the leaf's candidate photons into LDS once (64 at a time, one photon per lane, coalesced) and every lane
-// scans them from there -- a broadcast LDS read per candidate instead of an L2 round trip per lane.  Waves that straddle a leaf
-// boundary take the per-lane walk.  Both run g_key / g_acc / g_end, i.e. the same arithmetic in the same order.
-#define GI_GCHUNK 64
-#ifndef GI_GATHER_WAVES
-#define GI_GATHER_WAVES 4      // waves per SIMD the gather kernel is compiled for (launch bound)
-#endif
-// Pass 1 of the cooperative path keeps a lane's 32 smallest keys sorted in registers and folds the candidates in 32 at a time
-// (ksel_tau, gi_device.h): 18 branch-free instructions per candidate; the LDS heap costs ~55, because with 64 lanes some lane always has
-// to sift, so the wave pays a full sift for nearly every candidate.  The result (tau = 32nd smallest float key) is the same number.
-static_assert(GI_GCHUNK == 64, "ksel_tau stages the candidates 64 at a time");
-template <bool COUNT>
-__global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S, PathPool pool, const uint32_t* keys, const uint32_t* vals, uint32_t n_in,
-                                                                         const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
-{
-    unsigned long long n_q = 0, n_c = 0;   // COUNT: queries of this lane, candidates they scanned (a leaf's whole candidate list per query, as PhotonMap::getInRange returns it)
-    // 8 KB of LDS per wave: the staged candidates of the cooperative path (64 x 9 doubles) or the float heaps of the per-lane walk (32 x 64),
-    // never both at once -- a wave is in one of the two, and the tie pass runs after the last candidate was read
-    __shared__ __align__(16) float lds[GI_GATHER_K * GI_BLOCK];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    float* const heap = lds + wave * (GI_GATHER_K * 64) + lane;                       // element i of this lane's heap at heap[i * 64]
-    double (*const cand)[9] = reinterpret_cast<double (*)[9]>(lds + wave * (GI_GATHER_K * 64));   // cand[k] = staged candidate k of this wave
-    // the waves of a workgroup draw its chunks of the grid-stride loop 64 queries at a time (k_st_shade): leaves differ in candidates
-    __shared__ unsigned int s_next;
-    if (threadIdx.x == 0) s_next = 0u;
-    __syncthreads();
-    const uint32_t cs = (uint32_t)GI_GATHER_CHUNK;
-    const uint32_t total = seg_start(blockIdx.x + 1, n_in, gridDim.x, cs) - seg_start(blockIdx.x, n_in, gridDim.x, cs);
-    for (;;) {
-        unsigned int u = 0;
-        if (lane == 0) u = atomicAdd(&s_next, 64u);
-        u = (unsigned int)__shfl((int)u, 0);
-        if (u >= total) break;
-        const uint32_t i = chunk_item(u, cs) + lane;
-        const bool valid = i < n_in;
-        const uint32_t rank = valid ? keys[i] : 0xffffffffu;                       // rank of the query's leaf among the leaves with candidates
-        const bool has_leaf = valid && rank < (uint32_t)S.n_pleaf;
-        const uint32_t leaf = has_leaf ? (uint32_t)S.prank_leaf[rank] : 0xffffffffu;
-        const uint32_t leaf0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
-        const bool uniform = __ballot(valid && leaf != leaf0) == 0ull && leaf0 < (uint32_t)S.n_pnode;
-        if constexpr (COUNT) { if (valid) n_q++; }
-        if (!uniform) {
-            if (has_leaf) {
-                if constexpr (COUNT) n_c += (unsigned long long)S.pnodes[leaf].u.lf.nb_photons;
-                PathRef pr = pool[vals[i]];
-                stage_gather_in_leaf(S, pr, (int32_t)leaf, heap, 64, lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3);
-            }
-            continue;
-        }
-        const uint32_t rank0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rank);
-        const PNode& lf = S.pnodes[leaf0];
-        const int ncand = lf.u.lf.nb_photons;
-        if constexpr (COUNT) { if (valid) n_c += (unsigned long long)ncand; }
-        if (ncand == 0) continue;
-        const PRange* ranges = S.pranges + lf.nb_off;
-        GatherAcc a;
-        const uint32_t gslot = valid ? vals[i] : 0u;
-        g_begin(a, valid ? ld3(pool.hit[gslot].hpos) : v3(0, 0, 0), valid ? ld3(pool.gath[gslot].gdir) : v3(0, 0, 0), heap, 64, ncand);
-        // the leaf's candidates as one sequence (its ranges back to back, the order gather_in_leaf visits them), 64 per step: candidates
-        // [c0, c0 + m) into cand[0, m), positions only or (all9) positions, directions and colours
-        auto stage = [&](int32_t c0, int32_t m, bool all9) {
-            __builtin_amdgcn_wave_barrier();
-            if ((int32_t)lane < m) {
-                const double* pp;
-                const double* dc;
-                if (S.pcand) {
-                    const size_t at = (size_t)S.pcand_off[rank0] + (size_t)(c0 + (int32_t)lane);
-                    pp = S.pcand + at * 3; dc = S.pcand_dc + at * 6;
-                } else {
-                    int32_t off = c0 + (int32_t)lane, r = 0;
-                    while (off >= ranges[r].count) { off -= ranges[r].count; r++; }   // r < n_ranges: off < ncand = sum of the counts
-                    const size_t ph = (size_t)(ranges[r].first + off);
-                    pp = S.ph_pos + ph * 3; dc = S.ph_dircol + ph * 6;
-                }
-                cand[lane][0] = pp[0]; cand[lane][1] = pp[1]; cand[lane][2] = pp[2];
-                if (all9)
-                    for (int k = 0; k < 6; k++) cand[lane][3 + k] = dc[k];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        };
-        // pass 1 runs the chunks from the last to the first and stages chunk 0 whole, so pass 2 (chunks in candidate order) finds it in LDS
-        a.tau = ksel_tau(ncand, [&](int32_t c0, int32_t m) { stage(c0, m, c0 == 0); }, [&](int32_t k) {
-            const double* q = cand[k];
-            return (float)len2(v3(q[0], q[1], q[2]) - a.pos);   // same expression as g_key
-        });
-        for (int32_t c0 = 0; c0 < ncand; c0 += GI_GCHUNK) {
-            const int32_t m = min((int32_t)GI_GCHUNK, ncand - c0);
-            if (c0 != 0) stage(c0, m, true);
-            if (valid) {
-                // g_acc per candidate, with the rare case set aside: a candidate whose key EQUALS tau (the 32nd smallest itself; one per
-                // query, more only when float keys tie) is some lane's business for nearly every candidate of the wave, so its branch --
-                // a sum of its own, a count, a running maximum -- would run for nearly every candidate.  The loop only notes where such
-                // candidates are; they are added afterwards, in candidate order, by the same g_acc.
-                int n_eq = 0;
-                int32_t k_eq = 0;
-                for (int32_t k = 0; k < m; k++) {
-                    const double* q = cand[k];
-                    const double d2 = len2(v3(q[0], q[1], q[2]) - a.pos);
-                    const float key = (float)d2;
-                    if (key < a.tau) {
-                        const V3 contrib = v3(q[6], q[7], q[8]) * dot(v3(q[3], q[4], q[5]), a.dir);
-                        a.s_lt = a.s_lt + contrib; a.c_lt++;
-                    } else if (key == a.tau) {
-                        if (n_eq == 0) k_eq = k;
-                        n_eq++;
-                    }
-                }
-                if (n_eq == 1) {
-                    const double* q = cand[k_eq];
-                    g_acc(a, v3(q[0], q[1], q[2]), q + 3);
-                } else if (n_eq > 1) {     // float keys tie at tau: walk on from the first of them
-                    for (int32_t k = k_eq; n_eq > 0 && k < m; k++) {
-                        const double* q = cand[k];
-                        if ((float)len2(v3(q[0], q[1], q[2]) - a.pos) == a.tau) { g_acc(a, v3(q[0], q[1], q[2]), q + 3); n_eq--; }
-                    }
-                }
-            }
-        }
-        if (valid) {
-            V3 caustic;
-            if (!g_end(a, caustic)) caustic = gather_in_leaf(S, (int32_t)leaf0, a.pos, a.dir, heap, 64, nullptr, nullptr);   // float-key tie: exact pass
-            double* Lp = lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3;   // the path's radiance lives in the per-sample buffer
-            V3 L = ld3(Lp) + ld3(pool.gath[gslot].gcoef) * caustic;
-            Lp[0] = L.x; Lp[1] = L.y; Lp[2] = L.z;
-        }
-    }
-    if constexpr (COUNT) { flush_u64(&sc->gather_queries, n_q); flush_u64(&sc->gather_cand, n_c); }
-}
-
-// A query per WAVE, for the passes with few queries.  Late passes hold a handful of queries per photon-map leaf: a wave of k_st_gather then either serves
-// sixty leaves one after the other with one or two lanes at work, or lets every lane walk its own leaf -- either way the pass lasts as long as some
-// five thousand candidate steps of one wave (1.2 - 1.6 ms on the benchmark frame, whatever the number of queries).  Here the lanes take a CANDIDATE
-// each: 64 keys per step, the 32 smallest kept across the lanes (a bitonic sort of the 64 new keys through lane exchanges, the smaller half against
-// the best so far, a bitonic merge: ~110 instructions per 64 candidates instead of 18 per candidate and query), tau read off lane K - 1; the second
-// pass computes every lane's contribution and adds those below tau in CANDIDATE ORDER (a lane at a time, read off by v_readlane), so the sums are the
-// sums of g_acc to the last bit; the tie group (keys equal to tau) likewise; float-key ties across rank 32 go to lane 0's gather_in_leaf, as everywhere.
-__device__ __forceinline__ double wave_read(double v, int src_lane)      // src_lane is wave-uniform
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ V3 gather_wave(const Scene& S, int32_t leaf, uint32_t rank, V3 pos, V3 dir, float* heap32, uint32_t lane, int* n_cand_out)
-{
-    const PNode& lf = S.pnodes[leaf];
-    const int ncand = lf.u.lf.nb_photons;
-    if (n_cand_out) *n_cand_out = ncand;
-    V3 res = v3(0, 0, 0);
-    if (ncand == 0) return res;
-    const size_t cbase = (size_t)S.pcand_off[rank];
-    const int K = ncand < GI_GATHER_K ? ncand : GI_GATHER_K;
-    // pass 1: the K-th smallest float key.  lane j < 32 holds the j-th smallest so far
-    float best = INFINITY;
-    for (int32_t c0 = 0; c0 < ncand; c0 += 64) {
-        const int32_t c = c0 + (int32_t)lane;
-        float key = INFINITY;
-        if (c < ncand) {
-            const double* pp = S.pcand + (cbase + (size_t)c) * 3;
-            key = (float)len2(v3(pp[0], pp[1], pp[2]) - pos);            // the expression of g_key
-        }
-#pragma unroll
-        for (int k = 2; k <= 64; k <<= 1)
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                const float o = __shfl_xor(key, j);
-                const bool keep_min = ((lane & (uint32_t)j) == 0u) == ((lane & (uint32_t)k) == 0u);   // ascending blocks where bit k is clear (k = 64: everywhere)
-                key = keep_min ? fminf(key, o) : fmaxf(key, o);
-            }
-        const float r = __shfl(key, (int)((31u - lane) & 63u));         // the 32 smallest new keys, descending over lanes 0 .. 31
-        float m = lane < 32u ? fminf(best, r) : INFINITY;               // the 32 smallest of both, a bitonic sequence
-#pragma unroll
-        for (int j = 16; j > 0; j >>= 1) {
-            const float o = __shfl_xor(m, j);
-            m = (lane & (uint32_t)j) == 0u ? fminf(m, o) : fmaxf(m, o);
-        }
-        best = lane < 32u ? m : INFINITY;
-    }
-    const float tau = __shfl(best, K - 1);
-    // pass 2: g_acc over the candidates, in their order
-    V3 s_lt = v3(0, 0, 0), s_eq = v3(0, 0, 0);
-    int c_lt = 0, c_eq = 0;
-    double r_eq = 0;
-    for (int32_t c0 = 0; c0 < ncand; c0 += 64) {
-        const int32_t c = c0 + (int32_t)lane;
-        bool lt = false, eq = false;
-        double d2 = 0;
-        V3 contrib = v3(0, 0, 0);
-        if (c < ncand) {
-            const double* pp = S.pcand + (cbase + (size_t)c) * 3;
-            d2 = len2(v3(pp[0], pp[1], pp[2]) - pos);
-            const float key = (float)d2;
-            lt = key < tau; eq = key == tau;
-            if (lt || eq) {
-                const double* dc = S.pcand_dc + (cbase + (size_t)c) * 6;
-                contrib = v3(dc[3], dc[4], dc[5]) * dot(v3(dc[0], dc[1], dc[2]), dir);
-            }
-        }
-        unsigned long long mlt = __ballot(lt), meq = __ballot(eq);
-        c_lt += (int)__popcll(mlt); c_eq += (int)__popcll(meq);
-        while (mlt != 0ull) {
-            const int b = __ffsll((long long)mlt) - 1;
-            mlt &= mlt - 1ull;
-            s_lt = s_lt + v3(wave_read(contrib.x, b), wave_read(contrib.y, b), wave_read(contrib.z, b));
-        }
-        while (meq != 0ull) {
-            const int b = __ffsll((long long)meq) - 1;
-            meq &= meq - 1ull;
-            s_eq = s_eq + v3(wave_read(contrib.x, b), wave_read(contrib.y, b), wave_read(contrib.z, b));
-            const double de = wave_read(d2, b);
-            r_eq = de > r_eq ? de : r_eq;
-        }
-    }
-    const int need = K - c_lt;       // g_end
-    if (c_eq > need) {               // float keys tie across rank 32: the exact pass, by one lane
-        if (lane == 0u) res = gather_in_leaf(S, leaf, pos, dir, heap32, 1, nullptr, nullptr);
-        res = v3(wave_read(res.x, 0), wave_read(res.y, 0), wave_read(res.z, 0));
-        return res;
-    }
-    return (s_lt + s_eq) / (GI_PI * r_eq);
-}
-#define GI_GW_BLOCK 256      // four waves: a wave per SIMD and workgroup, five workgroups per CU at 87 registers
-template <bool COUNT>
-__global__ __launch_bounds__(GI_GW_BLOCK) void k_st_gather_wave(Scene S, PathPool pool, const uint32_t* keys, const uint32_t* vals, uint32_t n_in,
-                                                            const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
-{
-    __shared__ float heaps[(GI_GW_BLOCK / 64) * GI_GATHER_K];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-    unsigned long long n_q = 0, n_c = 0;
-    for (uint32_t q = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; q < n_in; q += n_waves) {
-        const uint32_t rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)keys[q]);
-        if constexpr (COUNT) n_q++;
-        if (rank >= (uint32_t)S.n_pleaf) continue;
-        const int32_t leaf = __builtin_amdgcn_readfirstlane(S.prank_leaf[rank]);
-        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)vals[q]);
-        int nc = 0;
-        const V3 caustic = gather_wave(S, leaf, rank, ld3(pool.hit[slot].hpos), ld3(pool.gath[slot].gdir), heaps + wave * GI_GATHER_K, lane, &nc);
-        if constexpr (COUNT) n_c += (unsigned long long)nc;
-        if (lane == 0u && nc > 0) {
-            double* Lp = lbuf + (sample_of(slot_sample, sample0, slot) - sample0) * 3;   // the path's radiance lives in the per-sample buffer
-            const V3 L = ld3(Lp) + ld3(pool.gath[slot].gcoef) * caustic;
-            Lp[0] = L.x; Lp[1] = L.y; Lp[2] = L.z;
-        }
-    }
-    if constexpr (COUNT) { if (lane != 0u) { n_q = 0; n_c = 0; } flush_u64(&sc->gather_queries, n_q); flush_u64(&sc->gather_cand, n_c); }
-}
-// gi_debug_gather_pass: query i in slot i of a pool of n (position, direction, factor 1, sample i) and its key as k_st_compact computes it
-__global__ __launch_bounds__(256) void k_gather_pass_prep(Scene S, PathPool pool, int32_t n, const double* q6, unsigned long long* slot_sample, uint32_t* keys, uint32_t* vals)
-{
-    const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    const double* q = q6 + (size_t)i * 6;
-    for (int k = 0; k < 3; k++) { pool.hit[i].hpos[k] = q[k]; pool.gath[i].gdir[k] = q[3 + k]; pool.gath[i].gcoef[k] = 1.0; }
-    slot_sample[i] = (unsigned long long)i;
-    keys[i] = gather_key(S, v3(q[0], q[1], q[2]));
-    vals[i] = (uint32_t)i;
-}
+// ================================================================================================= photon gather
+#include "gi_gather.inc"   // gather_wave, k_st_gather, k_st_gather_wave, finish_gathers, k_gather and the debug kernels (the selection itself: gi_gather.h)
 
 // the last stragglers of a chunk (paths bouncing between specular surfaces up to MAX_DEPTH), finished without one nearly
 // empty pass per remaining depth.  A wave's bounce costs what its most divergent lanes cost (one depth-65 path alone in a
@@ -1395,38 +1121,6 @@ __global__ __launch_bounds__(256) void k_gather_pass_prep(Scene S, PathPool pool
 #define GI_FINISH_COOP_RECORDS GI_LDS_WNODES
 #define GI_FINISH_COOP_HEAP_OFF ((GI_LDS_BOXES_BYTES(GI_FINISH_COOP_RECORDS) + 15) & ~15)
 #define GI_FINISH_COOP_LDS_BYTES (GI_FINISH_COOP_HEAP_OFF + (GI_FINISH_BLOCK / 16) * GI_GATHER_K * 4)
-// The photon gathers the paths of a finisher wave have pending after a vertex (`pending`: this lane's -- or, with G lanes per path, this group's --
-// path has one).  Up to GI_FIN_WAVE_GATHERS of them are served by the whole wave one after the other (gather_wave); more than that (a stage that still
-// holds a path in most lanes), or no written-out candidate lists, and every path walks its own leaf as before (stage_gather).  Called by all 64 lanes.
-#ifndef GI_FIN_WAVE_GATHERS
-#define GI_FIN_WAVE_GATHERS 24
-#endif
-__device__ __forceinline__ void finish_gathers(const Scene& S, PathRec& p, bool pending, uint32_t G, float* heap, int heap_stride, float* heap32, uint32_t lane)
-{
-    unsigned long long pend = __ballot(pending && (lane & (G - 1u)) == 0u);
-    if (pend == 0ull) return;
-    if (!S.pcand || (uint32_t)__popcll(pend) > (uint32_t)GI_FIN_WAVE_GATHERS) {
-        if (pending) stage_gather(S, p, heap, heap_stride, nullptr);
-        return;
-    }
-    while (pend != 0ull) {
-        const int src = __ffsll((long long)pend) - 1;
-        pend &= pend - 1ull;
-        const V3 gp = v3(wave_read(p.hpos[0], src), wave_read(p.hpos[1], src), wave_read(p.hpos[2], src));
-        const V3 gd = v3(wave_read(p.gdir[0], src), wave_read(p.gdir[1], src), wave_read(p.gdir[2], src));
-        int32_t leaf = S.pdescent ? gather_find_leaf_fast(S, gp) : -2;      // the descent k_st_compact keys the queries of a pass with
-        if (leaf == -2) leaf = gather_find_leaf(S, gp);
-        V3 caustic = v3(0, 0, 0);
-        if (leaf >= 0) {
-            const int32_t rank = S.pleaf_rank[leaf];
-            if (rank >= 0) caustic = gather_wave(S, leaf, (uint32_t)rank, gp, gd, heap32, lane, nullptr);
-        }
-        if (lane / G == (uint32_t)src / G) {                                  // stage_gather, on the path's own lanes
-            const V3 L = ld3(p.L) + ld3(p.gcoef) * caustic;
-            p.L[0] = L.x; p.L[1] = L.y; p.L[2] = L.z;
-        }
-    }
-}
 __device__ __forceinline__ int finish_mode(int wide, int lanes, uint32_t n_in, uint32_t n_waves, uint32_t coop_factor)
 {
     // coop_factor: low half = paths per group-of-16 slot up to which a stage runs one path per group, high half = paths per resident wave up to which it
@@ -1457,7 +1151,6 @@ __global__ __launch_bounds__(GI_FINISH_BLOCK) void k_st_finish(Scene S, uint64_t
         // every lane of the wave stays in the loops (a group without a path idles): a pending photon gather is served by the WHOLE wave, one query at a
         // time -- its lanes take a candidate each (gather_wave: gather_in_leaf's sums to the last bit).  A group's or lane's own walk through its leaf's
         // candidates is a chain of dependent reads that the stage's other paths all wait for (0.5 - 1 ms per vertex of a stage, whatever its size).
-        float* const heap32 = reinterpret_cast<float*>(gi_dyn_lds + GI_FINISH_COOP_HEAP_OFF) + (threadIdx.x >> 6) * GI_GATHER_K;
         for (uint32_t i0 = wave * per_wave; i0 < n_in; i0 += n_waves * per_wave) {
             const uint32_t i = i0 + grp;
             const bool have = i < n_in;
@@ -1472,7 +1165,7 @@ __global__ __launch_bounds__(GI_FINISH_BLOCK) void k_st_finish(Scene S, uint64_t
                     if (!stage_trace_nodes<FEAT>(S, NC, p, seed, nullptr)) { alive = false; running = false; }
                     if (running) fl = stage_shade_nodes<FEAT>(S, NC, p, seed, nullptr);
                 }
-                finish_gathers(S, p, running && (fl & ST_GATHER) != 0, G, heap, heap_stride, heap32, lane);
+                finish_gathers(S, p, running && (fl & ST_GATHER) != 0, G, heap, heap_stride, lane);
                 if (running && !(fl & ST_CONTINUE)) { alive = false; running = false; }
                 if (++b >= max_bounces) running = false;
                 if (__ballot(running) == 0ull) break;
@@ -1503,7 +1196,7 @@ __global__ __launch_bounds__(GI_FINISH_BLOCK) void k_st_finish(Scene S, uint64_t
                     if (!stage_trace_nodes<FEAT>(S, N, p, seed, nullptr)) { alive = false; running = false; }
                     else fl = stage_shade_nodes<FEAT>(S, N, p, seed, nullptr);
                 }
-                finish_gathers(S, p, running && (fl & ST_GATHER) != 0, 1u, heap + threadIdx.x, GI_FINISH_BLOCK, heap + (threadIdx.x & ~63u), lane);   // (heap32: row 0 of this wave's own lanes 0 .. 31)
+                finish_gathers(S, p, running && (fl & ST_GATHER) != 0, 1u, heap + threadIdx.x, GI_FINISH_BLOCK, lane);
                 if (running && !(fl & ST_CONTINUE)) { alive = false; running = false; }
                 if (++b >= max_bounces) running = false;
                 if (__ballot(running) == 0ull) break;
@@ -1649,18 +1342,6 @@ __global__ __launch_bounds__(GI_DEBUG_WALK_BLOCK) void k_debug_walk(Scene S, int
                 for (int k = 0; k < 8; k++) o[k] = 0;
         }
     }
-}
-
-__global__ __launch_bounds__(GI_BLOCK) void k_gather(Scene S, int n, const double* q, double* res3, int32_t* n_cand)
-{
-    __shared__ float heap[GI_GATHER_K * GI_BLOCK];
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double* p = q + (size_t)i * 6;
-    int nc = 0;
-    V3 r = gather(S, v3(p[0], p[1], p[2]), v3(p[3], p[4], p[5]), heap + threadIdx.x, GI_BLOCK, &nc, nullptr);
-    res3[(size_t)i * 3] = r.x; res3[(size_t)i * 3 + 1] = r.y; res3[(size_t)i * 3 + 2] = r.z;
-    if (n_cand) n_cand[i] = nc;
 }
 
 __global__ __launch_bounds__(GI_BLOCK) void k_radiance(Scene S, int n, const double* rays, const uint32_t* stream, uint64_t seed, double* out3)

@@ -372,14 +372,16 @@ int gi_debug_leaf_order(gi_ctx*, int32_t n, const double* rays, int32_t cap, int
 int gi_debug_sort_pairs(gi_ctx*, int32_t n, const uint32_t* keys, const uint32_t* vals, int32_t begin_bit, int32_t end_bit, uint32_t* keys_out, uint32_t* vals_out);
 /* gi_debug_find_leaves: the photon-map leaf around each position (PhotonMap::Node::getBounds, include/photonMap.cpp:115-134) as the two descents of the
  * pipeline find it: full_out the one that asks every box on the way (-1: no leaf contains the position), fast_out the one the gather keys of a pass
- * take (split records only, the first five levels through a jump table), -2 where that one declines (a position within 1e-12 of a split plane). */
+ * take (split records only, the first five levels through a jump table), -2 where that one declines (a position within 1e-12 of a split plane).
+ * (gi_gather.h: gather_find_leaf, gather_find_leaf_fast; gather_leaf_of is the two together.) */
 int gi_debug_find_leaves(gi_ctx*, int32_t n, const double* pos, int32_t* fast_out, int32_t* full_out);
 /* gi_debug_gather_pass: one gather pass of the streaming pipeline on caller queries q6 [n][6] = position, direction.  Query i takes slot i of a
  * path pool (gather factor 1, radiance 0) and the sort key k_st_compact gives it; sort = 1 puts the queries in leaf order with the pipeline's
  * radix sort, sort = 0 keeps the caller's order.  kernel: 0 k_st_gather, 1 its counting instance, 2 k_st_gather_wave, 3 its counting instance,
  * launched as the pass loop launches them (GI_E_STATE: the wave kernel without written-out candidate lists, GI_FLAT_CANDIDATES=0).
  * res3 [n][3] = the caustic term of query i (RayTracer::samplePhotons(pos, dir, 32)); keys_out / order_out [n] (optional) = the keys and slots
- * in the order the kernel read them; counters2 (optional) = gather queries and candidates a counting instance counted (0 otherwise).    */
+ * in the order the kernel read them; counters2 (optional) = gather queries and candidates a counting instance counted (0 otherwise).
+ * The kernels are in gi_gather.inc, the selection they share with gi_gather (k_gather) in gi_gather.h.                                  */
 int gi_debug_gather_pass(gi_ctx*, int32_t n, const double* q6, int32_t kernel, int32_t sort, double* res3, uint32_t* keys_out, uint32_t* order_out, int64_t* counters2);
 /* gi_debug_walk: caller rays [n][6] (origin, unit direction) through the octree walk in the forms the passes run it, with gi_trace's /
  * gi_visible_rays' keys (stream = ray index, seed 0, light 0): the same answers, ray by ray.  mt NULL: closest hit, hit_or_vis / ent / res8 as gi_trace

@@ -1,4 +1,4 @@
-"""CPU check of the selection networks behind pass 1 of k_st_gather (gi_device.h: ksort, kmerge32, ksel_tau).
+"""CPU check of the selection networks behind pass 1 of k_st_gather (gi_gather.h, through gi_device.h: ksort, kmerge32, ksel_tau).
 
 The GI_HD helpers are compiled for the host with the host emulator's flags (tests/host_emul/Makefile) and driven in the
 kernel's order: chunks of 64 from the last to the first, groups of 32 from the last to the first, the short group sized to
