@@ -1,7 +1,51 @@
 // gi_bake.inc -- light baking (gi_bake_*; an addition: everything else the project renders starts at the camera).  Included by gi_kernels.hip behind
-// gi_entries.inc, whose Entry the two check entries use.  The definition is stated in include/gi_hip.h; the per-lane functions are bake_point(),
-// bake_ray() and sh9_basis() in gi_device.h.
-//
+// gi_entries.inc, whose Entry the two check entries use.  The definition is stated in include/gi_hip.h; the per-lane functions, bake_point(),
+// bake_ray() and sh9_basis(), stand first with GI_BAKE_MODE_*, in namespace gi beside the functions of gi_device.h they call.
+
+namespace gi {
+// ------------------------------------------------------------------------------------------------ light baking (an addition: the reference starts every path at the camera)
+// gi_hip.h: gi_bake_*.  A bake's ray: sample `stream` of a point takes Halton dimensions 0 and 1 at that index for its direction -- the two a
+// primary ray takes for its place in the pixel -- and the rest of the index (dimensions 2 + 2d, 3 + 2d, the counter RNG) drives the path as a
+// primary ray's would.  A texel's rays leave the surface in the lobe of the diffuse bounce (stage_shade: hemi_cos_n(norm, sx, sy, 2)) from the
+// point lifted by the shadow bias; a probe's go anywhere on the sphere from the point itself.
+#define GI_BAKE_MODE_TEXEL 0
+#define GI_BAKE_MODE_SH9 1
+struct BakePoint { V3 o, n; };          // where the point's rays start, and the unit normal (texel; 0 for a probe)
+GI_HD BakePoint bake_point(int mode, const double* p)   // p: a row of `points`, [6] = position, normal (texel) or [3] = position (probe)
+{
+    BakePoint b;
+    if (mode == GI_BAKE_MODE_TEXEL) {
+        const V3 N = ld3(p + 3);
+        b.n = N / sqrt((N.x * N.x + N.y * N.y) + N.z * N.z);
+        b.o = ld3(p) + GI_SHADOW_BIAS * b.n;
+    } else {
+        b.n = v3(0, 0, 0);
+        b.o = ld3(p);
+    }
+    return b;
+}
+GI_HD Ray bake_ray(const Scene& S, int mode, const BakePoint& b, uint32_t stream)
+{
+    const float u = halton_sample(S, 0, stream);
+    const float v = halton_sample(S, 1, stream);
+    return make_ray(b.o, mode == GI_BAKE_MODE_TEXEL ? hemi_cos_n(b.n, u, v, 2) : random_unit_vec((double)u, (double)v));
+}
+// the real spherical harmonics of bands 0 to 2 at the unit direction d, in the header's order and with its literals; IEEE operations only
+GI_HD void sh9_basis(V3 d, double* Y)
+{
+    const double x = d.x, y = d.y, z = d.z;
+    Y[0] = 0.28209479177387814;
+    Y[1] = 0.4886025119029199 * y;
+    Y[2] = 0.4886025119029199 * z;
+    Y[3] = 0.4886025119029199 * x;
+    Y[4] = 1.0925484305920792 * (x * y);
+    Y[5] = 1.0925484305920792 * (y * z);
+    Y[6] = 0.31539156525252005 * (3.0 * (z * z) - 1.0);
+    Y[7] = 1.0925484305920792 * (x * z);
+    Y[8] = 0.5462742152960396 * (x * x - y * y);
+}
+}  // namespace gi
+
 // A bake is a second generator and a second fold around the stream passes (gi_stream.inc), as an adaptive round is k_ad_gen and k_ad_accum around
 // them: k_bake_gen prepares the paths of a chunk of points and a range of samples in work.q_new, stream_passes runs them with a RoundRefill, and
 // k_bake_fold adds what they left in lbuf to the points' sums.  No k_st_* kernel knows of it.

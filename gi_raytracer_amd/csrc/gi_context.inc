@@ -54,8 +54,8 @@ struct SceneStore {
     DevBuf<double> d_tex_lut;
     DevBuf<int32_t> d_refs;
     DevBuf<LeafTri> d_leaf_tris;
-    DevBuf<double> d_leaf_boxes;          // every leaf reference's own box (gi_device.h: entity_survivors)
-    DevBuf<double> d_trace_boxes;         // the closest-hit walk's boxes (gi_device.h: trace_wide_step)
+    DevBuf<double> d_leaf_boxes;          // every leaf reference's own box (gi_walk.h: entity_survivors)
+    DevBuf<double> d_trace_boxes;         // the closest-hit walk's boxes (gi_walk.h: trace_wide_step)
     DevBuf<float> d_tcboxes;              // and the content boxes made of them
     DevBuf<uint32_t> d_tcuse;
     WalkCuts cuts;                        // of the scene last uploaded: what it allows the walks' short cuts (gi_layout.h)

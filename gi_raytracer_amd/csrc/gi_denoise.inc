@@ -1,6 +1,53 @@
 // gi_denoise.inc -- the edge-avoiding a-trous denoiser (gi_denoise_*; an addition: the reference has no denoiser).  Included by gi_kernels.hip
-// after the context and its helpers.  The formula is stated in include/gi_hip.h; the per-tap function is dn_tap_weight() in gi_device.h.
-//
+// after the context and its helpers.  The formula is stated in include/gi_hip.h; the per-tap functions (dn_tap_weight(), and up_tap_weight()
+// of the upsampler) stand first with DnPix, DnInv and the GI_DN_* constants, in namespace gi as the kernels' parameter types were.
+
+namespace gi {
+// ------------------------------------------------------------------------------------------------ a-trous denoiser (an addition: the reference has no denoiser)
+// One tap of the edge-avoiding a-trous filter (gi_hip.h: gi_denoise_*; Dammertz et al. 2010 with Tukey's biweight as the edge-stopping function).
+// IEEE operations only, in the order the header states, so that with -ffp-contract=off the result equals the tests' numpy statement bit for bit.
+struct DnPix { V3 c, n, a; double z, cov; };     // what a tap reads of a pixel: demodulated colour, normal, albedo, depth, coverage
+struct DnInv { double c, n, z, a; };             // 4^level / sigma_color^2, 1 / sigma_normal^2, 1 / sigma_depth^2, 1 / sigma_albedo^2 (0 = term off)
+#define GI_DN_ALBEDO_FLOOR 1e-3
+#define GI_DN_DC_EPS 1e-12
+GI_HD double dn_sq3(V3 v) { return (v.x * v.x + v.y * v.y) + v.z * v.z; }
+GI_HD bool dn_finite(V3 c) { return fabs(c.x) <= 1.7976931348623157e308 && fabs(c.y) <= 1.7976931348623157e308 && fabs(c.z) <= 1.7976931348623157e308; }
+GI_HD double dn_modulation(double albedo, int demodulate) { return demodulate ? (albedo > GI_DN_ALBEDO_FLOOR ? albedo : GI_DN_ALBEDO_FLOOR) : 1.0; }
+// The three guide terms of a tap, shared by both filters' weights: squared normal difference, squared relative depth difference (0 unless
+// z_p + z_q > 0), squared albedo difference plus squared coverage difference.
+struct GuideDiff { double dn, dz, da; };
+GI_HD GuideDiff guide_diff(const DnPix& p, const DnPix& q)
+{
+    GuideDiff g;
+    g.dn = dn_sq3(p.n - q.n);
+    const double dcov = p.cov - q.cov;
+    g.da = dn_sq3(p.a - q.a) + dcov * dcov;
+    const double zs = p.z + q.z;
+    g.dz = 0.0;
+    if (zs > 0.0) { const double r = (p.z - q.z) / zs; g.dz = r * r; }
+    return g;
+}
+// weight of tap q for the centre p: hh = h[dy] h[dx]; p_c2 = |c_p|^2; p_ok = the centre's colour is finite (else the colour term is 0).
+// The caller skips taps outside the frame and taps whose colour is not finite.
+GI_HD double dn_tap_weight(const DnPix& p, double p_c2, bool p_ok, const DnPix& q, const DnInv& inv, double hh)
+{
+    const double dc = p_ok ? dn_sq3(p.c - q.c) / (p_c2 + (dn_sq3(q.c) + GI_DN_DC_EPS)) : 0.0;
+    const GuideDiff g = guide_diff(p, q);
+    const double d = ((dc * inv.c + g.dn * inv.n) + g.dz * inv.z) + g.da * inv.a;
+    const double t = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
+    return hh * (t * t);
+}
+// The guided upsampler's tap (gi_hip.h: gi_upsample_*): p = the full pixel's guide, q = a low pixel's; the denoiser's dn, dz and da without its
+// colour term, d = (dn inv_n + dz inv_z) + da inv_a (inv.c is not read); hh = ty tx, the tent.
+GI_HD double up_tap_weight(const DnPix& p, const DnPix& q, const DnInv& inv, double hh)
+{
+    const GuideDiff g = guide_diff(p, q);
+    const double d = (g.dn * inv.n + g.dz * inv.z) + g.da * inv.a;
+    const double e = d < 1.0 ? 1.0 - d : 0.0;      // 1 - min(d, 1); a NaN d counts as 1
+    return hh * (e * e);
+}
+}  // namespace gi
+
 // Three kernels, all on the context's stream, no atomics, no host sync between them:
 //   k_dn_pack   widens colour and features to f64, demodulates, and writes the two things a tap reads: the colour [h][w][3] (changes per
 //               level) and the level-invariant guide record [h][w][8] (albedo, normal, depth, coverage: 64 B, one half cache line);
@@ -11,7 +58,7 @@
 //   k_dn_copy   iterations = 0: out = colour, converted.
 // What this file shares with the guided upsampler (gi_upsample.inc), each written once here: on the device GuideTile (the LDS tile: its size, its
 // two staging loops, its cell reader), TapSum (the weighted sum over the taps) and dn_store3 (three values in the caller's type), beside k_dn_pack
-// and guide_diff() in gi_device.h; on the host filter_size_check / filter_sigma_check and the two refusals behind them, dn_inv and dn_reserve.
+// and guide_diff() above; on the host filter_size_check / filter_sigma_check and the two refusals behind them, dn_inv and dn_reserve.
 // The host-pointer forms are an Entry with the pass's timer and the timer reads are pass_ms (both gi_context.inc).
 // Workgroups that share a neighbourhood run next to each other: the sub-lattice index is the fastest part of blockIdx.x, so at large steps the
 // s^2 workgroups that read one region of the frame (each a 1/s^2 sample of its cache lines) are in flight together and the lines come from L2.

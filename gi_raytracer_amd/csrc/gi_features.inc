@@ -1,8 +1,41 @@
 // gi_features.inc -- the first-hit feature pass (gi_render_features_*; an addition: the reference renders radiance only; the values are those
 // RayTracer::radiance holds after trace() of the primary ray, include/raytracer.h:186-210).  Included by gi_kernels.hip behind gi_upsample.inc.
 // It also holds what this pass and the occlusion pass (gi_occlusion.inc) share on the host: pixel_pass_frame, pixel_pass and pixel_pass_to_host.
-//
-// One kernel, k_aov<FEAT, WIDE> (gi_device.h: aov_sample): one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, so a wave
+// The per-sample function, aov_sample(), stands first, in namespace gi beside the functions of gi_device.h it calls.
+
+namespace gi {
+// ------------------------------------------------------------------------------------------------ first-hit features (an addition: the reference has no such pass)
+// What RayTracer::radiance holds right after trace() of the primary ray of the sample with Halton index idx (include/raytracer.h:186-210):
+// current->material.diffuse->get(minUV), minNorm as trace returned it (not flipped, not renormalised), glm::length(minHit - ray.origin),
+// the entity and its material.  Same ray, same RNG keys (seed, stream idx, depth 0, P_TRACE_ALPHA) as the beauty pass, so the alpha-test
+// draws -- and with them the first hit -- are the beauty pass's.  Fog is not looked at: the features are those of the first surface.
+struct AovSample { V3 albedo, normal; double depth; int32_t ent, mat; };
+template <int FEAT, class Nodes>
+GI_HD bool aov_sample(const Scene& S, const Nodes& N, const Frame& F, uint64_t seed, uint32_t idx, AovSample& a)
+{
+    const Ray ray = primary_ray_at(S, F, idx);
+    const Rng rng = rng_make(seed, idx);   // depth 0
+    HitRec h;
+    h.tu = 0; h.tv = 0;
+    if (!trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr)) return false;
+    if constexpr (Nodes::kWide) {
+        // as the streaming trace kernel does: hit point and barycentrics again from the entity's record, by the same test with the same
+        // operands, so that the walk has to carry only WHICH entity it hit
+        const TriGeom& tg = S.tris[h.tri];
+        h.mf = ((uint32_t)tg.mat << 3) | tg.flags;
+        ent_hit<FEAT>(tg, h.mf, ray, h.u, h.v, h.pos);
+    }
+    const Mat& m = S.mats[h.mf >> 3];
+    a.albedo = ld3(m.diffuse);
+    if (FEAT & GI_FEAT_TEX) a.albedo = tex_get(S, m.dtex, a.albedo, h.tu, h.tv);
+    a.normal = shading_normal(S, h);
+    a.depth = length(h.pos - ray.o);
+    a.ent = h.tri; a.mat = (int32_t)(h.mf >> 3);
+    return true;
+}
+}  // namespace gi
+
+// One kernel, k_aov<FEAT, WIDE> (aov_sample above): one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, so a wave
 // is a tile and all its lanes are on the same sample index s -- rays as coherent as the new paths of k_st_trace, on the same records in LDS and the
 // same wave-uniform leaves.  A lane loops over s (Halton index of sample s = that of sample 0 + s * inc), keeps its eight sums in registers and
 // writes once: no queue, no sort, no per-sample buffer, no atomics, and nothing of the path pool.

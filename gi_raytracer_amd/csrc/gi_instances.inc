@@ -1,6 +1,6 @@
 // gi_instances.inc -- the instances of the kernels that take dynamic LDS, and the selectors that pick the one a launch runs.  Host code only;
 // included by gi_kernels.hip behind gi_context.inc.  Every instance of a family is named once, in its table (FEAT = scene_feat / scene_trace_feat,
-// gi_device.h); stream_grids (gi_stream.inc) and the two per-pixel passes walk the same tables when they ask for the LDS.
+// gi_scene.h); stream_grids (gi_stream.inc) and the two per-pixel passes walk the same tables when they ask for the LDS.
 
 // The two per-pixel passes' kernels stand with their entries (gi_features.inc, gi_occlusion.inc), behind this file.
 #ifndef GI_AOV_BLOCK

@@ -135,7 +135,7 @@ __device__ __forceinline__ LdsNodes stage_nodes_in_lds(const Scene& S)
     return N;
 }
 
-// the same for the wide records (gi_device.h: WNode): 292 of them = every inner node of the BASELINE scenes
+// the same for the wide records (gi_scene.h: WNode): 292 of them = every inner node of the BASELINE scenes
 #define GI_LDS_WNODES 292                     // 64 KB of 224-byte records
 // LDS layout "records + content boxes": cap records, 16 bytes of counters, the records' content boxes (192 bytes each), their flag words.
 // The kernels that own a CU with one 1024-thread workgroup (k_st_trace, k_st_shadow) use nearly all of its 160 KB: 384 records; the one-path-per-
@@ -161,7 +161,7 @@ struct LdsWideT {
     __device__ __forceinline__ void tick_tri() const { if constexpr (COUNT) wc.tris++; }
     __device__ __forceinline__ void tick_ebox(uint32_t n) const { if constexpr (COUNT) wc.ent_boxes += n; }
     const WNode* g;
-    const float* cboxes;      // content boxes of the children (gi_device.h: content_cull), read through L1 / L2; null = no culling
+    const float* cboxes;      // content boxes of the children (gi_walk.h: content_cull), read through L1 / L2; null = no culling
     const uint32_t* cuse;
     int32_t n_l;
     int32_t n_lc = 0;         // records whose content boxes are staged in LDS too
@@ -185,7 +185,7 @@ struct LdsWideT {
         tick_cull(nt);
         return res;
     }
-    // the tables cull() reads, for callers that test a record's children side by side (gi_device.h: walk_hits of the one-ray-per-group walks)
+    // the tables cull() reads, for callers that test a record's children side by side (gi_walk.h: walk_hits of the one-ray-per-group walks)
     __device__ __forceinline__ const float* cbox_table(int32_t node) const { return !cboxes ? nullptr : (node < n_lc ? reinterpret_cast<const float*>(gi_dyn_lds + box_off) : cboxes); }
     __device__ __forceinline__ uint32_t cuse_of(int32_t node) const { return node < n_lc ? reinterpret_cast<const uint32_t*>(gi_dyn_lds + use_off)[node] : cuse[node]; }
 };
@@ -213,7 +213,7 @@ extern "C" int gi_debug_div(unsigned long long* out, int reset)
     return 0;
 }
 #endif
-template <int G> struct LdsWideCoop : LdsWide { static constexpr bool kCoop = true; static constexpr int kGroup = G; };   // the same records, one ray per group of G lanes (gi_device.h: trace_wide_coop)
+template <int G> struct LdsWideCoop : LdsWide { static constexpr bool kCoop = true; static constexpr int kGroup = G; };   // the same records, one ray per group of G lanes (gi_walk.h: trace_wide_coop)
 template <bool COUNT = false>
 __device__ __forceinline__ LdsWideT<COUNT> stage_wide_in_lds(const Scene& S, bool with_boxes = false, int boxes_cap = GI_LDS_WNODES_BIG, int tables = 0)
 {
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(GI_SHADE_BLOCK, DEFER ? GI_DEFER_WAVES : 4) void k_
     unsigned int* const s_next = reinterpret_cast<unsigned int*>(gi_dyn_lds + (DEFER == 1 ? (size_t)GI_LDS_BIG_CNT_OFF : (size_t)GI_LDS_WNODES * sizeof(WNode)));
     if (WIDE != 0 && threadIdx.x == 0) *s_next = 0u;
     typename LdsSrc<WIDE>::type N;
-    // early_turns != 0 (stream_passes): the next ray of a vertex is walked for up to that many turns (ray_leaves_scene, gi_device.h); one that leaves
+    // early_turns != 0 (stream_passes): the next ray of a vertex is walked for up to that many turns (ray_leaves_scene, gi_walk.h); one that leaves
     // the scene without meeting a leaf ends its path here.  The walk is the trace stage's, over the trace stage's tables: NP is staged as k_st_trace stages N.
     // One-light instance only (DEFER 1): the several-lights instances have no registers to spare for a walk, and are always handed 0
     typename LdsSrc<WIDE>::type NP;

@@ -37,12 +37,12 @@ struct HostScene : WalkCuts {
     std::vector<TNode> tnodes;
     std::vector<WNode> wnodes;        // empty when the tree is not made of exact octants (layout_wide)
     std::vector<int32_t> wleaf_id;
-    std::vector<float> cboxes;        // [n_wnode][8][6] content boxes of the children (gi_device.h: content_cull); one dummy entry without wide records
+    std::vector<float> cboxes;        // [n_wnode][8][6] content boxes of the children (gi_walk.h: content_cull); one dummy entry without wide records
     std::vector<uint32_t> cuse;       // [n_wnode] children worth testing
     std::vector<int32_t> refs;
     std::vector<LeafTri> leaf_tris;
-    std::vector<double> leaf_boxes;   // [n_refs][6] the entity's own box, widened (gi_device.h: entity_box_missed), parallel to leaf_tris
-    std::vector<double> trace_boxes;  // [n_refs][6] for the closest-hit walk: the box of the part of an opaque entity inside its leaf (gi_device.h: trace_wide_over)
+    std::vector<double> leaf_boxes;   // [n_refs][6] the entity's own box, widened (gi_walk.h: entity_box_missed), parallel to leaf_tris
+    std::vector<double> trace_boxes;  // [n_refs][6] for the closest-hit walk: the box of the part of an opaque entity inside its leaf (gi_walk.h: trace_wide_over)
     std::vector<float> tcboxes;       // content boxes made of the trace boxes: what the closest-hit walk culls by (like cboxes; empty when !clipped)
     std::vector<uint32_t> tcuse;
     std::vector<int32_t> worder;      // canonical node of every wide record
@@ -103,7 +103,7 @@ inline void apply_scene_switches(Scene& S, const SceneTables& T, const SceneSwit
     const bool cut_to_leaves = clip && S.cboxes && T.n_tcboxes == T.n_cboxes;
     S.tcboxes = cut_to_leaves ? T.tcboxes : S.cboxes;
     S.tcuse = cut_to_leaves ? T.tcuse : S.cuse;
-    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_device.h: visible_leaf_blocks, shadow_cut)
+    // segments that end at a light (k_st_shadow): the same boxes, as long as nothing can block a segment inside its last GI_SHADOW_BIAS (gi_walk.h: visible_leaf_blocks, shadow_cut)
     const bool sh = T.lights_clear && clip;
     S.shadow_boxes = sh ? S.trace_boxes : S.leaf_boxes;
     S.scboxes = sh ? S.tcboxes : S.cboxes;
@@ -360,7 +360,7 @@ inline bool octant_planes(const gi_scene_desc* d, int n, int ax, double* pl)
     pl[0] = mn; pl[1] = mid; pl[2] = lo2; pl[3] = hi2; pl[4] = mx; pl[5] = mid;
     return true;
 }
-// Wide records (gi_device.h: WNode) for the inner nodes, breadth first; H.worder = the node of every record.  Every existing child's box must be
+// Wide records (gi_scene.h: WNode) for the inner nodes, breadth first; H.worder = the node of every record.  Every existing child's box must be
 // the octant Octree::Node::partition gives it (octant_planes), and no inner node lies deeper than 15: the walk keeps one mask byte per level in
 // 128 bits.  Returns false, with no wide records in H, for any other tree.
 inline bool layout_wide(const gi_scene_desc* d, HostScene& H)
@@ -543,7 +543,7 @@ inline bool clip_triangle_to_box(const double* P, const double* lo, const double
     for (int ax = 0; ax < 3; ax++) { cmin[ax] = mn[ax]; cmax[ax] = mx[ax]; }
     return mn[0] <= mx[0] && mn[1] <= mx[1] && mn[2] <= mx[2];
 }
-// The closest-hit walk's boxes (gi_device.h: trace_wide_over) and its margin, as closest_hit_cut_rule allows: the box of the part of an entity
+// The closest-hit walk's boxes (gi_walk.h: trace_wide_over) and its margin, as closest_hit_cut_rule allows: the box of the part of an entity
 // inside the leaf that refers to it -- the leaf taken m.wide larger, the box of what is left widened by as much again (scene_margins) and never
 // larger than the entity's own box.  Nothing of the entity near the leaf: a point no ray of the scene reaches (entity_box_missed has no empty box).
 inline void layout_trace_boxes(const gi_scene_desc* d, const SceneMargins& m, HostScene& H)

@@ -1,7 +1,7 @@
 // gi_lens.inc -- the thin-lens camera (gi_set_lens, gi_get_lens, gi_lens_vertices, gi_debug_primary_rays, gi_focus_distance; an addition: the
 // reference's camera is a pinhole).  Included by gi_kernels.hip behind gi_entries.inc, whose Entry the two device entries use.
 //
-// The lens itself is three fields of Scene (gi_device.h: lens_eye, primary_ray_at) that follow gi_ctx::lens; every pass that makes primary rays
+// The lens itself is three fields of Scene (gi_path.h: lens_eye, primary_ray_at) that follow gi_ctx::lens; every pass that makes primary rays
 // gets them with the Scene it is launched with.  What is here: the setter that keeps those fields and the vertex table, and two small kernels.
 
 // the rays of the samples with the given Halton indices, as every pass builds them

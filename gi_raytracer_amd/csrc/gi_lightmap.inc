@@ -1,7 +1,60 @@
 // gi_lightmap.inc -- lightmap atlases (gi_lightmap_*; an addition around the bake of gi_bake.inc).  Included by gi_kernels.hip behind gi_bake.inc, whose
-// bake_run is the middle stage.  The definition is stated in include/gi_hip.h; the per-lane functions are lm_edge(), lm_covers() and lm_point() in
-// gi_device.h.
-//
+// bake_run is the middle stage.  The definition is stated in include/gi_hip.h; the per-lane functions, lm_edge(), lm_covers(), lm_point() and their
+// kin, stand first, in namespace gi beside the types of gi_device.h they use.
+
+namespace gi {
+// ------------------------------------------------------------------------------------------------ lightmap atlases (an addition, around the bake)
+// gi_hip.h: gi_lightmap_*.  A chart row maps a triangle entity to three chart coordinates; a texel whose centre the row covers takes its point from
+// the entity at the centre's barycentrics.  IEEE + - * / only, in the header's order, so that with -ffp-contract=off the texel table equals the
+// tests' numpy statement bit for bit.  uv: a row of the chart, [3][2] = the coordinates of the entity's vertices 0, 1, 2.
+GI_HD double lm_edge(double ax, double ay, double bx, double by, double px, double py) { return (bx - ax) * (py - ay) - (by - ay) * (px - ax); }
+GI_HD bool lm_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+struct LmEdges { double area, e0, e1, e2; };
+GI_HD double lm_area(const double* uv) { return lm_edge(uv[0], uv[1], uv[2], uv[3], uv[4], uv[5]); }
+GI_HD LmEdges lm_edges(const double* uv, double pu, double pv)
+{
+    LmEdges e;
+    e.area = lm_area(uv);
+    e.e0 = lm_edge(uv[2], uv[3], uv[4], uv[5], pu, pv);
+    e.e1 = lm_edge(uv[4], uv[5], uv[0], uv[1], pu, pv);
+    e.e2 = lm_edge(uv[0], uv[1], uv[2], uv[3], pu, pv);
+    return e;
+}
+// the row's chart box: the smallest and largest of its three coordinates, per axis (plain comparisons)
+struct LmBox { double ulo, uhi, vlo, vhi; };
+GI_HD double lm_min3(double a, double b, double c) { const double m = b < a ? b : a; return c < m ? c : m; }
+GI_HD double lm_max3(double a, double b, double c) { const double m = b > a ? b : a; return c > m ? c : m; }
+GI_HD LmBox lm_box(const double* uv)
+{
+    LmBox b;
+    b.ulo = lm_min3(uv[0], uv[2], uv[4]); b.uhi = lm_max3(uv[0], uv[2], uv[4]);
+    b.vlo = lm_min3(uv[1], uv[3], uv[5]); b.vhi = lm_max3(uv[1], uv[3], uv[5]);
+    return b;
+}
+// A row covers the centre iff the centre lies in the row's chart box (inclusive) AND the edge test passes: edges inclusive, either winding; a row of
+// area 0 or of a non-finite area covers nothing (a NaN edge value fails every comparison).  The box is part of the definition: where the three
+// vertices are collinear up to rounding, the edge values round to 0 or to the area's sign all along the line extended, and the box ends the row.
+GI_HD bool lm_covers(const LmBox& b, const LmEdges& e, double pu, double pv)
+{
+    if (!lm_finite(e.area) || e.area == 0.0) return false;
+    if (!(pu >= b.ulo && pu <= b.uhi && pv >= b.vlo && pv <= b.vhi)) return false;
+    return e.area > 0.0 ? (e.e0 >= 0.0 && e.e1 >= 0.0 && e.e2 >= 0.0) : (e.e0 <= 0.0 && e.e1 <= 0.0 && e.e2 <= 0.0);
+}
+GI_HD double lm_centre(int32_t i, int32_t n) { return ((double)i + 0.5) / (double)n; }
+// the texel's point on the entity and its normal (shading_normal's expression for a triangle); ok: the normal is finite and not 0 0 0
+struct LmPoint { V3 P, N; bool ok; };
+GI_HD LmPoint lm_point(const TriGeom& g, const TriShade& sh, const LmEdges& e, int flip)
+{
+    LmPoint q;
+    const double b1 = e.e1 / e.area, b2 = e.e2 / e.area;
+    q.P = (ld3(g.p0) + b1 * ld3(g.e1)) + b2 * ld3(g.e2);
+    q.N = (g.flags & 1u) ? ((1 - b1 - b2) * ld3(sh.n0) + b1 * ld3(sh.n1)) + b2 * ld3(sh.n2) : ld3(sh.fnorm);
+    if (flip) q.N = v3(-q.N.x, -q.N.y, -q.N.z);
+    q.ok = lm_finite(q.N.x) && lm_finite(q.N.y) && lm_finite(q.N.z) && !(q.N.x == 0.0 && q.N.y == 0.0 && q.N.z == 0.0);
+    return q;
+}
+}  // namespace gi
+
 // One call is three stages on the context's stream, T = width x height texels:
 //   raster + rank    k_lm_raster decides every texel's owner row, k_lm_point makes the owned texels' points and counts the valid ones per workgroup,
 //                    k_rs_scan (gi_sort.inc) turns the counts into offsets, k_lm_compact writes the texel table in ascending texel order.  One 4-byte

@@ -1,7 +1,56 @@
 // gi_occlusion.inc -- the ambient-occlusion / bent-normal pass (gi_render_occlusion_*; an addition: the reference has none).  Included by
-// gi_kernels.hip behind gi_features.inc, whose host frame of a per-pixel pass it shares (pixel_pass_frame, pixel_pass, pixel_pass_to_host).  The definition is stated in include/gi_hip.h; the per-sample functions are ao_first_hit() and ao_segments()
-// in gi_device.h.
-//
+// gi_kernels.hip behind gi_features.inc, whose host frame of a per-pixel pass it shares (pixel_pass_frame, pixel_pass, pixel_pass_to_host).  The definition is stated in include/gi_hip.h; the per-sample functions,
+// ao_first_hit() and ao_segments(), stand first with their constants, in namespace gi beside the functions of gi_device.h they call.
+
+namespace gi {
+// ------------------------------------------------------------------------------------------------ ambient occlusion / bent normals (an addition: the reference has no such pass)
+// gi_hip.h: gi_render_occlusion_*.  The first hit of the sample with Halton index idx is aov_sample's (same ray, same RNG keys, same recomputation
+// of the hit from the entity's record on the wide walk); from it n_dirs segments of length `radius` go into the cosine hemisphere around the
+// normal turned towards the viewer, each asked of the any-hit walk as a shadow segment is -- RayTracer::visible on (O, O + radius d_j) -- with
+// alpha keys of its own (light index GI_AO_LIGHT_INDEX + j) and without the medium: fog does not occlude.
+enum { P_AO_U = 32, P_AO_V = 33 };      // RNG purposes of a direction's two numbers; `a` = j
+#define GI_AO_LIGHT_INDEX 0x10000u      // + j: the `light index` of segment j's alpha draws, beyond every real light's
+#define GI_AO_MAX_DIRS 64
+struct AoHit { V3 o, nf; };             // O = P + GI_SHADOW_BIAS Nf, and Nf = the unit shading normal on the viewer's side
+template <int FEAT, class Nodes>
+GI_HD bool ao_first_hit(const Scene& S, const Nodes& N, const Frame& F, uint64_t seed, uint32_t idx, Rng& rng, AoHit& a)
+{
+    const Ray ray = primary_ray_at(S, F, idx);
+    rng = rng_make(seed, idx);   // depth 0
+    HitRec h;
+    h.tu = 0; h.tv = 0;
+    if (!trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr)) return false;
+    if constexpr (Nodes::kWide) {   // as aov_sample
+        const TriGeom& tg = S.tris[h.tri];
+        h.mf = ((uint32_t)tg.mat << 3) | tg.flags;
+        ent_hit<FEAT>(tg, h.mf, ray, h.u, h.v, h.pos);
+    }
+    const V3 nh = normalize(shading_normal(S, h));
+    a.nf = dot(nh, ray.d) > 0 ? v3(-nh.x, -nh.y, -nh.z) : nh;
+    a.o = h.pos + GI_SHADOW_BIAS * a.nf;
+    return true;
+}
+// the n_dirs segments of one hit: returns the number of open ones, bent = the sum of their directions in ascending j.  VFEAT: the walk's level
+// without GI_FEAT_FOG.  mt is formed as k_visible forms it from (O, T_j), so gi_visible on those rows is the statement.
+template <int VFEAT, class Nodes>
+GI_HD int32_t ao_segments(const Scene& S, const Nodes& N, const AoHit& a, const Rng& rng, int32_t n_dirs, double radius, V3& bent)
+{
+    static_assert((VFEAT & GI_FEAT_FOG) == 0, "fog does not occlude");
+    int32_t open = 0;
+    bent = v3(0, 0, 0);
+    for (int32_t j = 0; j < n_dirs; j++) {
+        const float u = (float)rng_draw(rng, P_AO_U, (uint32_t)j);
+        const float v = (float)rng_draw(rng, P_AO_V, (uint32_t)j);
+        const V3 d = hemi_cos_n(a.nf, u, v, 1);
+        const V3 t = a.o + radius * d;
+        const double mt = len2(t - a.o);
+        const Ray sr = make_ray(a.o, d);
+        if (visible_nodes<VFEAT>(S, N, sr, mt, rng, GI_AO_LIGHT_INDEX + (uint32_t)j, nullptr)) { open++; bent = bent + d; }
+    }
+    return open;
+}
+}  // namespace gi
+
 // One kernel, k_ao<FEAT, WIDE>, of k_aov's shape: one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, a lane loops over its
 // samples and, per sample, over the n_dirs segments; it keeps its four f64 sums in registers and stores once.  No queue, no sort, no atomics, nothing
 // of the path pool -- and no reduction across lanes, so the bent vector is summed in ascending j and then ascending s whatever the launch shape.

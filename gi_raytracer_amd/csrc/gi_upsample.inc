@@ -1,6 +1,7 @@
 // gi_upsample.inc -- the guided (joint-bilateral) upsampler (gi_upsample_*; an addition: the reference has none).  Included by gi_kernels.hip after
 // gi_denoise.inc, whose pack kernel, LDS tile (GuideTile), tap sum, typed store, parameter checks and scratch it uses (listed there).  The formula
-// is stated in include/gi_hip.h; the per-tap function is up_tap_weight() in gi_device.h.
+// is stated in include/gi_hip.h; the per-tap function, up_tap_weight(), stands in gi_denoise.inc with the guide types it shares with the
+// denoiser's (DnPix, DnInv, GuideDiff), so this file has to be included after that one -- the order gi_kernels.hip has.
 //
 // Two kernels on the context's stream, no atomics, no host sync between them:
 //   k_dn_pack    on the LOW frame: widens and demodulates its colour and widens its guide records into the denoiser's scratch (f64);

@@ -1,5 +1,5 @@
 // include/gi/util.h -- the constants of the reference's include/util.h:12-31 that its callers (loaders, GUI, main.cpp) may name, and gamma().
-// The samplers, pow approximations and the RNG of that header are part of the render path and live in the kernels (gi_device.h).
+// The samplers, pow approximations and the RNG of that header are part of the render path and live in the kernels (gi_math.h; fast_pow in gi_intersect.h).
 #pragma once
 #include <cmath>
 #include "detail.h"

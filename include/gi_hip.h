@@ -142,7 +142,7 @@ int gi_set_content_culling(gi_ctx*, int enable);
  * same hits, same order, same frame bit for bit; exists so that the two can be compared.  Returns 1 when in use after the call.
  * The closest-hit walk's further cuts hang on the same switch (0 = off, the walks ask exactly what the reference asks): boxes cut to the part of an
  * opaque entity inside its leaf, content boxes made of those, no look behind the best hit -- and with them the re-walk of a ray that met two
- * entities at exactly the same distance, and the plain walk of rays along an axis plane (gi_device.h: trace_wide_step).       */
+ * entities at exactly the same distance, and the plain walk of rays along an axis plane (gi_walk.h: trace_wide_step).       */
 int gi_set_entity_boxes(gi_ctx*, int enable);
 /* Upper bound on paths in flight in the wavefront pipeline (232 B each, as field arrays).  Default: as many as 90 % of the free HBM holds
  * next to their queues, up to the whole frame (1080p x 256 spp = 531 M paths = 123 GB).                                                           */

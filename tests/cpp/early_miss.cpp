@@ -1,4 +1,4 @@
-// tests/cpp/early_miss.cpp -- CPU build of ray_leaves_scene (gi_device.h) next to the host emulator's trace, for tests/test_early_miss_cpu.py.
+// tests/cpp/early_miss.cpp -- CPU build of ray_leaves_scene (gi_walk.h) next to the host emulator's trace, for tests/test_early_miss_cpu.py.
 //
 // TEST INFRASTRUCTURE ONLY.  The host emulator (tests/host_emul/emul.cpp: scene layout, Emul::bind, emul_create / emul_upload_scene) is taken in
 // as it is; this file adds the probe the deferred shade kernel runs on the next ray of a vertex, and the rays to ask it about.

@@ -1,4 +1,4 @@
-// tests/cpp/lens_rays.cpp -- primary_ray_at (gi_device.h) under a thin lens, compiled for the host the way tests/host_emul compiles the device
+// tests/cpp/lens_rays.cpp -- primary_ray_at (gi_path.h) under a thin lens, compiled for the host the way tests/host_emul compiles the device
 // functions, as a program of its own (tests/test_lens_cpu.py builds and runs it, once plainly and once under the address and undefined-behaviour
 // sanitizers, and compares its output with tests/lens_expect.py bit for bit).  TEST INFRASTRUCTURE ONLY.
 //

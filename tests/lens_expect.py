@@ -26,7 +26,7 @@ def dot(a, b):
 
 
 def normalize(v):
-    """glm::normalize as gi_device.h writes it: v * (1 / sqrt(dot(v, v)))."""
+    """glm::normalize as gi_math.h writes it: v * (1 / sqrt(dot(v, v)))."""
     return v * (1.0 / np.sqrt(dot(v, v)))[..., None]
 
 

@@ -755,7 +755,7 @@ def check_photon_descent(rt, scene, photons=20000):
 
 
 # ------------------------------------------------------------------------------------------------ rays aimed at the geometry
-GI_EPSILON = 1e-5                    # gi_device.h / include/entities.h: tri_hit's |det| threshold
+GI_EPSILON = 1e-5                    # gi_intersect.h / include/entities.h: tri_hit's |det| threshold
 EDGE_RAYS_PER_CLASS = 1600           # (at most 4 000 per class and scene; six classes stay below 24 000 rays per launch)
 
 

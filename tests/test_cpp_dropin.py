@@ -6,14 +6,14 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "test_dropin")
 
 
 def build():
-    lib = os.path.join(ROOT, "gi_raytracer_amd")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "test_dropin.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", EXE], check=True)
+    host_build.client("tests/cpp/test_dropin.cpp", EXE, "-O1", "-Wall")
 
 
 def test_host_side_of_the_dropin_api():

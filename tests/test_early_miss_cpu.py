@@ -1,4 +1,4 @@
-"""The probe of the next ray in the deferred shade kernel (gi_device.h: ray_leaves_scene), on the CPU.
+"""The probe of the next ray in the deferred shade kernel (gi_walk.h: ray_leaves_scene), on the CPU.
 
 ray_leaves_scene is GI_HD: tests/cpp/early_miss.cpp compiles it for the host next to the host emulator's trace, with the emulator's flags.  The
 probe is a SUFFICIENT condition for a miss: whenever it says "leaves", trace() must find no hit -- over the wide records (the walk the streaming
@@ -14,10 +14,10 @@ import pytest
 
 import gi_raytracer_amd as gi
 
+import host_build
 import parity_checks as pc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-include", "cstring"]   # tests/host_emul/Makefile
 TURNS = (1, 2, 4, 64)
 N_ADVERSARIAL, N_NEXT = 36000, 30000     # at least 50 000 rays per scene
 
@@ -25,7 +25,7 @@ N_ADVERSARIAL, N_NEXT = 36000, 30000     # at least 50 000 rays per scene
 @pytest.fixture(scope="module")
 def em(tmp_path_factory):
     lib = tmp_path_factory.mktemp("early_miss") / "libearly_miss.so"
-    subprocess.run([os.environ.get("CXX", "g++")] + FLAGS + ["-shared", os.path.join(ROOT, "tests", "cpp", "early_miss.cpp"), "-o", str(lib)], check=True)
+    subprocess.run([os.environ.get("CXX", "g++")] + host_build.flags() + ["-shared", os.path.join(ROOT, "tests", "cpp", "early_miss.cpp"), "-o", str(lib)], check=True)
     L = C.CDLL(str(lib))
     vp = C.c_void_p
     L.emul_create.restype = vp

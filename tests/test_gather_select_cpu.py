@@ -10,8 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-include", "cstring"]
 
 SHIM = r"""
 #define GI_HD static inline
@@ -36,7 +37,7 @@ def sel(tmp_path_factory):
     d = tmp_path_factory.mktemp("gather_select")
     src, lib = d / "sel.cpp", d / "libsel.so"
     src.write_text(SHIM)
-    subprocess.run([os.environ.get("CXX", "g++")] + FLAGS + ["-I", ROOT, "-shared", str(src), "-o", str(lib)], check=True)
+    subprocess.run([os.environ.get("CXX", "g++")] + host_build.flags() + ["-I", ROOT, "-shared", str(src), "-o", str(lib)], check=True)
     h = ctypes.CDLL(str(lib))
     fp = ctypes.POINTER(ctypes.c_float)
     h.sel_sort.argtypes = [fp, ctypes.c_int]

@@ -12,6 +12,7 @@ import gi_raytracer_amd as gi
 from gi_raytracer_amd import __main__ as cli
 
 import denoise_expect as de
+import host_build
 import parity_checks as pc
 
 pytestmark = pytest.mark.gpu
@@ -257,10 +258,8 @@ def test_cpp_denoise_matches_the_python_mirror(tmp_path):
     """RayTracer::denoise of the drop-in C++ class (include/gi/raytracer.h) returns what RayTracer.denoise returns."""
     import re
     import subprocess
-    lib = os.path.join(pc.ROOT, "gi_raytracer_amd")
     exe = os.path.join(pc.ROOT, "tests", "cpp", "test_denoise")
-    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(pc.ROOT, "tests", "cpp", "test_denoise.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe], check=True)
+    host_build.client("tests/cpp/test_denoise.cpp", exe, "-O1")
     out = subprocess.run([exe, os.path.join(pc.ROOT, pc.SCN["caustics"]), "80", "56", "3", "4", str(tmp_path / "dump.bin")], check=True, capture_output=True, text=True).stdout
     assert f"denoise 80x56 iterations 4 size {80 * 56 * 3}" in out, out
     assert "defaults ok 1" in out and "iterations=9 ok 0 kept 1" in out and "short colour ok 0" in out, out

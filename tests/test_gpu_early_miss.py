@@ -1,4 +1,4 @@
-"""GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (gi_device.h: ray_leaves_scene), and
+"""GI_EARLY_MISS: the deferred shade kernel ends a path whose next ray leaves the scene without meeting a leaf (gi_walk.h: ray_leaves_scene), and
 with it releases the slot of a path that does not continue even while its gather is pending.  A schedule, not arithmetic: frames with the knob at 0
 and at 1 are the same bit for bit.  Open and closed triangle scenes (caustics; cornell, teapot), a textured scene, and three scenes where part or
 all of the frame takes the path the knob does not touch: spheres, the medium (the probe is off with fog) and two lights; and large alpha-tested

@@ -20,6 +20,7 @@ import gi_raytracer_amd as gi
 from gi_raytracer_amd import __main__ as cli
 
 import features_expect as fe
+import host_build
 import parity_checks as pc
 
 pytestmark = pytest.mark.gpu
@@ -251,10 +252,8 @@ def test_cpp_render_features_matches_the_python_mirror(setups):
     """RayTracer::renderFeatures of the drop-in C++ class (include/gi/raytracer.h) fills its struct with what run_features returns."""
     import re
     import subprocess
-    lib = os.path.join(pc.ROOT, "gi_raytracer_amd")
     exe = os.path.join(pc.ROOT, "tests", "cpp", "test_features")
-    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(pc.ROOT, "tests", "cpp", "test_features.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe], check=True)
+    host_build.client("tests/cpp/test_features.cpp", exe, "-O1")
     out = subprocess.run([exe, os.path.join(pc.ROOT, pc.SCN["caustics"]), "80", "56", "3"], check=True, capture_output=True, text=True).stdout
     npix = 80 * 56
     assert f"features 80x56 n 3 sizes {npix * 3} {npix * 3} {npix} {npix} {npix} {npix}" in out, out

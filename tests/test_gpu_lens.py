@@ -17,6 +17,7 @@ import pytest
 import gi_raytracer_amd as gi
 
 import features_expect as fe
+import host_build
 import lens_expect as le
 import occlusion_expect as oe
 import parity_checks as pc
@@ -451,10 +452,8 @@ def test_cli_renders_under_the_lens_with_the_other_passes(tmp_path, capsys):
 def test_cpp_members_set_the_lens_and_move_the_focus(cornell):
     """RayTracer::setLens and focusAt of the drop-in C++ class (include/gi/raytracer.h) over the C ABI: tests/cpp/test_lens.cpp renders a frame under a
     lens and prints the sum of its depth buffer with all digits, for the Python mirror to match."""
-    lib = os.path.join(pc.ROOT, "gi_raytracer_amd")
     exe = os.path.join(pc.ROOT, "tests", "cpp", "test_lens")
-    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(pc.ROOT, "tests", "cpp", "test_lens.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe], check=True)
+    host_build.client("tests/cpp/test_lens.cpp", exe, "-O1")
     out = subprocess.run([exe, os.path.join(pc.ROOT, pc.SCN["cornell"]), str(W), str(H)], check=True, capture_output=True, text=True).stdout
     m = re.search(r"lens sum (\S+) pinhole sum (\S+) focused sum (\S+)", out)
     assert m and "bad lens refused 1" in out and "lens kept 1" in out, out

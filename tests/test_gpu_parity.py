@@ -62,7 +62,7 @@ def test_wide_walk_equals_per_node_walk(setup):
 
 def test_hits_at_equal_distance_go_to_the_entity_met_first():
     """Coplanar, overlapping entities (a patch in the floor's plane, the same patch twice, a panel in the ceiling's): the closest-hit walk's short cuts
-    (gi_device.h: trace_wide_step) must not change which of two entities at the very same distance wins.  Whole frames: with the short cuts and
+    (gi_walk.h: trace_wide_step) must not change which of two entities at the very same distance wins.  Whole frames: with the short cuts and
     without them (every entity of every leaf asked, as the reference does) bit for bit the same.  (Against the oracle such a scene is compared on the
     CPU build of the device code only, tests/test_device_logic_cpu.py: where two surfaces of different colour coincide, the last bits of a bounce
     direction -- OCML's sin / cos against glibc's -- decide which one a ray sees.)"""
@@ -202,7 +202,7 @@ def test_photon_map_uploaded_with_wide_walk_off_keeps_its_own_descent():
 
 
 def test_content_culling_changes_nothing(setup):
-    """gi_set_content_culling: the walk with and without the content-box test of the children (gi_device.h: content_cull) -- same hits, same
+    """gi_set_content_culling: the walk with and without the content-box test of the children (gi_walk.h: content_cull) -- same hits, same
     visibility, same frame, bit for bit; on every fixture scene, and on the scenes with stochastic alpha, fog and a large tree below."""
     assert pc.check_content_culling(setup[2], setup[1]) or setup[0] == "textures_opaque"
 
@@ -220,7 +220,7 @@ def test_schedule_knobs_change_nothing(name, monkeypatch):
     textured scene has emitting and non-emitting texels on one material (both forms of the put-off query), fog adds the medium's march
     to the put-off segment.  GI_COOP_FACTOR moves the finisher between one path per lane, per group of 16 lanes and per wave.  The scenes with
     large alpha-tested entities (pc.large_alpha_scene, 96 x 64 at 4 spp) are where the cooperative and finisher walks' own copy of "no look behind the
-    best hit" (gi_device.h: trace_wide_coop) and GI_WALK_CUT / GI_CLIP_BOXES would show: there the scene turns the short cuts off."""
+    best hit" (gi_walk.h: trace_wide_coop) and GI_WALK_CUT / GI_CLIP_BOXES would show: there the scene turns the short cuts off."""
     scene = pc.named_scene(name)                 # two lights: one put-off query per light
     w, h, spp = (96, 64, 4) if name.startswith("large_alpha") else (160, 90, 12)
     frames = []
@@ -613,7 +613,7 @@ def test_streaming_work_counters_against_the_reference_counts(name, photons):
     # culling on: same rays, same shaded hits and gathers, fewer boxes and entity tests
     for k in ("trace_rays", "shadow_rays", "shaded", "gather_queries", "gather_candidates"):
         assert c1[k] == c0[k], k
-    # a closest-hit walk that met two entities at the very same distance is made again the plain way (gi_device.h: trace_wide_over): a few per thousand
+    # a closest-hit walk that met two entities at the very same distance is made again the plain way (gi_walk.h: trace_wide_over): a few per thousand
     assert c0["trace_walks"] <= c1["trace_walks"] <= 1.01 * c0["trace_walks"], (c0["trace_walks"], c1["trace_walks"])
     assert c1["trace_child_boxes"] < c0["trace_child_boxes"] and c1["trace_tris"] <= c0["trace_tris"] and c1["shadow_tris"] <= c0["shadow_tris"]
     print(name, "executed / reference: boxes %.3f, entity tests %.3f" % ((c1["trace_walks"] + c1["trace_child_boxes"] + c1["shadow_walks"] + c1["shadow_child_boxes"]) / (oc[0] + oc[1]),

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import gi_raytracer_amd as gi
+
+import host_build
 import parity_checks as pc
 
 pytestmark = pytest.mark.gpu
@@ -272,10 +274,8 @@ def test_cpp_caller_drives_a_session_through_the_c_abi(tmp_path):
     """tests/cpp/test_progressive.cpp: begin / step / status / save / restore / end from C++, compared there with gi_render_host and here with
     RayTracer.run on the same scene, photons and seed."""
     import subprocess
-    lib = os.path.join(pc.ROOT, "gi_raytracer_amd")
     exe = os.path.join(pc.ROOT, "tests", "cpp", "test_progressive")
-    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(pc.ROOT, "tests", "cpp", "test_progressive.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe], check=True)
+    host_build.client("tests/cpp/test_progressive.cpp", exe, "-O1")
     dump = tmp_path / "frame.bin"
     r = subprocess.run([exe, os.path.join(pc.ROOT, pc.SCN["caustics"]), str(W), str(H), str(SPP), "3000", str(dump)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr

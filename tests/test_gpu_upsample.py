@@ -12,6 +12,7 @@ import gi_raytracer_amd as gi
 from gi_raytracer_amd import __main__ as cli
 
 import denoise_expect as de
+import host_build
 import parity_checks as pc
 import upsample_expect as ue
 
@@ -288,10 +289,8 @@ def test_cli_writes_the_upsampled_frame(tmp_path, capsys):
 def test_cpp_upsample_matches_the_python_mirror(tmp_path, rt0):
     """RayTracer::upsample of the drop-in C++ class (include/gi/raytracer.h) returns what RayTracer.upsample returns on the program's own buffers."""
     import subprocess
-    lib = os.path.join(pc.ROOT, "gi_raytracer_amd")
     exe = os.path.join(pc.ROOT, "tests", "cpp", "test_upsample")
-    subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(pc.ROOT, "tests", "cpp", "test_upsample.cpp"), "-L" + lib, "-lgi_raytracer_hip",
-                    "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-o", exe], check=True)
+    host_build.client("tests/cpp/test_upsample.cpp", exe, "-O1")
     w, h, factor = 75, 41, 3
     wl, hl = ue.low_size(w, h, factor)
     out = subprocess.run([exe, str(w), str(h), str(factor), str(tmp_path / "dump.bin")], check=True, capture_output=True, text=True).stdout

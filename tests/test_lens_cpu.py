@@ -15,6 +15,7 @@ import pytest
 import gi_raytracer_amd as gi
 import gi_raytracer_amd.__main__ as cli
 
+import host_build
 import lens_expect as le
 from test_progressive_cpu import hand_made_blob
 
@@ -203,7 +204,6 @@ def test_lens_points_are_uniform_over_the_polygon(blades, rotation):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device function on the host
-FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-include", "cstring"]
 SANITIZE = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-fno-omit-frame-pointer"]
 
 
@@ -213,7 +213,7 @@ def programs(tmp_path_factory):
     out = {}
     for name, extra in (("plain", []), ("sanitized", SANITIZE)):
         out[name] = str(d / f"lens_rays_{name}")
-        subprocess.run([os.environ.get("CXX", "g++")] + FLAGS + extra + [os.path.join(ROOT, "tests", "cpp", "lens_rays.cpp"), "-o", out[name]], check=True)
+        subprocess.run([os.environ.get("CXX", "g++")] + host_build.flags() + extra + [os.path.join(ROOT, "tests", "cpp", "lens_rays.cpp"), "-o", out[name]], check=True)
     return out
 
 
