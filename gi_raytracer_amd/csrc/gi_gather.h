@@ -4,8 +4,8 @@
 // One selection, three ways of bringing candidates to it.  The selection is written once, here: the float key ((float)g_d2), a photon's
 // contribution (g_contrib), the sum below tau and the tie group at tau (g_add_lt, g_add_eq), the end rule (g_end) and the exact pass for float
 // keys tied across rank 32 (g_exact).  The forms differ in how a candidate reaches it:
-//   a lane per query with an LDS heap     gather_in_leaf, here (k_gather, the megakernel, the finisher, the straddling waves of k_st_gather)
-//   a wave of queries of one leaf         k_st_gather, gi_gather.inc: candidates staged in LDS, tau by ksel_tau
+//   a lane per query with an LDS heap     gather_in_leaf, here (k_gather, the megakernel, the finisher, the waves of k_st_gather that span too many leaves)
+//   a wave of queries, leaf by leaf       k_st_gather, gi_gather.inc: a leaf's candidates staged in LDS for its run of lanes, tau by ksel_tau
 //   a wave per query                      gather_wave, gi_gather.inc: a candidate per lane
 // Every form takes its sums in candidate order, so the three return the same bits (tests/test_gpu_gather_kernels.py).
 

@@ -1,16 +1,20 @@
 // gi_gather.inc -- the photon gather's wave-level forms and its kernels.  Included by gi_kernels.hip behind PathPool, sample_of, chunk_item and
 // k_st_compact (which keys the queries: gather_key).  The selection they share with the per-lane form -- key, contribution, the two sums, the
 // end rule, the exact pass -- and the one result write are in gi_gather.h; here is only how each form brings a leaf's candidates to them:
-//   k_st_gather        a wave of 64 queries of one leaf: candidates staged in LDS, 64 at a time (waves that straddle leaves: gather_in_leaf per lane)
+//   k_st_gather        a wave of 64 queries, served leaf by leaf: a leaf's candidates staged in LDS, 64 at a time, for the lanes whose query lies in it
+//                      (a wave that spans more than GI_GATHER_RUNS leaves, or a map without written-out candidate lists: gather_in_leaf per lane)
 //   gather_wave        a wave per query, a candidate per lane: k_st_gather_wave (late passes) and finish_gathers (the finisher)
 //   k_gather           gather() per lane, the function-level entry (parity tests, samplePhotons)
 
 // Gather queries are sorted by the photon-map leaf that contains them (keys from k_st_compact): queries of one leaf share their candidate
-// photons, so the lanes of a wave read the same photons and run loops of equal length.
-// Queries arrive sorted by leaf, and a leaf typically serves thousands of queries per pass, so most waves hold 64 queries of ONE
-// leaf: such a wave copies the leaf's candidate photons into LDS once (64 at a time, one photon per lane, coalesced) and every lane
-// scans them from there -- a broadcast LDS read per candidate instead of an L2 round trip per lane.  Waves that straddle a leaf
-// boundary take the per-lane walk.  Both fill a GatherAcc through the steps of gi_gather.h, i.e. the same arithmetic in the same order.
+// photons and stand side by side in a wave.  In a large pass a leaf serves thousands of queries, so most waves hold 64 queries of ONE leaf:
+// such a wave copies the leaf's candidate photons into LDS once (64 at a time, one photon per lane, coalesced) and every lane scans them
+// from there -- a broadcast LDS read per candidate instead of an L2 round trip per lane.  A wave that holds the queries of several leaves
+// (the tail of a large pass; nearly every wave of a pass of a few hundred thousand to a few million queries, where a leaf serves tens) does
+// the same once per leaf, one run of lanes after the other: all 64 lanes stage and select, the lanes of the run take the sums.  That is more
+// instructions than a walk per lane, but no chain of dependent L2 reads: the per-lane walk makes two passes of 70 to 120 candidates, four
+// loads at a time, and such a pass holds too few waves to hide them.  Every path fills a GatherAcc through the steps of gi_gather.h, i.e.
+// the same arithmetic in the same order.
 #define GI_GCHUNK 64
 #ifndef GI_GATHER_WAVES
 #define GI_GATHER_WAVES 4      // waves per SIMD the gather kernel is compiled for (launch bound)
@@ -19,6 +23,11 @@
 // (ksel_tau, gi_gather.h): 18 branch-free instructions per candidate; the LDS heap costs ~55, because with 64 lanes some lane always has
 // to sift, so the wave pays a full sift for nearly every candidate.  The result (tau = 32nd smallest float key) is the same number.
 static_assert(GI_GCHUNK == 64, "ksel_tau stages the candidates 64 at a time");
+// A wave whose queries lie in up to GI_GATHER_RUNS leaves takes them one leaf after the other through the cooperative path; with more leaves than
+// that the 64 lanes idle through too many selections that are not theirs, and every lane walks its own leaf (gather_in_leaf).
+#ifndef GI_GATHER_RUNS
+#define GI_GATHER_RUNS 16
+#endif
 template <bool COUNT>
 __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S, PathPool pool, const uint32_t* keys, const uint32_t* vals, uint32_t n_in,
                                                                          const unsigned long long* slot_sample, unsigned long long sample0, double* lbuf, StreamCounters* sc)
@@ -46,92 +55,110 @@ __global__ __launch_bounds__(GI_BLOCK, GI_GATHER_WAVES) void k_st_gather(Scene S
         const uint32_t rank = valid ? keys[i] : 0xffffffffu;                       // rank of the query's leaf among the leaves with candidates
         const bool has_leaf = valid && rank < (uint32_t)S.n_pleaf;
         const uint32_t leaf = has_leaf ? (uint32_t)S.prank_leaf[rank] : 0xffffffffu;
-        const uint32_t leaf0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
-        const bool uniform = __ballot(valid && leaf != leaf0) == 0ull && leaf0 < (uint32_t)S.n_pnode;
         if constexpr (COUNT) { if (valid) n_q++; }
-        if (!uniform) {
+        // the runs of the wave: lanes of one leaf stand side by side (the queries are in leaf order), so a run starts where a lane's leaf is not its left
+        // neighbour's.  (Queries in another order -- gi_debug_gather_pass, sort = 0 -- give more starts than leaves, which only moves the limit.)
+        unsigned long long todo = __ballot(has_leaf);                              // lanes whose query is still to be served
+        if (todo == 0ull) continue;
+        const uint32_t left = (uint32_t)__shfl_up((int)leaf, 1);
+        const int n_runs = __popcll(__ballot(has_leaf && (lane == 0u || leaf != left)));
+        const uint32_t gslot = valid ? vals[i] : 0u;
+        if (n_runs > 1 && (!S.pcand || n_runs > GI_GATHER_RUNS)) {
             if (has_leaf) {
                 if constexpr (COUNT) n_c += (unsigned long long)S.pnodes[leaf].u.lf.nb_photons;
-                PathRef pr = pool[vals[i]];
-                stage_gather_in_leaf(S, pr, (int32_t)leaf, heap, 64, lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3);
+                PathRef pr = pool[gslot];
+                stage_gather_in_leaf(S, pr, (int32_t)leaf, heap, 64, lbuf + (sample_of(slot_sample, sample0, gslot) - sample0) * 3);
             }
             continue;
         }
-        const uint32_t rank0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rank);
-        const PNode& lf = S.pnodes[leaf0];
-        const int ncand = lf.u.lf.nb_photons;
-        if constexpr (COUNT) { if (valid) n_c += (unsigned long long)ncand; }
-        if (ncand == 0) continue;
-        const PRange* ranges = S.pranges + lf.nb_off;
-        GatherAcc a;
-        const uint32_t gslot = valid ? vals[i] : 0u;
-        g_begin(a, valid ? ld3(pool.hit[gslot].hpos) : v3(0, 0, 0), valid ? ld3(pool.gath[gslot].gdir) : v3(0, 0, 0), heap, 64, ncand);
-        // the leaf's candidates as one sequence (its ranges back to back, the order gather_in_leaf visits them), 64 per step: candidates
-        // [c0, c0 + m) into cand[0, m), positions only or (all9) positions, directions and colours
-        auto stage = [&](int32_t c0, int32_t m, bool all9) {
-            __builtin_amdgcn_wave_barrier();
-            if ((int32_t)lane < m) {
-                const double* pp;
-                const double* dc;
-                if (S.pcand) {
-                    const size_t at = (size_t)S.pcand_off[rank0] + (size_t)(c0 + (int32_t)lane);
-                    pp = S.pcand + at * 3; dc = S.pcand_dc + at * 6;
-                } else {
-                    int32_t off = c0 + (int32_t)lane, r = 0;
-                    while (off >= ranges[r].count) { off -= ranges[r].count; r++; }   // r < n_ranges: off < ncand = sum of the counts
-                    const size_t ph = (size_t)(ranges[r].first + off);
-                    pp = S.ph_pos + ph * 3; dc = S.ph_dircol + ph * 6;
-                }
-                cand[lane][0] = pp[0]; cand[lane][1] = pp[1]; cand[lane][2] = pp[2];
-                if (all9)
-                    for (int k = 0; k < 6; k++) cand[lane][3 + k] = dc[k];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        };
-        // pass 1 runs the chunks from the last to the first and stages chunk 0 whole, so pass 2 (chunks in candidate order) finds it in LDS
-        a.tau = ksel_tau(ncand, [&](int32_t c0, int32_t m) { stage(c0, m, c0 == 0); }, [&](int32_t k) { return (float)g_d2(a, ld3(cand[k])); });
-        for (int32_t c0 = 0; c0 < ncand; c0 += GI_GCHUNK) {
-            const int32_t m = min((int32_t)GI_GCHUNK, ncand - c0);
-            if (c0 != 0) stage(c0, m, true);
-            if (valid) {
-                // g_acc per candidate, with the rare case set aside: a candidate whose key EQUALS tau (the 32nd smallest itself; one per
-                // query, more only when float keys tie) is some lane's business for nearly every candidate of the wave, so its branch --
-                // a sum of its own, a count, a running maximum -- would run for nearly every candidate.  The loop takes the below-tau half
-                // and only notes where such candidates are; they are added afterwards, in candidate order, by g_acc itself.
-                int n_eq = 0;
-                int32_t k_eq = 0;
-                for (int32_t k = 0; k < m; k++) {
-                    const double* q = cand[k];
-                    const float key = (float)g_d2(a, ld3(q));
-                    if (key < a.tau) g_add_lt(a, g_contrib(a, q + 3));
-                    else if (key == a.tau) {
-                        if (n_eq == 0) k_eq = k;
-                        n_eq++;
+        const V3 qpos = valid ? ld3(pool.hit[gslot].hpos) : v3(0, 0, 0), qdir = valid ? ld3(pool.gath[gslot].gdir) : v3(0, 0, 0);
+        // The cooperative gather of the queries of ONE leaf (leaf0, of rank rank0; both wave-uniform): `mine` = this lane holds one of them.  All 64 lanes
+        // stage and run the selection (the barriers in stage are wave barriers); only the lanes with a query take sums and write a result.
+        auto gather_leaf = [&](uint32_t leaf0, uint32_t rank0, bool mine) {
+            const PNode& lf = S.pnodes[leaf0];
+            const int ncand = lf.u.lf.nb_photons;
+            if constexpr (COUNT) { if (mine) n_c += (unsigned long long)ncand; }
+            if (ncand == 0) return;
+            const PRange* ranges = S.pranges + lf.nb_off;
+            GatherAcc a;
+            g_begin(a, qpos, qdir, heap, 64, ncand);
+            // the leaf's candidates as one sequence (its ranges back to back, the order gather_in_leaf visits them), 64 per step: candidates
+            // [c0, c0 + m) into cand[0, m), positions only or (all9) positions, directions and colours
+            auto stage = [&](int32_t c0, int32_t m, bool all9) {
+                __builtin_amdgcn_wave_barrier();
+                if ((int32_t)lane < m) {
+                    const double* pp;
+                    const double* dc;
+                    if (S.pcand) {
+                        const size_t at = (size_t)S.pcand_off[rank0] + (size_t)(c0 + (int32_t)lane);
+                        pp = S.pcand + at * 3; dc = S.pcand_dc + at * 6;
+                    } else {
+                        int32_t off = c0 + (int32_t)lane, r = 0;
+                        while (off >= ranges[r].count) { off -= ranges[r].count; r++; }   // r < n_ranges: off < ncand = sum of the counts
+                        const size_t ph = (size_t)(ranges[r].first + off);
+                        pp = S.ph_pos + ph * 3; dc = S.ph_dircol + ph * 6;
                     }
+                    cand[lane][0] = pp[0]; cand[lane][1] = pp[1]; cand[lane][2] = pp[2];
+                    if (all9)
+                        for (int k = 0; k < 6; k++) cand[lane][3 + k] = dc[k];
                 }
-                if (n_eq == 1) g_acc(a, ld3(cand[k_eq]), cand[k_eq] + 3);
-                else if (n_eq > 1) {       // float keys tie at tau: walk on from the first of them
-                    for (int32_t k = k_eq; n_eq > 0 && k < m; k++) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            };
+            // pass 1 runs the chunks from the last to the first and stages chunk 0 whole, so pass 2 (chunks in candidate order) finds it in LDS
+            a.tau = ksel_tau(ncand, [&](int32_t c0, int32_t m) { stage(c0, m, c0 == 0); }, [&](int32_t k) { return (float)g_d2(a, ld3(cand[k])); });
+            for (int32_t c0 = 0; c0 < ncand; c0 += GI_GCHUNK) {
+                const int32_t m = min((int32_t)GI_GCHUNK, ncand - c0);
+                if (c0 != 0) stage(c0, m, true);
+                if (mine) {
+                    // g_acc per candidate, with the rare case set aside: a candidate whose key EQUALS tau (the 32nd smallest itself; one per
+                    // query, more only when float keys tie) is some lane's business for nearly every candidate of the wave, so its branch --
+                    // a sum of its own, a count, a running maximum -- would run for nearly every candidate.  The loop takes the below-tau half
+                    // and only notes where such candidates are; they are added afterwards, in candidate order, by g_acc itself.
+                    int n_eq = 0;
+                    int32_t k_eq = 0;
+                    for (int32_t k = 0; k < m; k++) {
                         const double* q = cand[k];
-                        if ((float)g_d2(a, ld3(q)) == a.tau) { g_acc(a, ld3(q), q + 3); n_eq--; }
+                        const float key = (float)g_d2(a, ld3(q));
+                        if (key < a.tau) g_add_lt(a, g_contrib(a, q + 3));
+                        else if (key == a.tau) {
+                            if (n_eq == 0) k_eq = k;
+                            n_eq++;
+                        }
+                    }
+                    if (n_eq == 1) g_acc(a, ld3(cand[k_eq]), cand[k_eq] + 3);
+                    else if (n_eq > 1) {       // float keys tie at tau: walk on from the first of them
+                        for (int32_t k = k_eq; n_eq > 0 && k < m; k++) {
+                            const double* q = cand[k];
+                            if ((float)g_d2(a, ld3(q)) == a.tau) { g_acc(a, ld3(q), q + 3); n_eq--; }
+                        }
                     }
                 }
             }
-        }
-        if (valid) {
-            V3 caustic;
-            if (!g_end(a, caustic)) caustic = g_exact(S, (int32_t)leaf0, a);   // float keys tie across rank 32
-            gather_add(lbuf + (sample_of(slot_sample, sample0, vals[i]) - sample0) * 3, pool.gath[gslot].gcoef, caustic);   // the path's radiance lives in the per-sample buffer
-        }
+            if (mine) {
+                V3 caustic;
+                if (!g_end(a, caustic)) caustic = g_exact(S, (int32_t)leaf0, a);   // float keys tie across rank 32
+                gather_add(lbuf + (sample_of(slot_sample, sample0, gslot) - sample0) * 3, pool.gath[gslot].gcoef, caustic);   // the path's radiance lives in the per-sample buffer
+            }
+        };
+        // one run per turn, the leftmost lane not yet served names it; a wave of one leaf (nearly all of a large pass) makes one turn.  todo is wave-uniform
+        do {
+            const int src = __ffsll((long long)todo) - 1;
+            const uint32_t leaf0 = (uint32_t)__builtin_amdgcn_readlane((int)leaf, src), rank0 = (uint32_t)__builtin_amdgcn_readlane((int)rank, src);
+            const bool mine = leaf == leaf0;                                        // (a lane without a leaf holds 0xffffffff)
+            todo &= ~__ballot(mine);
+            gather_leaf(leaf0, rank0, mine);
+        } while (todo != 0ull);
     }
     if constexpr (COUNT) { flush_u64(&sc->gather_queries, n_q); flush_u64(&sc->gather_cand, n_c); }
 }
 
-// A query per WAVE, for the passes with few queries.  Late passes hold a handful of queries per photon-map leaf: a wave of k_st_gather then either serves
-// sixty leaves one after the other with one or two lanes at work, or lets every lane walk its own leaf -- either way the pass lasts as long as some
-// five thousand candidate steps of one wave (1.2 - 1.6 ms on the benchmark frame, whatever the number of queries).  Here the lanes take a CANDIDATE
+// A query per WAVE, for the passes with few queries.  Late passes hold a handful of queries per photon-map leaf: a wave of k_st_gather then spans
+// more leaves than it serves one after the other (GI_GATHER_RUNS) and lets every lane walk its own leaf, which lasts as long as some five thousand
+// candidate steps of one wave (1.2 - 1.6 ms on the benchmark frame, whatever the number of queries).  Passes whose waves still fit the runs take
+// 1.6 ms at 2.0 M queries, 1.0 at 1.0 M, 0.9 at 520 k, 0.7 at 337 k and 0.6 at 214 k; below GI_GATHER_WAVE_BELOW queries (200 000: 0.5 ms) this
+// form takes over.  Here the lanes take a CANDIDATE
 // each: 64 keys per step, the 32 smallest kept across the lanes (a bitonic sort of the 64 new keys through lane exchanges, the smaller half against
 // the best so far, a bitonic merge: ~110 instructions per 64 candidates instead of 18 per candidate and query), tau read off lane K - 1; the second
 // pass computes every lane's contribution and adds those below tau in CANDIDATE ORDER (a lane at a time, read off by v_readlane, through g_add_lt), so
