@@ -187,6 +187,13 @@ BakePlan bake_plan(size_t budget, uint32_t n_points, uint32_t n_samples)
     return pl;
 }
 
+// k_bake_fold of the mode over the np points of a chunk, one lane per point (the bake's ranges and gi_bake_fold's)
+void launch_bake_fold(int mode, hipStream_t st, const double* lbuf, const double* dirs, uint32_t np, uint32_t nk, double* sums, int first, int last, double n_samples, void* out, int out_f64)
+{
+    const auto fold = mode == GI_BAKE_SH9 ? k_bake_fold<GI_BAKE_MODE_SH9> : k_bake_fold<GI_BAKE_MODE_TEXEL>;
+    hipLaunchKernelGGL(fold, GI_GRID(np), 0, st, lbuf, dirs, np, nk, sums, first, last, n_samples, out, out_f64);
+}
+
 // the stream passes run on the frame's stage clock and, when asked, its work counters: a bake switches both off for its own passes and puts them back
 struct BakeQuiet {
     gi_ctx* c;
@@ -208,7 +215,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
     size_t budget = std::min<size_t>(c->tune.pool_slots_max, 0xfffffff0ull);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const size_t held = c->st.d_spool.n + c->st.d_lbuf.n * 8 + (c->st.work.q_new.n + c->st.work.q_free_b.n) * 4 * 7 + c->st.d_shq.n * sizeof(ShadowQ) + c->bake.d_dirs.n * 8;
+        const size_t held = c->st.held_bytes() + c->bake.d_dirs.n * 8;
         const size_t per_slot = kPoolRecordBytes + kBudgetWorkBytes + sizeof(ShadowQ) * (size_t)n_shadow + 24 + 24;
         budget = std::min(budget, std::max<size_t>(64, (size_t)((double)(free_b + held) * 0.90) / per_slot));
     }
@@ -220,7 +227,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
     if (bp.mode == GI_BAKE_SH9 && c->bake.d_dirs.n < slots * 3) HIP_TRY(c, c->bake.d_dirs.alloc(slots * 3));
     if (pl.range_k < n_samples && c->bake.d_sums.n < (size_t)terms * pl.chunk_points) HIP_TRY(c, c->bake.d_sums.alloc((size_t)terms * pl.chunk_points));
     if (!c->st.d_wfcnt.p) HIP_TRY(c, c->st.d_wfcnt.alloc(2));
-    const bool debug_wf = getenv("GI_DEBUG_WF") != nullptr;   // read at every call
+    const bool debug_wf = debug_wf_on();
     if (debug_wf) fprintf(stderr, "[bake] %u points x %u samples: chunks of %u points, ranges of %u samples\n", n_points, n_samples, pl.chunk_points, pl.range_k);
     // the passes take the seed from a frame, and the size of the finisher's share from its extent: a frame of one row of this chunk's points
     Frame F;
@@ -251,11 +258,7 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
             if (const int rc = stream_passes(c, F, c->st.d_slot_sample.p, 0ull, c->st.d_lbuf.p, 0u, refill, debug_wf, nullptr, launches)) { tm.reset(); return rc; }
             const int first = k0 == 0, last = k0 + nk == n_samples;
             void* const out = (char*)d_out + (size_t)i0 * out_row;
-            const dim3 grid((np + GI_BLOCK - 1) / GI_BLOCK), block(GI_BLOCK);
-            if (bp.mode == GI_BAKE_SH9)
-                hipLaunchKernelGGL(k_bake_fold<GI_BAKE_MODE_SH9>, grid, block, 0, st, c->st.d_lbuf.p, dirs, np, nk, c->bake.d_sums.p, first, last, (double)bp.n_samples, out, out_is_f64);
-            else
-                hipLaunchKernelGGL(k_bake_fold<GI_BAKE_MODE_TEXEL>, grid, block, 0, st, c->st.d_lbuf.p, dirs, np, nk, c->bake.d_sums.p, first, last, (double)bp.n_samples, out, out_is_f64);
+            launch_bake_fold(bp.mode, st, c->st.d_lbuf.p, dirs, np, nk, c->bake.d_sums.p, first, last, (double)bp.n_samples, out, out_is_f64);
             HIP_TRY(c, hipGetLastError());
         }
     }
@@ -355,8 +358,7 @@ int gi_bake_fold(gi_ctx* c, int32_t mode, int32_t n_points, int32_t n_samples, c
             const int first = k0 == 0, last = k0 + nk == ns;
             const double* l = d_l + (size_t)k0 * np * 3;
             const double* d = d_d ? d_d + (size_t)k0 * np * 3 : nullptr;
-            if (mode == GI_BAKE_SH9) hipLaunchKernelGGL(k_bake_fold<GI_BAKE_MODE_SH9>, GI_GRID(np), 0, c->stream, l, d, np, nk, d_sums, first, last, (double)n_samples, (void*)d_o, 1);
-            else hipLaunchKernelGGL(k_bake_fold<GI_BAKE_MODE_TEXEL>, GI_GRID(np), 0, c->stream, l, d, np, nk, d_sums, first, last, (double)n_samples, (void*)d_o, 1);
+            launch_bake_fold(mode, c->stream, l, d, np, nk, d_sums, first, last, (double)n_samples, (void*)d_o, 1);
         }
     });
 }

@@ -334,6 +334,10 @@ struct StreamState {
     // everything the pass loop needs for P paths in flight (the radiance buffer is the caller's); n_shadow: deferred shadow queries per path
     // need_table: the caller's passes read slot_sample (sample_of); a chunk whose samples are all in flight at once does without it
     hipError_t alloc(uint32_t P, bool need_table, int n_shadow);   // gi_stream.inc, behind the sort's constants
+    // Bytes of the above that the context holds already and the next frame would re-use (plan_pool: held_b): pool, radiance buffer, shadow queries and
+    // queues.  The queues are an estimate: q_new and q_free_b each stand for 7 workspaces of their size, 4 bytes an entry (the queues were two
+    // families of seven when the term was written).  kStreamWork holds more words per slot today; counting less as held only plans a smaller pool.
+    size_t held_bytes() const { return d_spool.n + d_lbuf.n * 8 + (work.q_new.n + work.q_free_b.n) * 4 * 7 + d_shq.n * sizeof(ShadowQ); }
 };
 
 // ------------------------------------------------------------------------------------------------------------------------ auxiliary passes

@@ -3,7 +3,7 @@
 // The functions stand in the parts below, by topic.  All of them are plain scalar-per-lane code marked GI_HD so that the very same
 // functions can also be compiled for the host by tests/host_emul (a CPU build used ONLY by unit tests and sanitizers to check the
 // kernel logic without a GPU; the product library never contains it).  Wave-level code (ballots, atomics, LDS carving, launches)
-// lives in gi_kernels.hip and its .inc files; the per-lane halves of the additions (features, occlusion, bake, lightmap, denoiser)
+// lives in the parts of gi_kernels.hip (gi_lds.h, gi_pool.h, the .inc files); the per-lane halves of the additions (features, occlusion, bake, lightmap, denoiser)
 // stand beside their kernels there, since no CPU build names them.
 //
 // The parts are included in this order inside namespace gi, and each needs exactly the parts above it; none includes another.

@@ -1,6 +1,142 @@
 // gi_entries.inc -- the function-level and debug entries of the C ABI: host arrays in, one kernel (or one pass), host arrays out.  Included by
 // gi_kernels.hip behind the passes.  Each reads: argument and state checks, buffers (Entry, gi_context.inc:
 // element counts once per buffer), the launch, and Entry::run copies the outputs back in the order they were named.
+// The kernels come first (nothing outside this file launches them), outside the anonymous namespace; the entries follow them.
+
+__global__ __launch_bounds__(GI_BLOCK) void k_trace(Scene S, int n, const double* rays, int32_t* hit, int32_t* ent, double* res)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* r = rays + (size_t)i * 6;
+    Ray ray = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+    Rng rng = rng_make(0, (uint32_t)i);
+    HitRec h;
+    bool ok = trace(S, ray, rng, P_TRACE_ALPHA, h, nullptr);
+    hit[i] = ok ? 1 : 0;
+    ent[i] = ok ? h.tri : -1;
+    double* o = res + (size_t)i * 8;
+    if (ok) {
+        V3 nn = shading_normal(S, h);
+        o[0] = h.pos.x; o[1] = h.pos.y; o[2] = h.pos.z; o[3] = nn.x; o[4] = nn.y; o[5] = nn.z; o[6] = h.u; o[7] = h.v;
+    } else
+        for (int k = 0; k < 8; k++) o[k] = 0;
+}
+
+__global__ __launch_bounds__(GI_BLOCK) void k_visible(Scene S, int n, const double* q, int32_t* vis)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* p = q + (size_t)i * 6;
+    V3 o = v3(p[0], p[1], p[2]), t = v3(p[3], p[4], p[5]);
+    V3 ld = t - o;
+    double maxt = len2(ld);
+    Ray sr = make_ray(o, ld);
+    Rng rng = rng_make(0, (uint32_t)i);
+    vis[i] = visible(S, sr, maxt, rng, 0, nullptr) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(GI_BLOCK) void k_visible_rays(Scene S, int n, const double* rays, const double* mt, int32_t* vis)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* r = rays + (size_t)i * 6;
+    Ray sr = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+    Rng rng = rng_make(0, (uint32_t)i);
+    vis[i] = visible(S, sr, mt[i], rng, 0, nullptr) ? 1 : 0;
+}
+
+// gi_debug_walk: caller rays through the walk forms the passes run, with k_trace's / k_visible_rays' keys (rng_make(0, i), P_TRACE_ALPHA, light 0) and
+// k_trace's output.  FORM 0: a ray per lane over the records and content boxes k_st_trace (closest hit) / a shadow kernel without lights to end at
+// (any hit) stages; FORM 1, 2: a ray per wave / per group of 16 lanes over what k_st_finish stages (ray i = group i, every lane of the group holds
+// it, the first writes).  lds = 0: the same source with nothing staged (n_l = n_lc = 0), every record and box from global memory.
+#define GI_DEBUG_WALK_BLOCK 256
+template <int FEAT, int FORM, bool ANY>
+__global__ __launch_bounds__(GI_DEBUG_WALK_BLOCK) void k_debug_walk(Scene S, int n, const double* rays, const double* mt, int lds, int32_t* hit, int32_t* ent, double* res)
+{
+    constexpr uint32_t G = FORM == 1 ? 64u : (FORM == 2 ? 16u : 1u);
+    typedef typename std::conditional<FORM == 0, LdsWide, LdsWideCoop<FORM == 2 ? 16 : 64>>::type Src;
+    const LdsWide L = FORM == 0 ? stage_wide_in_lds(S, true, GI_LDS_WNODES_BIG, ANY ? 0 : 1) : stage_wide_in_lds(S, true, GI_FINISH_COOP_RECORDS);   // ends with a barrier
+    Src N;
+    N.g = L.g; N.cboxes = L.cboxes; N.cuse = L.cuse; N.box_off = L.box_off; N.use_off = L.use_off;
+    N.n_l = lds ? L.n_l : 0; N.n_lc = lds ? L.n_lc : 0;
+    const uint32_t n_groups = gridDim.x * blockDim.x / G;
+    for (uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) / G; i < (uint32_t)n; i += n_groups) {   // uniform over a group: its lanes stay together
+        const double* r = rays + (size_t)i * 6;
+        const Ray ray = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+        const Rng rng = rng_make(0, i);
+        const bool writes = (threadIdx.x & (G - 1u)) == 0u;
+        if constexpr (ANY) {
+            const bool vis = visible_nodes<FEAT>(S, N, ray, mt[i], rng, 0, nullptr);
+            if (writes) hit[i] = vis ? 1 : 0;
+        } else {
+            HitRec h;
+            h.tu = 0; h.tv = 0;
+            const bool ok = trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr);
+            if (!writes) continue;
+            hit[i] = ok ? 1 : 0;
+            ent[i] = ok ? h.tri : -1;
+            double* o = res + (size_t)i * 8;
+            if (ok) {
+                const V3 nn = shading_normal(S, h);
+                o[0] = h.pos.x; o[1] = h.pos.y; o[2] = h.pos.z; o[3] = nn.x; o[4] = nn.y; o[5] = nn.z; o[6] = h.u; o[7] = h.v;
+            } else
+                for (int k = 0; k < 8; k++) o[k] = 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(GI_BLOCK) void k_radiance(Scene S, int n, const double* rays, const uint32_t* stream, uint64_t seed, double* out3)
+{
+    __shared__ float heap[GI_GATHER_K * GI_BLOCK];
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* r = rays + (size_t)i * 6;
+    Ray ray = make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]));
+    V3 L = radiance_path(S, ray, stream[i], seed, heap + threadIdx.x, GI_BLOCK, nullptr);
+    out3[(size_t)i * 3] = L.x; out3[(size_t)i * 3 + 1] = L.y; out3[(size_t)i * 3 + 2] = L.z;
+}
+
+__global__ __launch_bounds__(GI_BLOCK) void k_emit(Scene S, int count, int max_depth, uint64_t seed, PhotonOut* out, int32_t* stored, int32_t* tries)
+{
+    int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count * S.n_light) return;
+    int i = j / S.n_light, li = j % S.n_light;
+    PhotonOut po;
+    int32_t t = 0;
+    bool ok = emit_photon(S, i, li, count, max_depth, seed, po, t);
+    stored[j] = ok ? 1 : 0;
+    tries[j] = t;
+    if (ok) out[j] = po;
+}
+
+__global__ __launch_bounds__(GI_BLOCK) void k_leaf_order(Scene S, int n, const double* rays, int cap, int32_t* leaf_out, int32_t* n_out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* r = rays + (size_t)i * 6;
+    n_out[i] = leaf_order(S, make_ray_exact(v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5])), cap, leaf_out + (size_t)i * cap);
+}
+__global__ __launch_bounds__(GI_BLOCK) void k_kat(int what, int n, const double* in, int in_stride, double* out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double a[9], o[3];
+    for (int k = 0; k < 9; k++) a[k] = k < in_stride ? in[(size_t)i * in_stride + k] : 0.0;
+    kat_eval(what, a, o);
+    for (int k = 0; k < 3; k++) out[(size_t)i * 3 + k] = o[k];
+}
+
+__global__ void k_halton(Scene S, int n, const uint32_t* dim, const uint32_t* index, float* out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = halton_sample(S, dim[i], index[i]);
+}
+__global__ void k_halton_index(HaltonEnumD he, int n, const uint32_t* sxy, uint32_t* out)
+{
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = halton_index(he, sxy[i * 3], sxy[i * 3 + 1], sxy[i * 3 + 2]);
+}
+
 namespace {
 
 // The photon map's box: the caller's, or the scene's

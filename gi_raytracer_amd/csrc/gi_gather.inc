@@ -1,4 +1,4 @@
-// gi_gather.inc -- the photon gather's wave-level forms and its kernels.  Included by gi_kernels.hip behind PathPool, sample_of, chunk_item and
+// gi_gather.inc -- the photon gather's wave-level forms and its kernels.  Included by gi_stages.inc behind PathPool, sample_of, chunk_item and
 // k_st_compact (which keys the queries: gather_key).  The selection they share with the per-lane form -- key, contribution, the two sums, the
 // end rule, the exact pass -- and the one result write are in gi_gather.h; here is only how each form brings a leaf's candidates to them:
 //   k_st_gather        a wave of 64 queries, served leaf by leaf: a leaf's candidates staged in LDS, 64 at a time, for the lanes whose query lies in it

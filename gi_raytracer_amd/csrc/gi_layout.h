@@ -874,7 +874,7 @@ inline bool make_frame(const gi_render_params* p, Frame& F, std::string& err)
 // What a slot is budgeted, in bytes: the terms beside the record are kBudgetWorkBytes, which gi_stream.inc asserts to cover what its workspace
 // table (kStreamWork) really allocates per slot.  The figure is somewhat larger than that table's (124 against 112 bytes), and P of
 // the benchmark frame, which is bound by HBM, follows from it: changing a term changes that frame's speed.
-constexpr size_t kPoolRecordBytes = 232;         // the field arrays of PathPool (gi_kernels.hip: GI_POOL_BYTES_PER_SLOT, asserted there)
+constexpr size_t kPoolRecordBytes = 232;         // the field arrays of PathPool (gi_pool.h: GI_POOL_BYTES_PER_SLOT, asserted there)
 constexpr size_t kBudgetSampleIdBytes = 8;       // the slot -> sample table
 constexpr size_t kBudgetQueueBytes = 13 * 4;     // 13 queue / key words
 constexpr size_t kBudgetSortBytes = 24;          // sort scratch

@@ -66,7 +66,7 @@ GI_HD V3 shading_normal(const Scene& S, const HitRec& h)  // include/entities.h:
 // L = A_0 + f_0 (A_1 + f_1 (A_2 + ...)) is accumulated as sum_k (prod_{j<k} f_j) A_k with A = color*i + emissive (+ color*caustic,
 // added by the gather stage) on continue, color*i on a failed roulette, ambient on a miss and 0 past MAX_DEPTH.
 // The megakernel and the finisher run the stages back to back per lane on a PathRec in registers; the streaming passes run each
-// stage as its own kernel over compacted queues of path slots, on the same fields kept as field arrays (PathPool, gi_kernels.hip).
+// stage as its own kernel over compacted queues of path slots, on the same fields kept as field arrays (PathPool, gi_pool.h).
 struct alignas(16) PathRec {    // 224 B, one path (in registers; the streaming pool stores the same fields as arrays)
     double o[3], d[3];          // current ray (d normalised)
     uint32_t stream;            // Halton sample index = RNG stream

@@ -1,5 +1,5 @@
 // gi_stream.inc -- the host side of the streaming pipeline: which k_st_* kernel runs when, on which queue.  Host code only; the kernels are
-// gi_kernels.hip's, their instance tables and selectors (st_trace, st_shade, ...) gi_instances.inc's, the workspaces (StreamState, StreamWork,
+// gi_stages.inc's and gi_pixels.inc's, their instance tables and selectors (st_trace, st_shade, ...) gi_instances.inc's, the workspaces (StreamState, StreamWork,
 // kStreamWork) and the stage clock gi_context.inc's.  Included by gi_kernels.hip behind gi_sort.inc; the render entries that choose between the
 // schedules are in gi_api.inc.
 //
@@ -373,6 +373,8 @@ static int cont_sort_stage(Passes& p)
     return GI_OK;
 }
 
+// GI_DEBUG_WF in the environment: a line per pass on stderr.  Read at every call and never kept: the tests set it for single frames.
+static bool debug_wf_on() { return getenv("GI_DEBUG_WF") != nullptr; }
 static void print_pass(const Passes& p)   // GI_DEBUG_WF
 {
     fprintf(stderr, "[st] new %u cont %u free %u gather %u\n", p.n_new, p.n_cont, p.n_free, p.n_gather);
@@ -418,12 +420,11 @@ static int stream_samples(gi_ctx* c, const Frame& F, PixRec* pix, int s_begin, i
 {
     const uint32_t n_pix = (uint32_t)F.w * (uint32_t)F.local_rows;   // valid pixels only, enumerated in 8x8-tile order (st_pixel_xy)
     const int spp = s_end - s_begin;
-    const bool debug_wf = getenv("GI_DEBUG_WF") != nullptr;          // read at every call
+    const bool debug_wf = debug_wf_on();
     // paths in flight and samples per chunk: gi_layout.h's budget, of free memory plus what this context holds already and would re-use
     size_t free_b = 0, total_b = 0;
     const bool mem_known = hipMemGetInfo(&free_b, &total_b) == hipSuccess;
-    const size_t held = c->st.d_spool.n + c->st.d_lbuf.n * 8 + (c->st.work.q_new.n + c->st.work.q_free_b.n) * 4 * 7 + c->st.d_shq.n * sizeof(ShadowQ);
-    const PoolPlan plan = plan_pool(mem_known, free_b, held, n_pix, spp, c->tune.pool_slots_max, c->tune.lbuf_bytes_max, defers_shadows(c) ? c->S.n_light : 0);
+    const PoolPlan plan = plan_pool(mem_known, free_b, c->st.held_bytes(), n_pix, spp, c->tune.pool_slots_max, c->tune.lbuf_bytes_max, defers_shadows(c) ? c->S.n_light : 0);
     const uint32_t P = plan.P;
     const int chunk = plan.chunk;
     // The sample table.  A chunk of ns samples per pixel whose n_pix * ns samples all fit the pool is started whole by the first pass: refill hands
@@ -483,7 +484,7 @@ static int run_rounds(gi_ctx* c, const Frame& F, PixRec* pix, bool init, void* d
 {
     if (!rounds_fit(F)) return fail(c, GI_E_INVALID, "render: frame too large for 32-bit path slots");
     const uint32_t n_pix = rounds_records(F);   // padded to whole 8x8 tiles (tile_pixel_xy)
-    const bool debug_wf = getenv("GI_DEBUG_WF") != nullptr;   // read at every call
+    const bool debug_wf = debug_wf_on();
     int B = (int)std::min<size_t>(32, std::max<size_t>(1, std::min<size_t>(c->tune.pool_slots_max, 0xfffffff0ull) / n_pix));
     B = std::max(1, std::min(B, std::max(F.max_samples, 1)));
     const size_t slots = (size_t)n_pix * (size_t)B;

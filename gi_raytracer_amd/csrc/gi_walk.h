@@ -7,7 +7,7 @@
 //   trace            include/raytracer.h:382-478 + include/octree.cpp:188-211,285-313 + include/bbox.h:47-73
 //   visible          include/raytracer.h:280-319 + include/octree.cpp:150-185,256-282 + include/bbox.h:117-138
 
-// Where node records come from: plain global memory here; gi_kernels.hip adds a source that serves the first nodes from LDS.
+// Where node records come from: plain global memory here; gi_lds.h adds a source that serves the first nodes from LDS.
 struct NodeView { double bmin[3], bmax[3]; int32_t first_ref, n_ref, hit, skip; };
 struct GlobalNodes {
     static constexpr bool kWide = false;

@@ -1,5 +1,5 @@
 """GI_SAMPLE_IDENTITY: a chunk whose samples are all in flight at once is started whole by the first pass, slot s carries sample sample0 + s
-throughout, and the stream passes are given no slot -> sample table (gi_kernels.hip: sample_of; gi_stream.inc: stream_samples).  Where the table is kept -- the
+throughout, and the stream passes are given no slot -> sample table (gi_pool.h: sample_of; gi_stream.inc: stream_samples).  Where the table is kept -- the
 knob at 0, a pool smaller than the chunk so that freed slots take new samples -- the frame is the same bit for bit: which table a path's place in the
 radiance buffer is read from is bookkeeping, not arithmetic.  Scenes with a medium and with textures run the other kernel instances and the
 finisher; a progressive session takes the frame in two chunks with a sample0 of their own.  Which of the two a frame ran with, and the size of its

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Is the device code of gi_kernels.hip the same in two source trees?  For a change that is meant to move host code only.
+"""Is the device code of gi_kernels.hip the same in two source trees?  For a change that is meant to move host code only, or kernels between the files it includes.
 
 usage: tools/compare_device_code.py CSRC_A CSRC_B      (two gi_raytracer_amd/csrc directories; A == B checks the comparison itself)
 
