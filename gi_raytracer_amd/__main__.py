@@ -10,6 +10,7 @@
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
     python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
                                -o OUT.ppm [--pfm OUT.pfm]
+    python -m gi_raytracer_amd scene.scn --reflection-probe X Y Z [--probe-face N] [--probe-samples N] [--probe-levels L] [--photons N] -o OUT.npz
 
 The scene file's own `samples` / `photons` / `camera` lines apply unless overridden, exactly as loadScene sets RayTracer's fields
 (include/sceneLoader.cpp:160-179); the frame size defaults to the reference window, 1000 x 1000 (main.cpp:43).
@@ -41,6 +42,10 @@ coefficients to -o as a numpy array [NZ][NY][NX][9][3] (float32; include/gi_hip.
 texture coordinates, read as an unwrapped chart (v grows downwards) -- of the triangles of material index --lightmap-material M, or of all triangles
 -- with --lightmap-samples N rays per covered texel (default 256) and --lightmap-dilate D gutter passes (default 2), after the photon pass.  -o gets
 the 8-bit PPM of the display transform, --pfm the linear atlas; one line gives the number of covered texels and the device time.
+--reflection-probe X Y Z (one more addition) renders no frame either: it captures a reflection probe at that position (include/gi_hip.h:
+gi_cubemap_*) -- a cube map of --probe-face N texels per face edge (default 32) with --probe-samples N rays per texel (default 64) -- and filters
+--probe-levels L levels of its roughness chain (default 1: the capture alone; N must be divisible by 2^(L-1)), after the photon pass.  -o gets a
+numpy .npz with the keys level0, level1 ... as float32 [6][N >> l][N >> l][3].  Not together with --probes or --lightmap.
 """
 import argparse
 import os
@@ -53,6 +58,7 @@ import gi_raytracer_amd as gi
 FEATURE_FILES = ("albedo", "normal", "depth", "coverage")
 PROBE_SAMPLES = 256
 LIGHTMAP_SAMPLES = 256
+REFLECTION_FACE, REFLECTION_SAMPLES = 32, 64
 
 
 def parser():
@@ -88,7 +94,10 @@ def parser():
     ap.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: distance of the plane that stays sharp (default: the camera's focal distance)")
     ap.add_argument("--focus-pixel", type=int, nargs=2, default=None, metavar=("X", "Y"), help="with --aperture: focus on the first surface behind the centre of this pixel")
     ap.add_argument("--probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="bake a grid of light probes in the scene's box instead of a frame; -o gets a .npy [NZ][NY][NX][9][3]")
-    ap.add_argument("--probe-samples", type=int, default=None, metavar="N", help="with --probes: rays per probe (default 256)")
+    ap.add_argument("--probe-samples", type=int, default=None, metavar="N", help="with --probes: rays per probe (default 256); with --reflection-probe: rays per texel (default 64)")
+    ap.add_argument("--reflection-probe", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="capture a reflection probe at this position instead of a frame; -o gets a .npz of level0, level1 ...")
+    ap.add_argument("--probe-face", type=int, default=None, metavar="N", help="with --reflection-probe: texels per face edge (default 32)")
+    ap.add_argument("--probe-levels", type=int, default=None, metavar="L", help="with --reflection-probe: levels of the roughness chain, 1 .. 12 (default 1: the capture alone)")
     ap.add_argument("--lightmap", type=int, nargs=2, default=None, metavar=("W", "H"), help="bake a W x H lightmap atlas over the scene's texture coordinates instead of a frame")
     ap.add_argument("--lightmap-material", type=int, default=None, metavar="M", help="with --lightmap: only the triangles of this material index (default: all triangles)")
     ap.add_argument("--lightmap-samples", type=int, default=None, metavar="N", help="with --lightmap: rays per covered texel (default 256)")
@@ -114,8 +123,27 @@ def check_args(ap, a):
         ap.error("--progressive N: N must be at least 1")
     if a.time_limit is not None and not a.time_limit >= 0:
         ap.error("--time-limit SECONDS: a number >= 0")
-    if a.probes is None and a.probe_samples is not None:
-        ap.error("--probe-samples needs --probes NX NY NZ")
+    if a.probes is None and a.reflection_probe is None and a.probe_samples is not None:
+        ap.error("--probe-samples needs --probes NX NY NZ or --reflection-probe X Y Z")
+    if a.reflection_probe is None and (a.probe_face is not None or a.probe_levels is not None):
+        ap.error("--probe-face and --probe-levels need --reflection-probe X Y Z")
+    if a.reflection_probe is not None:
+        if a.probes is not None or a.lightmap is not None:
+            ap.error("--reflection-probe does not go together with --probes or --lightmap")
+        face = REFLECTION_FACE if a.probe_face is None else a.probe_face
+        ns = REFLECTION_SAMPLES if a.probe_samples is None else a.probe_samples
+        levels = 1 if a.probe_levels is None else a.probe_levels
+        if not all(-float("inf") < v < float("inf") for v in a.reflection_probe):
+            ap.error("--reflection-probe X Y Z: three finite numbers")
+        if face < 1 or ns < 1 or not 1 <= levels <= gi.CUBEMAP_MAX_LEVELS:
+            ap.error(f"--probe-face N and --probe-samples N must be at least 1, --probe-levels L from 1 to {gi.CUBEMAP_MAX_LEVELS}")
+        if face % (1 << (levels - 1)):
+            ap.error(f"--probe-levels {levels} needs a --probe-face divisible by {1 << (levels - 1)}")
+        if 6 * face * face * ns > 2 ** 32:
+            ap.error("--reflection-probe: texels x samples must keep the stream index within 32 bits")
+        frame_flags = (a.pfm, a.samples, a.features, a.feature_samples, a.denoise, a.progressive, a.upsample, a.occlusion, a.aperture)
+        if any(f is not None for f in frame_flags):
+            ap.error("--reflection-probe renders no frame: only --probe-*, --photons, --device and -o go with it")
     if a.probes is not None:
         if min(a.probes) < 1 or a.probes[0] * a.probes[1] * a.probes[2] >= 2 ** 31:
             ap.error("--probes NX NY NZ: three numbers >= 1, fewer than 2^31 probes in all")
@@ -188,6 +216,12 @@ def replace_file(path, write):
 def write_bytes(path, data):
     with open(path, "wb") as f:
         f.write(data)
+
+
+def write_npz(path, arrays):
+    import numpy as np
+    with open(path, "wb") as f:      # (np.savez would add ".npz" to a name without it)
+        np.savez(f, **arrays)
 
 
 def write_npy(path, array):
@@ -284,6 +318,16 @@ def main(argv=None):
         replace_file(a.output, lambda t: write_npy(t, sh))
         print(f"{a.scene}: {nx} x {ny} x {nz} probes of {ns} samples, {stored} photons stored; photon pass {t1 - t0:.2f} s, "
               f"bake {rt.last_bake_ms():.2f} ms -> {a.output}")
+        return 0
+    if a.reflection_probe:
+        face = REFLECTION_FACE if a.probe_face is None else a.probe_face
+        ns = REFLECTION_SAMPLES if a.probe_samples is None else a.probe_samples
+        levels = rt.bake_reflection_probe(a.reflection_probe, face, ns, 1 if a.probe_levels is None else a.probe_levels, f64=False)
+        replace_file(a.output, lambda t: write_npz(t, {f"level{l}": v for l, v in enumerate(levels)}))
+        ms, stages = rt.last_cubemap_ms()
+        print(f"{a.scene}: reflection probe at {a.reflection_probe[0]:g} {a.reflection_probe[1]:g} {a.reflection_probe[2]:g}, face {face}, {ns} samples a texel, "
+              f"{len(levels)} level(s), {stored} photons stored; photon pass {t1 - t0:.2f} s, probe {ms:.2f} ms (capture {stages['capture']:.2f}, "
+              f"prefilter {stages['prefilter']:.2f}) -> {a.output}")
         return 0
     if a.lightmap:
         w, h = a.lightmap

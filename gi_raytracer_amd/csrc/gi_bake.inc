@@ -48,7 +48,8 @@ GI_HD void sh9_basis(V3 d, double* Y)
 
 // A bake is a second generator and a second fold around the stream passes (gi_stream.inc), as an adaptive round is k_ad_gen and k_ad_accum around
 // them: k_bake_gen prepares the paths of a chunk of points and a range of samples in work.q_new, stream_passes runs them with a RoundRefill, and
-// k_bake_fold adds what they left in lbuf to the points' sums.  No k_st_* kernel knows of it.
+// k_bake_fold adds what they left in lbuf to the points' sums.  No k_st_* kernel knows of it.  The generator is a template over where its rays
+// come from (BakePoints here, the cube texels of gi_cubemap.inc), and bake_passes is the loop both share.
 //
 // Slots.  Sample k of point i of the chunk (both counted from the chunk's start) takes slot k * n_chunk_points + i -- the layout of the frame's
 // sample id = s * n_pix + i: the lanes of a wave start neighbouring points of one k, and the fold's lanes (one per point) read lbuf side by side.
@@ -56,26 +57,34 @@ GI_HD void sh9_basis(V3 d, double* Y)
 // sample each, and the samples of a chunk run in ranges of as many k as fit.  The fold of a range continues the sums of the range before in
 // ascending k (f64, [terms][points] of the chunk), so neither split can show in the result.
 struct BakeGen {
-    const double* points;       // rows of the chunk's first point on
-    int32_t mode, n_samples;
+    int32_t n_samples;
     uint32_t n_chunk_points, k_begin, k_count;
     uint32_t stream0;           // stream_base + (chunk's first point) * n_samples
 };
-__global__ __launch_bounds__(GI_BLOCK) void k_bake_gen(Scene S, BakeGen g, PathPool pool, unsigned long long* slot_sample, double* dirs, uint32_t* q_new, unsigned int* n_new)
+// Where a generator's rays come from: at(i) is what point i of the chunk holds for all its samples, ray() the ray of one of them.  A bake reads a
+// point list; a cube capture (gi_cubemap.inc: CubeTexels) numbers the texels of its cube.
+struct BakePoints {
+    const double* points;       // rows of the chunk's first point on
+    int32_t mode;
+    typedef BakePoint At;
+    __device__ BakePoint at(uint32_t i) const { return bake_point(mode, points + (size_t)i * (mode == GI_BAKE_MODE_TEXEL ? 6 : 3)); }
+    __device__ Ray ray(const Scene& S, const BakePoint& b, uint32_t stream) const { return bake_ray(S, mode, b, stream); }
+};
+template <class Src>
+__global__ __launch_bounds__(GI_BLOCK) void k_bake_gen(Scene S, Src src, BakeGen g, PathPool pool, unsigned long long* slot_sample, double* dirs, uint32_t* q_new, unsigned int* n_new)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_round = (g.n_chunk_points + 63u) & ~63u;
     for (uint32_t i0 = blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n_round; i0 += gridDim.x * blockDim.x) {
         const uint32_t i = i0 + lane;
         const bool start = i < g.n_chunk_points;
-        BakePoint b;
-        b.o = v3(0, 0, 0); b.n = v3(0, 0, 1);
-        if (start) b = bake_point(g.mode, g.points + (size_t)i * (g.mode == GI_BAKE_MODE_TEXEL ? 6 : 3));
+        typename Src::At b{};
+        if (start) b = src.at(i);
         for (uint32_t k = 0; k < g.k_count; k++) {          // wave-uniform trip count: the appends below are collective
             const uint32_t slot = k * g.n_chunk_points + i;
             if (start) {
                 const uint32_t stream = g.stream0 + i * (uint32_t)g.n_samples + (g.k_begin + k);
-                const Ray ray = bake_ray(S, g.mode, b, stream);
+                const Ray ray = src.ray(S, b, stream);
                 pool_begin(pool, slot, ray, stream);
                 slot_sample[slot] = slot;
                 if (dirs) { double* d = dirs + (size_t)slot * 3; d[0] = ray.d.x; d[1] = ray.d.y; d[2] = ray.d.z; }   // what the path record holds: the fold reads it here
@@ -86,14 +95,14 @@ __global__ __launch_bounds__(GI_BLOCK) void k_bake_gen(Scene S, BakeGen g, PathP
     }
 }
 
-// the rays k_bake_gen makes, sample by sample (gi_bake_rays): ray j = sample j % n_samples of point j / n_samples
-__global__ __launch_bounds__(GI_BLOCK) void k_bake_rays(Scene S, int mode, const double* points, uint32_t n_rays, uint32_t n_samples, uint32_t stream_base, double* rays, uint32_t* streams)
+// the rays k_bake_gen makes, sample by sample (gi_bake_rays, gi_cubemap_rays): ray j = sample j % n_samples of point j / n_samples
+template <class Src>
+__global__ __launch_bounds__(GI_BLOCK) void k_bake_rays(Scene S, Src src, uint32_t n_rays, uint32_t n_samples, uint32_t stream_base, double* rays, uint32_t* streams)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_rays) return;
-    const uint32_t i = j / n_samples;
     const uint32_t stream = stream_base + j;
-    const Ray r = bake_ray(S, mode, bake_point(mode, points + (size_t)i * (mode == GI_BAKE_MODE_TEXEL ? 6 : 3)), stream);
+    const Ray r = src.ray(S, src.at(j / n_samples), stream);
     double* o = rays + (size_t)j * 6;
     o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
     streams[j] = stream;
@@ -202,11 +211,13 @@ struct BakeQuiet {
     ~BakeQuiet() { c->clock.stage_timing = timing; c->count_stream = counting; }
 };
 
-// the bake itself: d_points and d_out on the device, arguments checked.  timer: the events around it -- the bake's own, or those of a pass that
-// bakes as one of its stages (gi_lightmap.inc) and leaves gi_last_bake_ms alone
-int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake_params& bp, void* d_out, int out_is_f64, EventTimer* timer = nullptr)
+// What every pass that feeds the stream passes from a generator shares: n_points points of bp.n_samples samples cut into chunks and ranges, k_bake_gen
+// on the chunk's source, the stream passes with a RoundRefill, the fold of bp.mode into d_out (on the device).  source(i0): the Src of the chunk
+// whose first point is i0.  tm: the events around it.  Arguments checked.
+template <class Source>
+int bake_passes(gi_ctx* c, uint32_t n_points, const gi_bake_params& bp, Source source, void* d_out, int out_is_f64, EventTimer& tm)
 {
-    EventTimer& tm = timer ? *timer : c->bake.timer;
+    using Src = decltype(source(0u));
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t n_samples = (uint32_t)bp.n_samples;
     const int n_shadow = defers_shadows(c) ? c->S.n_light : 0;
@@ -246,12 +257,11 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
             const uint32_t nk = std::min(pl.range_k, n_samples - k0);
             F.min_samples = F.max_samples = (int32_t)nk;
             BakeGen g;
-            g.points = d_points + (size_t)i0 * bake_row(bp.mode);
-            g.mode = bp.mode; g.n_samples = bp.n_samples;
+            g.n_samples = bp.n_samples;
             g.n_chunk_points = np; g.k_begin = k0; g.k_count = nk;
             g.stream0 = bp.stream_base + i0 * n_samples;
             HIP_TRY(c, hipMemsetAsync(c->st.d_wfcnt.p, 0, 2 * sizeof(unsigned int), st));
-            hipLaunchKernelGGL(k_bake_gen, dim3(std::min<uint32_t>((np + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)(4 * c->n_cu))), dim3(GI_BLOCK), 0, st, c->S, g,
+            hipLaunchKernelGGL(k_bake_gen<Src>, dim3(std::min<uint32_t>((np + GI_BLOCK - 1) / GI_BLOCK, (uint32_t)(4 * c->n_cu))), dim3(GI_BLOCK), 0, st, c->S, source(i0), g,
                                make_path_pool(c->st.d_spool.p, c->st.spool_slots), c->st.d_slot_sample.p, dirs, c->st.work.q_new.p, c->st.d_wfcnt.p);
             HIP_TRY(c, hipGetLastError());
             RoundRefill refill(F, np * nk);      // every sample of the range starts: the count needs no read-back
@@ -264,6 +274,14 @@ int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake
     }
     HIP_TRY(c, tm.end(st));
     return GI_OK;
+}
+
+// the bake itself: d_points and d_out on the device, arguments checked.  timer: the events around it -- the bake's own, or those of a pass that
+// bakes as one of its stages (gi_lightmap.inc) and leaves gi_last_bake_ms alone
+int bake_run(gi_ctx* c, const double* d_points, uint32_t n_points, const gi_bake_params& bp, void* d_out, int out_is_f64, EventTimer* timer = nullptr)
+{
+    const auto rows = [&](uint32_t i0) { BakePoints s; s.points = d_points + (size_t)i0 * bake_row(bp.mode); s.mode = bp.mode; return s; };
+    return bake_passes(c, n_points, bp, rows, d_out, out_is_f64, timer ? *timer : c->bake.timer);
 }
 
 }  // namespace
@@ -326,7 +344,9 @@ int gi_bake_rays(gi_ctx* c, const double* points, int32_t n_points, const gi_bak
     const double* d_p = e.in(points, (size_t)n_points * bake_row(bp->mode));
     double* d_r = e.out(rays6_out, n_rays * 6);
     uint32_t* d_s = e.out(stream_out, n_rays);
-    return e.run([&] { hipLaunchKernelGGL(k_bake_rays, GI_GRID(n_rays), 0, c->stream, c->S, bp->mode, d_p, (uint32_t)n_rays, (uint32_t)bp->n_samples, bp->stream_base, d_r, d_s); });
+    BakePoints src;
+    src.points = d_p; src.mode = bp->mode;
+    return e.run([&] { hipLaunchKernelGGL(k_bake_rays<BakePoints>, GI_GRID(n_rays), 0, c->stream, c->S, src, (uint32_t)n_rays, (uint32_t)bp->n_samples, bp->stream_base, d_r, d_s); });
 }
 
 int gi_bake_fold(gi_ctx* c, int32_t mode, int32_t n_points, int32_t n_samples, const double* dirs3, const double* L3, double* out)

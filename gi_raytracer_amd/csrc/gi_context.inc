@@ -6,7 +6,7 @@
 //   Tuning        every value taken from the environment when the context is made (from_env), and the two limits the setters change
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
-//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake, lightmap
+//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake, lightmap, reflection probe
 // Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
@@ -366,6 +366,12 @@ struct LightmapPass : AuxPass {
     DevBuf<double> d_work, d_points, d_rows;   // d_points [n_cov][6], d_rows [n_cov][3]: the bake's input and output
     DevBuf<unsigned char> d_fill;     // [2][T] filled flags of the two dilation buffers
 };
+// a reflection probe (gi_cubemap.inc): the stage timers beside the pass's own, and its scratch, sized on first use and kept: the capture B_0
+// [6 N^2][3], the box levels 1 .. levels - 2 behind one another, and the prefilter's partial sums [6][6 (N / 2)^2][4], all f64
+struct CubemapPass : AuxPass {
+    EventTimer t_stage[2];            // capture, prefilter
+    DevBuf<double> d_b0, d_box, d_part;
+};
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
 struct gi_ctx {
@@ -407,6 +413,7 @@ struct gi_ctx {
     DenoisePass dn;                   // gi_denoise_*
     BakePass bake;                    // gi_bake_*
     LightmapPass lm;                  // gi_lightmap_*
+    CubemapPass cm;                   // gi_cubemap_*
 };
 
 namespace {

@@ -47,4 +47,5 @@ using namespace gi;
 #include "gi_lens.inc"           // the thin lens: gi_set_lens, its vertex table, gi_debug_primary_rays, gi_focus_distance
 #include "gi_bake.inc"           // light baking: k_bake_gen, k_bake_fold and gi_bake_*
 #include "gi_lightmap.inc"       // lightmap atlases: k_lm_raster, k_lm_point, the rank, k_lm_scatter, k_lm_dilate and gi_lightmap_*
+#include "gi_cubemap.inc"        // reflection probes: the capture's source for k_bake_gen, k_cm_box, k_cm_filter, k_cm_resolve and gi_cubemap_*
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

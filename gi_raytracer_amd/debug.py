@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import BAKE_MODES, BAKE_SH9, BAKE_TEXEL, _f64, _ip, _p, _up, _fp
+from ._abi import BAKE_MODES, BAKE_SH9, BAKE_TEXEL, _dp, _f64, _ip, _p, _up, _fp
 
 
 class DebugEntries:
@@ -153,6 +153,28 @@ class DebugEntries:
             raise ValueError("bake_fold: radiance and directions [n][samples][3] expected")
         out = np.zeros((n, 3) if mode == BAKE_TEXEL else (n, 9, 3))
         self._check(self.L.gi_bake_fold(self.h, mode, n, ns, _p(d3), _p(L3), _p(out)), "bake_fold")
+        return out
+
+    def cubemap_rays(self, pos, face, samples, stream_base=0, seed=None):
+        """gi_cubemap_rays: the rays a reflection probe's capture makes -- (rays [6 face^2 samples][6] = origin, unit direction, streams
+        [6 face^2 samples]), sample k of texel t in row t * samples + k."""
+        p = self.cubemap_params(face, samples, 1, None, stream_base, seed)
+        P = _f64(pos).reshape(3)
+        n = max(self.L.gi_cubemap_chain_texels(p.face, 1), 0) * max(p.n_samples, 0)
+        n = n if n < 2 ** 31 else 0                        # (the library refuses such a call: nothing is written)
+        rays = np.zeros((n, 6)); streams = np.zeros(n, np.uint32)
+        self._check(self.L.gi_cubemap_rays(self.h, _p(P), C.byref(p), _p(rays), _p(streams, _up)), "cubemap_rays")
+        return rays, streams
+
+    def cubemap_prefilter(self, cube, levels, exponents=None):
+        """gi_cubemap_prefilter: the box levels and the lobe filter of a reflection probe on the caller's cube [6][face][face][3].  Returns the list
+        of levels bake_reflection_probe returns; level 0 is the input."""
+        cube = _f64(cube)
+        if cube.ndim != 4 or cube.shape[0] != 6 or cube.shape[1] != cube.shape[2] or cube.shape[3] != 3 or cube.shape[1] < 1:
+            raise ValueError(f"cubemap_prefilter: a cube [6][face][face][3] expected, got {cube.shape}")
+        p = self.cubemap_params(cube.shape[1], 1, levels, exponents)
+        _, o, out = self._cube_levels(p, True)
+        self._check(self.L.gi_cubemap_prefilter(self.h, C.byref(p), _p(cube), C.cast(o[0], _dp)), "cubemap_prefilter")
         return out
 
     def lightmap_texels(self, ent, uv, width, height, flip=False):

@@ -167,6 +167,39 @@ def probe_grid(box6, nx, ny, nz):
     return np.ascontiguousarray(np.stack([x, y, z], -1))
 
 
+def cube_directions(face, ju=0.5, jv=0.5):
+    """Unit directions [6][face][face][3] through the texels of a reflection probe's cube (RayTracer.bake_reflection_probe; include/gi_hip.h:
+    gi_cubemap_*) at the place (ju, jv) inside each texel, the centres by default: faces +X, -X, +Y, -Y, +Z, -Z, rows growing downward.  The
+    arithmetic is the header's, so the centres are the directions the prefilter uses, bit for bit."""
+    n = int(face)
+    if n < 1:
+        raise ValueError(f"cube_directions: face must be at least 1, got {face}")
+    a = (2.0 * (np.arange(n, dtype=np.float64) + float(ju))) / float(n) - 1.0
+    b = (2.0 * (np.arange(n, dtype=np.float64) + float(jv))) / float(n) - 1.0
+    b, a = np.meshgrid(b, a, indexing="ij")
+    one = np.ones_like(a)
+    u = np.stack([np.stack(v, -1) for v in ((one, -b, -a), (-one, -b, a), (a, one, b), (a, -one, -b), (a, -b, one), (-a, -b, -one))])
+    return np.ascontiguousarray(u * (1.0 / np.sqrt((u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2]))[..., None])
+
+
+def cube_texel_of(directions, face):
+    """The texel index t = (f * face + y) * face + x of the cube texel each direction [...][3] (any length but 0) falls into: how a consumer of a
+    reflection probe finds its texel.  The face is that of the largest component (the first of equals); (a, b) are the other two over its size."""
+    d = np.asarray(directions, np.float64)
+    n = int(face)
+    m = np.abs(d)
+    axis = np.argmax(m, -1)
+    size = np.take_along_axis(m, axis[..., None], -1)[..., 0]
+    x, y, z = (d[..., k] / size for k in range(3))
+    neg = np.take_along_axis(d, axis[..., None], -1)[..., 0] < 0
+    f = 2 * axis + neg
+    a = np.choose(f, [-z, z, x, x, x, -x])
+    b = np.choose(f, [-y, -y, z, -z, -y, -y])
+    col = np.clip(np.floor((a + 1.0) * 0.5 * n), 0, n - 1).astype(np.int64)
+    row = np.clip(np.floor((b + 1.0) * 0.5 * n), 0, n - 1).astype(np.int64)
+    return (f * n + row) * n + col
+
+
 def chart_of_material(scene, material=None):
     """(ent [n], uv [n][3][2]): the default chart of a lightmap (RayTracer.bake_lightmap) for a scene whose texture coordinates are already an
     unwrapped atlas -- the scene's own texture coordinates of all triangle entities of that material index, in entity order; None: of all

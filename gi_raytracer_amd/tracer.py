@@ -3,8 +3,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, DEFAULT_SEED, GI_OK, BakeParams, DenoiseParams, GiError, Lens, LightmapParams, RenderParams,
-                   UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
+from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
+                   LightmapParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
 from .params import _bake_points, _chart, _fill_params, _filter_array, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
@@ -331,6 +331,57 @@ class RayTracer(DebugEntries):
         ms, st = C.c_float(0), (C.c_float * 3)()
         self._check(self.L.gi_last_lightmap_ms(self.h, C.byref(ms), st), "last_lightmap_ms")
         return ms.value, dict(zip(("raster", "bake", "dilate"), (float(x) for x in st)))
+
+    def cubemap_params(self, face, samples, levels=1, exponents=None, stream_base=0, seed=None):
+        """gi_cubemap_params: texels per face edge, rays per texel, levels of the chain (1: the capture alone), log2 of the lobe exponent per level
+        (a sequence indexed by level, entry 0 ignored; default: the library's 16 - 3 l), the stream index of sample 0 of texel 0, the seed
+        (default: the tracer's)."""
+        p = CubemapParams()
+        self.L.gi_cubemap_default_params(C.byref(p))
+        p.face, p.n_samples, p.levels, p.stream_base = int(face), int(samples), int(levels), int(stream_base)
+        p.seed = self._seed(seed)
+        for l, e in enumerate(exponents if exponents is not None else ()):
+            if l >= CUBEMAP_MAX_LEVELS:
+                raise ValueError(f"cubemap: at most {CUBEMAP_MAX_LEVELS} exponents, got {len(exponents)}")
+            p.log2_exponent[l] = int(e)
+        return p
+
+    def _cube_levels(self, p, f64):
+        """A zeroed chain for p, its (void*, is_f64) pair, and the views [6][n_l][n_l][3] of its levels."""
+        n = self.L.gi_cubemap_chain_texels(p.face, p.levels)
+        flat, o = _out((max(n, 0), 3), f64)
+        levels, at = [], 0
+        for l in range(p.levels if n >= 0 else 0):
+            m = p.face >> l
+            levels.append(flat[at:at + 6 * m * m].reshape(6, m, m, 3))
+            at += 6 * m * m
+        return flat, o, levels
+
+    def bake_reflection_probe(self, pos, face, samples, levels=1, exponents=None, stream_base=0, seed=None, f64=True):
+        """A reflection probe (gi_cubemap_host; an addition beside the bakes): the cube map of the radiance seen from `pos`, `face` texels per face
+        edge and `samples` jittered rays per texel, and the roughness chain filtered from it -- level l is the cube seen through the Phong lobe of
+        exponent 2 ** exponents[l].  Returns a list of arrays [6][face >> l][face >> l][3], one per level; level 0 is the capture.  Faces +X, -X,
+        +Y, -Y, +Z, -Z, rows growing downward: cube_directions gives the texels' directions, cube_texel_of the texel of a direction.  The lights
+        themselves are not in it (no ray hits an analytic light).  Sample k of texel t runs on stream stream_base + t * samples + k; the
+        definition is stated in include/gi_hip.h."""
+        p = self.cubemap_params(face, samples, levels, exponents, stream_base, seed)
+        P = _f64(pos).reshape(3)
+        _, o, out = self._cube_levels(p, f64)
+        self._check(self.L.gi_cubemap_host(self.h, _p(P), C.byref(p), *o), "cubemap_host")
+        return out
+
+    def cubemap_device(self, p, pos, out_ptr, f64=False):
+        """A reflection probe into device memory (out_ptr: a raw device pointer to the whole chain, gi_cubemap_chain_texels texels of 3); p from
+        cubemap_params, pos a host position, taken as it is."""
+        P = _f64(pos).reshape(3)
+        self._check(self.L.gi_cubemap_device(self.h, _p(P), C.byref(p), *_dev(out_ptr, f64)), "cubemap_device")
+
+    def last_cubemap_ms(self):
+        """gi_last_cubemap_ms: (device time of the last reflection probe, {"capture": .., "prefilter": ..}); gi_last_bake_ms, the frame's and the
+        other passes' times keep theirs."""
+        ms, st = C.c_float(0), (C.c_float * 2)()
+        self._check(self.L.gi_last_cubemap_ms(self.h, C.byref(ms), st), "last_cubemap_ms")
+        return ms.value, dict(zip(("capture", "prefilter"), (float(x) for x in st)))
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
         """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,

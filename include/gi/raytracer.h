@@ -265,6 +265,31 @@ class RayTracer {
     {
         return bake(GI_BAKE_TEXEL, pointsAndNormals, 6, 3, samples, streamBase, out);
     }
+    // bakeReflectionProbe (gi_cubemap_host): the cube map of the radiance seen from pos, `face` texels per face edge and `samples` jittered rays per
+    // texel, and `levels` levels of the roughness chain filtered from it (1: the capture alone; face must be divisible by 2^(levels - 1)).  out gets
+    // one vector per level, [6][face >> l][face >> l][3]: faces +X, -X, +Y, -Y, +Z, -Z, rows growing downward.  log2Exponents (optional, indexed by
+    // level, entry 0 ignored) replaces the default lobe exponents 2^(16 - 3 l).  The lights themselves are not in it: no ray hits an analytic light.
+    bool bakeReflectionProbe(const gi::dvec3& pos, int face, int samples, std::vector<std::vector<double>>& out, int levels = 1,
+                             const std::vector<int>* log2Exponents = nullptr, uint32_t streamBase = 0)
+    {
+        if (!ready()) return false;
+        gi_cubemap_params p;
+        gi_cubemap_default_params(&p);
+        p.face = face; p.n_samples = samples; p.levels = levels; p.stream_base = streamBase; p.seed = seed;
+        for (size_t l = 0; log2Exponents && l < log2Exponents->size() && l < (size_t)GI_CUBEMAP_MAX_LEVELS; l++) p.log2_exponent[l] = (*log2Exponents)[l];
+        const int64_t texels = gi_cubemap_chain_texels(face, levels);
+        const double P[3] = {pos.x, pos.y, pos.z};
+        std::vector<double> buf((size_t)(texels > 0 ? texels : 0) * 3 + 1);
+        if (check(gi_cubemap_host(_st->ctx, P, &p, buf.data(), 1)) != 0) return false;
+        out.clear();
+        size_t at = 0;
+        for (int l = 0; l < levels; l++) {
+            const size_t n = (size_t)(face >> l), count = 6 * n * n * 3;
+            out.emplace_back(buf.begin() + at, buf.begin() + at + count);
+            at += count;
+        }
+        return true;
+    }
     // bakeLightmap (gi_lightmap_host): the chart -- ent [n] triangle entities of the uploaded scene, uv [n][3][2] their chart coordinates, v growing
     // with the row -- rasterised into width x height texels, the covered ones baked as bakeTexels does, put back into the image and dilated `dilate`
     // times.  atlas gets [height][width][3]; owner (optional) [height][width], the chart row of a covered texel or -1; nCovered (optional) their number.

@@ -601,6 +601,67 @@ int gi_last_lightmap_ms(gi_ctx*, float* ms, float* stages3);
 int gi_lightmap_texels(gi_ctx*, const gi_lightmap_params*, int32_t n_chart, const int32_t* ent, const double* uv, int32_t* owner, int32_t* n_covered, double* points6, int32_t* texel, int32_t cap);
 int gi_lightmap_dilate(gi_ctx*, int32_t width, int32_t height, int32_t passes, const double* values3, const int32_t* filled, double* out3);
 
+/* Reflection probes -- an ADDITION beside the bakes: the specular product.  A probe is a cube map of the radiance seen from a point, captured with
+ * the path tracer behind every ray as a bake's rays are, and the roughness mip chain filtered from it, in one device-side pass.
+ * Texels and faces.  A cube of face N has 6 N^2 texels.  Faces run in the order +X, -X, +Y, -Y, +Z, -Z; texel (x, y) of face f has index
+ *     t = (f * N + y) * N + x
+ * and row y grows downward.  With a = (2.0 * ((double) x + ju)) / (double) N - 1.0 and b the same from y and jv, the unnormalised direction is
+ *     f0 ( 1, -b, -a)   f1 (-1, -b,  a)   f2 ( a,  1,  b)   f3 ( a, -1, -b)   f4 ( a, -b,  1)   f5 (-a, -b, -1)
+ * the layout of the usual cube-map texture.  The texel centre is ju = jv = 0.5.  All arithmetic below is f64, IEEE + - * / and sqrt only, in the
+ * order written, compiled without contraction, so that it can be restated bit for bit (tests/cubemap_expect.py).
+ * Capture.  Sample k of texel t runs on stream = stream_base + t * n_samples + k: ju = (double) halton(0, stream), jv = (double) halton(1, stream),
+ *   the two dimensions a bake's ray takes for its direction; the ray is Ray(P, d) from the probe position P itself, with no bias (include/ray.h:7-17:
+ *   d is normalised there); the rest of the index drives the path as it does for a bake.  No device trigonometry is involved: the rays are the
+ *   statement's bit for bit, not within 4 ulp as a bake's are.  The texel's value is the texel fold of the bake: the sum over k of L_k in ascending k
+ *   from +0.0, divided by (double) n_samples, L_k as gi_bake_* defines it.  Chunks of texels and ranges of samples (gi_set_pool_slots, free memory)
+ *   do not show in the result.  As in a bake and in a frame, the analytic lights are not geometry: no ray hits one, so a probe holds no image of the
+ *   lights themselves -- what they light, it holds.  The lens and the render mode play no part.
+ * Box levels.  B_0 is the capture.  B_l has face N >> l, and each of its texels is ((p00 + p01) + (p10 + p11)) * 0.25 of B_(l-1), row-major in
+ *   the 2 x 2 block, per channel.  levels > 1 requires N to be divisible by 2^(levels - 1).
+ * Filtered levels.  F_0 = B_0, bit for bit.  For l >= 1, F_l has face n = N >> l and is filtered from B_(l-1), whose face is 2 n.  Per source
+ *   texel s with centre (a, b) and unnormalised centre direction u:  d_s = u * (1.0 / sqrt((ux ux + uy uy) + uz uz));  m_s = 1.0 / (r * sqrt(r))
+ *   with r = (1.0 + a a) + b b, the texel's solid angle up to a factor common to the level.  Per output texel with normalised centre direction R:
+ *   c = (Rx dx + Ry dy) + Rz dz;  w = c > 0 ? c : 0, squared log2_exponent[l] times (the Phong lobe of exponent 2^log2_exponent[l]), then multiplied
+ *   by m_s.  For each source face g, W_g += w and A_g[ch] += w * L_s[ch] over the face's texels in ascending s from +0.0.  Then
+ *   W = ((((W_0 + W_1) + W_2) + W_3) + W_4) + W_5, A likewise, and F_l = A / W per channel.  Every sum is per face first, then the faces in order,
+ *   whatever the launch.  A lobe so narrow that every weight underflows leaves W = 0 and the texel NaN (0 / 0): exponents are the caller's to suit to
+ *   the face of the source level; the defaults are safe for every cube of face 4 or more.
+ * Output.  The levels lie one after another, level l as [6][N >> l][N >> l][3], float (out_is_f64 = 0) or double (1); a float is the double rounded
+ * once.  gi_cubemap_chain_texels(face, levels) is the number of texels of the chain, or -1 for a pair a call would refuse.
+ * A consumer looks up level l at the direction d by the face of d's largest component and (a, b) of the table above divided by that component's size.
+ * GI_E_INVALID, before any pointer is used: a null pointer, face < 1, n_samples < 1, levels outside 1 .. GI_CUBEMAP_MAX_LEVELS, a face not
+ * divisible by 2^(levels - 1), log2_exponent[l] outside 0 .. 16 for a level 1 <= l < levels (entry 0 and the entries from `levels` on are ignored),
+ * stream_base + 6 N^2 n_samples beyond 2^32, and -- gi_cubemap_host and gi_cubemap_rays -- a position that is not finite.  GI_E_STATE: no scene.
+ * A refused call touches no output and no timer.
+ * gi_cubemap_default_params: face 32, 64 samples, 1 level (the capture alone), stream_base 0, seed 0x9E3779B97F4A7C15,
+ *   log2_exponent[l] = max(0, 16 - 3 l).
+ * gi_cubemap_host: pos3 and h_out are HOST pointers.  gi_cubemap_device: d_out is a DEVICE pointer, pos3 a HOST pointer read before the call returns
+ *   and taken as it is; asynchronous on the context's stream.  Scratch: 24 bytes per texel of the chain and 32 bytes per texel of level 1 and source
+ *   face (192 per texel of level 1) of device memory, kept by the context for the next call, beside the shared scratch of the stream passes.
+ * gi_last_cubemap_ms: device time of the last probe, and per stage in stages2 (may be null): capture, prefilter.  gi_last_bake_ms, the frame's and
+ *   the other passes' times keep their values across a probe; an open progressive session is left as it is.
+ * Check entries (host pointers): gi_cubemap_rays gives the capture's rays as gi_bake_rays does, rays6_out [6 N^2 n_samples][6] and stream_out
+ *   [6 N^2 n_samples], sample k of texel t in row t * n_samples + k; no scene is needed.  gi_cubemap_prefilter runs the box levels and the filter on
+ *   the caller's cube: cube_in [6][N][N][3] double, chain_out the whole chain, double, level 0 the input's bits; params as for a capture; no scene
+ *   is needed and no timer is touched.
+ * There is no gi_group_* form and one probe per call: a caller with many probes loops. */
+#define GI_CUBEMAP_MAX_LEVELS 12
+typedef struct gi_cubemap_params {
+    int32_t face;            /* N >= 1: texels per face edge */
+    int32_t n_samples;       /* >= 1 rays per texel */
+    int32_t levels;          /* 1 .. GI_CUBEMAP_MAX_LEVELS; 1: the capture alone */
+    uint32_t stream_base;    /* stream index of sample 0 of texel 0 */
+    uint64_t seed;           /* counter-RNG seed, as gi_bake_params::seed */
+    int32_t log2_exponent[GI_CUBEMAP_MAX_LEVELS];   /* 0 .. 16 each: level l is filtered with the lobe cos^(2^log2_exponent[l]); entry 0 is ignored */
+} gi_cubemap_params;
+void gi_cubemap_default_params(gi_cubemap_params*);
+int64_t gi_cubemap_chain_texels(int32_t face, int32_t levels);
+int gi_cubemap_host(gi_ctx*, const double* pos3, const gi_cubemap_params*, void* h_out, int out_is_f64);
+int gi_cubemap_device(gi_ctx*, const double* pos3, const gi_cubemap_params*, void* d_out, int out_is_f64);
+int gi_last_cubemap_ms(gi_ctx*, float* ms, float* stages2);
+int gi_cubemap_rays(gi_ctx*, const double* pos3, const gi_cubemap_params*, double* rays6_out, uint32_t* stream_out);
+int gi_cubemap_prefilter(gi_ctx*, const gi_cubemap_params*, const double* cube_in, double* chain_out);
+
 #ifdef __cplusplus
 }
 #endif
