@@ -7,6 +7,7 @@
                                [--upsample S [--upsample-pfm LOW.pfm]]
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
+                               [--baked PREFIX [--baked-samples N] [--baked-probes NX NY NZ] [--baked-reflection X Y Z]]
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
     python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
                                -o OUT.ppm [--pfm OUT.pfm]
@@ -46,6 +47,13 @@ the 8-bit PPM of the display transform, --pfm the linear atlas; one line gives t
 gi_cubemap_*) -- a cube map of --probe-face N texels per face edge (default 32) with --probe-samples N rays per texel (default 64) -- and filters
 --probe-levels L levels of its roughness chain (default 1: the capture alone; N must be divisible by 2^(L-1)), after the photon pass.  -o gets a
 numpy .npz with the keys level0, level1 ... as float32 [6][N >> l][N >> l][3].  Not together with --probes or --lightmap.
+--baked PREFIX (the consumer of those bakes; include/gi_hip.h: gi_render_baked_*) also writes a preview of the frame shaded from baked light, at
+--width x --height: after the photon pass it bakes a grid of --baked-probes NX NY NZ light probes (default 4 4 4, 256 rays each) in the octree's
+root box and a reflection probe at --baked-reflection X Y Z (default: the middle of that box; face 32, 64 rays per texel, 6 levels), then shades
+every pixel's first hit with --baked-samples N samples (default 4) from the lights, the probes and the cube.  PREFIX.ppm gets the display
+transform of the preview, PREFIX_direct.pfm, PREFIX_diffuse.pfm and PREFIX_specular.pfm its three terms.  It goes with the frame's flags as
+--occlusion does, not with --probes, --lightmap or --reflection-probe.  If -o is not given and PREFIX.ppm is the frame's default name, the frame
+goes to PREFIX_frame.ppm.
 """
 import argparse
 import os
@@ -59,12 +67,14 @@ FEATURE_FILES = ("albedo", "normal", "depth", "coverage")
 PROBE_SAMPLES = 256
 LIGHTMAP_SAMPLES = 256
 REFLECTION_FACE, REFLECTION_SAMPLES = 32, 64
+BAKED_SAMPLES, BAKED_PROBES, BAKED_LEVELS = 4, (4, 4, 4), 6
+BAKED_FILES = ("direct", "diffuse", "specular")
 
 
 def parser():
     ap = argparse.ArgumentParser(prog="python -m gi_raytracer_amd", description=__doc__.split("\n")[0])
     ap.add_argument("scene")
-    ap.add_argument("-o", "--output", default="out.ppm", help="8-bit PPM of the display transform (gamma 2.2, clamp)")
+    ap.add_argument("-o", "--output", default=None, help="(default out.ppm) " + "8-bit PPM of the display transform (gamma 2.2, clamp)")
     ap.add_argument("--pfm", default=None, help="also write the linear radiance as PFM")
     ap.add_argument("--width", type=int, default=1000)
     ap.add_argument("--height", type=int, default=1000)
@@ -102,6 +112,10 @@ def parser():
     ap.add_argument("--lightmap-material", type=int, default=None, metavar="M", help="with --lightmap: only the triangles of this material index (default: all triangles)")
     ap.add_argument("--lightmap-samples", type=int, default=None, metavar="N", help="with --lightmap: rays per covered texel (default 256)")
     ap.add_argument("--lightmap-dilate", type=int, default=None, metavar="D", help="with --lightmap: gutter dilation passes, 0 .. 64 (default 2)")
+    ap.add_argument("--baked", default=None, metavar="PREFIX", help="also write a preview shaded from baked light as PREFIX.ppm and its terms as PREFIX_{direct,diffuse,specular}.pfm")
+    ap.add_argument("--baked-samples", type=int, default=None, metavar="N", help="with --baked: samples per pixel (default 4)")
+    ap.add_argument("--baked-probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="with --baked: the light-probe grid in the scene's box (default 4 4 4)")
+    ap.add_argument("--baked-reflection", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --baked: position of the reflection probe (default: the middle of the scene's box)")
     return ap
 
 
@@ -115,6 +129,26 @@ def lens_of(a):
 
 def check_args(ap, a):
     """The rules between the flags; ap.error (exit status 2) on a breach.  Runs before anything touches the device."""
+    explicit_output = a.output is not None
+    if not explicit_output:
+        a.output = "out.ppm"
+    if a.baked is None and (a.baked_samples is not None or a.baked_probes is not None or a.baked_reflection is not None):
+        ap.error("--baked-samples, --baked-probes and --baked-reflection need --baked PREFIX")
+    if a.baked is not None:
+        if a.probes is not None or a.lightmap is not None or a.reflection_probe is not None:
+            ap.error("--baked does not go together with --probes, --lightmap or --reflection-probe")
+        ns = BAKED_SAMPLES if a.baked_samples is None else a.baked_samples
+        if ns < 1 or ns > gi.halton_sample_cap(a.width, a.height):
+            ap.error(f"--baked-samples N: from 1 to {gi.halton_sample_cap(a.width, a.height)} for a {a.width} x {a.height} frame")
+        grid = a.baked_probes or BAKED_PROBES
+        if min(grid) < 1 or grid[0] * grid[1] * grid[2] * PROBE_SAMPLES > 2 ** 32:
+            ap.error("--baked-probes NX NY NZ: three numbers >= 1; probes x 256 samples must keep the stream index within 32 bits")
+        if a.baked_reflection is not None and not all(-float("inf") < v < float("inf") for v in a.baked_reflection):
+            ap.error("--baked-reflection X Y Z: three finite numbers")
+        if os.path.abspath(a.baked + ".ppm") == os.path.abspath(a.output):
+            if explicit_output:
+                ap.error(f"--baked {a.baked} writes {a.baked}.ppm, which is -o: name one of them differently")
+            a.output = a.baked + "_frame.ppm"
     if a.denoise is None and (a.denoise_pfm or a.denoise_iterations is not None or a.denoise_sigmas is not None):
         ap.error("--denoise-pfm, --denoise-iterations and --denoise-sigmas need --denoise OUT.ppm")
     if a.progressive is None and (a.time_limit is not None or a.checkpoint is not None):
@@ -285,6 +319,23 @@ def occlusion_kwargs(a):
     return {k: v for k, v in kw.items() if v is not None}
 
 
+def render_baked(a, rt, scene):
+    """--baked: the probe grid and the reflection probe baked with the defaults of --probes and --reflection-probe, then the baked-light pass;
+    writes the four files and returns a note for the summary line."""
+    box = scene.tables()["node_bbox"][0]
+    nx, ny, nz = a.baked_probes or BAKED_PROBES
+    sh = rt.bake_probes(gi.probe_grid(box, nx, ny, nz).reshape(-1, 3), PROBE_SAMPLES).reshape(nz, ny, nx, 9, 3)
+    pos = a.baked_reflection if a.baked_reflection is not None else [0.5 * (box[k] + box[3 + k]) for k in range(3)]
+    chain = rt.bake_reflection_probe(pos, REFLECTION_FACE, REFLECTION_SAMPLES, BAKED_LEVELS)
+    ns = BAKED_SAMPLES if a.baked_samples is None else a.baked_samples
+    lit = rt.run_baked(a.width, a.height, ns, sh=sh, grid_box=box, chain=chain, f64=False)      # (the chain's exponents are the library's defaults, in both calls)
+    gi.save_ppm(f"{a.baked}.ppm", lit["beauty"])
+    for name in BAKED_FILES:
+        gi.save_pfm(f"{a.baked}_{name}.pfm", lit[name])
+    return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, cube {rt.last_cubemap_ms()[0]:.2f} ms, {ns} spp preview {rt.last_baked_ms():.2f} ms "
+            f"-> {a.baked}.ppm, {a.baked}_*.pfm")
+
+
 def feature_samples(a, max_samples):
     """n of the feature pass: --feature-samples, else the frame's max_samples cut to the Halton cap of the frame size."""
     if a.feature_samples is not None:
@@ -394,6 +445,8 @@ def main(argv=None):
         gi.save_pfm(f"{a.occlusion}.open.pfm", ao["open"])
         gi.save_pfm(f"{a.occlusion}.bent.pfm", ao["bent"])
         feat += f"; occlusion {rt.last_occlusion_ms():.2f} ms -> {a.occlusion}.open.pfm, {a.occlusion}.bent.pfm"
+    if a.baked:
+        feat += render_baked(a, rt, scene)
     n = int(spp.sum())
     print(f"{a.scene}: {a.width}x{a.height}, {n} samples (mean {n / spp.size:.1f} spp), {stored} photons stored; "
           f"photon pass {t1 - t0:.2f} s, frame {t2 - t1:.2f} s ({n / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s incl. host copies) -> {a.output}{lens_note}{feat}")

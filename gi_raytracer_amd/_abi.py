@@ -18,6 +18,7 @@ GI_OK, GI_E_NO_DEVICE, GI_E_INVALID, GI_E_HIP, GI_E_STATE, GI_E_CANCELLED = 0, -
 BAKE_TEXEL, BAKE_SH9 = 0, 1
 BAKE_MODES = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}
 CUBEMAP_MAX_LEVELS = 12
+BAKED_DIRECT, BAKED_DIFFUSE, BAKED_SPECULAR, BAKED_EMISSIVE = 1, 2, 4, 8
 
 _dp, _ip, _up, _fp, _lp, _bp = (C.POINTER(t) for t in (C.c_double, C.c_int32, C.c_uint32, C.c_float, C.c_int64, C.c_uint8))
 
@@ -85,6 +86,12 @@ class CubemapParams(C.Structure):
                 ("log2_exponent", C.c_int32 * CUBEMAP_MAX_LEVELS)]
 
 
+class BakedParams(C.Structure):
+    """gi_baked_params (include/gi_hip.h)."""
+    _fields_ = [("n_samples", C.c_int32), ("terms", C.c_int32), ("grid_min", C.c_double * 3), ("grid_max", C.c_double * 3), ("nx", C.c_int32),
+                ("ny", C.c_int32), ("nz", C.c_int32), ("face", C.c_int32), ("levels", C.c_int32), ("log2_exponent", C.c_int32 * CUBEMAP_MAX_LEVELS)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -94,7 +101,8 @@ class Settings(C.Structure):
 # header type -> its mirror (tests/test_abi_layout.py compiles sizeof / offsetof of every field against the headers)
 STRUCTS = {"gi_scene_desc": SceneDesc, "gi_photon_map_desc": PhotonMapDesc, "gi_render_params": RenderParams, "gi_denoise_params": DenoiseParams,
            "gi_upsample_params": UpsampleParams, "gi_occlusion_params": OcclusionParams, "gi_lens": Lens, "gi_bake_params": BakeParams,
-           "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gih_settings": Settings}
+           "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gi_baked_params": BakedParams,
+           "gih_settings": Settings}
 
 
 def _signatures():
@@ -103,7 +111,7 @@ def _signatures():
     P, ms, knob = C.POINTER, (i, [vp, _fp]), (i, [vp, i])
     scene, photons, rp = P(SceneDesc), P(PhotonMapDesc), P(RenderParams)
     dn, us, oc, lens, bake, lm = P(DenoiseParams), P(UpsampleParams), P(OcclusionParams), P(Lens), P(BakeParams), P(LightmapParams)
-    cm = P(CubemapParams)
+    cm, bk = P(CubemapParams), P(BakedParams)
     return {
         # include/gi_hip.h: context, uploads, frames
         "gi_create": (i, [P(vp), i]), "gi_destroy": (None, [vp]), "gi_last_error": (s, [vp]), "gi_set_stream": (i, [vp, vp]),
@@ -153,6 +161,9 @@ def _signatures():
         "gi_cubemap_default_params": (None, [cm]), "gi_cubemap_chain_texels": (i64, [i32, i32]), "gi_cubemap_host": (i, [vp, _dp, cm, vp, i]),
         "gi_cubemap_device": (i, [vp, _dp, cm, vp, i]), "gi_last_cubemap_ms": (i, [vp, _fp, _fp]), "gi_cubemap_rays": (i, [vp, _dp, cm, _dp, _up]),
         "gi_cubemap_prefilter": (i, [vp, cm, _dp, _dp]),
+        # the baked-light pass
+        "gi_baked_default_params": (None, [bk]), "gi_render_baked_device": (i, [vp, rp, bk, vp, vp, vp, i]),
+        "gi_render_baked_host": (i, [vp, rp, bk, _dp, _dp, vp, i]), "gi_last_baked_ms": ms,
         # csrc/gi_host.h: the host scene builder
         "gih_scene_create": (vp, []), "gih_scene_destroy": (None, [vp]), "gih_last_error": (s, [vp]), "gih_load_scn": (i, [vp, s]),
         "gih_load_obj": (i, [vp, s, _dp, _dp, i32]), "gih_add_material": (i, [vp, _dp]), "gih_add_texture": (i, [vp, i32, _dp, _bp, i64]),

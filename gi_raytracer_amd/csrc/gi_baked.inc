@@ -1,0 +1,196 @@
+// gi_baked.inc -- the baked-light pass (gi_render_baked_*; an addition: the consumer of the bakes).  Included by gi_kernels.hip behind gi_cubemap.inc,
+// whose gi_cubemap.h gives the cube's texel order; the host frame of a per-pixel pass is gi_features.inc's (pixel_pass_frame, pixel_pass,
+// pixel_pass_to_host).  The definition is stated in include/gi_hip.h; the per-lane functions are gi_baked.h, and lit_first_hit() stands here with
+// what a lane carries from it.
+
+namespace gi {
+#include "gi_baked.h"
+
+// ------------------------------------------------------------------------------------------------ baked light at the first hit (an addition: the reference has no such pass)
+// The first hit of the sample with Halton index idx: aov_sample's (same ray, same RNG keys, same recomputation of the hit from the entity's record on
+// the wide walk), and from it what the three later steps need.  norm is the shade stage's normal (secondary_ray turns it, nothing renormalises it),
+// nf ao_first_hit's.
+struct LitHit { V3 P, d, norm, nf, color, emissive; double roughness; int32_t mat; };
+template <int FEAT, class Nodes>
+GI_HD bool lit_first_hit(const Scene& S, const Nodes& N, const Frame& F, uint64_t seed, uint32_t idx, Rng& rng, LitHit& a)
+{
+    const Ray ray = primary_ray_at(S, F, idx);
+    rng = rng_make(seed, idx);   // depth 0
+    HitRec h;
+    h.tu = 0; h.tv = 0;
+    if (!trace_nodes<FEAT>(S, N, ray, rng, P_TRACE_ALPHA, h, nullptr)) return false;
+    if constexpr (Nodes::kWide) {   // as aov_sample
+        const TriGeom& tg = S.tris[h.tri];
+        h.mf = ((uint32_t)tg.mat << 3) | tg.flags;
+        ent_hit<FEAT>(tg, h.mf, ray, h.u, h.v, h.pos);
+    }
+    const Mat& m = S.mats[h.mf >> 3];
+    a.color = ld3(m.diffuse); a.emissive = ld3(m.emissive);
+    if (FEAT & GI_FEAT_TEX) {
+        a.color = tex_get(S, m.dtex, a.color, h.tu, h.tv);
+        a.emissive = tex_get(S, m.etex, a.emissive, h.tu, h.tv);
+    }
+    const V3 n = shading_normal(S, h);
+    a.norm = dot(n, ray.d) > 0 ? n * -1.0 : n;
+    const V3 nh = normalize(n);
+    a.nf = dot(nh, ray.d) > 0 ? v3(-nh.x, -nh.y, -nh.z) : nh;
+    a.P = h.pos; a.d = ray.d;
+    a.roughness = m.roughness; a.mat = (int32_t)(h.mf >> 3);
+    return true;
+}
+}  // namespace gi
+
+// What the kernel reads beside the scene: the probe grid, the chain and the level each material reads, through global memory (small, L2-resident).
+struct LitArgs {
+    int32_t terms;                                  // GI_BAKED_*
+    int32_t n3[3];                                  // nx, ny, nz
+    double gmin[3], gmax[3];
+    const double* sh;                               // [nz][ny][nx][9][3]
+    const double* chain;                            // the whole chain, [texels][3]
+    const int32_t* level_of_mat;                    // [n_mat]
+    uint32_t face;
+    uint32_t level_off[GI_CUBEMAP_MAX_LEVELS];      // texels before level l
+};
+
+// One kernel, k_lit<FEAT, WIDE>, of k_ao's shape: one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, a lane loops over its
+// samples; per sample the first hit, then one any-hit walk per light from the last light down until one is visible, then the look-ups.  It keeps its
+// twelve f64 sums in registers and stores once.  No queue, no sort, no atomics, nothing of the path pool, no reduction across lanes.
+// The three steps of a sample follow one another with little carried across: ray, hit record and entity record are dead when the light loop starts
+// (LitHit is what lives on), the walk's state is dead when the look-ups start, so the register need is that of the largest step, not the sum.
+// LDS as k_ao's: the records of the octree's top with the whole entities' content boxes, which the any-hit walks read; the closest-hit walk takes the
+// tables cut to the leaves through L2 where the two differ.  A light's segment ends at the light, but the boxes are the whole entities'
+// (Scene::leaf_boxes), valid for any segment: the answers are those of k_st_shadow's cut boxes.
+template <int FEAT, int WIDE>
+__global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64)
+{
+    const typename LdsSrc<WIDE>::type NV = LdsSrc<WIDE>::stage_with_boxes(S);   // ends with a barrier
+    typename LdsSrc<WIDE>::type NT = NV;                                        // the closest-hit walk's view of the same records
+    if constexpr (WIDE != 0) {
+        if (S.tcboxes != S.cboxes || S.tcuse != S.cuse) { NT.cboxes = S.tcboxes; NT.cuse = S.tcuse; NT.n_lc = 0; }
+    }
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pix) return;
+    int x, ly;
+    st_pixel_xy(F, p, x, ly);
+    uint32_t idx = halton_index(F.he, 0u, (uint32_t)x, (uint32_t)global_row(F, ly));
+    V3 sum[4] = {v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0), v3(0, 0, 0)};   // beauty, direct, diffuse, specular
+    for (int32_t s = 0; s < n; s++, idx += F.he.inc) {
+        LitHit a;
+        Rng rng;
+        if (!lit_first_hit<FEAT>(S, NT, F, F.seed, idx, rng, a)) { sum[0] = sum[0] + ld3(S.ambient); continue; }   // a miss: the ambient term, no share of the three
+        V3 direct = v3(0, 0, 0), diffuse = v3(0, 0, 0), specular = v3(0, 0, 0);
+        if (A.terms & GI_BAKED_DIRECT) direct = a.color * lit_direct<FEAT | GI_FEAT_FOG>(S, NV, a.P, a.norm, a.roughness, rng);
+        if (a.roughness < .9) {             // mirror (< .001: level 0) or glossy (the material's level): specular only
+            if (A.terms & GI_BAKED_SPECULAR) {
+                const uint32_t l = a.roughness < .001 ? 0u : (uint32_t)A.level_of_mat[a.mat];
+                const size_t t = (size_t)A.level_off[l] + cube_texel(reflect(a.d, a.nf), A.face >> l);
+                specular = a.color * ld3(A.chain + t * 3);
+            }
+        } else if (A.terms & GI_BAKED_DIFFUSE)
+            diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
+        const V3 beauty = ((direct + diffuse) + specular) + ((A.terms & GI_BAKED_EMISSIVE) ? a.emissive : v3(0, 0, 0));
+        sum[0] = sum[0] + beauty; sum[1] = sum[1] + direct; sum[2] = sum[2] + diffuse; sum[3] = sum[3] + specular;
+    }
+    const size_t o = ((size_t)ly * F.w + x) * 12;
+    const double dn = (double)n;
+    GI_UNROLL
+    for (int k = 0; k < 4; k++) {
+        const V3 v = sum[k] / dn;
+        if (out_f64) { double* q = (double*)out + o + k * 3; q[0] = v.x; q[1] = v.y; q[2] = v.z; }
+        else { float* q = (float*)out + o + k * 3; q[0] = (float)v.x; q[1] = (float)v.y; q[2] = (float)v.z; }
+    }
+}
+
+namespace {
+
+#define GI_BAKED_ALL_TERMS (GI_BAKED_DIRECT | GI_BAKED_DIFFUSE | GI_BAKED_SPECULAR | GI_BAKED_EMISSIVE)
+
+// false + message when the parameters and pointers are not the header's
+bool lit_check(const gi_baked_params* p, const void* sh, const void* chain, std::string& err)
+{
+    if (!p) { err = "render_baked: null parameters"; return false; }
+    if (p->n_samples < 1) { err = "render_baked: n_samples must be at least 1, got " + std::to_string(p->n_samples); return false; }
+    if (p->terms == 0 || (p->terms & ~GI_BAKED_ALL_TERMS)) { err = "render_baked: terms must be a non-empty set of GI_BAKED_DIRECT, _DIFFUSE, _SPECULAR and _EMISSIVE, got " + std::to_string(p->terms); return false; }
+    if (p->nx < 1 || p->ny < 1 || p->nz < 1) { err = "render_baked: every grid dimension must be at least 1, got " + std::to_string(p->nx) + " x " + std::to_string(p->ny) + " x " + std::to_string(p->nz); return false; }
+    if ((unsigned long long)p->nx * (unsigned long long)p->ny > (1ull << 31) || (unsigned long long)p->nx * (unsigned long long)p->ny * (unsigned long long)p->nz > (1ull << 31)) {
+        err = "render_baked: more than 2^31 probes";
+        return false;
+    }
+    if (p->terms & GI_BAKED_DIFFUSE) {
+        if (!sh) { err = "render_baked: the diffuse term needs the probe grid"; return false; }
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(p->grid_min[k]) || !std::isfinite(p->grid_max[k]) || !(p->grid_max[k] > p->grid_min[k])) { err = "render_baked: the grid box must be finite with grid_max > grid_min on every axis"; return false; }
+    }
+    if (p->terms & GI_BAKED_SPECULAR) {
+        if (!chain) { err = "render_baked: the specular term needs the chain"; return false; }
+        if (p->face < 1 || p->face > GI_CM_MAX_FACE) { err = "render_baked: face must be 1 .. " + std::to_string(GI_CM_MAX_FACE) + ", got " + std::to_string(p->face); return false; }
+        if (p->levels < 1 || p->levels > GI_CUBEMAP_MAX_LEVELS) { err = "render_baked: levels must be 1 .. " + std::to_string(GI_CUBEMAP_MAX_LEVELS) + ", got " + std::to_string(p->levels); return false; }
+        if (p->face & ((1 << (p->levels - 1)) - 1)) { err = "render_baked: " + std::to_string(p->levels) + " levels need a face divisible by " + std::to_string(1 << (p->levels - 1)) + ", got " + std::to_string(p->face); return false; }
+        for (int l = 1; l < p->levels; l++)
+            if (p->log2_exponent[l] < 0 || p->log2_exponent[l] > 16) { err = "render_baked: log2_exponent[" + std::to_string(l) + "] must be 0 .. 16, got " + std::to_string(p->log2_exponent[l]); return false; }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void gi_baked_default_params(gi_baked_params* p)
+{
+    if (!p) return;
+    p->n_samples = 4; p->terms = GI_BAKED_DIRECT | GI_BAKED_EMISSIVE;
+    for (int k = 0; k < 3; k++) { p->grid_min[k] = 0.0; p->grid_max[k] = 1.0; }
+    p->nx = p->ny = p->nz = 1;
+    p->face = 32; p->levels = 1;
+    for (int l = 0; l < GI_CUBEMAP_MAX_LEVELS; l++) p->log2_exponent[l] = std::max(0, 16 - 3 * l);
+}
+
+int gi_render_baked_device(gi_ctx* c, const gi_render_params* p, const gi_baked_params* bp, const double* d_sh, const double* d_chain, void* d_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    if (!p || !d_out) return fail(c, GI_E_INVALID, "render_baked: null frame parameters or output pointer");
+    std::string err;
+    if (!lit_check(bp, d_sh, d_chain, err)) return fail(c, GI_E_INVALID, err);
+    Frame F;
+    if (const int rc = pixel_pass_frame(c, "render_baked", p, F)) return rc;
+    LitArgs A{};
+    A.terms = bp->terms;
+    A.n3[0] = bp->nx; A.n3[1] = bp->ny; A.n3[2] = bp->nz;
+    for (int k = 0; k < 3; k++) { A.gmin[k] = bp->grid_min[k]; A.gmax[k] = bp->grid_max[k]; }
+    A.sh = d_sh; A.chain = d_chain;
+    // the level every material reads, made per call from the roughnesses kept at upload (baked_level_of: no transcendental on the device)
+    if (bp->terms & GI_BAKED_SPECULAR) {
+        A.face = (uint32_t)bp->face;
+        for (int l = 0; l < bp->levels; l++) A.level_off[l] = (uint32_t)cm_texels_before(bp->face, l);
+        std::vector<int32_t> levels(c->scene.mat_roughness.size());
+        for (size_t m = 0; m < levels.size(); m++) levels[m] = baked_level_of(c->scene.mat_roughness[m], bp->levels, bp->log2_exponent);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier pass on the stream may still read the table
+        if (c->lit.d_levels.n < levels.size()) HIP_TRY(c, c->lit.d_levels.alloc(levels.size()));
+        if (!levels.empty()) HIP_TRY(c, hipMemcpy(c->lit.d_levels.p, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        A.level_of_mat = c->lit.d_levels.p;
+    }
+    return pixel_pass(c, c->lit, "render_baked", F, bp->n_samples, kLit, GI_LIT_BLOCK, [&](const LitK& k, dim3 grid, dim3 block, uint32_t n_pix) {
+        hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
+    });
+}
+
+int gi_render_baked_host(gi_ctx* c, const gi_render_params* p, const gi_baked_params* bp, const double* sh, const double* chain, void* h_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    if (!p || !h_out) return fail(c, GI_E_INVALID, "render_baked: null frame parameters or output pointer");
+    std::string err;
+    if (!lit_check(bp, sh, chain, err)) return fail(c, GI_E_INVALID, err);
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "render_baked: no scene uploaded");
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<double> d_sh, d_chain;
+    if (bp->terms & GI_BAKED_DIFFUSE) HIP_TRY(c, d_sh.upload(sh, (size_t)bp->nx * (size_t)bp->ny * (size_t)bp->nz * 27));
+    if (bp->terms & GI_BAKED_SPECULAR) HIP_TRY(c, d_chain.upload(chain, cm_texels_before(bp->face, bp->levels) * 3));
+    return pixel_pass_to_host(c, c->lit, "render_baked_host", p, 12, h_out, out_is_f64, nullptr,
+                              [&](void* d_out, int32_t*) { return gi_render_baked_device(c, p, bp, d_sh.p, d_chain.p, d_out, out_is_f64); });
+}
+
+int gi_last_baked_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::lit, ms); }
+
+}  // extern "C"

@@ -6,7 +6,7 @@
 //   Tuning        every value taken from the environment when the context is made (from_env), and the two limits the setters change
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
-//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, denoiser, upsampler, bake, lightmap, reflection probe
+//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, baked light, denoiser, upsampler, bake, lightmap, reflection probe
 // Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
@@ -63,6 +63,7 @@ struct SceneStore {
     DevBuf<TriShade> d_shade;
     std::vector<uint32_t> tri_flags;      // TriGeom::flags of every entity, on the host: gi_lightmap_host refuses a chart row that names a sphere
     DevBuf<Mat> d_mats;
+    std::vector<double> mat_roughness;    // Mat::roughness of every material, on the host: gi_render_baked_* picks each material's level of the chain from it
     DevBuf<LightD> d_lights;
     DevBuf<FogD> d_fogs;
     DevBuf<double> d_fog_grid;
@@ -86,6 +87,8 @@ struct SceneStore {
         if (e != hipSuccess) return e;
         tri_flags.resize(H.tris.size());
         for (size_t i = 0; i < H.tris.size(); i++) tri_flags[i] = H.tris[i].flags;
+        mat_roughness.resize(H.mats.size());
+        for (size_t i = 0; i < H.mats.size(); i++) mat_roughness[i] = H.mats[i].roughness;
         S.tnodes = d_tnodes.p; S.leaf_refs = d_refs.p; S.leaf_tris = d_leaf_tris.p; S.tris = d_tris.p; S.shade = d_shade.p;
         S.mats = d_mats.p; S.lights = d_lights.p;
         S.n_node = H.n_node; S.n_tri = H.n_tri; S.n_light = H.n_light;
@@ -372,6 +375,10 @@ struct CubemapPass : AuxPass {
     EventTimer t_stage[2];            // capture, prefilter
     DevBuf<double> d_b0, d_box, d_part;
 };
+// the baked-light pass (gi_baked.inc): the level of the chain every material reads [n_mat], made per call, sized on first use and kept
+struct LitPass : AuxPass {
+    DevBuf<int32_t> d_levels;
+};
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
 struct gi_ctx {
@@ -410,6 +417,7 @@ struct gi_ctx {
         DevBuf<double> d_verts;       // [GI_LENS_MAX_BLADES + 1][2], allocated by the first lens with a radius
     } lens;
     AuxPass feat, ao, up;             // gi_render_features_*, gi_render_occlusion_*, gi_upsample_*
+    LitPass lit;                      // gi_render_baked_*
     DenoisePass dn;                   // gi_denoise_*
     BakePass bake;                    // gi_bake_*
     LightmapPass lm;                  // gi_lightmap_*

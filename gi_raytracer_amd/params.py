@@ -1,9 +1,10 @@
-"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens."""
+"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import GI_OK, Lens, OcclusionParams, _f64, _floats, _p, lib
+from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, BakedParams, Lens, OcclusionParams, _f64,
+                   _floats, _p, lib)
 
 
 def halton_sample_cap(w, h):
@@ -98,6 +99,65 @@ def _whole(name, v, what="occlusion"):
     if i != v or not -2 ** 31 <= i < 2 ** 31:
         raise ValueError(f"{what}: {name} must be a whole number, got {v!r}")
     return i
+
+
+BAKED_TERMS = BAKED_DIRECT | BAKED_DIFFUSE | BAKED_SPECULAR | BAKED_EMISSIVE
+
+
+def baked_params(n=None, sh=None, grid_box=None, chain=None, exponents=None, terms=None, width=None, height=None):
+    """(gi_baked_params, sh, chain) of RayTracer.run_baked: the library's defaults with n samples; sh [nz][ny][nx][9][3] the probe grid (bake_probes
+    on probe_grid(grid_box, nx, ny, nz), reshaped) with its box grid_box = (min xyz, max xyz); chain a reflection probe's levels
+    [6][face >> l][face >> l][3] (the list bake_reflection_probe returns, or one array for a single level) filtered with `exponents` (indexed by level,
+    entry 0 ignored; default: the library's); terms a set of BAKED_* bits, default: DIRECT | EMISSIVE plus DIFFUSE with sh and SPECULAR with chain.
+    The arrays come back contiguous float64, the chain concatenated [texels][3]; None where not given.  No device needed.  ValueError for what the
+    library would refuse and for shapes that do not fit."""
+    p = BakedParams()
+    lib().gi_baked_default_params(C.byref(p))
+    if n is not None:
+        p.n_samples = _whole("n", n, "baked")
+    if p.n_samples < 1:
+        raise ValueError(f"baked: n must be at least 1, got {p.n_samples}")
+    if width is not None and height is not None and p.n_samples > halton_sample_cap(width, height):
+        raise ValueError(f"baked: n = {p.n_samples} takes the Halton index of a {width} x {height} frame beyond 32 bits (at most {halton_sample_cap(width, height)})")
+    if sh is not None:
+        sh = _f64(sh)
+        if sh.ndim != 5 or sh.shape[3:] != (9, 3) or min(sh.shape[:3]) < 1:
+            raise ValueError(f"baked: sh [nz][ny][nx][9][3] expected, got {sh.shape}")
+        if grid_box is None:
+            raise ValueError("baked: a probe grid needs its box, grid_box = (min xyz, max xyz)")
+        box = _f64(grid_box).reshape(-1)
+        if box.shape != (6,) or not np.isfinite(box).all() or not (box[3:] > box[:3]).all():
+            raise ValueError(f"baked: grid_box must be six finite numbers with max > min on every axis, got {box.tolist()}")
+        p.nz, p.ny, p.nx = sh.shape[:3]
+        p.grid_min[:], p.grid_max[:] = box[:3].tolist(), box[3:].tolist()
+    elif grid_box is not None:
+        raise ValueError("baked: grid_box without sh")
+    if chain is not None:
+        levels = [_f64(chain)] if isinstance(chain, np.ndarray) else [_f64(c) for c in chain]
+        face = levels[0].shape[1] if levels and levels[0].ndim == 4 else 0
+        if not 1 <= len(levels) <= CUBEMAP_MAX_LEVELS or face < 1 or face % (1 << (len(levels) - 1)):
+            raise ValueError(f"baked: chain must be 1 .. {CUBEMAP_MAX_LEVELS} levels whose first face is divisible by 2^(levels - 1)")
+        for l, c in enumerate(levels):
+            if c.shape != (6, face >> l, face >> l, 3):
+                raise ValueError(f"baked: level {l} of a chain of face {face} is [6][{face >> l}][{face >> l}][3], got {c.shape}")
+        p.face, p.levels = face, len(levels)
+        for l, e in enumerate(exponents if exponents is not None else ()):
+            if l >= CUBEMAP_MAX_LEVELS:
+                raise ValueError(f"baked: at most {CUBEMAP_MAX_LEVELS} exponents, got {len(exponents)}")
+            p.log2_exponent[l] = _whole(f"exponents[{l}]", e, "baked")
+        if any(not 0 <= p.log2_exponent[l] <= 16 for l in range(1, p.levels)):
+            raise ValueError(f"baked: exponents must be 0 .. 16, got {list(p.log2_exponent)[:p.levels]}")
+        chain = np.ascontiguousarray(np.concatenate([c.reshape(-1, 3) for c in levels]))
+    elif exponents is not None:
+        raise ValueError("baked: exponents without chain")
+    if terms is None:
+        terms = BAKED_DIRECT | BAKED_EMISSIVE | (BAKED_DIFFUSE if sh is not None else 0) | (BAKED_SPECULAR if chain is not None else 0)
+    p.terms = _whole("terms", terms, "baked")
+    if p.terms == 0 or p.terms & ~BAKED_TERMS:
+        raise ValueError(f"baked: terms must be a non-empty set of the BAKED_* bits, got {p.terms}")
+    if (p.terms & BAKED_DIFFUSE and sh is None) or (p.terms & BAKED_SPECULAR and chain is None):
+        raise ValueError("baked: the diffuse term needs sh, the specular term needs chain")
+    return p, sh, chain
 
 
 LENS_BLADES = range(3, 17)

@@ -6,7 +6,7 @@ import numpy as np
 from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
                    LightmapParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
-from .params import _bake_points, _chart, _fill_params, _filter_array, lens_params, low_frame_size, occlusion_params, upsample_arrays
+from .params import _bake_points, _chart, _fill_params, _filter_array, baked_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
 from .sessions import ProgressiveRender, parse_checkpoint_header
 
@@ -382,6 +382,35 @@ class RayTracer(DebugEntries):
         ms, st = C.c_float(0), (C.c_float * 2)()
         self._check(self.L.gi_last_cubemap_ms(self.h, C.byref(ms), st), "last_cubemap_ms")
         return ms.value, dict(zip(("capture", "prefilter"), (float(x) for x in st)))
+
+    def baked_params(self, **kw):
+        """The module's baked_params: n, sh, grid_box, chain, exponents, terms (and width, height for the Halton cap) -> (gi_baked_params, sh,
+        chain); ValueError for bad values and shapes."""
+        return baked_params(**kw)
+
+    def run_baked(self, w, h, n, sh=None, grid_box=None, chain=None, exponents=None, terms=None, f64=True, **kw):
+        """The baked-light pass on the frame `run` renders (gi_render_baked_host; an addition, the consumer of the bakes): per pixel the mean over
+        samples 0 .. n-1 of the first hit shaded from the analytic lights (direct), the probe grid sh [nz][ny][nx][9][3] in grid_box (diffuse:
+        bake_probes(probe_grid(grid_box, nx, ny, nz)) reshaped) and the reflection probe's chain (specular: the list bake_reflection_probe returns,
+        filtered with `exponents`), plus the surface's emission.  terms: BAKED_* bits, default whatever data was given plus direct and emissive.
+        Returns a dict of views into one array `baked` [rows][w][12]: beauty, direct, diffuse, specular, [rows][w][3] each.  **kw as for run
+        (stripes, seed).  ValueError for bad values and shapes, before the library is called; the definition is stated in include/gi_hip.h."""
+        bp, sh, chain = baked_params(n=n, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=w, height=h)
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out, o = _out((rows, w, 12), f64)
+        self._check(self.L.gi_render_baked_host(self.h, C.byref(p), C.byref(bp), _p(sh), _p(chain), *o), "render_baked_host")
+        return {"baked": out, "beauty": out[:, :, 0:3], "direct": out[:, :, 3:6], "diffuse": out[:, :, 6:9], "specular": out[:, :, 9:12]}
+
+    def run_baked_device(self, p, bp, sh_ptr, chain_ptr, out_ptr, f64=False):
+        """The baked-light pass on device memory, asynchronous on the context's stream; p from params, bp from baked_params; sh_ptr
+        ([nz][ny][nx][9][3] f64), chain_ptr (the whole chain, f64) and out_ptr ([rows][w][12]) are raw device pointers, the first two None where
+        their term is off."""
+        self._check(self.L.gi_render_baked_device(self.h, C.byref(p), C.byref(bp), sh_ptr or None, chain_ptr or None, *_dev(out_ptr, f64)), "render_baked_device")
+
+    def last_baked_ms(self):
+        """gi_last_baked_ms: device time of the last baked-light pass (the frame's and the other passes' times keep theirs)."""
+        return self._last_ms("baked")
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):
         """gi_set_lens: the thin lens every pass of this context makes its primary rays through -- run (all render modes), progressive sessions,

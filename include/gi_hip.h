@@ -509,7 +509,7 @@ int gi_focus_distance(gi_ctx*, const gi_render_params*, int32_t x, int32_t y, do
  * term on a miss.  The fold is IEEE operations only (+ * /) in the order written, compiled without contraction: given the same L_k and d_k it can be
  * restated bit for bit (tests/bake_expect.py); gi_bake_fold runs it on caller data.
  * What a bake does NOT hold: the analytic lights are not geometry, so no ray ever hits one -- direct light of the lights at the point itself is not in
- * the result.  This is the usual indirect-only bake; a consumer adds direct light itself, and gi_visible answers the shadow segment.  The context's
+ * the result.  This is the usual indirect-only bake; the consumer adds direct light itself: gi_render_baked_* does, and gi_visible answers the shadow segment for any other.  The context's
  * lens plays no part (there is no primary ray), nor does the render mode: a bake always runs the streaming passes.  Points inside geometry are
  * baked like any other.  There is no gi_group_* form: split the point list.
  * out is float (out_is_f64 = 0) or double (1), rounded once on store.  Points that do not fit the path pool (gi_set_pool_slots, free memory) run in
@@ -628,7 +628,8 @@ int gi_lightmap_dilate(gi_ctx*, int32_t width, int32_t height, int32_t passes, c
  *   the face of the source level; the defaults are safe for every cube of face 4 or more.
  * Output.  The levels lie one after another, level l as [6][N >> l][N >> l][3], float (out_is_f64 = 0) or double (1); a float is the double rounded
  * once.  gi_cubemap_chain_texels(face, levels) is the number of texels of the chain, or -1 for a pair a call would refuse.
- * A consumer looks up level l at the direction d by the face of d's largest component and (a, b) of the table above divided by that component's size.
+ * A consumer looks up level l at the direction d by the face of d's largest component and (a, b) of the table above divided by that component's size:
+ * gi_render_baked_* is that consumer, and step 5 of its definition states the texel exactly.
  * GI_E_INVALID, before any pointer is used: a null pointer, face < 1, n_samples < 1, levels outside 1 .. GI_CUBEMAP_MAX_LEVELS, a face not
  * divisible by 2^(levels - 1), log2_exponent[l] outside 0 .. 16 for a level 1 <= l < levels (entry 0 and the entries from `levels` on are ignored),
  * stream_base + 6 N^2 n_samples beyond 2^32, and -- gi_cubemap_host and gi_cubemap_rays -- a position that is not finite.  GI_E_STATE: no scene.
@@ -661,6 +662,70 @@ int gi_cubemap_device(gi_ctx*, const double* pos3, const gi_cubemap_params*, voi
 int gi_last_cubemap_ms(gi_ctx*, float* ms, float* stages2);
 int gi_cubemap_rays(gi_ctx*, const double* pos3, const gi_cubemap_params*, double* rays6_out, uint32_t* stream_out);
 int gi_cubemap_prefilter(gi_ctx*, const gi_cubemap_params*, const double* cube_in, double* chain_out);
+
+/* The baked-light pass -- an ADDITION: the consumer of the bakes.  A per-pixel pass beside the first-hit features and the occlusion: it shades the
+ * frame's first hit from a grid of SH9 light probes (gi_bake_*, GI_BAKE_SH9), a reflection probe's chain (gi_cubemap_*) and the analytic lights -- a
+ * preview of the scene at about the cost of a feature pass, with no path pool, no sorts and no gather.  Every operation of steps 3 to 7 is f64, IEEE
+ * + - * / and sqrt only, in the order written, compiled without contraction, so that it can be restated bit for bit (tests/baked_expect.py).
+ * Inputs beside the parameters: sh [nz][ny][nx][9][3] f64, the rows gi_bake_* gives for the nx x ny x nz probes at the CELL CENTRES of the box
+ * grid_min .. grid_max, x fastest; chain, the whole chain as gi_cubemap_host writes it with out_is_f64 = 1, gi_cubemap_chain_texels(face, levels)
+ * texels of 3.  A pointer may be null when its term's bit is clear.
+ * Per pixel and per sample s = 0 .. n_samples-1 (Halton index, frame parameters, stripes and seed as for gi_render_occlusion_*; the context's lens applies):
+ *   1. First hit: that of gi_render_features_* (same ray, same RNG keys).  From it: color, the feature pass's albedo (texture included); emissive,
+ *      with its texture; N, minNorm of trace; P, the ray direction d, the material m.  norm = -N if dot(N, d) > 0 else N (secondaryRay's turn,
+ *      include/raytracer.h:321-379: not renormalised); Nf as step 3 of the occlusion pass.  A miss adds the scene's ambient colour to beauty and
+ *      nothing to the three terms.
+ *   2. Direct: by definition what the frame's depth-0 shade adds for the analytic lights (include/raytracer.h:230-256), as the streaming passes
+ *      compute it: per light li the draws P_LIGHT_Y | li << 8 and P_LIGHT_X | li << 8 of the stream at depth 0, the shadow ray from
+ *      P + 0.0001 norm towards the point drawn on the light, asked of RayTracer::visible with light index li (the medium included, as in the
+ *      frame), i_li = col * pow(max(0, dot(norm, normalize(lpos - P))), 1 / roughness) * (1 / (pi |lpos - P|^2)).  The reference keeps the share
+ *      of the LAST visible light, so i = i_li of the highest li that is visible, or 0.  direct = color * i.  A one-sample frame of a scene whose
+ *      paths all leave after the first hit, with no ambient light and no photons, is this term bit for bit.
+ *   3. Lobe, by the roughness alone (rayType and secondaryRay without their draws): roughness < .001, a mirror: specular only, from level 0;
+ *      .001 <= roughness < .9, glossy: specular only, from the material's level; otherwise diffuse only.  Opacity is ignored.
+ *      The material's level: with levels == 1, level 0; else the l of 1 .. levels-1 whose log2_exponent[l] is nearest to
+ *      log2(1 / roughness + 1) (host libm; the Phong exponent of the glossy bounce), ties to the lower l.  The table is made on the host per call.
+ *   4. Diffuse = color * D.  Per axis with n probes: g = ((P - gmin) / (gmax - gmin)) * (double) n - 0.5, clamped to [0, n - 1]; i0 = floor(g),
+ *      i1 = min(i0 + 1, n - 1), t = g - i0.  F_j = k_j * Y_j(Nf) with Y_j of GI_BAKE_SH9 (same order, same literals, each product as written
+ *      there) and k_j = 1.0 (band 0), 0.6666666666666666 (band 1), 0.25 (band 2): the cosine lobe's factors over pi, so D is on the scale of a
+ *      GI_BAKE_TEXEL result.  At each of the eight probes around P: D_c[ch] = sum over j, ascending from +0.0, of F_j * c_j[ch].  Then
+ *      a + t * (b - a) along x, then y, then z; then each channel < 0 becomes 0.
+ *   5. Specular = color * C_l(R), R = d - (Nf * dot(Nf, d)) * 2.0 with dot = (Nf.x d.x + Nf.y d.y) + Nf.z d.z.  The texel of R in level l of face
+ *      n = face >> l: the face of the largest |component|, the first of equals; x, y, z = R / that size; (a, b) = (-z, -y) on +X, (z, -y) on -X,
+ *      (x, z) on +Y, (x, -z) on -Y, (x, -y) on +Z, (-x, -y) on -Z; column = min(n - 1, max(0, (int) floor(((a + 1.0) * 0.5) * n))), row the same
+ *      from b.  The nearest texel: no parallax correction, no blending between levels.  A NaN texel of an over-narrow lobe passes through.
+ *   6. Emissive: the first hit's emissive.
+ *   7. beauty = ((direct + diffuse) + specular) + emissive, a term whose bit is clear being +0.0.
+ * Per pixel: the f64 sums over s in ascending order from +0.0 of the twelve channels, each divided once by (double) n_samples.  No reduction
+ * across lanes: the result does not depend on stripes, the octree walk in use or the launch.
+ * out [local_rows][width][12] = beauty rgb, direct rgb, diffuse rgb, specular rgb, float (out_is_f64 = 0) or double (1), rounded once on store.
+ * What the preview is not: a transparent surface is shaded as opaque; the camera segment is not marched through the medium (the first hit is the
+ * surface's, as in the feature pass); probes are looked up without visibility, the cube without parallax; lightmaps (gi_lightmap_*) are not read.
+ * GI_E_INVALID: null parameters or output; n_samples < 1 or taking the Halton index beyond 32 bits; terms 0 or with unknown bits; a grid dimension
+ * < 1 or more than 2^31 probes; with GI_BAKED_DIFFUSE: a null sh, non-finite bounds or grid_max <= grid_min on an axis; with GI_BAKED_SPECULAR: a
+ * null chain, face, levels and log2_exponent not as gi_cubemap_params allows.  GI_E_STATE: no scene.  A refused call touches no output and no
+ * timer; an open progressive session is left as it is.
+ * gi_baked_default_params: 4 samples, terms DIRECT | EMISSIVE, a 1 x 1 x 1 grid in the unit box, face 32, 1 level, log2_exponent as gi_cubemap's.
+ * gi_render_baked_device: DEVICE pointers (sh, chain, out), asynchronous on the context's stream, except that with GI_BAKED_SPECULAR it first waits
+ * for the stream's earlier work, to replace the level table.  gi_render_baked_host: HOST pointers.
+ * gi_last_baked_ms: device time of the last pass (HIP events around the kernel); the frame's and the other passes' times are left alone. */
+#define GI_BAKED_DIRECT 1
+#define GI_BAKED_DIFFUSE 2
+#define GI_BAKED_SPECULAR 4
+#define GI_BAKED_EMISSIVE 8
+typedef struct gi_baked_params {
+    int32_t n_samples;       /* >= 1 */
+    int32_t terms;           /* GI_BAKED_* bits, at least one */
+    double grid_min[3], grid_max[3];   /* the probe grid's box */
+    int32_t nx, ny, nz;      /* >= 1 each: probes per axis, at the cell centres */
+    int32_t face;            /* of the chain, as gi_cubemap_params::face */
+    int32_t levels;          /* 1 .. GI_CUBEMAP_MAX_LEVELS */
+    int32_t log2_exponent[GI_CUBEMAP_MAX_LEVELS];   /* as gi_cubemap_params::log2_exponent: what the levels were filtered with */
+} gi_baked_params;
+void gi_baked_default_params(gi_baked_params*);
+int gi_render_baked_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const double* d_sh, const double* d_chain, void* d_out, int out_is_f64);
+int gi_render_baked_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const double* sh, const double* chain, void* h_out, int out_is_f64);
+int gi_last_baked_ms(gi_ctx*, float* ms);
 
 #ifdef __cplusplus
 }
