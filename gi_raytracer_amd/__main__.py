@@ -7,7 +7,8 @@
                                [--upsample S [--upsample-pfm LOW.pfm]]
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
-                               [--baked PREFIX [--baked-samples N] [--baked-probes NX NY NZ] [--baked-reflection X Y Z]]
+                               [--baked PREFIX [--baked-samples N] [--baked-probes NX NY NZ] [--baked-reflection X Y Z]
+                                [--baked-lightmap W H [--lightmap-samples N]]]
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
     python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
                                -o OUT.ppm [--pfm OUT.pfm]
@@ -54,6 +55,10 @@ every pixel's first hit with --baked-samples N samples (default 4) from the ligh
 transform of the preview, PREFIX_direct.pfm, PREFIX_diffuse.pfm and PREFIX_specular.pfm its three terms.  It goes with the frame's flags as
 --occlusion does, not with --probes, --lightmap or --reflection-probe.  If -o is not given and PREFIX.ppm is the frame's default name, the frame
 goes to PREFIX_frame.ppm.
+--baked-lightmap W H (with --baked; include/gi_hip.h: gi_render_baked_lightmap_*) also bakes a W x H lightmap atlas over the scene's texture
+coordinates, as --lightmap does for all triangles, with --lightmap-samples N rays per covered texel (default 256) and 2 gutter passes, and the
+preview's diffuse surfaces read it: a first hit on a charted triangle takes its diffuse light from the atlas, every other one from the probes.  One
+more line names the atlas size and the texels covered.
 """
 import argparse
 import os
@@ -115,6 +120,7 @@ def parser():
     ap.add_argument("--baked", default=None, metavar="PREFIX", help="also write a preview shaded from baked light as PREFIX.ppm and its terms as PREFIX_{direct,diffuse,specular}.pfm")
     ap.add_argument("--baked-samples", type=int, default=None, metavar="N", help="with --baked: samples per pixel (default 4)")
     ap.add_argument("--baked-probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="with --baked: the light-probe grid in the scene's box (default 4 4 4)")
+    ap.add_argument("--baked-lightmap", type=int, nargs=2, default=None, metavar=("W", "H"), help="with --baked: bake a W x H lightmap over the scene's texture coordinates and shade charted diffuse surfaces from it")
     ap.add_argument("--baked-reflection", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --baked: position of the reflection probe (default: the middle of the scene's box)")
     return ap
 
@@ -132,8 +138,8 @@ def check_args(ap, a):
     explicit_output = a.output is not None
     if not explicit_output:
         a.output = "out.ppm"
-    if a.baked is None and (a.baked_samples is not None or a.baked_probes is not None or a.baked_reflection is not None):
-        ap.error("--baked-samples, --baked-probes and --baked-reflection need --baked PREFIX")
+    if a.baked is None and (a.baked_samples is not None or a.baked_probes is not None or a.baked_reflection is not None or a.baked_lightmap is not None):
+        ap.error("--baked-samples, --baked-probes, --baked-reflection and --baked-lightmap need --baked PREFIX")
     if a.baked is not None:
         if a.probes is not None or a.lightmap is not None or a.reflection_probe is not None:
             ap.error("--baked does not go together with --probes, --lightmap or --reflection-probe")
@@ -145,6 +151,14 @@ def check_args(ap, a):
             ap.error("--baked-probes NX NY NZ: three numbers >= 1; probes x 256 samples must keep the stream index within 32 bits")
         if a.baked_reflection is not None and not all(-float("inf") < v < float("inf") for v in a.baked_reflection):
             ap.error("--baked-reflection X Y Z: three finite numbers")
+        if a.baked_lightmap is not None:
+            w, h = a.baked_lightmap
+            if not (1 <= w <= 8192 and 1 <= h <= 8192):
+                ap.error("--baked-lightmap W H: two numbers from 1 to 8192")
+            if a.lightmap_samples is not None and a.lightmap_samples < 1:
+                ap.error("--lightmap-samples N: N must be at least 1")
+            if w * h * (a.lightmap_samples or LIGHTMAP_SAMPLES) > 2 ** 32:
+                ap.error("--baked-lightmap: texels x samples must keep the stream index within 32 bits")
         if os.path.abspath(a.baked + ".ppm") == os.path.abspath(a.output):
             if explicit_output:
                 ap.error(f"--baked {a.baked} writes {a.baked}.ppm, which is -o: name one of them differently")
@@ -188,8 +202,8 @@ def check_args(ap, a):
         frame_flags = (a.pfm, a.samples, a.features, a.feature_samples, a.denoise, a.progressive, a.upsample, a.occlusion, a.aperture)
         if any(f is not None for f in frame_flags):
             ap.error("--probes renders no frame: only --photons, --probe-samples, --device and -o go with it")
-    if a.lightmap is None and (a.lightmap_material is not None or a.lightmap_samples is not None or a.lightmap_dilate is not None):
-        ap.error("--lightmap-material, --lightmap-samples and --lightmap-dilate need --lightmap W H")
+    if a.lightmap is None and (a.lightmap_material is not None or (a.lightmap_samples is not None and a.baked_lightmap is None) or a.lightmap_dilate is not None):
+        ap.error("--lightmap-material, --lightmap-samples and --lightmap-dilate need --lightmap W H (--lightmap-samples also goes with --baked-lightmap W H)")
     if a.lightmap is not None:
         w, h = a.lightmap
         if not (1 <= w <= 8192 and 1 <= h <= 8192):
@@ -328,11 +342,20 @@ def render_baked(a, rt, scene):
     pos = a.baked_reflection if a.baked_reflection is not None else [0.5 * (box[k] + box[3 + k]) for k in range(3)]
     chain = rt.bake_reflection_probe(pos, REFLECTION_FACE, REFLECTION_SAMPLES, BAKED_LEVELS)
     ns = BAKED_SAMPLES if a.baked_samples is None else a.baked_samples
-    lit = rt.run_baked(a.width, a.height, ns, sh=sh, grid_box=box, chain=chain, f64=False)      # (the chain's exponents are the library's defaults, in both calls)
+    note = ""
+    if a.baked_lightmap is not None:
+        w, h = a.baked_lightmap
+        ent, uv = gi.chart_of_material(scene)
+        atlas, _, n_cov = rt.bake_lightmap(ent, uv, w, h, a.lightmap_samples or LIGHTMAP_SAMPLES, want_owner=True)
+        print(f"{a.scene}: baked lightmap {w}x{h}, {len(ent)} chart triangles, {n_cov} texels covered, {rt.last_lightmap_ms()[0]:.2f} ms")
+        lit = rt.run_baked_lightmap(a.width, a.height, ns, atlas, ent, uv, sh=sh, grid_box=box, chain=chain, f64=False)
+        note = f", lightmap {w}x{h}"
+    else:
+        lit = rt.run_baked(a.width, a.height, ns, sh=sh, grid_box=box, chain=chain, f64=False)      # (the chain's exponents are the library's defaults, in both calls)
     gi.save_ppm(f"{a.baked}.ppm", lit["beauty"])
     for name in BAKED_FILES:
         gi.save_pfm(f"{a.baked}_{name}.pfm", lit[name])
-    return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, cube {rt.last_cubemap_ms()[0]:.2f} ms, {ns} spp preview {rt.last_baked_ms():.2f} ms "
+    return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, cube {rt.last_cubemap_ms()[0]:.2f} ms{note}, {ns} spp preview {rt.last_baked_ms():.2f} ms "
             f"-> {a.baked}.ppm, {a.baked}_*.pfm")
 
 

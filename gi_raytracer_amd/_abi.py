@@ -19,6 +19,8 @@ BAKE_TEXEL, BAKE_SH9 = 0, 1
 BAKE_MODES = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}
 CUBEMAP_MAX_LEVELS = 12
 BAKED_DIRECT, BAKED_DIFFUSE, BAKED_SPECULAR, BAKED_EMISSIVE = 1, 2, 4, 8
+LM_NEAREST, LM_BILINEAR = 0, 1
+LM_FILTERS = {"nearest": LM_NEAREST, "bilinear": LM_BILINEAR}
 
 _dp, _ip, _up, _fp, _lp, _bp = (C.POINTER(t) for t in (C.c_double, C.c_int32, C.c_uint32, C.c_float, C.c_int64, C.c_uint8))
 
@@ -92,6 +94,11 @@ class BakedParams(C.Structure):
                 ("ny", C.c_int32), ("nz", C.c_int32), ("face", C.c_int32), ("levels", C.c_int32), ("log2_exponent", C.c_int32 * CUBEMAP_MAX_LEVELS)]
 
 
+class BakedLightmapParams(C.Structure):
+    """gi_baked_lightmap_params (include/gi_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("n_chart", C.c_int32)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -102,7 +109,7 @@ class Settings(C.Structure):
 STRUCTS = {"gi_scene_desc": SceneDesc, "gi_photon_map_desc": PhotonMapDesc, "gi_render_params": RenderParams, "gi_denoise_params": DenoiseParams,
            "gi_upsample_params": UpsampleParams, "gi_occlusion_params": OcclusionParams, "gi_lens": Lens, "gi_bake_params": BakeParams,
            "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gi_baked_params": BakedParams,
-           "gih_settings": Settings}
+           "gi_baked_lightmap_params": BakedLightmapParams, "gih_settings": Settings}
 
 
 def _signatures():
@@ -111,7 +118,7 @@ def _signatures():
     P, ms, knob = C.POINTER, (i, [vp, _fp]), (i, [vp, i])
     scene, photons, rp = P(SceneDesc), P(PhotonMapDesc), P(RenderParams)
     dn, us, oc, lens, bake, lm = P(DenoiseParams), P(UpsampleParams), P(OcclusionParams), P(Lens), P(BakeParams), P(LightmapParams)
-    cm, bk = P(CubemapParams), P(BakedParams)
+    cm, bk, bl = P(CubemapParams), P(BakedParams), P(BakedLightmapParams)
     return {
         # include/gi_hip.h: context, uploads, frames
         "gi_create": (i, [P(vp), i]), "gi_destroy": (None, [vp]), "gi_last_error": (s, [vp]), "gi_set_stream": (i, [vp, vp]),
@@ -164,6 +171,8 @@ def _signatures():
         # the baked-light pass
         "gi_baked_default_params": (None, [bk]), "gi_render_baked_device": (i, [vp, rp, bk, vp, vp, vp, i]),
         "gi_render_baked_host": (i, [vp, rp, bk, _dp, _dp, vp, i]), "gi_last_baked_ms": ms,
+        "gi_baked_lightmap_default_params": (None, [bl]), "gi_render_baked_lightmap_host": (i, [vp, rp, bk, bl, _dp, _dp, vp, i, _ip, _dp, vp, i]),
+        "gi_render_baked_lightmap_device": (i, [vp, rp, bk, bl, vp, vp, vp, vp, vp, vp, i]),
         # csrc/gi_host.h: the host scene builder
         "gih_scene_create": (vp, []), "gih_scene_destroy": (None, [vp]), "gih_last_error": (s, [vp]), "gih_load_scn": (i, [vp, s]),
         "gih_load_obj": (i, [vp, s, _dp, _dp, i32]), "gih_add_material": (i, [vp, _dp]), "gih_add_texture": (i, [vp, i32, _dp, _bp, i64]),

@@ -1,5 +1,6 @@
 // gi_baked.h -- the per-lane functions of the baked-light pass (gi_render_baked_*; include/gi_hip.h states the definition): the probe grid's cell, the
-// irradiance factors of an SH9 probe, the trilinear step, the texel of a direction in a reflection probe's cube, the direct-light loop, and -- host
+// irradiance factors of an SH9 probe, the trilinear step, the texel of a direction in a reflection probe's cube, the chart coordinate of a hit and the
+// two filters of a lightmap atlas (tests/cpp/baked_lightmap_lookup.cpp, tests/baked_lightmap_expect.py), the direct-light loop, and -- host
 // only -- the level a material's roughness reads from.  Needs gi_device.h (visible_nodes, the RNG, LightD) and gi_cubemap.h (the texel order).
 // Included by gi_baked.inc inside namespace gi; tests/cpp/baked_lookup.cpp compiles it for the host.  Apart from the light loop, which is the shade
 // stage's arithmetic, everything is IEEE + - * / and sqrt only, in the header's order, so that with -ffp-contract=off every value equals the
@@ -85,6 +86,46 @@ GI_HD uint32_t cube_texel(V3 R, uint32_t n)
     else { if (R.z < 0.0) { f = 5u; a = -x; b = -y; } else { f = 4u; a = x; b = -y; } }
     return (f * n + cube_coord_texel(b, n)) * n + cube_coord_texel(a, n);
 }
+// ---- the lightmap look-up (gi_render_baked_lightmap_*): from the hit point to the chart, from the chart to the atlas
+// (u, v) of the point P of the entity g under the chart row uv [3][2]: the barycentrics of P in the entity's plane from the normal equations of
+// P - p0 = b1 e1v + b2 e2v -- the inverse of lm_point (gi_lightmap.inc) -- then the row's three coordinates under them.  A function of the
+// entity's record and P alone.  A degenerate triangle has den = 0: NaN (or infinite) coordinates, which both filters send to a border texel.
+struct LmCoord { double u, v; };
+GI_HD LmCoord lm_coord(const TriGeom& g, V3 P, const double* uv)
+{
+    const V3 e1 = ld3(g.e1), e2 = ld3(g.e2), d = P - ld3(g.p0);
+    const double d00 = dot(e1, e1), d01 = dot(e1, e2), d11 = dot(e2, e2), d20 = dot(d, e1), d21 = dot(d, e2);
+    const double den = d00 * d11 - d01 * d01;
+    const double b1 = (d11 * d20 - d01 * d21) / den, b2 = (d00 * d21 - d01 * d20) / den;
+    const double b0 = 1 - b1 - b2;
+    LmCoord c;
+    c.u = (b0 * uv[0] + b1 * uv[2]) + b2 * uv[4];
+    c.v = (b0 * uv[1] + b1 * uv[3]) + b2 * uv[5];
+    return c;
+}
+// GI_LM_NEAREST: the texel column (or row) of n that the coordinate falls into, min(n - 1, max(0, floor(a * n))); a NaN goes to 0
+GI_HD int32_t lm_coord_texel(double a, int32_t n)
+{
+    const double v = a * (double)n;
+    return v >= 1.0 ? (v < (double)n ? (int32_t)v : n - 1) : 0;
+}
+GI_HD V3 lm_nearest(const double* atlas, int32_t w, int32_t h, LmCoord c)
+{
+    return ld3(atlas + ((size_t)lm_coord_texel(c.v, h) * (size_t)w + (size_t)lm_coord_texel(c.u, w)) * 3);
+}
+// GI_LM_BILINEAR: the four texels around (u, v), texel centres at (x + .5) / w as the bake places them (lm_centre), clamped to the border texels
+// (grid_cell: a NaN goes to texel 0); interpolated along x on both rows, then along y, then each channel clamped at 0 from below
+GI_HD V3 lm_bilinear(const double* atlas, int32_t w, int32_t h, LmCoord c)
+{
+    const GridCell cx = grid_cell(c.u, 0.0, 1.0, w), cy = grid_cell(c.v, 0.0, 1.0, h);
+    const auto row = [&](int32_t iy) {
+        const double* r = atlas + (size_t)iy * (size_t)w * 3;
+        return lerp3(ld3(r + (size_t)cx.i0 * 3), ld3(r + (size_t)cx.i1 * 3), cx.t);
+    };
+    const V3 d = lerp3(row(cy.i0), row(cy.i1), cy.t);
+    return v3(d.x < 0.0 ? 0.0 : d.x, d.y < 0.0 ? 0.0 : d.y, d.z < 0.0 ? 0.0 : d.z);
+}
+
 // The analytic lights at a first hit: what the frame's depth-0 shade adds for them, as the streaming passes compute it (stage_shade_nodes with the
 // walks put off, k_st_shadow): the share of the LAST light that is visible, asked from the last light down.  P the hit, norm the shading normal as
 // the shade stage holds it (turned to the viewer's side, not renormalised), rng the stream's at depth 0.  VFEAT: the shade stage's level of the

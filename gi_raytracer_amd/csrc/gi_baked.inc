@@ -10,8 +10,8 @@ namespace gi {
 // The first hit of the sample with Halton index idx: aov_sample's (same ray, same RNG keys, same recomputation of the hit from the entity's record on
 // the wide walk), and from it what the three later steps need.  norm is the shade stage's normal (secondary_ray turns it, nothing renormalises it),
 // nf ao_first_hit's.
-struct LitHit { V3 P, d, norm, nf, color, emissive; double roughness; int32_t mat; };
-template <int FEAT, class Nodes>
+struct LitHit { V3 P, d, norm, nf, color, emissive; double roughness; int32_t mat; };   // mat: under LM, on the diffuse lobe, the ENTITY instead (the lobe needs one of the two)
+template <int FEAT, int LM = 0, class Nodes>
 GI_HD bool lit_first_hit(const Scene& S, const Nodes& N, const Frame& F, uint64_t seed, uint32_t idx, Rng& rng, LitHit& a)
 {
     const Ray ray = primary_ray_at(S, F, idx);
@@ -36,11 +36,13 @@ GI_HD bool lit_first_hit(const Scene& S, const Nodes& N, const Frame& F, uint64_
     a.nf = dot(nh, ray.d) > 0 ? v3(-nh.x, -nh.y, -nh.z) : nh;
     a.P = h.pos; a.d = ray.d;
     a.roughness = m.roughness; a.mat = (int32_t)(h.mf >> 3);
+    if constexpr (LM != 0) { if (!(m.roughness < .9)) a.mat = h.tri; }
     return true;
 }
 }  // namespace gi
 
-// What the kernel reads beside the scene: the probe grid, the chain and the level each material reads, through global memory (small, L2-resident).
+// What the kernel reads beside the scene: the probe grid, the chain and the level each material reads, through global memory (small, L2-resident);
+// the lightmap instances (LM) also the atlas, the chart and the row that serves each entity, the same way.
 struct LitArgs {
     int32_t terms;                                  // GI_BAKED_*
     int32_t n3[3];                                  // nx, ny, nz
@@ -50,9 +52,30 @@ struct LitArgs {
     const int32_t* level_of_mat;                    // [n_mat]
     uint32_t face;
     uint32_t level_off[GI_CUBEMAP_MAX_LEVELS];      // texels before level l
+    const struct LitLm* lm;                         // gi_render_baked_lightmap_*: read by the LM instances only
+};
+// the lightmap of a call, in device memory (written by k_lm_rows): one pointer among the kernel's arguments, read where the look-up happens
+struct LitLm {
+    int32_t w, h, filter;                           // the atlas's size, GI_LM_*
+    const double* atlas;                            // [h][w][3]
+    const double* uv;                               // the chart's coordinates, [n_chart][3][2]
+    const int* row_of_ent;                          // [n_tri]: the lowest chart row of the entity, GI_LM_NONE where it has none
 };
 
-// One kernel, k_lit<FEAT, WIDE>, of k_ao's shape: one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, a lane loops over its
+// row_of_ent of a chart: one lane per chart row, the lowest row index of every entity by a 32-bit atomicMin on a table preset to GI_LM_NONE, as
+// k_lm_raster decides a texel's owner -- the minimum does not depend on the order of the atomics.  Rows that name no entity of the scene, or a
+// sphere, serve nothing.  Lane 0 also leaves the call's LitLm for k_lit.
+__global__ __launch_bounds__(GI_BLOCK) void k_lm_rows(Scene S, int32_t n_chart, const int32_t* ent, int* row_of_ent, LitLm lm, LitLm* lm_out)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j == 0u) *lm_out = lm;
+    if (j >= (uint32_t)n_chart) return;
+    const int32_t e = ent[j];
+    if (e < 0 || e >= S.n_tri || (S.tris[e].flags & 4u)) return;
+    atomicMin(row_of_ent + e, (int)j);
+}
+
+// One kernel, k_lit<FEAT, WIDE, LM>, of k_ao's shape: one lane per pixel of this rank's rows in the 8x8-tile order of st_pixel_xy, a lane loops over its
 // samples; per sample the first hit, then one any-hit walk per light from the last light down until one is visible, then the look-ups.  It keeps its
 // twelve f64 sums in registers and stores once.  No queue, no sort, no atomics, nothing of the path pool, no reduction across lanes.
 // The three steps of a sample follow one another with little carried across: ray, hit record and entity record are dead when the light loop starts
@@ -60,7 +83,10 @@ struct LitArgs {
 // LDS as k_ao's: the records of the octree's top with the whole entities' content boxes, which the any-hit walks read; the closest-hit walk takes the
 // tables cut to the leaves through L2 where the two differ.  A light's segment ends at the light, but the boxes are the whole entities'
 // (Scene::leaf_boxes), valid for any segment: the answers are those of k_st_shadow's cut boxes.
-template <int FEAT, int WIDE>
+// LM (gi_render_baked_lightmap_*): a diffuse-lobe hit on an entity with a chart row reads the atlas at the hit's chart coordinate instead of the
+// grid; one without a row reads the grid if there is one.  The look-up stands where the grid's does, behind the walks: no LDS, no atomics and no
+// step across lanes are added, and the LM = 0 instances carry none of it.
+template <int FEAT, int WIDE, int LM>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64)
 {
     const typename LdsSrc<WIDE>::type NV = LdsSrc<WIDE>::stage_with_boxes(S);   // ends with a barrier
@@ -77,7 +103,7 @@ __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs 
     for (int32_t s = 0; s < n; s++, idx += F.he.inc) {
         LitHit a;
         Rng rng;
-        if (!lit_first_hit<FEAT>(S, NT, F, F.seed, idx, rng, a)) { sum[0] = sum[0] + ld3(S.ambient); continue; }   // a miss: the ambient term, no share of the three
+        if (!lit_first_hit<FEAT, LM>(S, NT, F, F.seed, idx, rng, a)) { sum[0] = sum[0] + ld3(S.ambient); continue; }   // a miss: the ambient term, no share of the three
         V3 direct = v3(0, 0, 0), diffuse = v3(0, 0, 0), specular = v3(0, 0, 0);
         if (A.terms & GI_BAKED_DIRECT) direct = a.color * lit_direct<FEAT | GI_FEAT_FOG>(S, NV, a.P, a.norm, a.roughness, rng);
         if (a.roughness < .9) {             // mirror (< .001: level 0) or glossy (the material's level): specular only
@@ -86,8 +112,18 @@ __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs 
                 const size_t t = (size_t)A.level_off[l] + cube_texel(reflect(a.d, a.nf), A.face >> l);
                 specular = a.color * ld3(A.chain + t * 3);
             }
-        } else if (A.terms & GI_BAKED_DIFFUSE)
-            diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
+        } else if (A.terms & GI_BAKED_DIFFUSE) {
+            if constexpr (LM != 0) {
+                const LitLm& L = *A.lm;
+                const int32_t row = L.row_of_ent[a.mat];      // the entity: lit_first_hit
+                if (row != GI_LM_NONE) {
+                    const LmCoord uv = lm_coord(S.tris[a.mat], a.P, L.uv + (size_t)row * 6);
+                    diffuse = a.color * (L.filter == GI_LM_NEAREST ? lm_nearest(L.atlas, L.w, L.h, uv) : lm_bilinear(L.atlas, L.w, L.h, uv));
+                } else if (A.sh)
+                    diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
+            } else
+                diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
+        }
         const V3 beauty = ((direct + diffuse) + specular) + ((A.terms & GI_BAKED_EMISSIVE) ? a.emissive : v3(0, 0, 0));
         sum[0] = sum[0] + beauty; sum[1] = sum[1] + direct; sum[2] = sum[2] + diffuse; sum[3] = sum[3] + specular;
     }
@@ -132,6 +168,50 @@ bool lit_check(const gi_baked_params* p, const void* sh, const void* chain, std:
     return true;
 }
 
+// The pass itself on checked arguments: LitArgs from the parameters, the level table, the one launch.  terms: bp->terms, or fewer bits.  lm: null, or
+// a LitArgs whose `lm` points at the call's LitLm, which selects the LM instances.
+int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* bp, int32_t terms, const double* d_sh, const double* d_chain, const LitArgs* lm, void* d_out, int out_is_f64)
+{
+    LitArgs A{};
+    if (lm) A = *lm;
+    A.terms = terms;
+    A.n3[0] = bp->nx; A.n3[1] = bp->ny; A.n3[2] = bp->nz;
+    for (int k = 0; k < 3; k++) { A.gmin[k] = bp->grid_min[k]; A.gmax[k] = bp->grid_max[k]; }
+    A.sh = d_sh; A.chain = d_chain;
+    // the level every material reads, made per call from the roughnesses kept at upload (baked_level_of: no transcendental on the device)
+    if (terms & GI_BAKED_SPECULAR) {
+        A.face = (uint32_t)bp->face;
+        for (int l = 0; l < bp->levels; l++) A.level_off[l] = (uint32_t)cm_texels_before(bp->face, l);
+        std::vector<int32_t> levels(c->scene.mat_roughness.size());
+        for (size_t m = 0; m < levels.size(); m++) levels[m] = baked_level_of(c->scene.mat_roughness[m], bp->levels, bp->log2_exponent);
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier pass on the stream may still read the table
+        if (c->lit.d_levels.n < levels.size()) HIP_TRY(c, c->lit.d_levels.alloc(levels.size()));
+        if (!levels.empty()) HIP_TRY(c, hipMemcpy(c->lit.d_levels.p, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        A.level_of_mat = c->lit.d_levels.p;
+    }
+    const auto launch = [&](const LitK& k, dim3 grid, dim3 block, uint32_t n_pix) {
+        hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
+    };
+    return lm ? pixel_pass(c, c->lit, name, F, bp->n_samples, kLitLm, GI_LIT_BLOCK, launch) : pixel_pass(c, c->lit, name, F, bp->n_samples, kLit, GI_LIT_BLOCK, launch);
+}
+
+// ---- gi_render_baked_lightmap_*
+// lit_check's message under this entry's name
+std::string lm_named(const std::string& err) { return err.compare(0, 13, "render_baked:") == 0 ? "render_baked_lightmap:" + err.substr(13) : err; }
+// false + message when the lightmap's parameters and pointers are not the header's (behind lit_check, which has seen bp)
+bool lit_lm_check(const gi_baked_params* bp, const gi_baked_lightmap_params* lp, const void* atlas, const void* ent, const void* uv, std::string& err)
+{
+    if (!lp) { err = "render_baked_lightmap: null lightmap parameters"; return false; }
+    if (lp->width < 1 || lp->width > 8192 || lp->height < 1 || lp->height > 8192) { err = "render_baked_lightmap: width and height must be 1 .. 8192, got " + std::to_string(lp->width) + " x " + std::to_string(lp->height); return false; }
+    if (lp->filter != GI_LM_NEAREST && lp->filter != GI_LM_BILINEAR) { err = "render_baked_lightmap: filter must be GI_LM_NEAREST or GI_LM_BILINEAR, got " + std::to_string(lp->filter); return false; }
+    if (lp->n_chart < 0) { err = "render_baked_lightmap: n_chart must not be negative, got " + std::to_string(lp->n_chart); return false; }
+    if (lp->n_chart > 0 && (bp->terms & GI_BAKED_DIFFUSE) && (!atlas || !ent || !uv)) { err = "render_baked_lightmap: the diffuse term of a chart needs the atlas, ent and uv"; return false; }
+    return true;
+}
+// a chart with rows and the diffuse term: the look-up takes part; else the pass is gi_render_baked_*'s, bit for bit
+bool lit_lm_active(const gi_baked_params* bp, const gi_baked_lightmap_params* lp) { return lp->n_chart > 0 && (bp->terms & GI_BAKED_DIFFUSE); }
+
 }  // namespace
 
 extern "C" {
@@ -154,26 +234,7 @@ int gi_render_baked_device(gi_ctx* c, const gi_render_params* p, const gi_baked_
     if (!lit_check(bp, d_sh, d_chain, err)) return fail(c, GI_E_INVALID, err);
     Frame F;
     if (const int rc = pixel_pass_frame(c, "render_baked", p, F)) return rc;
-    LitArgs A{};
-    A.terms = bp->terms;
-    A.n3[0] = bp->nx; A.n3[1] = bp->ny; A.n3[2] = bp->nz;
-    for (int k = 0; k < 3; k++) { A.gmin[k] = bp->grid_min[k]; A.gmax[k] = bp->grid_max[k]; }
-    A.sh = d_sh; A.chain = d_chain;
-    // the level every material reads, made per call from the roughnesses kept at upload (baked_level_of: no transcendental on the device)
-    if (bp->terms & GI_BAKED_SPECULAR) {
-        A.face = (uint32_t)bp->face;
-        for (int l = 0; l < bp->levels; l++) A.level_off[l] = (uint32_t)cm_texels_before(bp->face, l);
-        std::vector<int32_t> levels(c->scene.mat_roughness.size());
-        for (size_t m = 0; m < levels.size(); m++) levels[m] = baked_level_of(c->scene.mat_roughness[m], bp->levels, bp->log2_exponent);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier pass on the stream may still read the table
-        if (c->lit.d_levels.n < levels.size()) HIP_TRY(c, c->lit.d_levels.alloc(levels.size()));
-        if (!levels.empty()) HIP_TRY(c, hipMemcpy(c->lit.d_levels.p, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        A.level_of_mat = c->lit.d_levels.p;
-    }
-    return pixel_pass(c, c->lit, "render_baked", F, bp->n_samples, kLit, GI_LIT_BLOCK, [&](const LitK& k, dim3 grid, dim3 block, uint32_t n_pix) {
-        hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
-    });
+    return lit_run(c, "render_baked", F, bp, bp->terms, d_sh, d_chain, nullptr, d_out, out_is_f64);
 }
 
 int gi_render_baked_host(gi_ctx* c, const gi_render_params* p, const gi_baked_params* bp, const double* sh, const double* chain, void* h_out, int out_is_f64)
@@ -192,5 +253,78 @@ int gi_render_baked_host(gi_ctx* c, const gi_render_params* p, const gi_baked_pa
 }
 
 int gi_last_baked_ms(gi_ctx* c, float* ms) { return pass_ms(c, &gi_ctx::lit, ms); }
+
+void gi_baked_lightmap_default_params(gi_baked_lightmap_params* p)
+{
+    if (!p) return;
+    p->width = 256; p->height = 256; p->filter = GI_LM_BILINEAR; p->n_chart = 0;
+}
+
+int gi_render_baked_lightmap_device(gi_ctx* c, const gi_render_params* p, const gi_baked_params* bp, const gi_baked_lightmap_params* lp, const double* d_sh, const double* d_chain,
+                                    const double* d_atlas, const int32_t* d_ent, const double* d_uv, void* d_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    if (!p || !d_out) return fail(c, GI_E_INVALID, "render_baked_lightmap: null frame parameters or output pointer");
+    std::string err;
+    // sh may be null with the diffuse term: hits without a chart row then have no diffuse term (lit_check asks only whether sh is null)
+    if (!lit_check(bp, (bp && !d_sh) ? (const void*)bp : (const void*)d_sh, d_chain, err)) return fail(c, GI_E_INVALID, lm_named(err));
+    if (!lit_lm_check(bp, lp, d_atlas, d_ent, d_uv, err)) return fail(c, GI_E_INVALID, err);
+    Frame F;
+    if (const int rc = pixel_pass_frame(c, "render_baked_lightmap", p, F)) return rc;
+    if (!lit_lm_active(bp, lp))      // no row serves anything: the LM = 0 instances; without a grid the diffuse term is +0.0 everywhere, as with its bit clear
+        return lit_run(c, "render_baked_lightmap", F, bp, d_sh ? bp->terms : (bp->terms & ~GI_BAKED_DIFFUSE), d_sh, d_chain, nullptr, d_out, out_is_f64);
+    HIP_TRY(c, hipSetDevice(c->device));
+    LitPass& lit = c->lit;
+    if (lit.lds_refused < 0) { lit.lds_refused = 0; ask_for_lds(kLit, lit.lds_refused); }       // (pixel_pass would take the LM table's answer for this one)
+    if (lit.lm_lds_refused < 0) { lit.lm_lds_refused = 0; ask_for_lds(kLitLm, lit.lm_lds_refused); }
+    if (lit.lm_lds_refused) return fail(c, GI_E_HIP, "render_baked_lightmap: the device refused " + std::to_string(lit.lm_lds_refused) + " bytes of dynamic LDS per workgroup");
+    // row_of_ent, rebuilt per call on the stream, behind whatever pass still reads the last one
+    const size_t n_ent = (size_t)std::max(c->S.n_tri, 0);
+    if (lit.d_lm_rows.n < n_ent || !lit.d_lm_rows.p) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, lit.d_lm_rows.alloc(n_ent));
+    }
+    if (!lit.d_lm.p) HIP_TRY(c, lit.d_lm.alloc(1));
+    if (n_ent) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)lit.d_lm_rows.p, GI_LM_NONE, n_ent, c->stream));
+    LitLm desc{};
+    desc.w = lp->width; desc.h = lp->height; desc.filter = lp->filter;
+    desc.atlas = d_atlas; desc.uv = d_uv; desc.row_of_ent = lit.d_lm_rows.p;
+    hipLaunchKernelGGL(k_lm_rows, GI_GRID((size_t)lp->n_chart), 0, c->stream, c->S, lp->n_chart, d_ent, lit.d_lm_rows.p, desc, lit.d_lm.p);
+    HIP_TRY(c, hipGetLastError());
+    LitArgs lm{};
+    lm.lm = lit.d_lm.p;
+    return lit_run(c, "render_baked_lightmap", F, bp, bp->terms, d_sh, d_chain, &lm, d_out, out_is_f64);
+}
+
+int gi_render_baked_lightmap_host(gi_ctx* c, const gi_render_params* p, const gi_baked_params* bp, const gi_baked_lightmap_params* lp, const double* sh, const double* chain,
+                                  const void* atlas, int atlas_is_f64, const int32_t* ent, const double* uv, void* h_out, int out_is_f64)
+{
+    if (!c) return GI_E_INVALID;
+    if (!p || !h_out) return fail(c, GI_E_INVALID, "render_baked_lightmap: null frame parameters or output pointer");
+    std::string err;
+    if (!lit_check(bp, (bp && !sh) ? (const void*)bp : (const void*)sh, chain, err)) return fail(c, GI_E_INVALID, lm_named(err));
+    if (!lit_lm_check(bp, lp, atlas, ent, uv, err)) return fail(c, GI_E_INVALID, err);
+    if (!c->scene.have_scene) return fail(c, GI_E_STATE, "render_baked_lightmap: no scene uploaded");
+    const bool active = lit_lm_active(bp, lp);
+    if (active && !lm_chart_ok(c, lp->n_chart, ent, uv, err)) return fail(c, GI_E_INVALID, "render_baked_" + err);      // ("lightmap: chart row ...")
+    HIP_TRY(c, hipSetDevice(c->device));
+    DevBuf<double> d_sh, d_chain, d_atlas, d_uv;
+    DevBuf<int32_t> d_ent;
+    if ((bp->terms & GI_BAKED_DIFFUSE) && sh) HIP_TRY(c, d_sh.upload(sh, (size_t)bp->nx * (size_t)bp->ny * (size_t)bp->nz * 27));
+    if (bp->terms & GI_BAKED_SPECULAR) HIP_TRY(c, d_chain.upload(chain, cm_texels_before(bp->face, bp->levels) * 3));
+    if (active) {
+        const size_t n = (size_t)lp->width * (size_t)lp->height * 3;
+        if (atlas_is_f64) HIP_TRY(c, d_atlas.upload((const double*)atlas, n));
+        else {                                                // widened here, exactly: the device reads f64
+            std::vector<double> wide(n);
+            for (size_t i = 0; i < n; i++) wide[i] = (double)((const float*)atlas)[i];
+            HIP_TRY(c, d_atlas.upload(wide));
+        }
+        HIP_TRY(c, d_ent.upload(ent, (size_t)lp->n_chart)); HIP_TRY(c, d_uv.upload(uv, (size_t)lp->n_chart * 6));
+    }
+    return pixel_pass_to_host(c, c->lit, "render_baked_lightmap_host", p, 12, h_out, out_is_f64, nullptr, [&](void* d_out, int32_t*) {
+        return gi_render_baked_lightmap_device(c, p, bp, lp, d_sh.p, d_chain.p, d_atlas.p, d_ent.p, d_uv.p, d_out, out_is_f64);
+    });
+}
 
 }  // extern "C"

@@ -375,9 +375,15 @@ struct CubemapPass : AuxPass {
     EventTimer t_stage[2];            // capture, prefilter
     DevBuf<double> d_b0, d_box, d_part;
 };
-// the baked-light pass (gi_baked.inc): the level of the chain every material reads [n_mat], made per call, sized on first use and kept
+// the baked-light pass (gi_baked.inc): the level of the chain every material reads [n_mat], made per call, sized on first use and kept; with a
+// lightmap (gi_render_baked_lightmap_*) also the chart row that serves every entity [n_tri], the call's LitLm, and lm_lds_refused: lds_refused of
+// the LM instances
+struct LitLm;
 struct LitPass : AuxPass {
     DevBuf<int32_t> d_levels;
+    DevBuf<int> d_lm_rows;
+    DevBuf<LitLm> d_lm;
+    int lm_lds_refused = -1;
 };
 
 // ------------------------------------------------------------------------------------------------------------------------ the context

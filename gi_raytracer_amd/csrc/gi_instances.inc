@@ -20,7 +20,7 @@ __global__ __launch_bounds__(GI_AOV_BLOCK) void k_aov(Scene S, Frame F, uint32_t
 template <int FEAT, int WIDE>
 __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n_pix, int32_t n, int32_t n_dirs, double radius, void* out, int out_f64);
 struct LitArgs;
-template <int FEAT, int WIDE>
+template <int FEAT, int WIDE, int LM = 0>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64);
 
 static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
@@ -75,10 +75,13 @@ static constexpr AovK kAov[] = {
 static constexpr AoK kAo[] = {
     {k_ao<0, 0>, kLdsNodes}, {k_ao<0, 1>, kLdsWideBoxes}, {k_ao<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_ao<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
     {k_ao<7, 0>, kLdsNodes}, {k_ao<7, 1>, kLdsWideBoxes}};
-// k_lit<FEAT, WIDE> (the baked-light pass): the same rows and LDS
+// k_lit<FEAT, WIDE, LM> (the baked-light pass): the same rows and LDS; then the rows again with the lightmap look-up (gi_render_baked_lightmap_*)
 static constexpr LitK kLit[] = {
     {k_lit<0, 0>, kLdsNodes}, {k_lit<0, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
     {k_lit<7, 0>, kLdsNodes}, {k_lit<7, 1>, kLdsWideBoxes}};
+static constexpr LitK kLitLm[] = {
+    {k_lit<0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 1>, kLdsWideBoxes},
+    {k_lit<7, 0, 1>, kLdsNodes}, {k_lit<7, 1, 1>, kLdsWideBoxes}};
 // k_st_gather / k_st_gather_wave<COUNT>: no template argument of the scene's, no dynamic LDS
 static auto st_gather(bool counting) { return counting ? k_st_gather<true> : k_st_gather<false>; }
 static auto st_gather_wave(bool counting) { return counting ? k_st_gather_wave<true> : k_st_gather_wave<false>; }

@@ -1,10 +1,10 @@
-"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params."""
+"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, BakedParams, Lens, OcclusionParams, _f64,
-                   _floats, _p, lib)
+from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, BakedLightmapParams, BakedParams,
+                   Lens, OcclusionParams, _f64, _floats, _p, lib)
 
 
 def halton_sample_cap(w, h):
@@ -104,13 +104,14 @@ def _whole(name, v, what="occlusion"):
 BAKED_TERMS = BAKED_DIRECT | BAKED_DIFFUSE | BAKED_SPECULAR | BAKED_EMISSIVE
 
 
-def baked_params(n=None, sh=None, grid_box=None, chain=None, exponents=None, terms=None, width=None, height=None):
+def baked_params(n=None, sh=None, grid_box=None, chain=None, exponents=None, terms=None, width=None, height=None, lightmap=False):
     """(gi_baked_params, sh, chain) of RayTracer.run_baked: the library's defaults with n samples; sh [nz][ny][nx][9][3] the probe grid (bake_probes
     on probe_grid(grid_box, nx, ny, nz), reshaped) with its box grid_box = (min xyz, max xyz); chain a reflection probe's levels
     [6][face >> l][face >> l][3] (the list bake_reflection_probe returns, or one array for a single level) filtered with `exponents` (indexed by level,
     entry 0 ignored; default: the library's); terms a set of BAKED_* bits, default: DIRECT | EMISSIVE plus DIFFUSE with sh and SPECULAR with chain.
     The arrays come back contiguous float64, the chain concatenated [texels][3]; None where not given.  No device needed.  ValueError for what the
-    library would refuse and for shapes that do not fit."""
+    library would refuse and for shapes that do not fit.  lightmap: the block of run_baked_lightmap, whose atlas serves the diffuse term -- DIFFUSE
+    is a default term and needs no sh."""
     p = BakedParams()
     lib().gi_baked_default_params(C.byref(p))
     if n is not None:
@@ -151,13 +152,40 @@ def baked_params(n=None, sh=None, grid_box=None, chain=None, exponents=None, ter
     elif exponents is not None:
         raise ValueError("baked: exponents without chain")
     if terms is None:
-        terms = BAKED_DIRECT | BAKED_EMISSIVE | (BAKED_DIFFUSE if sh is not None else 0) | (BAKED_SPECULAR if chain is not None else 0)
+        terms = BAKED_DIRECT | BAKED_EMISSIVE | (BAKED_DIFFUSE if sh is not None or lightmap else 0) | (BAKED_SPECULAR if chain is not None else 0)
     p.terms = _whole("terms", terms, "baked")
     if p.terms == 0 or p.terms & ~BAKED_TERMS:
         raise ValueError(f"baked: terms must be a non-empty set of the BAKED_* bits, got {p.terms}")
-    if (p.terms & BAKED_DIFFUSE and sh is None) or (p.terms & BAKED_SPECULAR and chain is None):
+    if (p.terms & BAKED_DIFFUSE and sh is None and not lightmap) or (p.terms & BAKED_SPECULAR and chain is None):
         raise ValueError("baked: the diffuse term needs sh, the specular term needs chain")
     return p, sh, chain
+
+
+def baked_lightmap_params(atlas, ent, uv, filter="bilinear"):
+    """(gi_baked_lightmap_params, atlas, ent, uv) of RayTracer.run_baked_lightmap: atlas [height][width][3] as bake_lightmap returns it (float32
+    stays, anything else becomes float64), the chart ent [n] and uv [n][3][2] it was baked for, filter "bilinear" / "nearest" or LM_BILINEAR /
+    LM_NEAREST.  The arrays come back contiguous.  No device needed.  ValueError for what the library would refuse without looking at the scene
+    and for shapes that do not fit."""
+    p = BakedLightmapParams()
+    lib().gi_baked_lightmap_default_params(C.byref(p))
+    a = _floats(atlas)
+    if a.ndim != 3 or a.shape[2] != 3 or not (1 <= a.shape[0] <= 8192 and 1 <= a.shape[1] <= 8192):
+        raise ValueError(f"baked_lightmap: atlas [height][width][3] with height and width 1 .. 8192 expected, got {a.shape}")
+    if isinstance(filter, str):
+        if filter not in LM_FILTERS:
+            raise ValueError(f"baked_lightmap: filter must be one of {sorted(LM_FILTERS)}, got {filter!r}")
+        filter = LM_FILTERS[filter]
+    p.filter = _whole("filter", filter, "baked_lightmap")
+    if p.filter not in LM_FILTERS.values():
+        raise ValueError(f"baked_lightmap: filter must be LM_NEAREST or LM_BILINEAR, got {p.filter}")
+    try:
+        e, c = _chart(ent, uv)
+    except ValueError as err:
+        raise ValueError(f"baked_lightmap: {err}") from None
+    if not np.isfinite(c).all():
+        raise ValueError("baked_lightmap: the chart has a non-finite coordinate")
+    p.height, p.width, p.n_chart = a.shape[0], a.shape[1], len(e)
+    return p, a, e, c
 
 
 LENS_BLADES = range(3, 17)

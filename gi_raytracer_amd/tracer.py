@@ -6,7 +6,7 @@ import numpy as np
 from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
                    LightmapParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
-from .params import _bake_points, _chart, _fill_params, _filter_array, baked_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
+from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
 from .sessions import ProgressiveRender, parse_checkpoint_header
 
@@ -408,8 +408,31 @@ class RayTracer(DebugEntries):
         their term is off."""
         self._check(self.L.gi_render_baked_device(self.h, C.byref(p), C.byref(bp), sh_ptr or None, chain_ptr or None, *_dev(out_ptr, f64)), "render_baked_device")
 
+    def run_baked_lightmap(self, w, h, n, atlas, ent, uv, filter="bilinear", sh=None, grid_box=None, chain=None, exponents=None, terms=None, f64=True, **kw):
+        """The baked-light pass with a lightmap (gi_render_baked_lightmap_host; an addition, the reader of bake_lightmap's atlas): run_baked, except
+        that a first hit on a diffuse surface whose entity has a row in the chart -- ent [n_chart], uv [n_chart][3][2], the chart the atlas
+        [height][width][3] was baked for -- takes its irradiance from the atlas at the hit's chart coordinate, filtered "bilinear" or "nearest".  Diffuse
+        hits on entities without a row read the probe grid sh if it is given and have no diffuse term otherwise.  terms: BAKED_* bits, default
+        direct, diffuse and emissive, plus specular with a chain.  Returns the dict run_baked returns.  ValueError for bad values and shapes, before
+        the library is called; the definition is stated in include/gi_hip.h."""
+        bp, sh, chain = baked_params(n=n, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=w, height=h, lightmap=True)
+        lp, atlas, e, c = baked_lightmap_params(atlas, ent, uv, filter)
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out, o = _out((rows, w, 12), f64)
+        self._check(self.L.gi_render_baked_lightmap_host(self.h, C.byref(p), C.byref(bp), C.byref(lp), _p(sh), _p(chain), *_buf(atlas), _p(e, _ip), _p(c), *o),
+                    "render_baked_lightmap_host")
+        return {"baked": out, "beauty": out[:, :, 0:3], "direct": out[:, :, 3:6], "diffuse": out[:, :, 6:9], "specular": out[:, :, 9:12]}
+
+    def run_baked_lightmap_device(self, p, bp, lp, sh_ptr, chain_ptr, atlas_ptr, ent_ptr, uv_ptr, out_ptr, f64=False):
+        """The baked-light pass with a lightmap on device memory, asynchronous on the context's stream; p from params, bp from baked_params (with
+        lightmap=True), lp from baked_lightmap_params; sh_ptr, chain_ptr, atlas_ptr ([height][width][3] f64), ent_ptr ([n_chart] int32), uv_ptr
+        ([n_chart][3][2] f64) and out_ptr ([rows][w][12]) are raw device pointers, None where they are not needed.  The chart is not looked at."""
+        self._check(self.L.gi_render_baked_lightmap_device(self.h, C.byref(p), C.byref(bp), C.byref(lp), sh_ptr or None, chain_ptr or None, atlas_ptr or None,
+                                                           ent_ptr or None, uv_ptr or None, *_dev(out_ptr, f64)), "render_baked_lightmap_device")
+
     def last_baked_ms(self):
-        """gi_last_baked_ms: device time of the last baked-light pass (the frame's and the other passes' times keep theirs)."""
+        """gi_last_baked_ms: device time of the last baked-light pass, with a lightmap or without (the frame's and the other passes' times keep theirs)."""
         return self._last_ms("baked")
 
     def set_lens(self, radius=None, blades=None, rotation=None, lens=None):

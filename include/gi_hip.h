@@ -700,7 +700,8 @@ int gi_cubemap_prefilter(gi_ctx*, const gi_cubemap_params*, const double* cube_i
  * across lanes: the result does not depend on stripes, the octree walk in use or the launch.
  * out [local_rows][width][12] = beauty rgb, direct rgb, diffuse rgb, specular rgb, float (out_is_f64 = 0) or double (1), rounded once on store.
  * What the preview is not: a transparent surface is shaded as opaque; the camera segment is not marched through the medium (the first hit is the
- * surface's, as in the feature pass); probes are looked up without visibility, the cube without parallax; lightmaps (gi_lightmap_*) are not read.
+ * surface's, as in the feature pass); probes are looked up without visibility, the cube without parallax; a lightmap atlas (gi_lightmap_*) is read by gi_render_baked_lightmap_*
+ * below, not by these two entries.
  * GI_E_INVALID: null parameters or output; n_samples < 1 or taking the Halton index beyond 32 bits; terms 0 or with unknown bits; a grid dimension
  * < 1 or more than 2^31 probes; with GI_BAKED_DIFFUSE: a null sh, non-finite bounds or grid_max <= grid_min on an axis; with GI_BAKED_SPECULAR: a
  * null chain, face, levels and log2_exponent not as gi_cubemap_params allows.  GI_E_STATE: no scene.  A refused call touches no output and no
@@ -726,6 +727,57 @@ void gi_baked_default_params(gi_baked_params*);
 int gi_render_baked_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const double* d_sh, const double* d_chain, void* d_out, int out_is_f64);
 int gi_render_baked_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const double* sh, const double* chain, void* h_out, int out_is_f64);
 int gi_last_baked_ms(gi_ctx*, float* ms);
+
+/* The baked-light pass with a lightmap -- an ADDITION: the reader of the atlas gi_lightmap_* bakes.  The pass above, except that a first hit on a
+ * diffuse surface that has a chart row takes its irradiance from a lightmap atlas at the hit's chart coordinate instead of the probe grid: the
+ * per-texel detail an atlas is baked for -- contact shadows, colour bleeding -- shows in the preview.  Steps 1 to 3 and 5 to 7, the sums, the output
+ * layout, the Halton index, the stripes and the lens are gi_render_baked_*'s.  Everything in the look-up is f64, IEEE + - * / only, in the order
+ * written, compiled without contraction, so that it can be restated bit for bit (tests/baked_lightmap_expect.py).
+ * Inputs beside those of gi_render_baked_*: a chart of n_chart rows, ent [n_chart] and uv [n_chart][3][2] in the form gi_lightmap_* takes, and
+ * the atlas [height][width][3] baked for it (or any other image of that shape).  On the device the atlas is f64; the host entry takes float
+ * (atlas_is_f64 = 0) or double (1) and widens a float exactly.
+ *   Row of an entity.  row_of_ent[e] = the lowest chart row j with ent[j] == e, or none.  A row that names a sphere or no entity of the scene
+ *     serves nothing.
+ *   Which hits read the atlas.  A sample's first hit reads the atlas iff GI_BAKED_DIFFUSE is set, the material is on the diffuse lobe (step 3:
+ *     roughness >= .9) and the hit entity has a row.  A diffuse-lobe hit on an entity without a row reads the probe grid as in step 4 if sh is
+ *     given; if sh is null its diffuse term is +0.0.  The side the surface is seen from plays no part: a texel baked for the front is read from
+ *     the back too.
+ *   Chart coordinate.  A function of the entity and the hit position P alone (the P of step 1).  With the entity's vertex 0 and edges p0,
+ *     e1v = p1 - p0, e2v = p2 - p0 as the library lays them out, and every dot written (x x' + y y') + z z':
+ *       d = P - p0;  d00 = e1v.e1v, d01 = e1v.e2v, d11 = e2v.e2v, d20 = d.e1v, d21 = d.e2v;  den = d00 * d11 - d01 * d01;
+ *       b1 = (d11 * d20 - d01 * d21) / den;  b2 = (d00 * d21 - d01 * d20) / den;
+ *       u = ((1 - b1 - b2) * uv0.x + b1 * uv1.x) + b2 * uv2.x, and v the same from the .y components, uv0 uv1 uv2 the row's three coordinates.
+ *     This inverts the point a lightmap puts under a texel, P = (p0 + b1 * e1v) + b2 * e2v.  A degenerate triangle has den = 0 and gives NaN or
+ *     infinite coordinates, which the clamps below send to a border texel (a NaN to texel 0 of its axis).
+ *   GI_LM_BILINEAR.  Per axis with n texels, centres at (x + 0.5) / n as in a lightmap: g = ((a - 0.0) / (1.0 - 0.0)) * (double) n - 0.5 clamped to
+ *     [0, n - 1] (a NaN to 0), i0 = floor(g), i1 = min(i0 + 1, n - 1), t = g - i0 -- the cell of step 4 for the box 0 .. 1: coordinates beyond the
+ *     outermost centres read the border texels.  Then a + t * (b - a) along x on rows y0 and y1, then along y; then each channel < 0 becomes 0.
+ *   GI_LM_NEAREST.  Texel min(n - 1, max(0, (int) floor(a * (double) n))) per axis, a NaN going to 0; the texel's value as it is.
+ *   Diffuse = color * E, E the filtered value: the atlas is on the scale of a GI_BAKE_TEXEL result, as a lightmap's is.
+ * Texels no row of the chart covers are read as they are -- the filter knows nothing of owners: the caller dilates (gi_lightmap_params::dilate).
+ * With n_chart = 0, or without GI_BAKED_DIFFUSE, the result is gi_render_baked_*'s on the same arguments, bit for bit (with a null sh, that of
+ * the terms without GI_BAKED_DIFFUSE), and atlas, ent and uv may be null.
+ * GI_E_INVALID, with a message that names render_baked_lightmap: everything gi_render_baked_* refuses, except that sh may be null with
+ * GI_BAKED_DIFFUSE; null lightmap parameters; width or height outside 1 .. 8192; a filter other than the two; n_chart < 0; a null atlas, ent or uv
+ * with n_chart > 0 and GI_BAKED_DIFFUSE; and -- gi_render_baked_lightmap_host, which looks at the chart as gi_lightmap_host does -- an entity
+ * index out of range, an entity that is a sphere, a non-finite coordinate.  GI_E_STATE: no scene.  A refused call touches no output and no timer;
+ * an open progressive session is left as it is.
+ * gi_baked_lightmap_default_params: 256 x 256, GI_LM_BILINEAR, 0 rows.
+ * gi_render_baked_lightmap_device: DEVICE pointers (sh, chain, atlas f64, ent, uv, out); it does not look at its chart; asynchronous on the
+ * context's stream as gi_render_baked_device is.  The table row_of_ent [n_tri] is the context's, rebuilt by every call.
+ * gi_last_baked_ms is this pass's timer too.  There is one atlas per call and no gi_group_* form. */
+#define GI_LM_NEAREST 0
+#define GI_LM_BILINEAR 1
+typedef struct gi_baked_lightmap_params {
+    int32_t width, height;   /* of the atlas, 1 .. 8192 each */
+    int32_t filter;          /* GI_LM_NEAREST or GI_LM_BILINEAR */
+    int32_t n_chart;         /* >= 0 rows of the chart */
+} gi_baked_lightmap_params;
+void gi_baked_lightmap_default_params(gi_baked_lightmap_params*);
+int gi_render_baked_lightmap_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_lightmap_params*, const double* sh, const double* chain,
+                                  const void* atlas, int atlas_is_f64, const int32_t* ent, const double* uv, void* h_out, int out_is_f64);
+int gi_render_baked_lightmap_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_lightmap_params*, const double* d_sh, const double* d_chain,
+                                    const double* d_atlas, const int32_t* d_ent, const double* d_uv, void* d_out, int out_is_f64);
 
 #ifdef __cplusplus
 }
