@@ -171,12 +171,40 @@ def check_emission(rt, scene, n):
     return o, ph
 
 
-def check_render(rt, scene, w, h, spp, photons, adaptive=False, tol=RMSE_TOL, spp_mismatch=0.0):
-    o = oracle_for(scene)
-    if photons > 0 and scene.desc().n_light > 0:
-        ph, _ = rt.tracePhotons(photons)
-        o.set_photons(ph)
-    o.build_photon_map()
+class FrameOracle:
+    """oracle_for(scene) holding the photon map `rt` holds after tracePhotons(photons) (none for photons = 0), for tests that compare many
+    frames of one context with the oracle: check_render(..., oracle=this) emits and builds nothing, and render() keeps its answer per argument
+    list (read-only arrays), so that the schedules of one frame share one reference.  Everything else is the oracle's own."""
+
+    def __init__(self, rt, scene, photons):
+        self.o = oracle_for(scene)
+        if photons > 0 and scene.desc().n_light > 0:
+            ph, _ = rt.tracePhotons(photons)
+            self.o.set_photons(ph)
+        self.o.build_photon_map()
+        self._frames = {}
+
+    def render(self, *args):
+        if args not in self._frames:
+            ref = self.o.render(*args)
+            for a in ref.values():
+                a.setflags(write=False)
+            self._frames[args] = ref
+        return self._frames[args]
+
+    def __getattr__(self, name):
+        return getattr(self.o, name)
+
+
+def check_render(rt, scene, w, h, spp, photons, adaptive=False, tol=RMSE_TOL, spp_mismatch=0.0, oracle=None):
+    """oracle: a FrameOracle of rt and scene, which holds rt's photon map already; without one, an oracle is built and `photons` emitted here."""
+    o = oracle
+    if o is None:
+        o = oracle_for(scene)
+        if photons > 0 and scene.desc().n_light > 0:
+            ph, _ = rt.tracePhotons(photons)
+            o.set_photons(ph)
+        o.build_photon_map()
     if adaptive:
         img, nspp = rt.run(w, h, min_samples=spp, max_samples=4 * spp, noise_thresh=0.0015, want_spp=True)
         ref = o.render(w, h, spp, 4 * spp, 0.0015)
@@ -188,6 +216,19 @@ def check_render(rt, scene, w, h, spp, photons, adaptive=False, tol=RMSE_TOL, sp
     rmse = float(np.sqrt(((img - ref["lin"]) ** 2).mean()))
     assert rmse < tol, rmse
     return rmse, img, ref["lin"]
+
+
+def frame_primary_rays(o, w, h, n):
+    """The oracle's primary rays of samples 0 .. n-1 of every pixel of a w x h frame, sample after sample and row-major inside one:
+    (sxy [m][3] uint32 = sample, x, y; Halton index [m] uint32; rays [m][6] = origin, unit direction)."""
+    sxy = np.array([(s, x, y) for s in range(n) for y in range(h) for x in range(w)], np.uint32)
+    got = [o.primary_ray(w, h, int(s), int(x), int(y)) for s, x, y in sxy]
+    return sxy, np.array([i for i, _ in got], np.uint32), np.array([r for _, r in got])
+
+
+def padded_records(w, h):
+    """Records of the rounds schedule for a w x h frame: whole 8 x 8 tiles (gi_pixels.inc: tile_pixel_xy)."""
+    return ((w + 7) // 8) * ((h + 7) // 8) * 64
 
 
 def two_light_scene(with_glass=True):
@@ -638,16 +679,25 @@ def check_gather_exact_duplicates(rt_factory):
         np.testing.assert_allclose(got, ref, rtol=1e-9)
 
 
-def check_stripes(rt, scene, w, h, spp, world, stripe_h):
-    """Row-stripe sharding: rendering the stripes of every rank and interleaving them gives the single-GPU frame exactly."""
-    full = rt.run(w, h, min_samples=spp, max_samples=spp)
-    frame = np.zeros_like(full)
+def check_stripes(rt, scene, w, h, spp, world, stripe_h, adaptive=False):
+    """Row-stripe sharding: rendering the stripes of every rank and interleaving them gives the single-GPU frame exactly, and its per-pixel
+    sample counts.  adaptive: spp .. 4 spp samples under check_render's threshold.  A rank without rows returns empty arrays.  Returns the
+    assembled (frame, sample counts)."""
+    kw = dict(min_samples=spp, max_samples=4 * spp, noise_thresh=0.0015) if adaptive else dict(min_samples=spp, max_samples=spp)
+    full, full_spp = rt.run(w, h, want_spp=True, **kw)
+    frame, counts = np.full_like(full, np.nan), np.full_like(full_spp, -1)
+    seen = np.zeros(h, int)
     for rank in range(world):
-        part = rt.run(w, h, min_samples=spp, max_samples=spp, stripe_h=stripe_h, rank=rank, world=world)
+        part, part_spp = rt.run(w, h, want_spp=True, stripe_h=stripe_h, rank=rank, world=world, **kw)
         rows = stripe_rows(h, stripe_h, rank, world)
         assert len(rows) == len(part)
-        frame[rows] = part
+        assert part.shape == (len(rows), w, 3) and part_spp.shape == (len(rows), w)
+        frame[rows], counts[rows] = part, part_spp
+        seen[rows] += 1
+    assert (seen == 1).all()                          # every row from exactly one rank
     assert np.array_equal(frame, full)
+    assert np.array_equal(counts, full_spp)
+    return frame, counts
 
 
 from gi_raytracer_amd.sharding import stripe_rows  # noqa: E402  (re-exported for the tests)
