@@ -18,6 +18,7 @@ GI_OK, GI_E_NO_DEVICE, GI_E_INVALID, GI_E_HIP, GI_E_STATE, GI_E_CANCELLED = 0, -
 BAKE_TEXEL, BAKE_SH9 = 0, 1
 BAKE_MODES = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}
 CUBEMAP_MAX_LEVELS = 12
+PROBE_VISIBILITY_MAX_SIZE = 64
 BAKED_DIRECT, BAKED_DIFFUSE, BAKED_SPECULAR, BAKED_EMISSIVE = 1, 2, 4, 8
 LM_NEAREST, LM_BILINEAR = 0, 1
 LM_FILTERS = {"nearest": LM_NEAREST, "bilinear": LM_BILINEAR}
@@ -99,6 +100,16 @@ class BakedLightmapParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("filter", C.c_int32), ("n_chart", C.c_int32)]
 
 
+class ProbeVisibilityParams(C.Structure):
+    """gi_probe_visibility_params (include/gi_hip.h)."""
+    _fields_ = [("size", C.c_int32), ("n_samples", C.c_int32), ("stream_base", C.c_uint32), ("seed", C.c_uint64), ("max_dist", C.c_double)]
+
+
+class BakedVisibilityParams(C.Structure):
+    """gi_baked_visibility_params (include/gi_hip.h)."""
+    _fields_ = [("size", C.c_int32), ("normal_bias", C.c_double), ("vis_floor", C.c_double)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -109,7 +120,8 @@ class Settings(C.Structure):
 STRUCTS = {"gi_scene_desc": SceneDesc, "gi_photon_map_desc": PhotonMapDesc, "gi_render_params": RenderParams, "gi_denoise_params": DenoiseParams,
            "gi_upsample_params": UpsampleParams, "gi_occlusion_params": OcclusionParams, "gi_lens": Lens, "gi_bake_params": BakeParams,
            "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gi_baked_params": BakedParams,
-           "gi_baked_lightmap_params": BakedLightmapParams, "gih_settings": Settings}
+           "gi_baked_lightmap_params": BakedLightmapParams, "gi_probe_visibility_params": ProbeVisibilityParams,
+           "gi_baked_visibility_params": BakedVisibilityParams, "gih_settings": Settings}
 
 
 def _signatures():
@@ -119,6 +131,7 @@ def _signatures():
     scene, photons, rp = P(SceneDesc), P(PhotonMapDesc), P(RenderParams)
     dn, us, oc, lens, bake, lm = P(DenoiseParams), P(UpsampleParams), P(OcclusionParams), P(Lens), P(BakeParams), P(LightmapParams)
     cm, bk, bl = P(CubemapParams), P(BakedParams), P(BakedLightmapParams)
+    pv, bv = P(ProbeVisibilityParams), P(BakedVisibilityParams)
     return {
         # include/gi_hip.h: context, uploads, frames
         "gi_create": (i, [P(vp), i]), "gi_destroy": (None, [vp]), "gi_last_error": (s, [vp]), "gi_set_stream": (i, [vp, vp]),
@@ -173,6 +186,12 @@ def _signatures():
         "gi_render_baked_host": (i, [vp, rp, bk, _dp, _dp, vp, i]), "gi_last_baked_ms": ms,
         "gi_baked_lightmap_default_params": (None, [bl]), "gi_render_baked_lightmap_host": (i, [vp, rp, bk, bl, _dp, _dp, vp, i, _ip, _dp, vp, i]),
         "gi_render_baked_lightmap_device": (i, [vp, rp, bk, bl, vp, vp, vp, vp, vp, vp, i]),
+        # probe visibility: the capture, and the baked-light pass that reads the maps
+        "gi_probe_visibility_default_params": (None, [pv]), "gi_probe_visibility_device": (i, [vp, vp, i32, pv, vp, i]),
+        "gi_probe_visibility_host": (i, [vp, _dp, i32, pv, vp, i]), "gi_last_probe_visibility_ms": ms,
+        "gi_probe_visibility_rays": (i, [vp, _dp, i32, pv, _dp, _up]), "gi_probe_visibility_fold": (i, [vp, i32, i32, _dp, _dp]),
+        "gi_baked_visibility_default_params": (None, [bv]), "gi_render_baked_visibility_device": (i, [vp, rp, bk, bv, vp, vp, vp, vp, i]),
+        "gi_render_baked_visibility_host": (i, [vp, rp, bk, bv, _dp, _dp, vp, i, vp, i]),
         # csrc/gi_host.h: the host scene builder
         "gih_scene_create": (vp, []), "gih_scene_destroy": (None, [vp]), "gih_last_error": (s, [vp]), "gih_load_scn": (i, [vp, s]),
         "gih_load_obj": (i, [vp, s, _dp, _dp, i32]), "gih_add_material": (i, [vp, _dp]), "gih_add_texture": (i, [vp, i32, _dp, _bp, i64]),

@@ -5,6 +5,7 @@
 
 namespace gi {
 #include "gi_baked.h"
+#include "gi_visibility.h"      // probe visibility: the PV instances' step 4 (pv_irradiance), and what gi_visibility.inc captures the maps with
 
 // ------------------------------------------------------------------------------------------------ baked light at the first hit (an addition: the reference has no such pass)
 // The first hit of the sample with Halton index idx: aov_sample's (same ray, same RNG keys, same recomputation of the hit from the entity's record on
@@ -53,6 +54,9 @@ struct LitArgs {
     uint32_t face;
     uint32_t level_off[GI_CUBEMAP_MAX_LEVELS];      // texels before level l
     const struct LitLm* lm;                         // gi_render_baked_lightmap_*: read by the LM instances only
+    const double* vis;                              // gi_render_baked_visibility_*: the probes' maps [nz][ny][nx][M][M][2], read by the PV instances only
+    int32_t vis_size;                               //   M
+    double normal_bias, vis_floor;                  //   gi_baked_visibility_params
 };
 // the lightmap of a call, in device memory (written by k_lm_rows): one pointer among the kernel's arguments, read where the look-up happens
 struct LitLm {
@@ -86,7 +90,10 @@ __global__ __launch_bounds__(GI_BLOCK) void k_lm_rows(Scene S, int32_t n_chart, 
 // LM (gi_render_baked_lightmap_*): a diffuse-lobe hit on an entity with a chart row reads the atlas at the hit's chart coordinate instead of the
 // grid; one without a row reads the grid if there is one.  The look-up stands where the grid's does, behind the walks: no LDS, no atomics and no
 // step across lanes are added, and the LM = 0 instances carry none of it.
-template <int FEAT, int WIDE, int LM>
+// PV (gi_render_baked_visibility_*): the grid's look-up weights its eight probes by their octahedral depth maps (pv_irradiance, gi_visibility.h)
+// instead of interpolating them trilinearly; it stands where the grid's does, reads the maps through global memory as it reads the probes, and
+// adds no LDS, no atomics and no step across lanes.  The PV = 0 instances carry none of it; LM and PV are not combined.
+template <int FEAT, int WIDE, int LM, int PV>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64)
 {
     const typename LdsSrc<WIDE>::type NV = LdsSrc<WIDE>::stage_with_boxes(S);   // ends with a barrier
@@ -121,7 +128,9 @@ __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs 
                     diffuse = a.color * (L.filter == GI_LM_NEAREST ? lm_nearest(L.atlas, L.w, L.h, uv) : lm_bilinear(L.atlas, L.w, L.h, uv));
                 } else if (A.sh)
                     diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
-            } else
+            } else if constexpr (PV != 0)
+                diffuse = a.color * pv_irradiance(A.sh, A.vis, A.vis_size, A.n3, A.gmin, A.gmax, a.P, a.nf, A.normal_bias, A.vis_floor);
+            else
                 diffuse = a.color * grid_irradiance(A.sh, A.n3, A.gmin, A.gmax, a.P, a.nf);
         }
         const V3 beauty = ((direct + diffuse) + specular) + ((A.terms & GI_BAKED_EMISSIVE) ? a.emissive : v3(0, 0, 0));
@@ -169,7 +178,8 @@ bool lit_check(const gi_baked_params* p, const void* sh, const void* chain, std:
 }
 
 // The pass itself on checked arguments: LitArgs from the parameters, the level table, the one launch.  terms: bp->terms, or fewer bits.  lm: null, or
-// a LitArgs whose `lm` points at the call's LitLm, which selects the LM instances.
+// a LitArgs whose `lm` points at the call's LitLm, which selects the LM instances, or one whose `vis` points at the probes' maps (with vis_size,
+// normal_bias and vis_floor), which selects the PV instances.
 int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* bp, int32_t terms, const double* d_sh, const double* d_chain, const LitArgs* lm, void* d_out, int out_is_f64)
 {
     LitArgs A{};
@@ -193,12 +203,14 @@ int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* 
     const auto launch = [&](const LitK& k, dim3 grid, dim3 block, uint32_t n_pix) {
         hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
     };
-    return lm ? pixel_pass(c, c->lit, name, F, bp->n_samples, kLitLm, GI_LIT_BLOCK, launch) : pixel_pass(c, c->lit, name, F, bp->n_samples, kLit, GI_LIT_BLOCK, launch);
+    if (!lm) return pixel_pass(c, c->lit, name, F, bp->n_samples, kLit, GI_LIT_BLOCK, launch);
+    return lm->lm ? pixel_pass(c, c->lit, name, F, bp->n_samples, kLitLm, GI_LIT_BLOCK, launch) : pixel_pass(c, c->lit, name, F, bp->n_samples, kLitPv, GI_LIT_BLOCK, launch);
 }
 
 // ---- gi_render_baked_lightmap_*
 // lit_check's message under this entry's name
-std::string lm_named(const std::string& err) { return err.compare(0, 13, "render_baked:") == 0 ? "render_baked_lightmap:" + err.substr(13) : err; }
+std::string lit_named(const std::string& err, const char* entry) { return err.compare(0, 13, "render_baked:") == 0 ? std::string(entry) + ":" + err.substr(13) : err; }
+std::string lm_named(const std::string& err) { return lit_named(err, "render_baked_lightmap"); }
 // false + message when the lightmap's parameters and pointers are not the header's (behind lit_check, which has seen bp)
 bool lit_lm_check(const gi_baked_params* bp, const gi_baked_lightmap_params* lp, const void* atlas, const void* ent, const void* uv, std::string& err)
 {

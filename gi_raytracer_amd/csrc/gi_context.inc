@@ -6,7 +6,8 @@
 //   Tuning        every value taken from the environment when the context is made (from_env), and the two limits the setters change
 //   StageClock    per-stage device times of the last streaming frame (begin, end, read)
 //   StreamState   workspaces of the stream passes and the rounds (stream_alloc)
-//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, baked light, denoiser, upsampler, bake, lightmap, reflection probe
+//   AuxPass       timer and LDS answer of an auxiliary pass: features, occlusion, baked light, denoiser, upsampler, bake, lightmap, reflection probe,
+//                 probe visibility
 // Behind gi_ctx, what the entries of every .inc file share: fail, pass_ms (gi_last_*_ms) and Entry (a host-pointer call's device side).
 #include "gi_scratch.h"   // DevBuf, EventTimer, finish_to_host
 
@@ -384,6 +385,7 @@ struct LitPass : AuxPass {
     DevBuf<int> d_lm_rows;
     DevBuf<LitLm> d_lm;
     int lm_lds_refused = -1;
+    int pv_lds_refused = -1;          // lds_refused of the PV instances (gi_render_baked_visibility_*)
 };
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
@@ -428,6 +430,7 @@ struct gi_ctx {
     BakePass bake;                    // gi_bake_*
     LightmapPass lm;                  // gi_lightmap_*
     CubemapPass cm;                   // gi_cubemap_*
+    AuxPass pv;                       // gi_probe_visibility_*
 };
 
 namespace {

@@ -2,7 +2,8 @@
 // included by gi_kernels.hip behind gi_context.inc.  Every instance of a family is named once, in its table (FEAT = scene_feat / scene_trace_feat,
 // gi_scene.h); stream_grids (gi_stream.inc) and the per-pixel passes walk the same tables when they ask for the LDS.
 
-// The three per-pixel passes' kernels stand with their entries (gi_features.inc, gi_occlusion.inc, gi_baked.inc), behind this file.
+// The three per-pixel passes' kernels stand with their entries (gi_features.inc, gi_occlusion.inc, gi_baked.inc), behind this file; so does the
+// per-texel capture of the probes' visibility maps (gi_visibility.inc).
 #ifndef GI_AOV_BLOCK
 // One workgroup per CU next to the 160 KB of records and boxes, as k_st_trace -- but of 512 lanes: the lane keeps a pixel's eight sums and the
 // frame constants next to the walk, which at the 128 registers of a 1024-lane workgroup spills 408 B per lane (wide triangle instance); at 512
@@ -15,13 +16,20 @@
 #ifndef GI_LIT_BLOCK
 #define GI_LIT_BLOCK 512    // as GI_AO_BLOCK: the closest-hit walk, then any-hit walks, next to the same records; the look-ups behind them need fewer registers than either
 #endif
+#ifndef GI_PV_BLOCK
+#define GI_PV_BLOCK 512     // as GI_AOV_BLOCK: a closest-hit walk per sample next to the same records, two f64 sums per lane
+#endif
 template <int FEAT, int WIDE>
 __global__ __launch_bounds__(GI_AOV_BLOCK) void k_aov(Scene S, Frame F, uint32_t n_pix, int32_t n, void* out, int out_f64, int32_t* ids);
 template <int FEAT, int WIDE>
 __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n_pix, int32_t n, int32_t n_dirs, double radius, void* out, int out_f64);
 struct LitArgs;
-template <int FEAT, int WIDE, int LM = 0>
+template <int FEAT, int WIDE, int LM = 0, int PV = 0>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64);
+
+struct PvArgs;
+template <int FEAT, int WIDE>
+__global__ __launch_bounds__(GI_PV_BLOCK) void k_pv_capture(Scene S, PvArgs A, unsigned long long n_texels, void* out, int out_f64);
 
 static constexpr size_t kLdsNodes = (size_t)GI_LDS_NODES * sizeof(TNode);
 static constexpr size_t kLdsFinishCoop = (size_t)GI_FINISH_COOP_LDS_BYTES;   // the one-path-per-group forms of the finisher: 292 records + content boxes + a heap per group
@@ -35,6 +43,7 @@ using FinishK = StKernel<decltype(&k_st_finish<0, 0, 0>)>;
 using AovK = StKernel<decltype(&k_aov<0, 0>)>;
 using AoK = StKernel<decltype(&k_ao<0, 0>)>;
 using LitK = StKernel<decltype(&k_lit<0, 0>)>;
+using PvK = StKernel<decltype(&k_pv_capture<0, 0>)>;
 
 static int first_hit_row(int feat, bool wide) { return (feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0); }   // the first-hit families: FEAT 0, spheres, textures x per-node, wide
 static int feat_row(int feat) { return feat == 7 ? 3 : (feat == 3 ? 2 : feat); }                        // the others: the levels 0, spheres, fog, textures
@@ -82,6 +91,14 @@ static constexpr LitK kLit[] = {
 static constexpr LitK kLitLm[] = {
     {k_lit<0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 1>, kLdsWideBoxes},
     {k_lit<7, 0, 1>, kLdsNodes}, {k_lit<7, 1, 1>, kLdsWideBoxes}};
+// and once more with the probes' visibility maps in the grid's look-up (gi_render_baked_visibility_*)
+static constexpr LitK kLitPv[] = {
+    {k_lit<0, 0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 0, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 0, 1>, kLdsWideBoxes},
+    {k_lit<7, 0, 0, 1>, kLdsNodes}, {k_lit<7, 1, 0, 1>, kLdsWideBoxes}};
+// k_pv_capture<FEAT, WIDE> (a probe's visibility map, gi_probe_visibility_*): the first-hit rows, with k_aov's LDS -- its walks are closest-hit walks
+static constexpr PvK kPv[] = {
+    {k_pv_capture<0, 0>, kLdsNodes}, {k_pv_capture<0, 1>, kLdsWideBoxes}, {k_pv_capture<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_pv_capture<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
+    {k_pv_capture<7, 0>, kLdsNodes}, {k_pv_capture<7, 1>, kLdsWideBoxes}};
 // k_st_gather / k_st_gather_wave<COUNT>: no template argument of the scene's, no dynamic LDS
 static auto st_gather(bool counting) { return counting ? k_st_gather<true> : k_st_gather<false>; }
 static auto st_gather_wave(bool counting) { return counting ? k_st_gather_wave<true> : k_st_gather_wave<false>; }

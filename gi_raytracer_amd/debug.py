@@ -166,6 +166,26 @@ class DebugEntries:
         self._check(self.L.gi_cubemap_rays(self.h, _p(P), C.byref(p), _p(rays), _p(streams, _up)), "cubemap_rays")
         return rays, streams
 
+    def probe_visibility_rays(self, points, size=8, n_samples=16, stream_base=0, seed=None):
+        """gi_probe_visibility_rays: the rays bake_probe_visibility's capture makes -- (rays [n size^2 n_samples][6] = origin, unit direction,
+        streams [n size^2 n_samples]), sample k of texel t = (i * size + y) * size + x in row t * n_samples + k."""
+        pts = self._bake_points(points)
+        p = self.probe_visibility_params(size, n_samples, 1.0, stream_base, seed)
+        n = len(pts) * max(p.size, 0) ** 2 * max(p.n_samples, 0)
+        n = n if n < 2 ** 31 else 0                        # (the library refuses such a call: nothing is written)
+        rays = np.zeros((n, 6)); streams = np.zeros(n, np.uint32)
+        self._check(self.L.gi_probe_visibility_rays(self.h, _p(pts), len(pts), C.byref(p), _p(rays), _p(streams, _up)), "probe_visibility_rays")
+        return rays, streams
+
+    def probe_visibility_fold(self, dist):
+        """gi_probe_visibility_fold: the capture's fold on caller distances [n_texels][n_samples].  Returns [n_texels][2] = mean, mean square."""
+        d = _f64(dist)
+        if d.ndim != 2 or d.shape[1] < 1:
+            raise ValueError("probe_visibility_fold: distances [n_texels][n_samples] expected")
+        out = np.zeros((d.shape[0], 2))
+        self._check(self.L.gi_probe_visibility_fold(self.h, d.shape[0], d.shape[1], _p(d), _p(out)), "probe_visibility_fold")
+        return out
+
     def cubemap_prefilter(self, cube, levels, exponents=None):
         """gi_cubemap_prefilter: the box levels and the lobe filter of a reflection probe on the caller's cube [6][face][face][3].  Returns the list
         of levels bake_reflection_probe returns; level 0 is the input."""

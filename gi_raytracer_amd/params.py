@@ -1,10 +1,10 @@
-"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params."""
+"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params, gi_baked_visibility_params."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, BakedLightmapParams, BakedParams,
-                   Lens, OcclusionParams, _f64, _floats, _p, lib)
+from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, PROBE_VISIBILITY_MAX_SIZE, BakedLightmapParams,
+                   BakedParams, BakedVisibilityParams, Lens, OcclusionParams, _f64, _floats, _p, lib)
 
 
 def halton_sample_cap(w, h):
@@ -186,6 +186,32 @@ def baked_lightmap_params(atlas, ent, uv, filter="bilinear"):
         raise ValueError("baked_lightmap: the chart has a non-finite coordinate")
     p.height, p.width, p.n_chart = a.shape[0], a.shape[1], len(e)
     return p, a, e, c
+
+
+def baked_visibility_params(vis, grid=None, normal_bias=None, vis_floor=None):
+    """(gi_baked_visibility_params, vis) of RayTracer.run_baked_visibility: vis [nz][ny][nx][M][M][2] the probes' maps (bake_probe_visibility on
+    the grid's points, reshaped; float32 stays, anything else becomes float64), or None for no maps; grid = (nz, ny, nx) of the probe grid the maps
+    must fit; normal_bias and vis_floor default to the library's 0.0 and 0.05.  The array comes back contiguous.  No device needed.  ValueError for
+    what the library would refuse and for shapes that do not fit."""
+    p = BakedVisibilityParams()
+    lib().gi_baked_visibility_default_params(C.byref(p))
+    if normal_bias is not None:
+        p.normal_bias = float(normal_bias)
+    if vis_floor is not None:
+        p.vis_floor = float(vis_floor)
+    if not (0.0 <= p.normal_bias < float("inf")):
+        raise ValueError(f"baked_visibility: normal_bias must be finite and >= 0, got {p.normal_bias}")
+    if not (0.0 < p.vis_floor <= 1.0):
+        raise ValueError(f"baked_visibility: vis_floor must be in (0, 1], got {p.vis_floor}")
+    if vis is None:
+        return p, None
+    v = _floats(vis)
+    if v.ndim != 6 or v.shape[5] != 2 or v.shape[3] != v.shape[4] or not 1 <= v.shape[3] <= PROBE_VISIBILITY_MAX_SIZE or min(v.shape[:3]) < 1:
+        raise ValueError(f"baked_visibility: vis [nz][ny][nx][M][M][2] with M 1 .. {PROBE_VISIBILITY_MAX_SIZE} expected, got {v.shape}")
+    if grid is not None and tuple(v.shape[:3]) != tuple(int(g) for g in grid):
+        raise ValueError(f"baked_visibility: the maps are those of a {v.shape[2]} x {v.shape[1]} x {v.shape[0]} grid, the probes' is {grid[2]} x {grid[1]} x {grid[0]}")
+    p.size = v.shape[3]
+    return p, v
 
 
 LENS_BLADES = range(3, 17)

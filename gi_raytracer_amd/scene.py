@@ -200,6 +200,36 @@ def cube_texel_of(directions, face):
     return (f * n + row) * n + col
 
 
+def _octa_fold(px, py):
+    sx, sy = np.where(px >= 0.0, 1.0, -1.0), np.where(py >= 0.0, 1.0, -1.0)
+    return (1.0 - np.abs(py)) * sx, (1.0 - np.abs(px)) * sy
+
+
+def octa_decode(a, b):
+    """The unnormalised direction [...][3] of the point (a, b) in [0, 1]^2 of a probe's octahedral visibility map (RayTracer.bake_probe_visibility;
+    include/gi_hip.h: gi_probe_visibility_*): the upper half sphere is the square's inner diamond, the lower half its corners folded outward.  The
+    arithmetic is the header's, bit for bit.  Texel (x, y) of a map of M x M has its centre at ((x + 0.5) / M, (y + 0.5) / M)."""
+    a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+    px, py = 2.0 * a - 1.0, 2.0 * b - 1.0
+    vz = (1.0 - np.abs(px)) - np.abs(py)
+    fx, fy = _octa_fold(px, py)
+    low = vz < 0.0
+    return np.stack([np.where(low, fx, px), np.where(low, fy, py), vz], -1)
+
+
+def octa_encode(v):
+    """(a, b) of the vectors v [...][3] (any length but 0) in the octahedral map: the inverse of octa_decode up to the length, the header's
+    arithmetic bit for bit.  How the look-up of run_baked_visibility finds the texels of a direction."""
+    v = np.asarray(v, np.float64)
+    s = (np.abs(v[..., 0]) + np.abs(v[..., 1])) + np.abs(v[..., 2])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px, py = v[..., 0] / s, v[..., 1] / s
+    fx, fy = _octa_fold(px, py)
+    low = v[..., 2] < 0.0
+    px, py = np.where(low, fx, px), np.where(low, fy, py)
+    return (px + 1.0) * 0.5, (py + 1.0) * 0.5
+
+
 def chart_of_material(scene, material=None):
     """(ent [n], uv [n][3][2]): the default chart of a lightmap (RayTracer.bake_lightmap) for a scene whose texture coordinates are already an
     unwrapped atlas -- the scene's own texture coordinates of all triangle entities of that material index, in entity order; None: of all

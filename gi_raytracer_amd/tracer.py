@@ -4,9 +4,9 @@ import ctypes as C
 import numpy as np
 
 from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
-                   LightmapParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
+                   LightmapParams, ProbeVisibilityParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
-from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
+from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, baked_visibility_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
 from .sessions import ProgressiveRender, parse_checkpoint_header
 
@@ -430,6 +430,68 @@ class RayTracer(DebugEntries):
         ([n_chart][3][2] f64) and out_ptr ([rows][w][12]) are raw device pointers, None where they are not needed.  The chart is not looked at."""
         self._check(self.L.gi_render_baked_lightmap_device(self.h, C.byref(p), C.byref(bp), C.byref(lp), sh_ptr or None, chain_ptr or None, atlas_ptr or None,
                                                            ent_ptr or None, uv_ptr or None, *_dev(out_ptr, f64)), "render_baked_lightmap_device")
+
+    def probe_visibility_params(self, size=8, samples=16, max_dist=None, stream_base=0, seed=None):
+        """gi_probe_visibility_params: texels per map edge, rays per texel, the distance a miss counts as (None: the diagonal of the scene's root
+        box, or the library's 1e30 without a scene), the stream index of sample 0 of texel 0 of point 0, the seed (default: the tracer's)."""
+        p = ProbeVisibilityParams()
+        self.L.gi_probe_visibility_default_params(C.byref(p))
+        p.size, p.n_samples, p.stream_base = int(size), int(samples), int(stream_base)
+        p.seed = self._seed(seed)
+        if max_dist is not None:
+            p.max_dist = float(max_dist)
+        elif self.scene is not None:
+            b = self.scene.tables()["node_bbox"][0]
+            p.max_dist = float(np.sqrt(((b[3] - b[0]) ** 2 + (b[4] - b[1]) ** 2) + (b[5] - b[2]) ** 2))
+        return p
+
+    def bake_probe_visibility(self, points, size=8, n_samples=16, max_dist=None, stream_base=0, seed=None, f64=True):
+        """Probe visibility maps (gi_probe_visibility_host; an addition beside bake_probes): per point [n][3] an octahedral map of size x size
+        texels holding the mean and the mean squared distance to the nearest surface over n_samples jittered rays per texel, distances cut at
+        max_dist (None: the scene's diagonal), which is also what a miss counts as.  Returns [n][size][size][2]; octa_decode gives a texel's
+        direction.  run_baked_visibility reads the maps of a probe grid (reshaped [nz][ny][nx][size][size][2]) so that probes behind a wall do
+        not light a hit.  Sample k of texel t = (i * size + y) * size + x runs on stream stream_base + t * n_samples + k; the definition is
+        stated in include/gi_hip.h."""
+        pts = self._bake_points(points)
+        p = self.probe_visibility_params(size, n_samples, max_dist, stream_base, seed)
+        m = max(p.size, 0)
+        out, o = _out((len(pts), m, m, 2), f64)
+        self._check(self.L.gi_probe_visibility_host(self.h, _p(pts), len(pts), C.byref(p), *o), "probe_visibility_host")
+        return out
+
+    def probe_visibility_device(self, p, points_ptr, n_points, out_ptr, f64=False):
+        """Probe visibility maps on device memory (raw device pointers: points [n][3] f64, out [n][size][size][2]); p from probe_visibility_params.
+        The points are not looked at."""
+        self._check(self.L.gi_probe_visibility_device(self.h, points_ptr, int(n_points), C.byref(p), *_dev(out_ptr, f64)), "probe_visibility_device")
+
+    def last_probe_visibility_ms(self):
+        """gi_last_probe_visibility_ms: device time of the last capture of visibility maps (the frame's and the other passes' times keep theirs)."""
+        return self._last_ms("probe_visibility")
+
+    def run_baked_visibility(self, w, h, n, vis, sh=None, grid_box=None, chain=None, exponents=None, terms=None, normal_bias=None, vis_floor=None, f64=True, **kw):
+        """The baked-light pass with probe visibility (gi_render_baked_visibility_host; an addition, the reader of bake_probe_visibility's maps):
+        run_baked, except that the eight probes around a diffuse hit are not interpolated trilinearly but weighted by the trilinear weight, a
+        back-face term and a Chebyshev test of the hit (moved normal_bias along its normal) against each probe's map, never below vis_floor -- a
+        probe on the far side of a wall counts for little.  vis [nz][ny][nx][M][M][2] for the grid of sh; None gives run_baked's result bit for
+        bit.  Returns the dict run_baked returns.  ValueError for bad values and shapes, before the library is called; the definition is stated in
+        include/gi_hip.h."""
+        bp, sh, chain = baked_params(n=n, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=w, height=h)
+        vp, vis = baked_visibility_params(vis, None if sh is None else sh.shape[:3], normal_bias, vis_floor)
+        if vis is not None and sh is None:
+            raise ValueError("baked_visibility: the maps belong to a probe grid, sh")
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out, o = _out((rows, w, 12), f64)
+        v = _buf(vis) if vis is not None else (None, 1)
+        self._check(self.L.gi_render_baked_visibility_host(self.h, C.byref(p), C.byref(bp), C.byref(vp), _p(sh), _p(chain), *v, *o), "render_baked_visibility_host")
+        return {"baked": out, "beauty": out[:, :, 0:3], "direct": out[:, :, 3:6], "diffuse": out[:, :, 6:9], "specular": out[:, :, 9:12]}
+
+    def run_baked_visibility_device(self, p, bp, vp, sh_ptr, chain_ptr, vis_ptr, out_ptr, f64=False):
+        """The baked-light pass with probe visibility on device memory, asynchronous on the context's stream; p from params, bp from baked_params,
+        vp from baked_visibility_params; sh_ptr, chain_ptr, vis_ptr ([nz][ny][nx][M][M][2] f64) and out_ptr ([rows][w][12]) are raw device
+        pointers, None where they are not needed."""
+        self._check(self.L.gi_render_baked_visibility_device(self.h, C.byref(p), C.byref(bp), C.byref(vp), sh_ptr or None, chain_ptr or None, vis_ptr or None,
+                                                             *_dev(out_ptr, f64)), "render_baked_visibility_device")
 
     def last_baked_ms(self):
         """gi_last_baked_ms: device time of the last baked-light pass, with a lightmap or without (the frame's and the other passes' times keep theirs)."""

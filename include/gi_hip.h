@@ -700,7 +700,7 @@ int gi_cubemap_prefilter(gi_ctx*, const gi_cubemap_params*, const double* cube_i
  * across lanes: the result does not depend on stripes, the octree walk in use or the launch.
  * out [local_rows][width][12] = beauty rgb, direct rgb, diffuse rgb, specular rgb, float (out_is_f64 = 0) or double (1), rounded once on store.
  * What the preview is not: a transparent surface is shaded as opaque; the camera segment is not marched through the medium (the first hit is the
- * surface's, as in the feature pass); probes are looked up without visibility, the cube without parallax; a lightmap atlas (gi_lightmap_*) is read by gi_render_baked_lightmap_*
+ * surface's, as in the feature pass); probes are looked up without visibility (gi_render_baked_visibility_* below looks them up with it), the cube without parallax; a lightmap atlas (gi_lightmap_*) is read by gi_render_baked_lightmap_*
  * below, not by these two entries.
  * GI_E_INVALID: null parameters or output; n_samples < 1 or taking the Halton index beyond 32 bits; terms 0 or with unknown bits; a grid dimension
  * < 1 or more than 2^31 probes; with GI_BAKED_DIFFUSE: a null sh, non-finite bounds or grid_max <= grid_min on an axis; with GI_BAKED_SPECULAR: a
@@ -778,6 +778,91 @@ int gi_render_baked_lightmap_host(gi_ctx*, const gi_render_params*, const gi_bak
                                   const void* atlas, int atlas_is_f64, const int32_t* ent, const double* uv, void* h_out, int out_is_f64);
 int gi_render_baked_lightmap_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_lightmap_params*, const double* d_sh, const double* d_chain,
                                     const double* d_atlas, const int32_t* d_ent, const double* d_uv, void* d_out, int out_is_f64);
+
+/* Probe visibility, capture -- an ADDITION beside the bakes: what keeps a probe grid from leaking light through walls.  Beside its SH9 coefficients a
+ * probe gets a small octahedral map of the mean and the mean squared distance to the nearest surface per direction, as the probe volumes of dynamic
+ * diffuse GI keep; gi_render_baked_visibility_* below weights the probes around a hit by a Chebyshev test against these maps.  All arithmetic named
+ * here is f64, IEEE + - * / and sqrt only, in the order written, compiled without contraction, so that it can be restated bit for bit
+ * (tests/visibility_expect.py).
+ * Octahedral map.  A map has M x M texels; texel (x, y) of probe i has index t = (i * M + y) * M + x.  sgn(q) = q >= 0 ? 1.0 : -1.0.
+ *   Decode of (a, b) in [0, 1]^2:  px = 2.0 * a - 1.0;  py = 2.0 * b - 1.0;  vz = (1.0 - |px|) - |py|;  if vz < 0:
+ *     (vx, vy) = ((1.0 - |py|) * sgn(px), (1.0 - |px|) * sgn(py)), otherwise (vx, vy) = (px, py).  The direction is (vx, vy, vz), not normalised.
+ *   Encode of a vector v that is not 0 0 0:  s = (|vx| + |vy|) + |vz|;  px = vx / s;  py = vy / s;  the same fold when vz < 0;
+ *     a = (px + 1.0) * 0.5;  b = (py + 1.0) * 0.5.
+ * Rays.  Sample k of texel t runs on stream = stream_base + t * n_samples + k: ju = (double) halton(0, stream), jv = (double) halton(1, stream),
+ *   a = ((double) x + ju) / (double) M, b the same from y and jv; the ray is Ray(P_i, decode(a, b)): the direction is normalised there, and the ray
+ *   leaves the probe's position itself, with no bias, as a reflection probe's.
+ * Distance.  The closest hit is RayTracer::trace of that ray, as the frame's primary ray gets it, alpha draws keyed by (seed, stream) at depth 0;
+ *   on a scene whose alpha tests cannot depend on the draw this is gi_trace's answer.  On a hit at H, r = sqrt(((Hx-Px)^2 + (Hy-Py)^2) + (Hz-Pz)^2);
+ *   on a miss r = max_dist; then r = r < max_dist ? r : max_dist.  The lens and the render mode play no part; no analytic light is hit.
+ * Fold.  Per texel, in ascending k from +0.0:  m = sum(r_k) / (double) n_samples,  m2 = sum(r_k * r_k) / (double) n_samples.
+ * out [n_points][M][M][2] = (m, m2), float (out_is_f64 = 0) or double (1), rounded once on store.  One lane owns a texel and nothing is reduced across
+ * lanes: the result does not depend on the launch, the octree walk in use or gi_set_pool_slots, and a point list split over calls gives the same
+ * maps when call a, starting at point a, passes stream_base + a * M * M * n_samples.
+ * GI_E_INVALID, before any pointer is used: null parameters, size outside 1 .. 64, n_samples < 1, n_points < 0, a max_dist that is not finite or not
+ * positive, stream_base + n_points * M * M * n_samples beyond 2^32, null points or output with n_points > 0, and -- gi_probe_visibility_host and
+ * gi_probe_visibility_rays -- a position that is not finite.  GI_E_STATE: no scene.  n_points = 0 is GI_OK and writes nothing.  A refused call
+ * touches no output and no timer; an open progressive session is left as it is.
+ * gi_probe_visibility_default_params: size 8, 16 samples, stream_base 0, seed 0x9E3779B97F4A7C15, max_dist 1e30 (callers pass the scene's diagonal).
+ * gi_probe_visibility_device: DEVICE pointers (points [n][3] f64, out), asynchronous on the context's stream; the points are not looked at.
+ * gi_probe_visibility_host: HOST pointers.  gi_last_probe_visibility_ms: device time of the last capture (HIP events around the kernel); the
+ * frame's and the other passes' times are left alone.
+ * Check entries (host pointers): gi_probe_visibility_rays gives the capture's rays as gi_cubemap_rays does, rays6_out [n M M n_samples][6] and
+ *   stream_out [n M M n_samples], sample k of texel t in row t * n_samples + k; no scene is needed.  gi_probe_visibility_fold runs the fold on
+ *   caller distances dist [n_texels][n_samples] and writes out2 [n_texels][2], double; no scene is needed and no timer is touched.
+ * There is no gi_group_* form: split the point list. */
+typedef struct gi_probe_visibility_params {
+    int32_t size;            /* M, 1 .. 64: the map is M x M texels */
+    int32_t n_samples;       /* >= 1 rays per texel */
+    uint32_t stream_base;    /* stream index of sample 0 of texel 0 of point 0 */
+    uint64_t seed;           /* counter-RNG seed, as gi_bake_params::seed */
+    double max_dist;         /* finite, > 0: a miss, and any hit farther away, counts as this distance */
+} gi_probe_visibility_params;
+void gi_probe_visibility_default_params(gi_probe_visibility_params*);
+int gi_probe_visibility_device(gi_ctx*, const double* d_points, int32_t n_points, const gi_probe_visibility_params*, void* d_out, int out_is_f64);
+int gi_probe_visibility_host(gi_ctx*, const double* points, int32_t n_points, const gi_probe_visibility_params*, void* h_out, int out_is_f64);
+int gi_last_probe_visibility_ms(gi_ctx*, float* ms);
+int gi_probe_visibility_rays(gi_ctx*, const double* points, int32_t n_points, const gi_probe_visibility_params*, double* rays6_out, uint32_t* stream_out);
+int gi_probe_visibility_fold(gi_ctx*, int32_t n_texels, int32_t n_samples, const double* dist, double* out2);
+
+/* The baked-light pass with probe visibility -- an ADDITION: gi_render_baked_* with the probes looked up WITH visibility, so that a probe behind a
+ * wall does not light the hit.  Steps 1 to 3 and 5 to 7, the sums, the output layout, the Halton index, the stripes, the lens and the timer
+ * (gi_last_baked_ms) are gi_render_baked_*'s.  Input beside theirs: vis [nz][ny][nx][M][M][2] f64, the maps gi_probe_visibility_* gives for the
+ * grid's probes in the grid's order (M = size); the host entry takes float (vis_is_f64 = 0) or double (1) and widens a float exactly.  Everything
+ * below is f64, IEEE + - * / and sqrt only, in the order written (tests/visibility_expect.py).
+ *   4. Diffuse = color * D.  The cell per axis (i0, i1, t), F_j and D_c at a probe are step 4's of gi_render_baked_*.  For the eight corners
+ *      c = cx + 2 cy + 4 cz in ascending c, with c_a the corner's bit of axis a:
+ *      probe      j_a = c_a ? i1_a : i0_a;  q = (jz * ny + jy) * nx + jx.
+ *      trilinear  w_a = c_a ? t_a : 1.0 - t_a;  tw = (wx * wy) * wz;  tw = tw > 0.001 ? tw : 0.001.
+ *      position   Q_a = gmin_a + (((double) j_a + 0.5) / (double) n_a) * (gmax_a - gmin_a).
+ *      back face  e = Q - P;  le = sqrt((ex ex + ey ey) + ez ez);  cb = le > 0 ? ((ex Nfx + ey Nfy) + ez Nfz) / le : 1.0;  h = (cb + 1.0) * 0.5;
+ *                 wb = h * h + 0.2.
+ *      visibility v = (P + Nf * normal_bias) - Q per component;  r = sqrt((vx vx + vy vy) + vz vz).  If r == 0, vis = 1.0.  Otherwise (a, b) =
+ *                 encode(v), and (m, m2) = the bilinear value of map q at (a, b): per axis the cell of step 4 for the box 0 .. 1 with n = M (texel
+ *                 centres at (x + 0.5) / M, clamped at the map's border, a NaN going to texel 0), then a + t * (b - a) along x on both rows, then
+ *                 along y -- GI_LM_BILINEAR's rule without its clamp at 0, and with no wrap across the octahedral map's edges.  A texel value that
+ *                 is NaN or not finite is the caller's: it passes through.  If r > m: var = |m * m - m2|;  dd = r - m;  ch = var / (var + dd * dd);
+ *                 ch = (ch * ch) * ch;  vis = ch > vis_floor ? ch : vis_floor.  Otherwise vis = 1.0.
+ *      weight     w = (tw * wb) * vis;  num[ch] += w * D_c[ch];  den += w, both from +0.0.
+ *      Then D = num / den per channel, and each channel < 0 becomes 0.  den > 0: every factor has a positive floor.
+ * With a null vis, or without GI_BAKED_DIFFUSE, the result is gi_render_baked_*'s on the same arguments, bit for bit, through the same kernel
+ * instances.  gi_render_baked_lightmap_* takes no maps: combining a lightmap and probe visibility in one call is out of scope.
+ * GI_E_INVALID, with a message that names render_baked_visibility: everything gi_render_baked_* refuses (a null sh with GI_BAKED_DIFFUSE among it,
+ * with a map or without); null visibility parameters; size outside 1 .. 64; a normal_bias that is not finite or negative; a vis_floor outside
+ * (0, 1].  GI_E_STATE: no scene.  A refused call touches no output and no timer; an open progressive session is left as it is.
+ * gi_baked_visibility_default_params: size 8, normal_bias 0.0, vis_floor 0.05.
+ * gi_render_baked_visibility_device: DEVICE pointers (sh, chain, vis f64, out), asynchronous on the context's stream as gi_render_baked_device is.
+ * gi_render_baked_visibility_host: HOST pointers.  There is no gi_group_* form. */
+typedef struct gi_baked_visibility_params {
+    int32_t size;            /* M of the maps, 1 .. 64 */
+    double normal_bias;      /* finite, >= 0: the hit is moved this far along Nf before it is tested against the maps */
+    double vis_floor;        /* 0 < vis_floor <= 1: the least visibility weight of a probe */
+} gi_baked_visibility_params;
+void gi_baked_visibility_default_params(gi_baked_visibility_params*);
+int gi_render_baked_visibility_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_visibility_params*, const double* d_sh, const double* d_chain,
+                                      const double* d_vis, void* d_out, int out_is_f64);
+int gi_render_baked_visibility_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_visibility_params*, const double* sh, const double* chain,
+                                    const void* vis, int vis_is_f64, void* h_out, int out_is_f64);
 
 #ifdef __cplusplus
 }
