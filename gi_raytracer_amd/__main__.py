@@ -8,7 +8,8 @@
                                [--occlusion PREFIX [--occlusion-samples N] [--occlusion-dirs K] [--occlusion-radius R]]
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
                                [--baked PREFIX [--baked-samples N] [--baked-probes NX NY NZ] [--baked-reflection X Y Z]
-                                [--baked-lightmap W H [--lightmap-samples N]] [--probe-visibility M]]
+                                [--baked-lightmap W H [--lightmap-samples N]] [--probe-visibility M]
+                                [--baked-reflections NX NY NZ [--baked-reflection-fade F]]]
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
     python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
                                -o OUT.ppm [--pfm OUT.pfm]
@@ -63,6 +64,11 @@ more line names the atlas size and the texels covered.
 map (M = 1 .. 64, 16 rays per texel, distances up to the scene box's diagonal) at every probe of the --baked-probes grid -- the grid probe_grid
 gives -- and the preview looks the probes up through them: a probe behind a wall no longer lights the hit.  It needs that grid, so it is refused
 without --baked, and it does not go with --baked-lightmap (the lightmap entry takes no maps).
+--baked-reflections NX NY NZ (with --baked; include/gi_hip.h: gi_render_baked_reflections_*) bakes a SET of reflection probes instead of the one:
+the scene's box is cut into NX x NY x NZ cells (at most 64), a chain is baked at every cell's centre, every cell grown by --baked-reflection-fade F
+(default: a tenth of the cell's shortest edge) is its probe's influence box, and the preview's mirror and glossy surfaces read each cube at the
+direction projected onto that box, blending where boxes overlap: reflections line up with the walls they show.  One more line names the set.
+--baked-reflection X Y Z has no part in it; it does not go with --baked-lightmap or --probe-visibility (one look-up per call).
 """
 import argparse
 import os
@@ -79,6 +85,7 @@ REFLECTION_FACE, REFLECTION_SAMPLES = 32, 64
 BAKED_SAMPLES, BAKED_PROBES, BAKED_LEVELS = 4, (4, 4, 4), 6
 BAKED_FILES = ("direct", "diffuse", "specular")
 VISIBILITY_SAMPLES, VISIBILITY_MAX_SIZE = 16, gi.PROBE_VISIBILITY_MAX_SIZE
+REFLECTIONS_MAX_PROBES, REFLECTIONS_FADE = gi.REFLECTIONS_MAX_PROBES, 0.1      # the default fade: this share of a cell's shortest edge
 
 
 def parser():
@@ -127,6 +134,8 @@ def parser():
     ap.add_argument("--baked-probes", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="with --baked: the light-probe grid in the scene's box (default 4 4 4)")
     ap.add_argument("--baked-lightmap", type=int, nargs=2, default=None, metavar=("W", "H"), help="with --baked: bake a W x H lightmap over the scene's texture coordinates and shade charted diffuse surfaces from it")
     ap.add_argument("--probe-visibility", type=int, default=None, metavar="M", help="with --baked: bake an M x M visibility map per probe of the grid and look the probes up through them (no light leaks through walls)")
+    ap.add_argument("--baked-reflections", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="with --baked: bake one reflection probe per cell of the scene's box cut NX x NY x NZ and shade mirror and glossy surfaces from the set, box-projected and blended")
+    ap.add_argument("--baked-reflection-fade", type=float, default=None, metavar="F", help="with --baked-reflections: how far every cell's influence box reaches beyond the cell, the band probes blend over (default: a tenth of the cell's shortest edge)")
     ap.add_argument("--baked-reflection", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --baked: position of the reflection probe (default: the middle of the scene's box)")
     return ap
 
@@ -146,6 +155,10 @@ def check_args(ap, a):
         a.output = "out.ppm"
     if a.baked is None and (a.baked_samples is not None or a.baked_probes is not None or a.baked_reflection is not None or a.baked_lightmap is not None):
         ap.error("--baked-samples, --baked-probes, --baked-reflection and --baked-lightmap need --baked PREFIX")
+    if a.baked is None and (a.baked_reflections is not None or a.baked_reflection_fade is not None):
+        ap.error("--baked-reflections NX NY NZ and --baked-reflection-fade F need --baked PREFIX")
+    if a.baked_reflections is None and a.baked_reflection_fade is not None:
+        ap.error("--baked-reflection-fade F needs --baked-reflections NX NY NZ")
     if a.baked is None and a.probe_visibility is not None:
         ap.error("--probe-visibility M needs the probe grid of --baked PREFIX [--baked-probes NX NY NZ]")
     if a.baked is not None:
@@ -173,6 +186,16 @@ def check_args(ap, a):
             m = a.probe_visibility
             if not 1 <= m <= VISIBILITY_MAX_SIZE or grid[0] * grid[1] * grid[2] * m * m * VISIBILITY_SAMPLES > 2 ** 32:
                 ap.error(f"--probe-visibility M: from 1 to {VISIBILITY_MAX_SIZE}; probes x M x M x {VISIBILITY_SAMPLES} samples must keep the stream index within 32 bits")
+        if a.baked_reflections is not None:
+            if a.baked_lightmap is not None or a.probe_visibility is not None:
+                ap.error("--baked-reflections does not go together with --baked-lightmap or --probe-visibility: one look-up per call")
+            if a.baked_reflection is not None:
+                ap.error("--baked-reflections places its probes itself: not together with --baked-reflection X Y Z")
+            cells = a.baked_reflections
+            if min(cells) < 1 or cells[0] * cells[1] * cells[2] > REFLECTIONS_MAX_PROBES:
+                ap.error(f"--baked-reflections NX NY NZ: three numbers >= 1 with at most {REFLECTIONS_MAX_PROBES} cells")
+            if a.baked_reflection_fade is not None and not 0.0 <= a.baked_reflection_fade < float("inf"):
+                ap.error("--baked-reflection-fade F: a finite number >= 0")
         if os.path.abspath(a.baked + ".ppm") == os.path.abspath(a.output):
             if explicit_output:
                 ap.error(f"--baked {a.baked} writes {a.baked}.ppm, which is -o: name one of them differently")
@@ -354,10 +377,24 @@ def render_baked(a, rt, scene):
     nx, ny, nz = a.baked_probes or BAKED_PROBES
     points = gi.probe_grid(box, nx, ny, nz).reshape(-1, 3)
     sh = rt.bake_probes(points, PROBE_SAMPLES).reshape(nz, ny, nx, 9, 3)
-    pos = a.baked_reflection if a.baked_reflection is not None else [0.5 * (box[k] + box[3 + k]) for k in range(3)]
-    chain = rt.bake_reflection_probe(pos, REFLECTION_FACE, REFLECTION_SAMPLES, BAKED_LEVELS)
     ns = BAKED_SAMPLES if a.baked_samples is None else a.baked_samples
     note = ""
+    if a.baked_reflections is not None:
+        cx, cy, cz = a.baked_reflections
+        fade = a.baked_reflection_fade
+        if fade is None:
+            fade = REFLECTIONS_FADE * min((box[3 + k] - box[k]) / c for k, c in enumerate((cx, cy, cz)))
+        table = gi.reflection_probe_cells(box, cx, cy, cz, fade)
+        chains = rt.bake_reflection_probes(table[:, 0:3], REFLECTION_FACE, REFLECTION_SAMPLES, BAKED_LEVELS)
+        print(f"{a.scene}: reflection probes {cx}x{cy}x{cz}, {len(table)} chains of face {REFLECTION_FACE} with {BAKED_LEVELS} levels, fade {fade:.4g}")
+        lit = rt.run_baked_reflections(a.width, a.height, ns, table, chains, sh=sh, grid_box=box, f64=False, face=REFLECTION_FACE, levels=BAKED_LEVELS)
+        gi.save_ppm(f"{a.baked}.ppm", lit["beauty"])
+        for name in BAKED_FILES:
+            gi.save_pfm(f"{a.baked}_{name}.pfm", lit[name])
+        return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, reflection probes {cx}x{cy}x{cz}, {ns} spp preview {rt.last_baked_ms():.2f} ms "
+                f"-> {a.baked}.ppm, {a.baked}_*.pfm")
+    pos = a.baked_reflection if a.baked_reflection is not None else [0.5 * (box[k] + box[3 + k]) for k in range(3)]
+    chain = rt.bake_reflection_probe(pos, REFLECTION_FACE, REFLECTION_SAMPLES, BAKED_LEVELS)
     if a.baked_lightmap is not None:
         w, h = a.baked_lightmap
         ent, uv = gi.chart_of_material(scene)

@@ -19,6 +19,7 @@ BAKE_TEXEL, BAKE_SH9 = 0, 1
 BAKE_MODES = {"texel": BAKE_TEXEL, "sh9": BAKE_SH9}
 CUBEMAP_MAX_LEVELS = 12
 PROBE_VISIBILITY_MAX_SIZE = 64
+REFLECTIONS_MAX_PROBES = 64
 BAKED_DIRECT, BAKED_DIFFUSE, BAKED_SPECULAR, BAKED_EMISSIVE = 1, 2, 4, 8
 LM_NEAREST, LM_BILINEAR = 0, 1
 LM_FILTERS = {"nearest": LM_NEAREST, "bilinear": LM_BILINEAR}
@@ -110,6 +111,11 @@ class BakedVisibilityParams(C.Structure):
     _fields_ = [("size", C.c_int32), ("normal_bias", C.c_double), ("vis_floor", C.c_double)]
 
 
+class BakedReflectionsParams(C.Structure):
+    """gi_baked_reflections_params (include/gi_hip.h)."""
+    _fields_ = [("n_probes", C.c_int32)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -121,7 +127,7 @@ STRUCTS = {"gi_scene_desc": SceneDesc, "gi_photon_map_desc": PhotonMapDesc, "gi_
            "gi_upsample_params": UpsampleParams, "gi_occlusion_params": OcclusionParams, "gi_lens": Lens, "gi_bake_params": BakeParams,
            "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gi_baked_params": BakedParams,
            "gi_baked_lightmap_params": BakedLightmapParams, "gi_probe_visibility_params": ProbeVisibilityParams,
-           "gi_baked_visibility_params": BakedVisibilityParams, "gih_settings": Settings}
+           "gi_baked_visibility_params": BakedVisibilityParams, "gi_baked_reflections_params": BakedReflectionsParams, "gih_settings": Settings}
 
 
 def _signatures():
@@ -131,7 +137,7 @@ def _signatures():
     scene, photons, rp = P(SceneDesc), P(PhotonMapDesc), P(RenderParams)
     dn, us, oc, lens, bake, lm = P(DenoiseParams), P(UpsampleParams), P(OcclusionParams), P(Lens), P(BakeParams), P(LightmapParams)
     cm, bk, bl = P(CubemapParams), P(BakedParams), P(BakedLightmapParams)
-    pv, bv = P(ProbeVisibilityParams), P(BakedVisibilityParams)
+    pv, bv, br = P(ProbeVisibilityParams), P(BakedVisibilityParams), P(BakedReflectionsParams)
     return {
         # include/gi_hip.h: context, uploads, frames
         "gi_create": (i, [P(vp), i]), "gi_destroy": (None, [vp]), "gi_last_error": (s, [vp]), "gi_set_stream": (i, [vp, vp]),
@@ -192,6 +198,9 @@ def _signatures():
         "gi_probe_visibility_rays": (i, [vp, _dp, i32, pv, _dp, _up]), "gi_probe_visibility_fold": (i, [vp, i32, i32, _dp, _dp]),
         "gi_baked_visibility_default_params": (None, [bv]), "gi_render_baked_visibility_device": (i, [vp, rp, bk, bv, vp, vp, vp, vp, i]),
         "gi_render_baked_visibility_host": (i, [vp, rp, bk, bv, _dp, _dp, vp, i, vp, i]),
+        # reflection probe sets: the baked-light pass with box-projected, blended cube look-ups
+        "gi_baked_reflections_default_params": (None, [br]), "gi_render_baked_reflections_device": (i, [vp, rp, bk, br, vp, vp, vp, vp, vp, i]),
+        "gi_render_baked_reflections_host": (i, [vp, rp, bk, br, _dp, _dp, _dp, _dp, vp, i]),
         # csrc/gi_host.h: the host scene builder
         "gih_scene_create": (vp, []), "gih_scene_destroy": (None, [vp]), "gih_last_error": (s, [vp]), "gih_load_scn": (i, [vp, s]),
         "gih_load_obj": (i, [vp, s, _dp, _dp, i32]), "gih_add_material": (i, [vp, _dp]), "gih_add_texture": (i, [vp, i32, _dp, _bp, i64]),

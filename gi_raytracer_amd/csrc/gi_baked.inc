@@ -6,6 +6,7 @@
 namespace gi {
 #include "gi_baked.h"
 #include "gi_visibility.h"      // probe visibility: the PV instances' step 4 (pv_irradiance), and what gi_visibility.inc captures the maps with
+#include "gi_reflections.h"     // reflection probe sets: the RS instances' step 5 (rs_specular); the entries are gi_reflections.inc's
 
 // ------------------------------------------------------------------------------------------------ baked light at the first hit (an addition: the reference has no such pass)
 // The first hit of the sample with Halton index idx: aov_sample's (same ray, same RNG keys, same recomputation of the hit from the entity's record on
@@ -57,6 +58,10 @@ struct LitArgs {
     const double* vis;                              // gi_render_baked_visibility_*: the probes' maps [nz][ny][nx][M][M][2], read by the PV instances only
     int32_t vis_size;                               //   M
     double normal_bias, vis_floor;                  //   gi_baked_visibility_params
+    const double* rs_probes;                        // gi_render_baked_reflections_*: the set's table [K][10], read by the RS instances only
+    const double* rs_chains;                        //   its chains [K][rs_texels][3]
+    int32_t rs_n;                                   //   K
+    uint32_t rs_texels;                             //   texels of one chain
 };
 // the lightmap of a call, in device memory (written by k_lm_rows): one pointer among the kernel's arguments, read where the look-up happens
 struct LitLm {
@@ -93,7 +98,12 @@ __global__ __launch_bounds__(GI_BLOCK) void k_lm_rows(Scene S, int32_t n_chart, 
 // PV (gi_render_baked_visibility_*): the grid's look-up weights its eight probes by their octahedral depth maps (pv_irradiance, gi_visibility.h)
 // instead of interpolating them trilinearly; it stands where the grid's does, reads the maps through global memory as it reads the probes, and
 // adds no LDS, no atomics and no step across lanes.  The PV = 0 instances carry none of it; LM and PV are not combined.
-template <int FEAT, int WIDE, int LM, int PV>
+// RS (gi_render_baked_reflections_*): the specular term blends the probes of a set whose boxes contain the hit, each cube read at the direction
+// from the probe to where the reflection ray leaves its box (rs_specular, gi_reflections.h), instead of reading one chain at R.  It stands where
+// step 5 stands, behind the walks.  The loop over the probes has the same trip count and the same table addresses in every lane, so the table's
+// rows come through the scalar cache; a chain's texel is a lane's own read through global memory, as the one chain's is.  No LDS, no atomics and
+// no step across lanes are added, and the RS = 0 instances carry none of it; RS goes with LM = PV = 0 only.
+template <int FEAT, int WIDE, int LM, int PV, int RS>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64)
 {
     const typename LdsSrc<WIDE>::type NV = LdsSrc<WIDE>::stage_with_boxes(S);   // ends with a barrier
@@ -116,8 +126,12 @@ __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs 
         if (a.roughness < .9) {             // mirror (< .001: level 0) or glossy (the material's level): specular only
             if (A.terms & GI_BAKED_SPECULAR) {
                 const uint32_t l = a.roughness < .001 ? 0u : (uint32_t)A.level_of_mat[a.mat];
-                const size_t t = (size_t)A.level_off[l] + cube_texel(reflect(a.d, a.nf), A.face >> l);
-                specular = a.color * ld3(A.chain + t * 3);
+                if constexpr (RS != 0)
+                    specular = a.color * rs_specular(A.rs_probes, A.rs_chains, A.rs_n, A.rs_texels, A.level_off[l], A.face >> l, a.P, reflect(a.d, a.nf));
+                else {
+                    const size_t t = (size_t)A.level_off[l] + cube_texel(reflect(a.d, a.nf), A.face >> l);
+                    specular = a.color * ld3(A.chain + t * 3);
+                }
             }
         } else if (A.terms & GI_BAKED_DIFFUSE) {
             if constexpr (LM != 0) {
@@ -179,7 +193,8 @@ bool lit_check(const gi_baked_params* p, const void* sh, const void* chain, std:
 
 // The pass itself on checked arguments: LitArgs from the parameters, the level table, the one launch.  terms: bp->terms, or fewer bits.  lm: null, or
 // a LitArgs whose `lm` points at the call's LitLm, which selects the LM instances, or one whose `vis` points at the probes' maps (with vis_size,
-// normal_bias and vis_floor), which selects the PV instances.
+// normal_bias and vis_floor), which selects the PV instances, or one whose `rs_probes` points at a probe set's table (with rs_chains, rs_n and
+// rs_texels), which selects the RS instances.
 int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* bp, int32_t terms, const double* d_sh, const double* d_chain, const LitArgs* lm, void* d_out, int out_is_f64)
 {
     LitArgs A{};
@@ -204,7 +219,8 @@ int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* 
         hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
     };
     if (!lm) return pixel_pass(c, c->lit, name, F, bp->n_samples, kLit, GI_LIT_BLOCK, launch);
-    return lm->lm ? pixel_pass(c, c->lit, name, F, bp->n_samples, kLitLm, GI_LIT_BLOCK, launch) : pixel_pass(c, c->lit, name, F, bp->n_samples, kLitPv, GI_LIT_BLOCK, launch);
+    if (lm->lm) return pixel_pass(c, c->lit, name, F, bp->n_samples, kLitLm, GI_LIT_BLOCK, launch);
+    return lm->rs_probes ? pixel_pass(c, c->lit, name, F, bp->n_samples, kLitRs, GI_LIT_BLOCK, launch) : pixel_pass(c, c->lit, name, F, bp->n_samples, kLitPv, GI_LIT_BLOCK, launch);
 }
 
 // ---- gi_render_baked_lightmap_*

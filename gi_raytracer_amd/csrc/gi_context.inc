@@ -386,6 +386,7 @@ struct LitPass : AuxPass {
     DevBuf<LitLm> d_lm;
     int lm_lds_refused = -1;
     int pv_lds_refused = -1;          // lds_refused of the PV instances (gi_render_baked_visibility_*)
+    int rs_lds_refused = -1;          // lds_refused of the RS instances (gi_render_baked_reflections_*)
 };
 
 // ------------------------------------------------------------------------------------------------------------------------ the context

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(GI_AOV_BLOCK) void k_aov(Scene S, Frame F, uint32_t
 template <int FEAT, int WIDE>
 __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n_pix, int32_t n, int32_t n_dirs, double radius, void* out, int out_f64);
 struct LitArgs;
-template <int FEAT, int WIDE, int LM = 0, int PV = 0>
+template <int FEAT, int WIDE, int LM = 0, int PV = 0, int RS = 0>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64);
 
 struct PvArgs;
@@ -95,6 +95,10 @@ static constexpr LitK kLitLm[] = {
 static constexpr LitK kLitPv[] = {
     {k_lit<0, 0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 0, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 0, 1>, kLdsWideBoxes},
     {k_lit<7, 0, 0, 1>, kLdsNodes}, {k_lit<7, 1, 0, 1>, kLdsWideBoxes}};
+// and with a reflection probe set in the specular term (gi_render_baked_reflections_*)
+static constexpr LitK kLitRs[] = {
+    {k_lit<0, 0, 0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 0, 0, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 0, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 0, 0, 1>, kLdsWideBoxes},
+    {k_lit<7, 0, 0, 0, 1>, kLdsNodes}, {k_lit<7, 1, 0, 0, 1>, kLdsWideBoxes}};
 // k_pv_capture<FEAT, WIDE> (a probe's visibility map, gi_probe_visibility_*): the first-hit rows, with k_aov's LDS -- its walks are closest-hit walks
 static constexpr PvK kPv[] = {
     {k_pv_capture<0, 0>, kLdsNodes}, {k_pv_capture<0, 1>, kLdsWideBoxes}, {k_pv_capture<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_pv_capture<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},

@@ -50,4 +50,5 @@ using namespace gi;
 #include "gi_cubemap.inc"        // reflection probes: the capture's source for k_bake_gen, k_cm_box, k_cm_filter, k_cm_resolve and gi_cubemap_*
 #include "gi_baked.inc"          // the baked-light pass: k_lit and gi_render_baked_*, the consumer of probes and cube chains
 #include "gi_visibility.inc"     // probe visibility: k_pv_capture and gi_probe_visibility_*; gi_render_baked_visibility_*, the PV instances of k_lit
+#include "gi_reflections.inc"    // reflection probe sets: gi_render_baked_reflections_*, the RS instances of k_lit
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

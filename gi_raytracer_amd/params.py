@@ -1,10 +1,10 @@
-"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params, gi_baked_visibility_params."""
+"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params, gi_baked_visibility_params, gi_baked_reflections_params."""
 import ctypes as C
 
 import numpy as np
 
-from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, PROBE_VISIBILITY_MAX_SIZE, BakedLightmapParams,
-                   BakedParams, BakedVisibilityParams, Lens, OcclusionParams, _f64, _floats, _p, lib)
+from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, PROBE_VISIBILITY_MAX_SIZE, REFLECTIONS_MAX_PROBES, BakedLightmapParams,
+                   BakedParams, BakedReflectionsParams, BakedVisibilityParams, Lens, OcclusionParams, _f64, _floats, _p, lib)
 
 
 def halton_sample_cap(w, h):
@@ -212,6 +212,55 @@ def baked_visibility_params(vis, grid=None, normal_bias=None, vis_floor=None):
         raise ValueError(f"baked_visibility: the maps are those of a {v.shape[2]} x {v.shape[1]} x {v.shape[0]} grid, the probes' is {grid[2]} x {grid[1]} x {grid[0]}")
     p.size = v.shape[3]
     return p, v
+
+
+def baked_reflections_params(probes, chains):
+    """(gi_baked_reflections_params, probes, chains, face, levels) of RayTracer.run_baked_reflections: probes [K][10] the set's table, one row per
+    probe = pos xyz, box_min xyz, box_max xyz, fade (reflection_probe_cells makes one); chains the K chains of the probes, each the list of levels
+    [6][face >> l][face >> l][3] bake_reflection_probe returns (bake_reflection_probes returns them concatenated, [K][texels][3], which is taken
+    as it is), all of one face and one number of levels.  probes None or of no rows: no set -- (params with 0 probes, None, None, None, None).
+    The arrays come back contiguous float64, the chains as [K][texels][3]; a set given as [K][texels][3] has face and levels None, the caller's
+    to state.  No device needed.  ValueError for what the library would refuse and for shapes that do not fit each other."""
+    p = BakedReflectionsParams()
+    lib().gi_baked_reflections_default_params(C.byref(p))
+    if probes is None or len(probes) == 0:
+        if chains is not None and len(chains):
+            raise ValueError("baked_reflections: chains without probes")
+        return p, None, None, None, None
+    t = _f64(probes)
+    if t.ndim != 2 or t.shape[1] != 10 or not 1 <= t.shape[0] <= REFLECTIONS_MAX_PROBES:
+        raise ValueError(f"baked_reflections: probes [K][10] with K 1 .. {REFLECTIONS_MAX_PROBES} expected, got {t.shape}")
+    if not np.isfinite(t).all():
+        raise ValueError("baked_reflections: a probe has a non-finite position, box or fade")
+    if not (t[:, 6:9] > t[:, 3:6]).all():
+        raise ValueError("baked_reflections: every probe needs box_max > box_min on every axis")
+    if (t[:, 9] < 0).any():
+        raise ValueError("baked_reflections: fade must not be negative")
+    if chains is None or len(chains) != len(t):
+        raise ValueError(f"baked_reflections: {len(t)} probes need {len(t)} chains, got {0 if chains is None else len(chains)}")
+    face = levels = None
+    if isinstance(chains, np.ndarray) and chains.ndim == 3:
+        c = _f64(chains)
+        if c.shape[2] != 3 or c.shape[1] < 6:
+            raise ValueError(f"baked_reflections: chains [K][texels][3] expected, got {c.shape}")
+    else:
+        flat = []
+        for k, chain in enumerate(chains):
+            lv = [_f64(chain)] if isinstance(chain, np.ndarray) else [_f64(q) for q in chain]
+            f = lv[0].shape[1] if lv and lv[0].ndim == 4 else 0
+            if not 1 <= len(lv) <= CUBEMAP_MAX_LEVELS or f < 1 or f % (1 << (len(lv) - 1)):
+                raise ValueError(f"baked_reflections: chain {k} must be 1 .. {CUBEMAP_MAX_LEVELS} levels whose first face is divisible by 2^(levels - 1)")
+            if face is None:
+                face, levels = f, len(lv)
+            if (f, len(lv)) != (face, levels):
+                raise ValueError(f"baked_reflections: chain {k} has face {f} and {len(lv)} levels, chain 0 has face {face} and {levels}")
+            for l, q in enumerate(lv):
+                if q.shape != (6, face >> l, face >> l, 3):
+                    raise ValueError(f"baked_reflections: level {l} of chain {k} of face {face} is [6][{face >> l}][{face >> l}][3], got {q.shape}")
+            flat.append(np.concatenate([q.reshape(-1, 3) for q in lv]))
+        c = np.ascontiguousarray(np.stack(flat))
+    p.n_probes = len(t)
+    return p, t, c, face, levels
 
 
 LENS_BLADES = range(3, 17)

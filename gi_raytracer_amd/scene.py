@@ -167,6 +167,31 @@ def probe_grid(box6, nx, ny, nz):
     return np.ascontiguousarray(np.stack([x, y, z], -1))
 
 
+def reflection_probe_cells(box6, nx, ny, nz, fade):
+    """The table [K][10] of a reflection probe set (RayTracer.run_baked_reflections; include/gi_hip.h: gi_render_baked_reflections_*) that cuts the
+    box (min xyz, max xyz) into nx x ny x nz cells, x fastest: one probe per cell at the cell's centre (probe_grid's positions), its influence box
+    the cell grown by `fade` on every side, so that neighbours overlap by 2 * fade and blend across that band.  Row = pos xyz, box_min xyz,
+    box_max xyz, fade."""
+    b = np.asarray(box6, np.float64).reshape(6)
+    n = [int(nx), int(ny), int(nz)]
+    fade = float(fade)
+    if min(n) < 1 or n[0] * n[1] * n[2] > 64:
+        raise ValueError(f"reflection_probe_cells: 1 .. 64 cells expected, got {n[0]} x {n[1]} x {n[2]}")
+    if not np.isfinite(b).all() or not (b[3:] > b[:3]).all() or not 0.0 <= fade < float("inf"):
+        raise ValueError("reflection_probe_cells: a finite box with max > min on every axis and a finite fade >= 0 expected")
+    step = [(b[3 + k] - b[k]) / n[k] for k in range(3)]
+    lo = [b[k] + np.arange(n[k]) * step[k] for k in range(3)]
+    hi = [np.concatenate([lo[k][1:], b[3 + k:4 + k]]) for k in range(3)]      # a cell ends where the next begins; the last at the box
+    iz, iy, ix = (q.reshape(-1) for q in np.meshgrid(np.arange(n[2]), np.arange(n[1]), np.arange(n[0]), indexing="ij"))
+    out = np.empty((len(ix), 10))
+    out[:, 0:3] = probe_grid(b, *n).reshape(-1, 3)
+    for k, i in enumerate((ix, iy, iz)):
+        out[:, 3 + k] = lo[k][i] - fade
+        out[:, 6 + k] = hi[k][i] + fade
+    out[:, 9] = fade
+    return out
+
+
 def cube_directions(face, ju=0.5, jv=0.5):
     """Unit directions [6][face][face][3] through the texels of a reflection probe's cube (RayTracer.bake_reflection_probe; include/gi_hip.h:
     gi_cubemap_*) at the place (ju, jv) inside each texel, the centres by default: faces +X, -X, +Y, -Y, +Z, -Z, rows growing downward.  The

@@ -6,7 +6,7 @@ import numpy as np
 from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
                    LightmapParams, ProbeVisibilityParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
-from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, baked_visibility_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
+from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, baked_reflections_params, baked_visibility_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
 from .sessions import ProgressiveRender, parse_checkpoint_header
 
@@ -492,6 +492,53 @@ class RayTracer(DebugEntries):
         pointers, None where they are not needed."""
         self._check(self.L.gi_render_baked_visibility_device(self.h, C.byref(p), C.byref(bp), C.byref(vp), sh_ptr or None, chain_ptr or None, vis_ptr or None,
                                                              *_dev(out_ptr, f64)), "render_baked_visibility_device")
+
+    def bake_reflection_probes(self, positions, face, samples, levels=1, exponents=None, stream_base=0, seed=None):
+        """The chains of a reflection probe set: bake_reflection_probe once per position [K][3], every chain concatenated as the library holds it.
+        Returns [K][texels][3] float64, texels = the sum over the levels of 6 (face >> l)^2 -- the `chains` of run_baked_reflections."""
+        pts = self._bake_points(positions)
+        return np.ascontiguousarray(np.stack([np.concatenate([c.reshape(-1, 3) for c in self.bake_reflection_probe(q, face, samples, levels, exponents, stream_base, seed)])
+                                              for q in pts])) if len(pts) else np.zeros((0, 0, 3))
+
+    def _reflections_blocks(self, w, h, n, probes, chains, sh, grid_box, chain, exponents, terms, face, levels):
+        """(gi_baked_params, gi_baked_reflections_params, sh, chain, probes, chains) of run_baked_reflections: a chain of the set's shape stands in
+        for the one chain where baked_params checks face, levels and exponents; without a set the one chain is run_baked's."""
+        rp, t, c, f, lv = baked_reflections_params(probes, chains)
+        if t is None:
+            bp, sh, chain = baked_params(n=n, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=w, height=h)
+            return bp, rp, sh, chain, None, None
+        if f is None:                                      # chains [K][texels][3]: the caller states the face; the levels follow from the texels
+            if face is None:
+                raise ValueError("baked_reflections: chains [K][texels][3] need face= (and levels=, if not 1)")
+            f, lv = int(face), int(levels or 1)
+        if f < 1 or not 1 <= lv <= CUBEMAP_MAX_LEVELS or f % (1 << (lv - 1)) or c.shape[1] != sum(6 * (f >> l) ** 2 for l in range(lv)):
+            raise ValueError(f"baked_reflections: chains of {c.shape[1]} texels do not fit face {f} with {lv} levels")
+        first = [np.zeros((6, f >> l, f >> l, 3)) for l in range(lv)]
+        bp, sh, _ = baked_params(n=n, sh=sh, grid_box=grid_box, chain=first, exponents=exponents, terms=terms, width=w, height=h)
+        return bp, rp, sh, None, t, c
+
+    def run_baked_reflections(self, w, h, n, probes, chains, sh=None, grid_box=None, exponents=None, terms=None, f64=True, chain=None, face=None, levels=None, **kw):
+        """The baked-light pass with a reflection probe set (gi_render_baked_reflections_host; an addition): run_baked, except that the specular
+        term of a mirror or glossy first hit blends the probes whose influence boxes contain the hit, each probe's cube read in the direction
+        from the probe to the point where the reflection ray leaves its box -- reflections line up with the walls they show, and every room
+        shows its own.  A hit in no box reads the nearest probe as run_baked would.  probes [K][10] = pos, box_min, box_max, fade per probe
+        (reflection_probe_cells); chains the K chains, a list of bake_reflection_probe results or bake_reflection_probes' [K][texels][3] (then
+        with face= and levels=), filtered with `exponents`.  With probes None (or of no rows) the pass is run_baked's on `chain`, bit for bit;
+        with a set, `chain` is not read.  Returns the dict run_baked returns.  ValueError for bad values and shapes, before
+        the library is called; the definition is stated in include/gi_hip.h."""
+        bp, rp, sh, chain, t, c = self._reflections_blocks(w, h, n, probes, chains, sh, grid_box, chain, exponents, terms, face, levels)
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out, o = _out((rows, w, 12), f64)
+        self._check(self.L.gi_render_baked_reflections_host(self.h, C.byref(p), C.byref(bp), C.byref(rp), _p(sh), _p(chain), _p(t), _p(c), *o), "render_baked_reflections_host")
+        return {"baked": out, "beauty": out[:, :, 0:3], "direct": out[:, :, 3:6], "diffuse": out[:, :, 6:9], "specular": out[:, :, 9:12]}
+
+    def run_baked_reflections_device(self, p, bp, rp, sh_ptr, chain_ptr, probes_ptr, chains_ptr, out_ptr, f64=False):
+        """The baked-light pass with a reflection probe set on device memory, asynchronous on the context's stream; p from params, bp from
+        baked_params, rp from baked_reflections_params; sh_ptr, chain_ptr, probes_ptr ([K][10] f64), chains_ptr ([K][texels][3] f64) and out_ptr
+        ([rows][w][12]) are raw device pointers, None where they are not needed.  The table is not looked at."""
+        self._check(self.L.gi_render_baked_reflections_device(self.h, C.byref(p), C.byref(bp), C.byref(rp), sh_ptr or None, chain_ptr or None, probes_ptr or None,
+                                                              chains_ptr or None, *_dev(out_ptr, f64)), "render_baked_reflections_device")
 
     def last_baked_ms(self):
         """gi_last_baked_ms: device time of the last baked-light pass, with a lightmap or without (the frame's and the other passes' times keep theirs)."""

@@ -693,14 +693,15 @@ int gi_cubemap_prefilter(gi_ctx*, const gi_cubemap_params*, const double* cube_i
  *   5. Specular = color * C_l(R), R = d - (Nf * dot(Nf, d)) * 2.0 with dot = (Nf.x d.x + Nf.y d.y) + Nf.z d.z.  The texel of R in level l of face
  *      n = face >> l: the face of the largest |component|, the first of equals; x, y, z = R / that size; (a, b) = (-z, -y) on +X, (z, -y) on -X,
  *      (x, z) on +Y, (x, -z) on -Y, (x, -y) on +Z, (-x, -y) on -Z; column = min(n - 1, max(0, (int) floor(((a + 1.0) * 0.5) * n))), row the same
- *      from b.  The nearest texel: no parallax correction, no blending between levels.  A NaN texel of an over-narrow lobe passes through.
+ *      from b.  The nearest texel, read at R as if the surface stood at the probe; no blending between levels.  A NaN texel of an over-narrow lobe passes through.
  *   6. Emissive: the first hit's emissive.
  *   7. beauty = ((direct + diffuse) + specular) + emissive, a term whose bit is clear being +0.0.
  * Per pixel: the f64 sums over s in ascending order from +0.0 of the twelve channels, each divided once by (double) n_samples.  No reduction
  * across lanes: the result does not depend on stripes, the octree walk in use or the launch.
  * out [local_rows][width][12] = beauty rgb, direct rgb, diffuse rgb, specular rgb, float (out_is_f64 = 0) or double (1), rounded once on store.
  * What the preview is not: a transparent surface is shaded as opaque; the camera segment is not marched through the medium (the first hit is the
- * surface's, as in the feature pass); probes are looked up without visibility (gi_render_baked_visibility_* below looks them up with it), the cube without parallax; a lightmap atlas (gi_lightmap_*) is read by gi_render_baked_lightmap_*
+ * surface's, as in the feature pass); probes are looked up without visibility (gi_render_baked_visibility_* below looks them up with it), one cube is read for the whole scene at R itself
+ * (gi_render_baked_reflections_* below reads a set of probes, each at the direction projected onto its box); a lightmap atlas (gi_lightmap_*) is read by gi_render_baked_lightmap_*
  * below, not by these two entries.
  * GI_E_INVALID: null parameters or output; n_samples < 1 or taking the Halton index beyond 32 bits; terms 0 or with unknown bits; a grid dimension
  * < 1 or more than 2^31 probes; with GI_BAKED_DIFFUSE: a null sh, non-finite bounds or grid_max <= grid_min on an axis; with GI_BAKED_SPECULAR: a
@@ -863,6 +864,48 @@ int gi_render_baked_visibility_device(gi_ctx*, const gi_render_params*, const gi
                                       const double* d_vis, void* d_out, int out_is_f64);
 int gi_render_baked_visibility_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_visibility_params*, const double* sh, const double* chain,
                                     const void* vis, int vis_is_f64, void* h_out, int out_is_f64);
+
+/* The baked-light pass with a reflection probe set -- an ADDITION: gi_render_baked_* with the specular term read from a SET of reflection probes,
+ * box-projected and blended, so that a mirror floor shows the room as seen from the floor and every room shows its own reflections.  Each probe
+ * has an influence box that also serves as proxy geometry: the reflection ray is cut with the box, the probe's cube is read in the direction
+ * from the probe to that point, and probes whose boxes overlap are blended by the distance of the hit to their boxes' faces.  Steps 1 to 4, 6 and
+ * 7, the sums, the output layout, the Halton index, the stripes, the lens and the timer (gi_last_baked_ms) are gi_render_baked_*'s.  Inputs beside
+ * theirs: probes [K][10] f64, one row per probe: pos[3], box_min[3], box_max[3], fade; chains [K][texels][3] f64, K chains as gi_cubemap_* makes
+ * them, all of the face, levels and log2_exponent of gi_baked_params, texels = gi_cubemap_chain_texels(face, levels); K = n_probes, 1 ..
+ * GI_REFLECTIONS_MAX_PROBES.  Everything below is f64, IEEE + - * / and comparisons only, in the order written (tests/reflections_expect.py).
+ *   5. Specular = color * S, for a first hit on the mirror or glossy lobe.  P, d, Nf, the level l and R = d - (Nf * dot(Nf, d)) * 2.0 are step
+ *      5's of gi_render_baked_*; n = face >> l, off_l the texels before level l.  For k = 0 .. K-1 in ascending order, acc and W from +0.0:
+ *      containment  box_min[a] <= P[a] <= box_max[a] on all three axes (a NaN fails); a probe that does not contain P adds nothing.
+ *      edge         the least of P.x - min.x, max.x - P.x, P.y - min.y, max.y - P.y, P.z - min.z, max.z - P.z: the first, then each later one
+ *                   where it is smaller.
+ *      weight       w = fade > 0 ? (edge / fade < 1 ? edge / fade : 1.0) : 1.0.
+ *      exit         per axis a with R[a] != 0: v_a = ((R[a] > 0 ? box_max[a] : box_min[a]) - P[a]) / R[a]; t = v of the first such axis in the
+ *                   order x, y, z, then each later v where it is smaller; with no such axis t = 0.
+ *      direction    Q = P + t * R;  D = Q - pos.  If a component of D is not finite, or all three are 0, D = R.
+ *      accumulate   v = chains[k][off_l + texel(D, n)] with step 5's texel rule;  acc[ch] += w * v[ch];  W += w.
+ *      If W > 0: S = acc / W per channel.  Otherwise -- the hit is in no box, or only on faces of boxes with a fade -- k* = the probe with the
+ *      least ((dx dx + dy dy) + dz dz), d = P - pos, the first of equals, a NaN never less (k* = 0 when none is less than infinity), and
+ *      S = chains[k*][off_l + texel(R, n)]: step 5 of gi_render_baked_* on that probe's chain.
+ * The texel rule clamps rows and columns and sends a NaN to texel 0, so whatever the table holds no read leaves chains[k].
+ * With n_probes = 0, or without GI_BAKED_SPECULAR, the result is gi_render_baked_*'s on (sh, chain), bit for bit, through the same kernel
+ * instances; probes and chains may then be null.  With n_probes > 0 chain is not read and may be null.  Combining a probe set with a lightmap or
+ * with visibility maps in one call is out of scope.
+ * GI_E_INVALID, with a message that names render_baked_reflections: everything gi_render_baked_* refuses, except a null chain when n_probes > 0;
+ * null reflections parameters; n_probes outside 0 .. 64; null probes or chains with n_probes > 0 and GI_BAKED_SPECULAR; and --
+ * gi_render_baked_reflections_host, which looks at the table -- a pos, box or fade that is not finite, box_max <= box_min on an axis, fade < 0.
+ * GI_E_STATE: no scene.  A refused call touches no output and no timer; an open progressive session is left as it is.
+ * gi_baked_reflections_default_params: 0 probes.
+ * gi_render_baked_reflections_device: DEVICE pointers (sh, chain, probes, chains, out); it does not look at its table; asynchronous on the
+ * context's stream as gi_render_baked_device is.  gi_render_baked_reflections_host: HOST pointers.  There is no gi_group_* form. */
+#define GI_REFLECTIONS_MAX_PROBES 64
+typedef struct gi_baked_reflections_params {
+    int32_t n_probes;        /* K, 0 .. GI_REFLECTIONS_MAX_PROBES; 0: gi_render_baked_* on (sh, chain) */
+} gi_baked_reflections_params;
+void gi_baked_reflections_default_params(gi_baked_reflections_params*);
+int gi_render_baked_reflections_device(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_reflections_params*, const double* d_sh, const double* d_chain,
+                                       const double* d_probes, const double* d_chains, void* d_out, int out_is_f64);
+int gi_render_baked_reflections_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_reflections_params*, const double* sh, const double* chain,
+                                     const double* probes, const double* chains, void* h_out, int out_is_f64);
 
 #ifdef __cplusplus
 }
