@@ -9,7 +9,7 @@
                                [--aperture R [--blades N] [--blade-rotation DEG] [--focus D | --focus-pixel X Y]]
                                [--baked PREFIX [--baked-samples N] [--baked-probes NX NY NZ] [--baked-reflection X Y Z]
                                 [--baked-lightmap W H [--lightmap-samples N]] [--probe-visibility M]
-                                [--baked-reflections NX NY NZ [--baked-reflection-fade F]]]
+                                [--baked-reflections NX NY NZ [--baked-reflection-fade F]] [--final-gather DIRS]]
     python -m gi_raytracer_amd scene.scn --probes NX NY NZ [--probe-samples N] [--photons N] -o OUT.npy
     python -m gi_raytracer_amd scene.scn --lightmap W H [--lightmap-material M] [--lightmap-samples N] [--lightmap-dilate D] [--photons N]
                                -o OUT.ppm [--pfm OUT.pfm]
@@ -69,6 +69,10 @@ the scene's box is cut into NX x NY x NZ cells (at most 64), a chain is baked at
 (default: a tenth of the cell's shortest edge) is its probe's influence box, and the preview's mirror and glossy surfaces read each cube at the
 direction projected onto that box, blending where boxes overlap: reflections line up with the walls they show.  One more line names the set.
 --baked-reflection X Y Z has no part in it; it does not go with --baked-lightmap or --probe-visibility (one look-up per call).
+--final-gather DIRS (with --baked; include/gi_hip.h: gi_render_final_gather_*) renders the same four images from the same grid and chain through the
+final-gather pass: a diffuse first hit shoots DIRS (1 .. 64) cosine-distributed rays and takes the mean of what they hit, shaded from the lights, the
+grid, the chain and emission, so the grid is read one bounce away.  It reads the plain grid and one chain: not together with --baked-lightmap,
+--probe-visibility or --baked-reflections.
 """
 import argparse
 import os
@@ -136,6 +140,7 @@ def parser():
     ap.add_argument("--probe-visibility", type=int, default=None, metavar="M", help="with --baked: bake an M x M visibility map per probe of the grid and look the probes up through them (no light leaks through walls)")
     ap.add_argument("--baked-reflections", type=int, nargs=3, default=None, metavar=("NX", "NY", "NZ"), help="with --baked: bake one reflection probe per cell of the scene's box cut NX x NY x NZ and shade mirror and glossy surfaces from the set, box-projected and blended")
     ap.add_argument("--baked-reflection-fade", type=float, default=None, metavar="F", help="with --baked-reflections: how far every cell's influence box reaches beyond the cell, the band probes blend over (default: a tenth of the cell's shortest edge)")
+    ap.add_argument("--final-gather", type=int, default=None, metavar="DIRS", help="with --baked: shade diffuse first hits by a final gather of DIRS (1 .. 64) rays into the baked light instead of reading the grid at the hit")
     ap.add_argument("--baked-reflection", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"), help="with --baked: position of the reflection probe (default: the middle of the scene's box)")
     return ap
 
@@ -159,6 +164,8 @@ def check_args(ap, a):
         ap.error("--baked-reflections NX NY NZ and --baked-reflection-fade F need --baked PREFIX")
     if a.baked_reflections is None and a.baked_reflection_fade is not None:
         ap.error("--baked-reflection-fade F needs --baked-reflections NX NY NZ")
+    if a.baked is None and a.final_gather is not None:
+        ap.error("--final-gather DIRS needs the grid and the chain of --baked PREFIX")
     if a.baked is None and a.probe_visibility is not None:
         ap.error("--probe-visibility M needs the probe grid of --baked PREFIX [--baked-probes NX NY NZ]")
     if a.baked is not None:
@@ -196,6 +203,11 @@ def check_args(ap, a):
                 ap.error(f"--baked-reflections NX NY NZ: three numbers >= 1 with at most {REFLECTIONS_MAX_PROBES} cells")
             if a.baked_reflection_fade is not None and not 0.0 <= a.baked_reflection_fade < float("inf"):
                 ap.error("--baked-reflection-fade F: a finite number >= 0")
+        if a.final_gather is not None:
+            if a.baked_lightmap is not None or a.probe_visibility is not None or a.baked_reflections is not None:
+                ap.error("--final-gather reads the plain grid and one chain: not together with --baked-lightmap, --probe-visibility or --baked-reflections")
+            if not 1 <= a.final_gather <= gi.FINAL_GATHER_MAX_DIRS:
+                ap.error(f"--final-gather DIRS: from 1 to {gi.FINAL_GATHER_MAX_DIRS}")
         if os.path.abspath(a.baked + ".ppm") == os.path.abspath(a.output):
             if explicit_output:
                 ap.error(f"--baked {a.baked} writes {a.baked}.ppm, which is -o: name one of them differently")
@@ -378,7 +390,7 @@ def render_baked(a, rt, scene):
     points = gi.probe_grid(box, nx, ny, nz).reshape(-1, 3)
     sh = rt.bake_probes(points, PROBE_SAMPLES).reshape(nz, ny, nx, 9, 3)
     ns = BAKED_SAMPLES if a.baked_samples is None else a.baked_samples
-    note = ""
+    note, preview_ms = "", None                     # preview_ms: the time of the pass that made the preview where it is not the baked-light pass
     if a.baked_reflections is not None:
         cx, cy, cz = a.baked_reflections
         fade = a.baked_reflection_fade
@@ -407,12 +419,15 @@ def render_baked(a, rt, scene):
         vis = rt.bake_probe_visibility(points, m, VISIBILITY_SAMPLES).reshape(nz, ny, nx, m, m, 2)
         lit = rt.run_baked_visibility(a.width, a.height, ns, vis, sh=sh, grid_box=box, chain=chain, f64=False)
         note = f", visibility maps {m}x{m} {rt.last_probe_visibility_ms():.2f} ms"
+    elif a.final_gather is not None:
+        lit = rt.run_final_gather(a.width, a.height, ns, dirs=a.final_gather, sh=sh, grid_box=box, chain=chain, f64=False)
+        note, preview_ms = f", final gather of {a.final_gather} rays", rt.last_final_gather_ms()
     else:
         lit = rt.run_baked(a.width, a.height, ns, sh=sh, grid_box=box, chain=chain, f64=False)      # (the chain's exponents are the library's defaults, in both calls)
     gi.save_ppm(f"{a.baked}.ppm", lit["beauty"])
     for name in BAKED_FILES:
         gi.save_pfm(f"{a.baked}_{name}.pfm", lit[name])
-    return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, cube {rt.last_cubemap_ms()[0]:.2f} ms{note}, {ns} spp preview {rt.last_baked_ms():.2f} ms "
+    return (f"; baked light {nx} x {ny} x {nz} probes {rt.last_bake_ms():.2f} ms, cube {rt.last_cubemap_ms()[0]:.2f} ms{note}, {ns} spp preview {rt.last_baked_ms() if preview_ms is None else preview_ms:.2f} ms "
             f"-> {a.baked}.ppm, {a.baked}_*.pfm")
 
 

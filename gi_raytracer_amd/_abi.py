@@ -116,6 +116,11 @@ class BakedReflectionsParams(C.Structure):
     _fields_ = [("n_probes", C.c_int32)]
 
 
+class FinalGatherParams(C.Structure):
+    """gi_final_gather_params (include/gi_hip.h)."""
+    _fields_ = [("baked", BakedParams), ("n_dirs", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Settings(C.Structure):
     _fields_ = [("photons", C.c_int32), ("photon_depth", C.c_int32), ("min_samples", C.c_int32), ("max_samples", C.c_int32),
                 ("noise_thresh", C.c_double), ("ambient", C.c_double * 3), ("cam_pos", C.c_double * 3), ("cam_up", C.c_double * 3),
@@ -127,7 +132,8 @@ STRUCTS = {"gi_scene_desc": SceneDesc, "gi_photon_map_desc": PhotonMapDesc, "gi_
            "gi_upsample_params": UpsampleParams, "gi_occlusion_params": OcclusionParams, "gi_lens": Lens, "gi_bake_params": BakeParams,
            "gi_lightmap_params": LightmapParams, "gi_cubemap_params": CubemapParams, "gi_baked_params": BakedParams,
            "gi_baked_lightmap_params": BakedLightmapParams, "gi_probe_visibility_params": ProbeVisibilityParams,
-           "gi_baked_visibility_params": BakedVisibilityParams, "gi_baked_reflections_params": BakedReflectionsParams, "gih_settings": Settings}
+           "gi_baked_visibility_params": BakedVisibilityParams, "gi_baked_reflections_params": BakedReflectionsParams,
+           "gi_final_gather_params": FinalGatherParams, "gih_settings": Settings}
 
 
 def _signatures():
@@ -138,6 +144,7 @@ def _signatures():
     dn, us, oc, lens, bake, lm = P(DenoiseParams), P(UpsampleParams), P(OcclusionParams), P(Lens), P(BakeParams), P(LightmapParams)
     cm, bk, bl = P(CubemapParams), P(BakedParams), P(BakedLightmapParams)
     pv, bv, br = P(ProbeVisibilityParams), P(BakedVisibilityParams), P(BakedReflectionsParams)
+    fg = P(FinalGatherParams)
     return {
         # include/gi_hip.h: context, uploads, frames
         "gi_create": (i, [P(vp), i]), "gi_destroy": (None, [vp]), "gi_last_error": (s, [vp]), "gi_set_stream": (i, [vp, vp]),
@@ -201,6 +208,9 @@ def _signatures():
         # reflection probe sets: the baked-light pass with box-projected, blended cube look-ups
         "gi_baked_reflections_default_params": (None, [br]), "gi_render_baked_reflections_device": (i, [vp, rp, bk, br, vp, vp, vp, vp, vp, i]),
         "gi_render_baked_reflections_host": (i, [vp, rp, bk, br, _dp, _dp, _dp, _dp, vp, i]),
+        # the final-gather pass: one bounce from the first hits into the baked light
+        "gi_final_gather_default_params": (None, [fg]), "gi_render_final_gather_device": (i, [vp, rp, fg, vp, vp, vp, i, vp]),
+        "gi_render_final_gather_host": (i, [vp, rp, fg, _dp, _dp, vp, i, _ip]), "gi_last_final_gather_ms": ms,
         # csrc/gi_host.h: the host scene builder
         "gih_scene_create": (vp, []), "gih_scene_destroy": (None, [vp]), "gih_last_error": (s, [vp]), "gih_load_scn": (i, [vp, s]),
         "gih_load_obj": (i, [vp, s, _dp, _dp, i32]), "gih_add_material": (i, [vp, _dp]), "gih_add_texture": (i, [vp, i32, _dp, _bp, i64]),

@@ -191,6 +191,23 @@ bool lit_check(const gi_baked_params* p, const void* sh, const void* chain, std:
     return true;
 }
 
+// The chain's layout and the level every material reads, into A: face, the texels before each level, and the table [n_mat] in `d_levels` (a pass's
+// own, sized on first use and kept), made per call from the roughnesses kept at upload (baked_level_of: no transcendental on the device).  It waits
+// for the stream first: an earlier pass on it may still read the table.
+int lit_level_table(gi_ctx* c, const gi_baked_params* bp, DevBuf<int32_t>& d_levels, LitArgs& A)
+{
+    A.face = (uint32_t)bp->face;
+    for (int l = 0; l < bp->levels; l++) A.level_off[l] = (uint32_t)cm_texels_before(bp->face, l);
+    std::vector<int32_t> levels(c->scene.mat_roughness.size());
+    for (size_t m = 0; m < levels.size(); m++) levels[m] = baked_level_of(c->scene.mat_roughness[m], bp->levels, bp->log2_exponent);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (d_levels.n < levels.size()) HIP_TRY(c, d_levels.alloc(levels.size()));
+    if (!levels.empty()) HIP_TRY(c, hipMemcpy(d_levels.p, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    A.level_of_mat = d_levels.p;
+    return GI_OK;
+}
+
 // The pass itself on checked arguments: LitArgs from the parameters, the level table, the one launch.  terms: bp->terms, or fewer bits.  lm: null, or
 // a LitArgs whose `lm` points at the call's LitLm, which selects the LM instances, or one whose `vis` points at the probes' maps (with vis_size,
 // normal_bias and vis_floor), which selects the PV instances, or one whose `rs_probes` points at a probe set's table (with rs_chains, rs_n and
@@ -203,18 +220,8 @@ int lit_run(gi_ctx* c, const char* name, const Frame& F, const gi_baked_params* 
     A.n3[0] = bp->nx; A.n3[1] = bp->ny; A.n3[2] = bp->nz;
     for (int k = 0; k < 3; k++) { A.gmin[k] = bp->grid_min[k]; A.gmax[k] = bp->grid_max[k]; }
     A.sh = d_sh; A.chain = d_chain;
-    // the level every material reads, made per call from the roughnesses kept at upload (baked_level_of: no transcendental on the device)
-    if (terms & GI_BAKED_SPECULAR) {
-        A.face = (uint32_t)bp->face;
-        for (int l = 0; l < bp->levels; l++) A.level_off[l] = (uint32_t)cm_texels_before(bp->face, l);
-        std::vector<int32_t> levels(c->scene.mat_roughness.size());
-        for (size_t m = 0; m < levels.size(); m++) levels[m] = baked_level_of(c->scene.mat_roughness[m], bp->levels, bp->log2_exponent);
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier pass on the stream may still read the table
-        if (c->lit.d_levels.n < levels.size()) HIP_TRY(c, c->lit.d_levels.alloc(levels.size()));
-        if (!levels.empty()) HIP_TRY(c, hipMemcpy(c->lit.d_levels.p, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        A.level_of_mat = c->lit.d_levels.p;
-    }
+    if (terms & GI_BAKED_SPECULAR)
+        if (const int rc = lit_level_table(c, bp, c->lit.d_levels, A)) return rc;
     const auto launch = [&](const LitK& k, dim3 grid, dim3 block, uint32_t n_pix) {
         hipLaunchKernelGGL(k.fn, grid, block, k.lds, c->stream, c->S, F, A, n_pix, bp->n_samples, d_out, out_is_f64);
     };

@@ -388,6 +388,11 @@ struct LitPass : AuxPass {
     int pv_lds_refused = -1;          // lds_refused of the PV instances (gi_render_baked_visibility_*)
     int rs_lds_refused = -1;          // lds_refused of the RS instances (gi_render_baked_reflections_*)
 };
+// the final-gather pass (gi_finalgather.inc): a timer, an LDS answer and a level table of its own [n_mat], made per call with a chain, sized on
+// first use and kept -- the baked-light pass's are left alone
+struct FgPass : AuxPass {
+    DevBuf<int32_t> d_levels;
+};
 
 // ------------------------------------------------------------------------------------------------------------------------ the context
 struct gi_ctx {
@@ -427,6 +432,7 @@ struct gi_ctx {
     } lens;
     AuxPass feat, ao, up;             // gi_render_features_*, gi_render_occlusion_*, gi_upsample_*
     LitPass lit;                      // gi_render_baked_*
+    FgPass fg;                        // gi_render_final_gather_*
     DenoisePass dn;                   // gi_denoise_*
     BakePass bake;                    // gi_bake_*
     LightmapPass lm;                  // gi_lightmap_*

@@ -84,15 +84,23 @@ int pixel_pass_frame(gi_ctx* c, const char* name, const gi_render_params* p, Fra
     return GI_OK;
 }
 
+// the one refusal that needs the frame: Halton index of sample s = (offset of the pixel < inc) + s * inc, in 32 bits as in the beauty pass.
+// pixel_pass asks it; an entry that has work to do between the frame and the pass (a table to replace) asks it first, so that a refused call
+// has touched nothing
+int pixel_pass_cap(gi_ctx* c, const char* name, const Frame& F, int32_t n_samples)
+{
+    if ((unsigned long long)n_samples * F.he.inc > (1ull << 32))
+        return fail(c, GI_E_INVALID, std::string(name) + ": n_samples = " + std::to_string(n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
+                                     " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
+    return GI_OK;
+}
+
 // n_samples of every pixel of F through the instance of `kernels` (a first-hit family, gi_instances.inc) that fits the scene, in workgroups of
 // `block` lanes, timed by the pass's timer.  launch(kernel, grid, block, n_pix) makes the one launch.
 template <class K, size_t N, class Launch>
 int pixel_pass(gi_ctx* c, AuxPass& pass, const char* name, const Frame& F, int32_t n_samples, const K (&kernels)[N], unsigned block, Launch launch)
 {
-    // Halton index of sample s = (offset of the pixel < inc) + s * inc, in 32 bits as in the beauty pass
-    if ((unsigned long long)n_samples * F.he.inc > (1ull << 32))
-        return fail(c, GI_E_INVALID, std::string(name) + ": n_samples = " + std::to_string(n_samples) + " takes the Halton index of a " + std::to_string(F.w) + " x " + std::to_string(F.h) +
-                                     " frame beyond 32 bits (at most " + std::to_string((1ull << 32) / F.he.inc) + ")");
+    if (const int rc = pixel_pass_cap(c, name, F, n_samples)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (F.local_rows == 0) return GI_OK;
     if (pass.lds_refused < 0) { pass.lds_refused = 0; ask_for_lds(kernels, pass.lds_refused); }

@@ -16,6 +16,13 @@
 #ifndef GI_LIT_BLOCK
 #define GI_LIT_BLOCK 512    // as GI_AO_BLOCK: the closest-hit walk, then any-hit walks, next to the same records; the look-ups behind them need fewer registers than either
 #endif
+#ifndef GI_FG_BLOCK
+// 256 lanes, not 512: a gather ray's any-hit walks run with the loop's state (O, Nf, the running sum, the first hit's direct term) on top of what
+// k_lit holds there, which at the 256 registers of a 512-lane workgroup spills 96 to 224 B per lane more than k_lit does.  At 256 lanes a wave may
+// take the whole 512-entry file (256 VGPRs + 52 .. 203 AGPRs) and nothing spills, at one wave per SIMD.  The 512-lane build is the faster one on the
+// benchmark frame (DESIGN.md has both sets of figures); -DGI_FG_BLOCK=512 builds it.
+#define GI_FG_BLOCK 256
+#endif
 #ifndef GI_PV_BLOCK
 #define GI_PV_BLOCK 512     // as GI_AOV_BLOCK: a closest-hit walk per sample next to the same records, two f64 sums per lane
 #endif
@@ -26,6 +33,9 @@ __global__ __launch_bounds__(GI_AO_BLOCK) void k_ao(Scene S, Frame F, uint32_t n
 struct LitArgs;
 template <int FEAT, int WIDE, int LM = 0, int PV = 0, int RS = 0>
 __global__ __launch_bounds__(GI_LIT_BLOCK) void k_lit(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, void* out, int out_f64);
+
+template <int FEAT, int WIDE>
+__global__ __launch_bounds__(GI_FG_BLOCK) void k_fg(Scene S, Frame F, LitArgs A, uint32_t n_pix, int32_t n, int32_t n_dirs, void* out, int out_f64, int32_t* ids);
 
 struct PvArgs;
 template <int FEAT, int WIDE>
@@ -43,6 +53,7 @@ using FinishK = StKernel<decltype(&k_st_finish<0, 0, 0>)>;
 using AovK = StKernel<decltype(&k_aov<0, 0>)>;
 using AoK = StKernel<decltype(&k_ao<0, 0>)>;
 using LitK = StKernel<decltype(&k_lit<0, 0>)>;
+using FgK = StKernel<decltype(&k_fg<0, 0>)>;
 using PvK = StKernel<decltype(&k_pv_capture<0, 0>)>;
 
 static int first_hit_row(int feat, bool wide) { return (feat == 7 ? 2 : feat) * 2 + (wide ? 1 : 0); }   // the first-hit families: FEAT 0, spheres, textures x per-node, wide
@@ -99,6 +110,10 @@ static constexpr LitK kLitPv[] = {
 static constexpr LitK kLitRs[] = {
     {k_lit<0, 0, 0, 0, 1>, kLdsNodes}, {k_lit<0, 1, 0, 0, 1>, kLdsWideBoxes}, {k_lit<GI_FEAT_SPHERES, 0, 0, 0, 1>, kLdsNodes}, {k_lit<GI_FEAT_SPHERES, 1, 0, 0, 1>, kLdsWideBoxes},
     {k_lit<7, 0, 0, 0, 1>, kLdsNodes}, {k_lit<7, 1, 0, 0, 1>, kLdsWideBoxes}};
+// k_fg<FEAT, WIDE> (the final-gather pass, gi_render_final_gather_*): kLit's rows and LDS
+static constexpr FgK kFg[] = {
+    {k_fg<0, 0>, kLdsNodes}, {k_fg<0, 1>, kLdsWideBoxes}, {k_fg<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_fg<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},
+    {k_fg<7, 0>, kLdsNodes}, {k_fg<7, 1>, kLdsWideBoxes}};
 // k_pv_capture<FEAT, WIDE> (a probe's visibility map, gi_probe_visibility_*): the first-hit rows, with k_aov's LDS -- its walks are closest-hit walks
 static constexpr PvK kPv[] = {
     {k_pv_capture<0, 0>, kLdsNodes}, {k_pv_capture<0, 1>, kLdsWideBoxes}, {k_pv_capture<GI_FEAT_SPHERES, 0>, kLdsNodes}, {k_pv_capture<GI_FEAT_SPHERES, 1>, kLdsWideBoxes},

@@ -49,6 +49,7 @@ using namespace gi;
 #include "gi_lightmap.inc"       // lightmap atlases: k_lm_raster, k_lm_point, the rank, k_lm_scatter, k_lm_dilate and gi_lightmap_*
 #include "gi_cubemap.inc"        // reflection probes: the capture's source for k_bake_gen, k_cm_box, k_cm_filter, k_cm_resolve and gi_cubemap_*
 #include "gi_baked.inc"          // the baked-light pass: k_lit and gi_render_baked_*, the consumer of probes and cube chains
+#include "gi_finalgather.inc"    // the final gather: k_fg and gi_render_final_gather_*, one bounce from the first hits into the baked light
 #include "gi_visibility.inc"     // probe visibility: k_pv_capture and gi_probe_visibility_*; gi_render_baked_visibility_*, the PV instances of k_lit
 #include "gi_reflections.inc"    // reflection probe sets: gi_render_baked_reflections_*, the RS instances of k_lit
 #include "gi_group.inc"          // one frame over several devices (gi_group_*)

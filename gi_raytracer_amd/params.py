@@ -1,10 +1,10 @@
-"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params, gi_baked_visibility_params, gi_baked_reflections_params."""
+"""Parameter blocks built and validated before the library is called: the Halton cap, the upsampler's sizes and arrays, gi_occlusion_params, gi_lens, gi_baked_params, gi_baked_lightmap_params, gi_baked_visibility_params, gi_baked_reflections_params, gi_final_gather_params."""
 import ctypes as C
 
 import numpy as np
 
 from ._abi import (BAKED_DIFFUSE, BAKED_DIRECT, BAKED_EMISSIVE, BAKED_SPECULAR, CUBEMAP_MAX_LEVELS, GI_OK, LM_FILTERS, PROBE_VISIBILITY_MAX_SIZE, REFLECTIONS_MAX_PROBES, BakedLightmapParams,
-                   BakedParams, BakedReflectionsParams, BakedVisibilityParams, Lens, OcclusionParams, _f64, _floats, _p, lib)
+                   BakedParams, BakedReflectionsParams, BakedVisibilityParams, FinalGatherParams, Lens, OcclusionParams, _f64, _floats, _p, lib)
 
 
 def halton_sample_cap(w, h):
@@ -158,6 +158,25 @@ def baked_params(n=None, sh=None, grid_box=None, chain=None, exponents=None, ter
         raise ValueError(f"baked: terms must be a non-empty set of the BAKED_* bits, got {p.terms}")
     if (p.terms & BAKED_DIFFUSE and sh is None and not lightmap) or (p.terms & BAKED_SPECULAR and chain is None):
         raise ValueError("baked: the diffuse term needs sh, the specular term needs chain")
+    return p, sh, chain
+
+
+FINAL_GATHER_MAX_DIRS = 64
+
+
+def final_gather_params(n=None, dirs=None, sh=None, grid_box=None, chain=None, exponents=None, terms=None, width=None, height=None):
+    """(gi_final_gather_params, sh, chain) of RayTracer.run_final_gather: baked_params on the same arguments inside the library's defaults (16
+    directions), with dirs set when given.  terms defaults as in baked_params: DIRECT | EMISSIVE, DIFFUSE with sh, SPECULAR with chain; a chain
+    without the SPECULAR bit is kept for the secondary hits.  No device needed.  ValueError for what the library would refuse: everything
+    baked_params refuses, dirs outside 1 .. 64."""
+    p = FinalGatherParams()
+    lib().gi_final_gather_default_params(C.byref(p))
+    bp, sh, chain = baked_params(n=n, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=width, height=height)
+    p.baked = bp
+    if dirs is not None:
+        p.n_dirs = _whole("dirs", dirs, "final_gather")
+    if not 1 <= p.n_dirs <= FINAL_GATHER_MAX_DIRS:
+        raise ValueError(f"final_gather: dirs must be 1 .. {FINAL_GATHER_MAX_DIRS}, got {p.n_dirs}")
     return p, sh, chain
 
 

@@ -6,7 +6,7 @@ import numpy as np
 from ._abi import (BAKE_MODES, BAKE_SH9, BAKE_TEXEL, CUBEMAP_MAX_LEVELS, DEFAULT_SEED, GI_OK, BakeParams, CubemapParams, DenoiseParams, GiError, Lens,
                    LightmapParams, ProbeVisibilityParams, RenderParams, UpsampleParams, _buf, _dev, _f64, _ip, _out, _p, lib)
 from .debug import DebugEntries
-from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, baked_reflections_params, baked_visibility_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
+from .params import _bake_points, _chart, _fill_params, _filter_array, baked_lightmap_params, baked_params, baked_reflections_params, baked_visibility_params, final_gather_params, lens_params, low_frame_size, occlusion_params, upsample_arrays
 from .scene import Scene
 from .sessions import ProgressiveRender, parse_checkpoint_header
 
@@ -407,6 +407,36 @@ class RayTracer(DebugEntries):
         ([nz][ny][nx][9][3] f64), chain_ptr (the whole chain, f64) and out_ptr ([rows][w][12]) are raw device pointers, the first two None where
         their term is off."""
         self._check(self.L.gi_render_baked_device(self.h, C.byref(p), C.byref(bp), sh_ptr or None, chain_ptr or None, *_dev(out_ptr, f64)), "render_baked_device")
+
+    def run_final_gather(self, w, h, n, dirs=16, sh=None, grid_box=None, chain=None, exponents=None, terms=None, want_ids=False, f64=True, **kw):
+        """The final-gather pass on the frame `run` renders (gi_render_final_gather_host; an addition, one bounce from the first hits into the
+        baked light): run_baked, except that the diffuse term of a first hit on the diffuse lobe is its colour times the mean over `dirs`
+        cosine-distributed rays of what they hit, shaded from the analytic lights, the probe grid sh, the chain and emission (the ambient colour
+        on a miss).  A chain given without the SPECULAR bit serves the secondary hits alone.  Returns run_baked's dict under the key
+        `final_gather` for the array [rows][w][12]; with want_ids also `ids` [rows][w][n][dirs] int32: the entity each gather ray hit, -1 on a
+        miss, -2 where the sample gathered nothing.  **kw as for run (stripes, seed).  ValueError for bad values and shapes, before the library
+        is called; the definition is stated in include/gi_hip.h."""
+        fp, sh, chain = final_gather_params(n=n, dirs=dirs, sh=sh, grid_box=grid_box, chain=chain, exponents=exponents, terms=terms, width=w, height=h)
+        p = self.params(w, h, **kw)
+        rows = self.local_rows(p)
+        out, o = _out((rows, w, 12), f64)
+        ids = np.zeros((rows, w, fp.baked.n_samples, fp.n_dirs), np.int32) if want_ids else None
+        self._check(self.L.gi_render_final_gather_host(self.h, C.byref(p), C.byref(fp), _p(sh), _p(chain), *o, _p(ids, _ip)), "render_final_gather_host")
+        res = {"final_gather": out, "beauty": out[:, :, 0:3], "direct": out[:, :, 3:6], "diffuse": out[:, :, 6:9], "specular": out[:, :, 9:12]}
+        if want_ids:
+            res["ids"] = ids
+        return res
+
+    def run_final_gather_device(self, p, fp, sh_ptr, chain_ptr, out_ptr, f64=False, ids_ptr=None):
+        """The final-gather pass on device memory, asynchronous on the context's stream; p from params, fp from final_gather_params; sh_ptr
+        ([nz][ny][nx][9][3] f64), chain_ptr (the whole chain, f64), out_ptr ([rows][w][12]) and ids_ptr ([rows][w][n][dirs] int32) are raw device
+        pointers, None where they are not needed."""
+        self._check(self.L.gi_render_final_gather_device(self.h, C.byref(p), C.byref(fp), sh_ptr or None, chain_ptr or None, *_dev(out_ptr, f64), ids_ptr or None),
+                    "render_final_gather_device")
+
+    def last_final_gather_ms(self):
+        """gi_last_final_gather_ms: device time of the last final-gather pass (the frame's and the other passes' times keep theirs)."""
+        return self._last_ms("final_gather")
 
     def run_baked_lightmap(self, w, h, n, atlas, ent, uv, filter="bilinear", sh=None, grid_box=None, chain=None, exponents=None, terms=None, f64=True, **kw):
         """The baked-light pass with a lightmap (gi_render_baked_lightmap_host; an addition, the reader of bake_lightmap's atlas): run_baked, except

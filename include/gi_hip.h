@@ -907,6 +907,65 @@ int gi_render_baked_reflections_device(gi_ctx*, const gi_render_params*, const g
 int gi_render_baked_reflections_host(gi_ctx*, const gi_render_params*, const gi_baked_params*, const gi_baked_reflections_params*, const double* sh, const double* chain,
                                      const double* probes, const double* chains, void* h_out, int out_is_f64);
 
+/* The final-gather pass -- an ADDITION: one bounce from the first hits into the baked light, the step between gi_render_baked_* (which reads the
+ * probe grid at the first hit itself, so the picture has the grid's resolution) and the path tracer.  From a diffuse first hit it shoots n_dirs
+ * cosine-distributed rays, shades what they hit from the baked data -- the analytic lights, the probe grid, one cube chain, emission -- and
+ * averages: the grid is read one bounce away, where its coarseness is averaged over the hemisphere, at the cost of n_dirs closest-hit walks per
+ * sample, with no path pool, no sorts and no gather.  Inputs: sh and chain as gi_render_baked_* takes them.  sh is needed with GI_BAKED_DIFFUSE
+ * (pass a grid of zeros for a frame without baked irradiance); chain is needed with GI_BAKED_SPECULAR and otherwise optional: when given,
+ * secondary hits on mirror and glossy surfaces read it, when null that read is +0.0 -- face, levels and log2_exponent are checked whenever a
+ * chain is given.  Per pixel and per sample s = 0 .. n_samples-1 with Halton index idx:
+ *   1. First hit: step 1 of gi_render_baked_* (same ray, same RNG keys: seed, stream idx, depth 0; the context's lens applies).  A miss adds the
+ *      ambient colour to beauty and nothing to the three terms.
+ *   2. Direct, specular and emissive of the first hit: steps 2, 3, 5 and 6 of gi_render_baked_*, unchanged.  Without GI_BAKED_DIFFUSE the pass is
+ *      gi_render_baked_* bit for bit.
+ *   3. Diffuse, for a first hit on the diffuse lobe (roughness >= .9) with GI_BAKED_DIFFUSE: O = P + 0.0001 Nf.  For j = 0 .. n_dirs-1:
+ *      u = (float) draw(purpose 36, a = j), v = (float) draw(purpose 37, a = j) of the stream at depth 0; d_j = hemisphereSample_cos(Nf, u, v, 2)
+ *      (include/util.cpp:35-58), the lobe of the path tracer's diffuse bounce and of GI_BAKE_TEXEL.  The closest hit of the ray (O, d_j) -- d_j as
+ *      the sampler gave it, not renormalised: gi_trace on the row (O, d_j) states it -- is RayTracer::trace's, its alpha draws those of the
+ *      stream's RNG with depth = 1 + j.  The medium is not marched along the ray.
+ *        a miss:  L_j = ambient.
+ *        a hit at Q on entity e with material m: color_Q, emissive_Q (textures applied) and roughness_Q are m's; N = minNorm of trace;
+ *                 normQ = -N if dot(N, d_j) > 0 else N (not renormalised); NfQ = normQ * (1 / sqrt(dot(normQ, normQ)));
+ *                 i_Q = step 2's i at (Q, normQ, roughness_Q) with the RNG at depth 1 + j (light draws and shadow-ray alpha draws alike; the
+ *                 medium included, as in step 2);  base_Q = emissive_Q + color_Q * i_Q.
+ *                 roughness_Q >= .9:            L_j = base_Q + color_Q * D(Q, NfQ), D step 4's of gi_render_baked_* (the plain grid).
+ *                 roughness_Q < .9, a chain:    L_j = base_Q + color_Q * chain[l][texel(R)], R = d_j - (NfQ * dot(NfQ, d_j)) * 2.0, step 5's
+ *                                               texel rule, l = 0 for roughness_Q < .001 else m's level (step 3's table).
+ *                 roughness_Q < .9, no chain:   L_j = base_Q.
+ *      The terms bits do not gate what a secondary hit adds.  E = (((+0.0 + L_0) + L_1) + ... + L_{n_dirs-1}) / (double) n_dirs per channel;
+ *      diffuse = color * E.  Each product and sum above is one IEEE operation per channel, in the order written.
+ *   4. beauty = ((direct + diffuse) + specular) + emissive, a term whose bit is clear being +0.0.
+ * Per pixel: the f64 sums over s in ascending order from +0.0 of the twelve channels, each divided once by (double) n_samples; no reduction
+ * across lanes, so the result does not depend on stripes, the octree walk in use or the launch.
+ * out [local_rows][width][12] = beauty rgb, direct rgb, diffuse rgb, specular rgb, as gi_render_baked_* lays them out, float or double, rounded
+ * once on store.  ids (optional) [local_rows][width][n_samples][n_dirs] int32: the entity gather ray j of sample s hit; -1: it left the scene;
+ * -2: no gather for that sample (the first hit missed or is not on the diffuse lobe, or GI_BAKED_DIFFUSE is clear).
+ * What is exact and what is not: d_j comes from sin, cos and sqrt of the device's math library, a few ulp from the host's, so Q and what is read
+ * there carry that, and a ray that grazes an edge may hit another entity; everything else is stated bit for bit (tests/finalgather_expect.py).
+ * Out of scope: lightmap atlases, probe visibility and probe sets at the secondary hits (only the plain grid and one chain are read there);
+ * gathering from mirror and glossy first hits; the medium along the gather rays.
+ * GI_E_INVALID, with a message that names render_final_gather: everything gi_render_baked_* refuses on the baked block (a null sh with
+ * GI_BAKED_DIFFUSE, a null chain with GI_BAKED_SPECULAR, face / levels / log2_exponent not as gi_cubemap_params allows when there is a chain),
+ * n_dirs outside 1 .. 64, reserved != 0, null parameters or output.  GI_E_STATE: no scene.  A refused call touches no output and no timer; an
+ * open progressive session is left as it is.
+ * gi_final_gather_default_params: gi_baked_default_params with terms DIRECT | DIFFUSE | EMISSIVE, 16 directions.
+ * gi_render_final_gather_device: DEVICE pointers (sh, chain, out, ids), asynchronous on the context's stream, except that with a chain it first
+ * waits for the stream's earlier work, to replace its level table.  gi_render_final_gather_host: HOST pointers.
+ * gi_last_final_gather_ms: device time of the last pass (HIP events around the kernel); the frame's and every other pass's times are left alone.
+ * There is no gi_group_* form. */
+typedef struct gi_final_gather_params {
+    gi_baked_params baked;   /* n_samples, terms, the grid, face, levels, log2_exponent: as gi_render_baked_* */
+    int32_t n_dirs;          /* 1 .. 64 gather rays per sample */
+    int32_t reserved;        /* must be 0 */
+} gi_final_gather_params;
+void gi_final_gather_default_params(gi_final_gather_params*);
+int gi_render_final_gather_device(gi_ctx*, const gi_render_params*, const gi_final_gather_params*, const double* d_sh, const double* d_chain, void* d_out, int out_is_f64,
+                                  int32_t* d_ids);
+int gi_render_final_gather_host(gi_ctx*, const gi_render_params*, const gi_final_gather_params*, const double* sh, const double* chain, void* h_out, int out_is_f64,
+                                int32_t* h_ids);
+int gi_last_final_gather_ms(gi_ctx*, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
